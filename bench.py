@@ -16,9 +16,22 @@ write-back, plus the periodic target sync / FIFO eviction at their cadences.
 Precision: ``--dtype fp32`` (default) matches the reference learner
 (``learner.py:37-38`` computes in fp32): the hand-written kernels run split
 hi/lo bf16 operands (three MFMAs per product, fp32 accumulation; see
-learner/fused_learner.py).  The JSON's ``value`` is that fp32 number; unless
-``--no-bf16-extra``, the same run also times the bf16-operand learner and reports
-it as ``value_bf16``.
+learner/fused_learner.py).  The JSON's ``value`` is that fp32 number.
+
+A plain run does only what that headline needs: set-up, warm-up, the timed steps, the
+result line (``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``,
+``ms_per_step`` = milliseconds per timed step, ...).  ``--full`` adds everything else
+the benchmark measures or checks, each described below: the bf16-operand learner timed
+in the same run (``value_bf16``; ``--no-bf16-extra`` skips it), at N > 1 the other batch
+scope, the replica / graph-vs-eager self-checks of the DP step and ``param_sha256``.
+
+``--dump-outputs DIR`` writes what the last timed update left with its caller as
+``DIR/<name>.npy`` (float32 / float64): the fp32 master weights (``params``), the
+centered-RMSprop state (``rms_v``, ``rms_m``), the batch's |TD| priorities and
+per-sample losses (``td_abs``, ``loss_per_sample``) and the ``loss`` / ``grad_norm``
+scalars -- at most 64 MB in all (a larger array is cut to a fixed, seeded sample of
+its elements).  Replay contents, initial weights and the sampler's counters are all
+seeded from the arguments, so two runs with the same arguments see the same inputs.
 
 Timing: ``--warmup`` untimed updates, then every HIP graph the timed region
 replays is captured (``learner.prepare_graphs``: state-preserving, no updates) and
@@ -42,8 +55,8 @@ data parallelism (``--batch-scope``):
   averages up to N x 512 samples; ``value`` = (sum of M over the timed steps) / 512 /
   time (``value_weak``), ``value_nominal`` = N x (DP steps/s).
 
-At N > 1 the run also measures the other scope (fp32) and prints both ``value_strong``
-and ``value_weak`` with the rows each rank computed (``per_rank_rows``).
+At N > 1 a ``--full`` run also measures the other scope (fp32) and prints both
+``value_strong`` and ``value_weak`` with the rows each rank computed (``per_rank_rows``).
 
 N > 1 diagnostics in the JSON: ``comm_world`` (the rank count the communicator itself
 reports), ``init_allreduce_ok`` (a checked all-reduce of rank + 1 through the DP step's
@@ -55,8 +68,8 @@ Before this process makes any HIP call, each rank at N > 1 captures and replays 
 step in ONE child process (``runtime/capture_probe.py``: its own RCCL communicator and
 rendezvous under a separate store prefix); a child that crashes, hangs or fails on any
 rank sends every rank to the eager DP step for that measurement (``dp_capture_probe``:
-exit status per rank, verdict per measurement, seconds).  After the timed region the
-run checks itself: ``replicas_identical`` (checksums of every rank's fp32 master weights
+exit status per rank, verdict per measurement, seconds).  After the timed region a
+``--full`` run checks itself: ``replicas_identical`` (checksums of every rank's fp32 master weights
 and RMSprop state agree) and ``graph_matches_eager`` (one captured update equals the same
 update run eagerly from the same snapshot, bit for bit, on every rank); ``param_sha256``
 fingerprints the final fp32 weights.
@@ -134,9 +147,9 @@ def measurements(args, world: int):
     dp = world > 1 or args.force_dp
     scope = args.batch_scope if dp else "global"
     out = [("headline", args.dtype, scope)]
-    if world > 1 and not args.no_scope_extra:
+    if args.full and world > 1 and not args.no_scope_extra:
         out.append(("other_scope", args.dtype, "per_rank" if scope == "global" else "global"))
-    if not args.no_bf16_extra and args.dtype == "fp32":
+    if args.full and not args.no_bf16_extra and args.dtype == "fp32":
         out.append(("bf16", "bf16", scope))
     return out
 
@@ -246,6 +259,41 @@ def measure(cfg, learner, replay, comm, warmup: int, steps: int, prep_warm: int 
                 metrics=learner.last_metrics())
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(learner, metrics, out_dir: str, rank: int = 0) -> None:
+    """What the last timed update left with its caller, as ``out_dir/<name>.npy`` (rank 0
+    writes): fp32 master weights, RMSprop state, the batch's |TD| priorities and per-sample
+    losses, loss and gradient norm.  At most ``DUMP_BUDGET_BYTES`` in all: small arrays
+    are written whole, one over its share of what is left is cut to a seeded (fixed) sample."""
+    if hasattr(learner, "materialize"):
+        learner.materialize()          # sharded DP update: every rank's fc rows (a collective)
+    torch.cuda.synchronize()
+    if rank != 0:
+        return
+    arrays = {}
+    for name, attr in (("params", "p32"), ("rms_v", "rms_v"), ("rms_m", "rms_m"), ("td_abs", "td_abs"),
+                       ("loss_per_sample", "loss_b")):
+        t = getattr(learner, attr, None)
+        if t is not None:
+            arrays[name] = t.detach().to(torch.float32).cpu().numpy().reshape(-1)
+    for name in ("loss", "grad_norm"):
+        if name in metrics:
+            arrays[name] = np.asarray([metrics[name]], dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    order = sorted(arrays, key=lambda k: arrays[k].nbytes)      # small arrays whole, the rest share what is left
+    for i, name in enumerate(order):
+        a = arrays[name]
+        keep = left // (len(order) - i) // a.itemsize
+        if a.size > keep:
+            idx = np.sort(np.random.default_rng(20240 + i).choice(a.size, size=keep, replace=False))
+            a = a[idx]
+        left -= a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     # diagnostics: APEX_TRACEBACK_AFTER=<s> dumps every thread's stack to stderr after s
     # seconds (a hung multi-rank run names its blocking call instead of going silent)
@@ -282,8 +330,14 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--replay", type=int, default=100000, help="transitions per shard")
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"],
                     help="learner precision of the headline value (fp32 = the reference's)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the bf16-operand measurement (value_bf16), at N > 1 the other "
+                         "--batch-scope, the DP step's replica / graph-vs-eager self-checks, param_sha256")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last update computed (weights, RMSprop state, "
+                         "priorities, per-sample losses, loss, grad norm) as DIR/<name>.npy, at most 64 MB")
     ap.add_argument("--no-bf16-extra", action="store_true",
-                    help="skip the extra bf16-operand measurement (value_bf16)")
+                    help="--full: skip the extra bf16-operand measurement (value_bf16)")
     ap.add_argument("--learner", default="fused", choices=["fused", "graph"],
                     help="fused = hand-written HIP learner; graph = torch autograd on MIOpen / hipBLASLt "
                          "(the vendor-library baseline)")
@@ -300,7 +354,7 @@ def parser() -> argparse.ArgumentParser:
                     help="DP: global = one 512-sample update over all ranks (strong scaling, the reference's "
                          "update); per_rank = 512 rows per rank (weak scaling)")
     ap.add_argument("--no-scope-extra", action="store_true",
-                    help="N > 1: skip measuring the other --batch-scope (value_weak / value_strong)")
+                    help="--full at N > 1: skip measuring the other --batch-scope (value_weak / value_strong)")
     ap.add_argument("--dp-fc-exchange", default="auto", choices=["auto", "factors", "allreduce"],
                     help="DP exchange of the fc gradient (Runtime.dp_fc_exchange)")
     ap.add_argument("--allreduce-dtype", default="fp32", choices=["fp32", "bf16"],
@@ -395,24 +449,28 @@ def run(args) -> None:
     fallback = getattr(learner, "graph_fallback", None)
     shard = bool(getattr(learner, "_shard", False))
     if dp:
-        # after the timed region: did the replicas stay bit-identical, and does the
-        # captured update equal the eager one from the same state (both collectives)
         diag["dp_capture_probe"] = probe if probe is not None else "not run (%s)" % (
             "emulated world" if emu else "eager DP step" if not dp_graphs else "off" if args.capture_probe == "off"
             else "world 1")
+    if args.dump_outputs:
+        with wd.phase("dump outputs", to):
+            dump_outputs(learner, res["metrics"], args.dump_outputs, rank)
+    if dp and args.full:
+        # after the timed region: did the replicas stay bit-identical, and does the
+        # captured update equal the eager one from the same state (both collectives)
         with wd.phase("replica check", to):
             diag["replicas_identical"] = bool(learner.check_replicas()) if hasattr(learner, "check_replicas") \
                 else None
         with wd.phase("graph vs eager check", to):
             diag["graph_matches_eager"] = learner.graph_matches_eager() \
                 if hasattr(learner, "graph_matches_eager") else None
-    if hasattr(learner, "p32") and not emu:
+    if args.full and hasattr(learner, "p32") and not emu:
         if hasattr(learner, "materialize"):
             learner.materialize()      # (sharded update: every rank's fc rows; a collective)
         import hashlib
         diag["param_sha256"] = hashlib.sha256(learner.p32.detach().cpu().numpy().tobytes()).hexdigest()[:16]
     other = None
-    if world > 1 and not args.no_scope_extra:
+    if args.full and world > 1 and not args.no_scope_extra:
         # the other batch scope, fp32: both scalings from one run
         osc = "per_rank" if scope == "global" else "global"
         del learner
@@ -423,7 +481,7 @@ def run(args) -> None:
                      scope=osc, rows=learner_o.B)
         learner = learner_o
     extra = None
-    if not args.no_bf16_extra and args.dtype == "fp32":
+    if args.full and not args.no_bf16_extra and args.dtype == "fp32":
         del learner
         torch.cuda.empty_cache()
         cfg_b, learner_b = make_learner(args, "bf16", device, comm, rank, replay, scope, probe, "bf16")

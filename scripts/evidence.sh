@@ -3,7 +3,7 @@
 # PMC pass (LDS conflicts / MFMA busy; EV_NO_PMC=1 skips it), IMPALA, forced DP at world 1.  Each GPU step under its own limit, chained.
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd "$R"; mkdir -p gpurun_out/ev; export TMPDIR=/tmp
-b() { timeout -k 10 300 python -u bench.py "$@"; }
+b() { timeout -k 10 300 python -u bench.py --full "$@"; }   # --full: bf16 extra, DP self-checks, param_sha256
 b --gpus 1 --steps 20 --warmup 5 > gpurun_out/ev/bench_20_5.json 2> gpurun_out/ev/bench_20_5.err && \
 b --steps 200 --warmup 20 > gpurun_out/ev/bench_200.json 2> gpurun_out/ev/bench_200.err && \
 for W in 2 4 8; do

@@ -343,12 +343,35 @@ def _bench_json(stdout: str) -> dict:
     return out
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain bench.py run times the headline only (no bf16 extra, no self-checks) and
+    --dump-outputs writes the last update's arrays as float32 / float64 .npy files, at
+    most 64 MB in all."""
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "25", "--warmup", "5",
+                        "--replay", "20000", "--dump-outputs", str(d)],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = _bench_json(r.stdout)
+    assert out["steps"] == 25 and out["value"] > 0 and out["dtype"] == "fp32" and out["higher_is_better"] is True
+    assert abs(out["ms_per_step"] * out["value"] - 1e3) < 1.0      # value = steps/s of the timed steps
+    assert out["graph_captures_in_timed"] == 0
+    assert not {"value_bf16", "param_sha256", "replicas_identical", "graph_matches_eager"} & set(out)
+    files = {f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))}
+    assert {"params", "rms_v", "rms_m", "td_abs", "loss_per_sample", "loss", "grad_norm"} == set(files)
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64e6
+    assert files["td_abs"].shape == (512,) and files["params"].size == files["rms_v"].size > 3_000_000
+    assert np.abs(files["params"]).max() > 0 and files["rms_v"].max() > 0
+    assert abs(float(files["loss"][0]) - out["loss"]) < 1e-4
+
+
 def test_bench_contract_one_gpu():
-    """bench.py prints exactly one JSON line with the driver's keys; the headline is
-    the fp32 (reference-precision) learner, bf16 rides along as value_bf16, and no
+    """bench.py --full prints exactly one JSON line with the driver's keys; the headline
+    is the fp32 (reference-precision) learner, bf16 rides along as value_bf16, and no
     HIP graph is captured inside either timed window (warmup 5 < graph_steps 20:
     the 20-update graph is captured by prepare_graphs, before the clock starts)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "5",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "30", "--warmup", "5",
                         "--replay", "20000"], capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     out = _bench_json(r.stdout)
@@ -365,7 +388,7 @@ def test_bench_two_ranks_gloo_rehearsal():
     rank 0 alone prints the whole-job JSON line (RCCL itself refuses 2 ranks on 1 GPU)."""
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29541", os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "20", "--warmup", "5", "--replay", "20000",
+                        "--gpus", "2", "--full", "--steps", "20", "--warmup", "5", "--replay", "20000",
                         "--dist-backend", "gloo", "--no-bf16-extra"], capture_output=True, text=True, timeout=300,
                        cwd=ROOT)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
@@ -393,7 +416,7 @@ def test_bench_two_ranks_gloo_rehearsal():
 
 def _bench_force_dp(extra_env, port, tmp):
     env = dict(os.environ, **extra_env)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dp", "--capture-probe", "on",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-dp", "--capture-probe", "on",
                         "--steps", "20", "--warmup", "5", "--replay", "20000", "--no-bf16-extra", "--prep-warm", "0",
                         "--capture-probe-timeout", "120", "--capture-probe-log", str(tmp)],
                        capture_output=True, text=True, timeout=400, cwd=ROOT,
