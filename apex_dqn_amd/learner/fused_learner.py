@@ -474,11 +474,10 @@ class FusedNatureLearner(IsNormMixin, DataParallelStep):
                        **self._lo(dy_lo=self.dY3_lo, w_lo=sp and Pl["w3"], dx_lo=self.dY2_lo))
         ops.conv_wgrad(self.dY2, self.y1[:B], 4, 2, G["w2"], G["b2"], jobs=jobs,
                        **self._lo(dy_lo=self.dY2_lo, x_lo=sp and self.y1_lo[:B]))
-        ops.conv_dgrad(self.dY2, Pb["w2"], 2, self.y1[:B], self.dY1,
-                       **self._lo(dy_lo=self.dY2_lo, w_lo=sp and Pl["w2"], dx_lo=self.dY1_lo))
         jobs1 = []
-        ops.conv1_wgrad_ring(self.dY1, self.replay.frames, self.slots[:B], self.frames, rt.obs_scale, G["w1"],
-                             G["b1"], jobs=jobs1, **self._lo(dy_lo=self.dY1_lo))
+        ops.conv2_dgrad_conv1_wgrad(self.dY2, Pb["w2"], self.y1[:B], self.dY1, self.replay.frames, self.slots[:B],
+                                    self.frames, rt.obs_scale, G["w1"], G["b1"], jobs=jobs1,
+                                    **self._lo(dy2_lo=self.dY2_lo, w2_lo=sp and Pl["w2"], dy1_lo=self.dY1_lo))
         # two finalisations, as the branched step runs them (conv3 / conv2 + the head
         # region's norm partials, then conv1): the same norm-partial slots, so the two
         # schedules give bit-identical updates
@@ -594,11 +593,15 @@ class FusedNatureLearner(IsNormMixin, DataParallelStep):
         # slack at 512 rows: 2,674 / 2,668 vs 2,677 / 2,675 fp32, 4,271 / 4,312 vs 4,388 /
         # 4,489 bf16, 6,078 / 6,056 vs 6,478 / 6,437 at 74 rows -- the co-running kernels
         # stretch instead, profiles/r4_ab_wgrad3_main_rejected.txt)
-        self._conv32_branched(main, side, jobs)
-        fuse = self._fuse_norm
         jobs1 = []
-        ops.conv1_wgrad_ring(self.dY1, self.replay.frames, self.slots[:B], self.frames, rt.obs_scale, G["w1"],
-                             G["b1"], jobs=jobs1, **self._lo(dy_lo=self.dY1_lo))
+        # conv2's data gradient + conv1's weight gradient as one kernel where the backend has
+        # it; else the pair, conv1's weight gradient enqueued after the branch's conv2 wgrad
+        fuse21 = ops.conv21_fused_ok(self.dY2, self.slots[:B], **self._lo(dy2_lo=self.dY2_lo, w2_lo=sp and Pl["w2"]))
+        self._conv32_branched(main, side, jobs, jobs1=jobs1 if fuse21 else None)
+        if not fuse21:
+            ops.conv1_wgrad_ring(self.dY1, self.replay.frames, self.slots[:B], self.frames, rt.obs_scale, G["w1"],
+                                 G["b1"], jobs=jobs1, **self._lo(dy_lo=self.dY1_lo))
+        fuse = self._fuse_norm
         with torch.cuda.stream(side):
             # conv3 / conv2 split-K reductions (+ the head region's norm partials) on the
             # branch, beside conv1's weight gradient
@@ -619,13 +622,15 @@ class FusedNatureLearner(IsNormMixin, DataParallelStep):
         self.ops.conv_wgrad(self.dY3, self.y2[:B], 3, 1, self.G["w3"], self.G["b3"], jobs=jobs,
                             **self._lo(dy_lo=self.dY3_lo, x_lo=sp and self.y2_lo[:B]))
 
-    def _conv32_branched(self, main, side, jobs, wgrad2: bool = True) -> None:
+    def _conv32_branched(self, main, side, jobs, wgrad2: bool = True, jobs1=None) -> None:
         """Branched backward, middle part: conv3 / conv2 data gradients on the main stream,
         conv3 and (``wgrad2``) conv2 weight gradients on the branch, each after a wait for
         the data gradient it reads.  (One wait before both weight gradients -- one graph
         edge fewer -- measured 5,937 / 6,062 vs 6,240 / 6,437 steps/s at 74 rows and
-        neutral at 512, profiles/r4_ab_bwd_one_wait_rejected.txt.)"""
-        B, ops, G, Pb, Pl, sp = self.B, self.ops, self.G, self.Pb, self.Pl, self.split
+        neutral at 512, profiles/r4_ab_bwd_one_wait_rejected.txt.)  ``jobs1``: conv1's
+        weight gradient follows conv2's data gradient here, as one call the backend may
+        fuse (ops/fused_ops.py conv2_dgrad_conv1_wgrad); its reduction joins that list."""
+        B, ops, G, Pb, Pl, sp, rt = self.B, self.ops, self.G, self.Pb, self.Pl, self.split, self.rt
         ev3 = torch.cuda.Event()
         ev3.record(main)
         ops.conv_dgrad(self.dY3, Pb["w3"], 1, self.y2[:B], self.dY2,
@@ -635,8 +640,13 @@ class FusedNatureLearner(IsNormMixin, DataParallelStep):
             self._conv3_wgrad(jobs)
         ev2 = torch.cuda.Event()
         ev2.record(main)
-        ops.conv_dgrad(self.dY2, Pb["w2"], 2, self.y1[:B], self.dY1,
-                       **self._lo(dy_lo=self.dY2_lo, w_lo=sp and Pl["w2"], dx_lo=self.dY1_lo))
+        if jobs1 is None:
+            ops.conv_dgrad(self.dY2, Pb["w2"], 2, self.y1[:B], self.dY1,
+                           **self._lo(dy_lo=self.dY2_lo, w_lo=sp and Pl["w2"], dx_lo=self.dY1_lo))
+        else:
+            ops.conv2_dgrad_conv1_wgrad(self.dY2, Pb["w2"], self.y1[:B], self.dY1, self.replay.frames,
+                                        self.slots[:B], self.frames, rt.obs_scale, G["w1"], G["b1"], jobs=jobs1,
+                                        **self._lo(dy2_lo=self.dY2_lo, w2_lo=sp and Pl["w2"], dy1_lo=self.dY1_lo))
         side.wait_event(ev2)
         if wgrad2:
             with torch.cuda.stream(side):

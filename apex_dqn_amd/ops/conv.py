@@ -33,13 +33,17 @@ class Workspace:
     # during the conv backward.  SW.work_queue = "on" / "off" forces them on / off.
     work_queue = False
 
+    def wq_on(self, overlapped: bool = True) -> bool:
+        """Whether a launch gets a work queue (see :meth:`wq`)."""
+        mode = SW.work_queue
+        return mode == "on" or (mode != "off" and self.work_queue and overlapped)
+
     def wq(self, key, device, overlapped: bool = True) -> int:
         """Counter pair of a work queue, or 0 (null: static order) when queues are off.
         ``overlapped``: the launch can run beside the step's collectives (the conv
         backward); the forward never does (it follows the optimizer's join), so it keeps
         the static order unless SW.work_queue = "on"."""
-        mode = SW.work_queue
-        on = mode == "on" or (mode != "off" and self.work_queue and overlapped)
+        on = self.wq_on(overlapped)
         # one never-reset 64-bit counter per (call site, items, grid): a launch consumes
         # exactly items + grid values (csrc/mfma_common.h wq_fetch)
         return self.get_zeroed(key, 1, device, dtype=torch.int64).data_ptr() if on else 0
@@ -590,6 +594,54 @@ def conv1_wgrad_ring(lib, ws: Workspace, dy: torch.Tensor, ring: torch.Tensor, s
     d.wq = ws.wq(("c1w_wq", N, int(G)), dy.device)
     st = _lib.stream_ptr()
     _lib.check(lib.apex_conv1_wgrad_img(d, G, st), "conv1_wgrad_img")
+    if jobs is not None:
+        jobs.append(dict(slab=slab, bslab=bslab, out=dw_out, bout=db_out, n=64 * K, nsplit=G, nb=64, s2dC=C, Kc=K,
+                         scale=float(scale)))
+        return
+    _lib.check(lib.apex_slab_reduce(slab.data_ptr(), G, 64 * K, float(scale), dw_out.data_ptr(), bslab.data_ptr(),
+                                    64, db_out.data_ptr(), C, K, st), "slab_reduce")
+
+
+def conv2_dgrad_conv1_wgrad_fused(lib, ws: Workspace, dy: torch.Tensor, dy_lo: torch.Tensor, w2: torch.Tensor,
+                                  w_lo: torch.Tensor, mask: torch.Tensor, ring: torch.Tensor, slots: torch.Tensor,
+                                  scale: float, dw_out: torch.Tensor, db_out: torch.Tensor, grid: int = 0,
+                                  jobs: Optional[list] = None, packed: bool = False,
+                                  dx: Optional[torch.Tensor] = None, dx_lo: Optional[torch.Tensor] = None,
+                                  wq: int = 0) -> None:
+    """conv2's masked data gradient and conv1's weight / bias gradient in one persistent
+    per-image kernel (csrc/conv21_bwd_fused.hip; split mode, 4 frames, static image
+    order): dY1 lives in LDS only.  The same workspace buffers, partial-slab layout and
+    ``jobs`` entry as :func:`conv1_wgrad_ring`; ``dx`` / ``dx_lo``: also store the masked
+    dY1 planes (tests and diagnostics -- bit-identical to :func:`conv2_dgrad_img`)."""
+    from .conv_sigs import Conv21BwdDesc
+    N = dy.shape[0]
+    C = slots.shape[1]
+    assert tuple(dy.shape) == (N, 9, 9, 64) and tuple(mask.shape) == (N, 20, 20, 64)
+    assert tuple(w2.shape) == (64, 4, 4, 64) and slots.dtype == torch.int32 and slots.shape[0] == N
+    assert dy.is_contiguous() and mask.is_contiguous() and w2.is_contiguous() and slots.is_contiguous()
+    for t in (dy_lo, w_lo):
+        assert t is not None and t.is_contiguous() and t.dtype == torch.bfloat16
+    for t in (dx, dx_lo):
+        assert t is None or (tuple(t.shape) == (N, 20, 20, 64) and t.is_contiguous() and t.dtype == torch.bfloat16)
+    G = grid if grid > 0 else min(N, 256)
+    K = 64 * C
+    slab = ws.get(("wg1img", C, G), G * 64 * K, dy.device)
+    bslab = ws.get(("wg1imgb", G), G * 64, dy.device)
+    zero = ws.get(("zero16",), 64, ring.device, torch.uint8)
+    if not getattr(ws, "_zeroed", False):
+        zero.zero_()
+        ws._zeroed = True
+    d = Conv21BwdDesc()
+    d.dy, d.dy_lo, d.w, d.w_lo, d.mask = dy.data_ptr(), dy_lo.data_ptr(), w2.data_ptr(), w_lo.data_ptr(), mask.data_ptr()
+    d.wfrag = c2d_wfrag_buffer(ws, dy.device).data_ptr()
+    d.wfrag_ready = int(packed)
+    d.ring, d.slots, d.zero16 = ring.data_ptr(), slots.data_ptr(), zero.data_ptr()
+    d.slab, d.bias_slab = slab.data_ptr(), bslab.data_ptr()
+    d.dx, d.dx_lo = _lib.ptr(dx), _lib.ptr(dx_lo)
+    d.wq = wq or None
+    d.N, d.C = N, C
+    st = _lib.stream_ptr()
+    _lib.check(lib.apex_conv21_bwd_fused(d, G, st), "conv21_bwd_fused")
     if jobs is not None:
         jobs.append(dict(slab=slab, bslab=bslab, out=dw_out, bout=db_out, n=64 * K, nsplit=G, nb=64, s2dC=C, Kc=K,
                          scale=float(scale)))

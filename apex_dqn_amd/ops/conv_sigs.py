@@ -33,6 +33,14 @@ class Conv2DgradImgDesc(ctypes.Structure):
                 ("dx_lo", c_p), ("wfrag", c_p), ("wfrag_ready", c_i), ("wq", c_p), ("cls_split", c_i)]
 
 
+class Conv21BwdDesc(ctypes.Structure):
+    """conv2 data gradient fused with conv1 weight gradient (mirrors ``Conv21BwdDesc`` in
+    csrc/conv21_bwd_fused.hip)."""
+    _fields_ = [("dy", c_p), ("dy_lo", c_p), ("w", c_p), ("w_lo", c_p), ("mask", c_p), ("wfrag", c_p),
+                ("wfrag_ready", c_i), ("ring", c_p), ("slots", c_p), ("zero16", c_p), ("slab", c_p),
+                ("bias_slab", c_p), ("dx", c_p), ("dx_lo", c_p), ("wq", c_p), ("N", c_i), ("C", c_i)]
+
+
 class C2dPackJob(ctypes.Structure):
     """conv2 weight-fragment pack riding on the fc epilogue launch (``C2dPackJob``)."""
     _fields_ = [("w", c_p), ("w_lo", c_p), ("out", c_p)]
@@ -51,6 +59,7 @@ def declare(lib: ctypes.CDLL) -> None:
         "apex_conv12_pack": ([Conv12Desc, c_p], c_i),
         "apex_conv2_dgrad_img": ([Conv2DgradImgDesc, c_i, c_p], c_i),
         "apex_conv3_dgrad_img": ([Conv3DgradImgDesc, c_i, c_p], c_i),
+        "apex_conv21_bwd_fused": ([Conv21BwdDesc, c_i, c_p], c_i),
         "apex_conv_fwd": ([ConvDesc, c_p], c_i),
         "apex_fc_gemm128": ([ConvDesc, c_p, c_i64, c_i, c_i, c_i, C2dPackJob, c_p], c_i),
         "apex_conv_wgrad": ([WgradDesc, c_p, c_p, c_i, c_f, c_p], c_i),

@@ -284,6 +284,18 @@ class TorchBackend:
     def conv1_wgrad_ring(self, dy, ring, slots, frames_buf, scale, dw_out, db_out, jobs=None, dy_lo=None):
         self.conv1_wgrad(dy, frames_buf[:slots.shape[0]], scale, dw_out, db_out, dy_lo=dy_lo)
 
+    def conv21_fused_ok(self, dy2, slots, dy2_lo=None, w2_lo=None) -> bool:
+        """Whether :meth:`conv2_dgrad_conv1_wgrad` runs as one fused kernel for these arguments."""
+        return False
+
+    def conv2_dgrad_conv1_wgrad(self, dy2, w2, y1, dy1, ring, slots, frames_buf, scale, dw_out, db_out, jobs=None,
+                                dy2_lo=None, w2_lo=None, dy1_lo=None):
+        """conv2's data gradient (dY2 -> dY1, masked by y1) followed by conv1's weight gradient
+        on dY1 -- the arguments of :meth:`conv_dgrad` and :meth:`conv1_wgrad_ring`.  Here the
+        two calls; the HIP backend fuses them where it can (then ``dy1`` is not written)."""
+        self.conv_dgrad(dy2, w2, 2, y1, dy1, dy_lo=dy2_lo, w_lo=w2_lo, dx_lo=dy1_lo)
+        self.conv1_wgrad_ring(dy1, ring, slots, frames_buf, scale, dw_out, db_out, jobs=jobs, dy_lo=dy1_lo)
+
     # ----------------------------------------------------------- optimizer
     def optimizer(self, p32, g32, v, m, pbf, lr, alpha, eps, clip, centered, partials, norm_out, norm_total=None,
                   sample=None, pb_lo=None, wnorm=None, frag_out=None, segs=None, norm_prefix=None):
@@ -518,6 +530,25 @@ class HipBackend(TorchBackend):
         if not self.native_conv:
             return super().conv1_wgrad_ring(dy, ring, slots, frames_buf, scale, dw_out, db_out, dy_lo=dy_lo)
         C.conv1_wgrad_ring(self.lib, self.ws, dy, ring, slots, scale, dw_out, db_out, jobs=jobs, dy_lo=dy_lo)
+
+    def conv21_fused_ok(self, dy2, slots, dy2_lo=None, w2_lo=None) -> bool:
+        # split mode, 4 frames, static image order (no work queue for this launch), and a batch
+        # above the (image, class) data gradient's range, which spreads few images over the chip
+        return bool(self.native_conv and SW.conv21_bwd_fused and SW.conv2_dgrad_img and dy2_lo is not None
+                    and w2_lo is not None and slots.shape[1] == 4 and dy2.shape[0] > SW.conv2_dgrad_cls_max
+                    and hasattr(self.lib, "apex_conv21_bwd_fused") and not self.ws.wq_on())
+
+    def conv2_dgrad_conv1_wgrad(self, dy2, w2, y1, dy1, ring, slots, frames_buf, scale, dw_out, db_out, jobs=None,
+                                dy2_lo=None, w2_lo=None, dy1_lo=None):
+        # one kernel, dY1 in LDS only (csrc/conv21_bwd_fused.hip), where it applies; else the pair
+        if self.conv21_fused_ok(dy2, slots, dy2_lo, w2_lo):
+            packed = getattr(self, "_c2d_packed", None) == (w2.data_ptr(), _lib.ptr(w2_lo))
+            self._c2d_packed = None
+            C.conv2_dgrad_conv1_wgrad_fused(self.lib, self.ws, dy2, dy2_lo, w2, w2_lo, y1, ring, slots, scale,
+                                            dw_out, db_out, jobs=jobs, packed=packed)
+            return
+        super().conv2_dgrad_conv1_wgrad(dy2, w2, y1, dy1, ring, slots, frames_buf, scale, dw_out, db_out, jobs=jobs,
+                                        dy2_lo=dy2_lo, w2_lo=w2_lo, dy1_lo=dy1_lo)
 
     @staticmethod
     def _hp(P):

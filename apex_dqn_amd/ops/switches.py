@@ -46,6 +46,13 @@ class Switches:
     # split conv2 data gradient: one workgroup per (image, stride-parity class) up to this
     # many images (0: never), per image above it
     conv2_dgrad_cls_max: int = 256
+    # conv2's data gradient and conv1's weight gradient in one per-image kernel, dY1 in LDS
+    # only (csrc/conv21_bwd_fused.hip): split mode, 4 frames, static order, batches above
+    # conv2_dgrad_cls_max; on or off the step's results are the same bits.  Isolated at 512
+    # images 44.9 us vs 38.2 + 25.2 for the pair; the 512-row fp32 step, 5 interleaved runs
+    # each: 2,838-2,862 (median 2,843) vs 2,696-2,716 (2,699) updates/s at 200 / 20 steps,
+    # 2,819-2,836 (2,826) vs 2,669-2,715 (2,683) at 20 / 5 (profiles/pr2_ab_conv21_bwd_fused.txt)
+    conv21_bwd_fused: bool = True
     # the optimizer + sample launch stores the fused forward's online weight fragments
     # (+0.5-1 %, profiles/r3_ab_optimizer_frag_stores_*.txt)
     opt_frags: bool = True

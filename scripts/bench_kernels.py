@@ -83,6 +83,20 @@ def main():
         ops[f"conv1_wgrad@g{gr}"] = (lambda gr=gr: C.conv1_wgrad_ring(lib, ws, dY1, ring, slots[:B], 1 / 255.,
                                                                      gw[:64 * 256].view(64, 4, 8, 8), gb[:64],
                                                                      grid=gr), F(B * 400 * 64 * 256))
+    # fp32-class (split) conv2 dgrad -> conv1 wgrad: the pair against the fused kernel, on the
+    # same hi / lo planes, weights pre-packed (as in the step) and the slab reduce left out
+    lo = lambda t: (t.float() * 2.0 ** -9).to(bf)  # noqa: E731
+    dY2l, dY1l, w2l = lo(dY2), lo(dY1), lo(w2)
+    C.conv2_dgrad_img(lib, dY2, w2, y1[:B], dY1, dy_lo=dY2l, w_lo=w2l, out_lo=dY1l, ws=ws)   # packs the fragments
+    gw1 = gw[:64 * 256].view(64, 4, 8, 8)
+    ops["conv2_dgrad@split"] = (lambda: C.conv2_dgrad_img(lib, dY2, w2, y1[:B], dY1, dy_lo=dY2l, w_lo=w2l, out_lo=dY1l,
+                                                          ws=ws, packed=True), F(3 * B * 400 * 64 * 256))
+    ops["conv1_wgrad@split"] = (lambda: C.conv1_wgrad_ring(lib, ws, dY1, ring, slots[:B], 1 / 255., gw1, gb[:64],
+                                                           jobs=[], dy_lo=dY1l), F(2 * B * 400 * 64 * 256))
+    if hasattr(lib, "apex_conv21_bwd_fused") and B > 0:
+        ops["conv21_bwd_fused@split"] = (lambda: C.conv2_dgrad_conv1_wgrad_fused(
+            lib, ws, dY2, dY2l, w2, w2l, y1[:B], ring, slots[:B], 1 / 255., gw1, gb[:64], jobs=[], packed=True),
+            F(5 * B * 400 * 64 * 256))
     # launch-shape sweep of the forward-family GEMMs (tile 1: BM=128, 2: BM=64; order 1: M fastest, 2: N fastest)
     for tile in (1, 2):
         for order in (1, 2):
