@@ -183,8 +183,11 @@ class GpuActorGroup:
 
     # --------------------------------------------------------------- acting
     def _ingest(self, frames: np.ndarray, reset_mask: np.ndarray) -> np.ndarray:
+        # an env in device-preprocessing mode hands over raw frame pairs: the replay's kernel
+        # turns them into ring frames (Runtime.atari_preprocess)
+        raw = getattr(self.env, "raw_frames", False)
         with self._on_stream():
-            seqs = self.replay.append_frames(frames)
+            seqs = self.replay.append_raw_frames(frames) if raw else self.replay.append_frames(frames)
         if self.payload is None:
             cur = np.repeat(seqs[:, None], self.C, axis=1)
         else:
@@ -297,7 +300,10 @@ class GpuActorGroup:
         # frame-producing envs write straight into the replay's pinned staging buffer (the
         # frame append then starts its H2D copy from it: no staging copy on the host thread)
         stage = getattr(self.replay, "stage_frames", None) if getattr(self.env, "frame_out", False) else None
-        buf = stage(self.E) if stage is not None else None
+        if stage is None:
+            buf = None
+        else:
+            buf = stage(self.E, raw=True) if getattr(self.env, "raw_frames", False) else stage(self.E)
         frames, rew, done, info = self.env.step(actions, out=buf) if buf is not None else self.env.step(actions)
         prev = self.payload
         self.payload = self._ingest(frames, done)
@@ -479,10 +485,13 @@ class ImpalaActorGroup(GpuActorGroup):
 
 
 def make_gpu_actor_group(cfg, learner, replay, num_envs: int, rank: int = 0, world: int = 1,
-                         seed: int = 0, pipeline: int = 1):
+                         seed: int = 0, pipeline: int = 1, preprocess: Optional[str] = None):
     """The rank's actor group; ``pipeline`` K > 1 (NatureCNN learners on a GPU): K groups
-    of num_envs / K envs stepped in turn (PipelinedActorGroups)."""
+    of num_envs / K envs stepped in turn (PipelinedActorGroups).  ``preprocess``
+    (default ``Runtime.atari_preprocess``): "device" = the envs hand over raw Atari frame
+    pairs and the replay's kernel preprocesses them (emulator-backed backends)."""
     from ..envs.vector_envs import make_vec_env
+    pre = preprocess if preprocess is not None else getattr(cfg.Runtime, "atari_preprocess", "host")
     total = max(cfg.Actor.num_actors, num_envs * world)
     K = int(pipeline)
     if K > 1 and num_envs % K == 0 and num_envs // K >= 1 and getattr(learner, "kind", "") not in ("graph", "impala"):
@@ -491,14 +500,14 @@ def make_gpu_actor_group(cfg, learner, replay, num_envs: int, rank: int = 0, wor
         groups = []
         for k in range(K):
             env = make_vec_env(cfg.env_backend, cfg.env_conf.name, h, cfg.env_conf.action_dim,
-                               seed=seed + 1000 * rank + 100003 * k)
+                               seed=seed + 1000 * rank + 100003 * k, preprocess=pre)
             g = GpuActorGroup(cfg, learner, replay, env, h, global_offset=rank * num_envs + k * h,
                               total_actors=total, seed=seed + rank, rank=rank, world=world)
             g.eps = torch.tensor(eps_all[k * h:(k + 1) * h], dtype=torch.float32, device=learner.device)
             groups.append(g)
         return PipelinedActorGroups(groups)
     env = make_vec_env(cfg.env_backend, cfg.env_conf.name, num_envs, cfg.env_conf.action_dim,
-                       seed=seed + 1000 * rank)
+                       seed=seed + 1000 * rank, preprocess=pre)
     kind = getattr(learner, "kind", "")
     cls = {"graph": GraphActorGroup, "impala": ImpalaActorGroup}.get(kind, GpuActorGroup)
     return cls(cfg, learner, replay, env, num_envs, global_offset=rank * num_envs,

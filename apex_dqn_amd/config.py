@@ -150,6 +150,11 @@ class RuntimeConf:
     actor_pipeline: int = 2         # async GPU actors: the rank's envs as this many groups stepped in
                                     # turn, so one group's host env step overlaps another's inference
                                     # (actors/gpu_actor.py PipelinedActorGroups; 1 = one group)
+    atari_preprocess: str = "host"  # emulator-backed envs (ale / fake_ale / fake_ale_target) on the GPU loop:
+                                    # "host" (fp32 numpy max / gray / area resize in the actor's host thread,
+                                    # the 84x84 frame goes H2D) | "device" (the two raw 210x160x3 frames go H2D
+                                    # and one kernel, csrc/atari_frames.hip, preprocesses them into the frame
+                                    # ring in exact integer arithmetic; 84x84 states only)
     learner_stream_priority: bool = True   # async GPU actors: learner on a high-priority HIP stream
                                     # (runtime/actor_thread.py), concurrent with the learner
 
@@ -234,6 +239,14 @@ class ApexConfig:
             raise ValueError("Runtime.dp_shard_update must be 'auto', 'on' or 'off'")
         if self.Runtime.dp_fc_exchange not in ("auto", "factors", "allreduce"):
             raise ValueError("Runtime.dp_fc_exchange must be 'auto', 'factors' or 'allreduce'")
+        if self.Runtime.atari_preprocess not in ("host", "device"):
+            raise ValueError("Runtime.atari_preprocess must be 'host' or 'device'")
+        if self.Runtime.atari_preprocess == "device":
+            if self.env_backend not in ("ale", "fake_ale", "fake_ale_target"):
+                raise ValueError(f"Runtime.atari_preprocess='device' needs an env backend with raw Atari frames "
+                                 f"(ale, fake_ale, fake_ale_target), got {self.env_backend!r}")
+            if len(ss) != 3 or tuple(ss[1:]) != (84, 84):
+                raise ValueError(f"Runtime.atari_preprocess='device' produces 84x84 frames, got state_shape {ss}")
         if self.Runtime.loss not in ("huber", "mse"):
             raise ValueError("Runtime.loss must be 'huber' or 'mse'")
         net = self.network

@@ -10,7 +10,9 @@ image (nor on the offline GPU box), so the engine ships:
   learnable dynamics, for the GPU configs on synthetic frames;
 * ``AtariPreprocess`` + ``ALEVec`` -- correct Atari preprocessing (gray,
   area-resize to 84x84, frame-skip with max-pool, no-op starts, reward clip)
-  around ``ale_py`` when it is importable.
+  around ``ale_py`` when it is importable;
+* ``AtariPreprocessExact`` -- the same preprocessing in exact integer arithmetic: the host
+  mirror of the GPU kernel that takes it over in the wrappers' device mode.
 
 All envs auto-reset: ``step`` returns the first observation of the next
 episode for envs that finished.
@@ -182,6 +184,63 @@ class AtariPreprocess:
         return np.clip(np.rint(out), 0, 255).astype(np.uint8)
 
 
+RAW_FRAME_SHAPE = (2, 210, 160, 3)   # the last two emulator frames of an env step, untouched
+
+
+class AtariPreprocessExact:
+    """The device preprocessing path's arithmetic on the host (mirror of csrc/atari_frames.hip,
+    and its oracle): max over the frame pair, gray and area resize 210x160 -> 84x84 in exact
+    integers, so the result does not depend on a summation order.
+
+    * gray ``g = 299 R + 587 G + 114 B``;
+    * row weights ``5 * _area_matrix(84, 210)`` (integers 2, 2, 1 / 1, 2, 2) and column weights
+      ``40 * _area_matrix(84, 160)`` (overlap lengths in 1/21 pixel, 0..21), both exact;
+    * ``acc = sum w_r w_c g`` (<= 51 000 000), output ``acc / 200000`` rounded half to even.
+
+    The matmuls run in float64, which is exact at these magnitudes (every partial sum is an
+    integer below 2**53); the rounding is integer."""
+
+    DENOM = 1000 * 5 * 40
+
+    def __init__(self):
+        ry, rx = _area_matrix(84, 210) * 5.0, _area_matrix(84, 160) * 40.0
+        self.ry, self.rx = np.rint(ry), np.rint(rx)
+        if np.abs(self.ry - ry).max() > 1e-9 or np.abs(self.rx - rx).max() > 1e-9:  # pragma: no cover
+            raise AssertionError("area weights are not integers")
+        self.rxT = np.ascontiguousarray(self.rx.T)
+        self.w = np.array([299.0, 587.0, 114.0])
+
+    def __call__(self, raw: np.ndarray, pooled: Optional[bool] = None) -> np.ndarray:
+        """raw: (..., 2, 210, 160, 3) uint8 frame pairs, or already pooled (..., 210, 160, 3)
+        -> (..., 84, 84) uint8.  ``pooled`` None: an axis of length 2 before the frame axes is
+        the pair (pass ``pooled=True`` for a batch of exactly two pooled frames)."""
+        raw = np.asarray(raw)
+        if raw.dtype != np.uint8 or raw.shape[-3:] != RAW_FRAME_SHAPE[1:]:
+            raise ValueError(f"expected uint8 (..., [2,] 210, 160, 3) frames, got {raw.dtype} {raw.shape}")
+        if pooled is None:
+            pooled = not (raw.ndim >= 4 and raw.shape[-4] == 2)
+        if not pooled:
+            if raw.ndim < 4 or raw.shape[-4] != 2:
+                raise ValueError(f"expected frame pairs (..., 2, 210, 160, 3), got {raw.shape}")
+            raw = np.maximum(raw[..., 0, :, :, :], raw[..., 1, :, :, :])
+        gray = raw.astype(np.float64) @ self.w
+        acc = np.matmul(np.matmul(self.ry, gray), self.rxT).astype(np.int64)
+        q, r = np.divmod(acc, self.DENOM)
+        q += (2 * r > self.DENOM) | ((2 * r == self.DENOM) & ((q & 1) == 1))
+        return q.astype(np.uint8)
+
+
+_EXACT: Optional[AtariPreprocessExact] = None
+
+
+def atari_preprocess_exact(raw: np.ndarray, pooled: Optional[bool] = None) -> np.ndarray:
+    """:class:`AtariPreprocessExact` on a shared instance."""
+    global _EXACT
+    if _EXACT is None:
+        _EXACT = AtariPreprocessExact()
+    return _EXACT(raw, pooled)
+
+
 class FakeALE:
     """Deterministic stand-in for one ALE emulator (``ale_py.ALEInterface``
     subset: act / getScreenRGB / game_over / reset_game / lives /
@@ -250,15 +309,31 @@ class AtariWrapperVec:
     * gray + area resize to 84x84 uint8 (``AtariPreprocess``).
 
     ``info`` carries the UNCLIPPED game-episode return / length when a game
-    ends (``real_done``), NaN / -1 otherwise."""
+    ends (``real_done``), NaN / -1 otherwise.
+
+    ``preprocess="device"``: the last item moves to the GPU.  ``reset`` / ``step`` then
+    return (or fill ``out`` with) ``(E,) + raw_shape`` uint8: the last two emulator frames
+    of the skip, untouched -- the same frame twice when only one exists (reset, first frame
+    after a game over, early game over inside the skip).  Everything else is identical to
+    the host mode; ``obs_shape`` stays the preprocessed (84, 84)."""
 
     obs_dtype = np.uint8
     frame_based = True
     obs_shape = (84, 84)
     frame_out = True          # step(actions, out=...) writes the frames into ``out``
 
+    raw_frames = False        # device mode: reset / step hand over raw frame pairs (raw_shape)
+
     def __init__(self, emulators, frame_skip: int = 4, noop_max: int = 30, clip_rewards: bool = True,
-                 episodic_life: bool = True, fire_reset: bool = False, seed: int = 0):
+                 episodic_life: bool = True, fire_reset: bool = False, seed: int = 0,
+                 preprocess: str = "host"):
+        if preprocess not in ("host", "device"):
+            raise ValueError(f"preprocess must be 'host' or 'device', got {preprocess!r}")
+        # "device": the max / gray / resize run on the GPU (csrc/atari_frames.hip, through
+        # GpuReplayShard.append_raw_frames); the wrapper only copies the two raw frames out
+        self.raw_frames = preprocess == "device"
+        self.raw_shape = RAW_FRAME_SHAPE if self.raw_frames else None
+        self._out_shape = RAW_FRAME_SHAPE if self.raw_frames else (84, 84)
         self.envs = list(emulators)
         self.E = len(self.envs)
         self.actions = list(self.envs[0].getMinimalActionSet())
@@ -281,7 +356,8 @@ class AtariWrapperVec:
         if self.fire_reset and len(self.actions) > 1:
             emu.act(self.actions[1])
         self.lives[i] = emu.lives()
-        return self.pre(emu.getScreenRGB())
+        screen = emu.getScreenRGB()
+        return np.stack([screen, screen]) if self.raw_frames else self.pre(screen)
 
     def reset(self) -> np.ndarray:
         self.ep_ret[:] = 0
@@ -289,7 +365,8 @@ class AtariWrapperVec:
         return np.stack([self._reset_one(i) for i in range(self.E)])
 
     def step(self, actions, out: Optional[np.ndarray] = None):
-        obs = np.zeros((self.E, 84, 84), np.uint8) if out is None else out    # every row is written below
+        # every row is written below
+        obs = np.zeros((self.E,) + self._out_shape, np.uint8) if out is None else out
         rew = np.zeros(self.E, np.float32)
         done = np.zeros(self.E, bool)
         real_done = np.zeros(self.E, bool)
@@ -306,7 +383,8 @@ class AtariWrapperVec:
                     break
             if not last2:
                 last2.append(emu.getScreenRGB())
-            frame = np.maximum(last2[0], last2[-1])
+            if not self.raw_frames:
+                frame = np.maximum(last2[0], last2[-1])
             self.ep_ret[i] += r
             self.ep_len[i] += 1
             rew[i] = np.sign(r) if self.clip else r
@@ -320,7 +398,10 @@ class AtariWrapperVec:
             if self.episodic_life and lives < self.lives[i]:
                 done[i] = True          # a lost life ends the transition chain, not the game
             self.lives[i] = lives
-            obs[i] = self.pre(frame)
+            if self.raw_frames:
+                obs[i, 0], obs[i, 1] = last2[0], last2[-1]
+            else:
+                obs[i] = self.pre(frame)
         return obs, rew, done, {"episode_return": ep_r, "episode_length": ep_l, "real_done": real_done}
 
 
@@ -342,8 +423,13 @@ class ALEVec(AtariWrapperVec):  # pragma: no cover - ale_py is not available in 
 
 
 def make_vec_env(backend: str, name: str, num_envs: int, action_dim: int,
-                 seed: int = 0, frame_hw: Optional[Tuple[int, int]] = None):
-    """Factory replacing ``make_local_env`` (``env.py:3-4``)."""
+                 seed: int = 0, frame_hw: Optional[Tuple[int, int]] = None, preprocess: str = "host"):
+    """Factory replacing ``make_local_env`` (``env.py:3-4``).  ``preprocess`` "device": the
+    emulator-backed envs hand over raw frame pairs (``AtariWrapperVec``)."""
+    if preprocess not in ("host", "device"):
+        raise ValueError(f"preprocess must be 'host' or 'device', got {preprocess!r}")
+    if preprocess == "device" and backend in ("cartpole", "synthetic"):
+        raise ValueError(f"env backend {backend!r} has no raw Atari frames to preprocess on the device")
     if backend == "cartpole":
         from ..runtime import native
         return native.NativeCartPoleVec(num_envs, seed=seed) if native.available() else CartPoleVec(num_envs, seed)
@@ -352,7 +438,7 @@ def make_vec_env(backend: str, name: str, num_envs: int, action_dim: int,
                                  frame_hw=frame_hw or (84, 84))
     if backend in ("fake_ale", "fake_ale_target"):
         return AtariWrapperVec([FakeALE(seed=seed + i, n_actions=action_dim, target=backend == "fake_ale_target")
-                                for i in range(num_envs)], seed=seed)
+                                for i in range(num_envs)], seed=seed, preprocess=preprocess)
     if backend == "ale":  # pragma: no cover
-        return ALEVec(name, num_envs, seed=seed)
+        return ALEVec(name, num_envs, seed=seed, preprocess=preprocess)
     raise ValueError(f"unknown env backend {backend!r}")

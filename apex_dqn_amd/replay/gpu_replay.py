@@ -41,6 +41,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
+from ..envs.vector_envs import RAW_FRAME_SHAPE, atari_preprocess_exact
 from ..ops import _lib
 
 
@@ -273,6 +274,15 @@ class GpuReplayShard:
         with self.lock:
             return self._append_frames_locked(frames)
 
+    def append_raw_frames(self, raw) -> np.ndarray:
+        """Store the frames of raw Atari frame pairs (n, 2, 210, 160, 3) uint8 (an
+        ``AtariWrapperVec`` in device mode); returns their sequence numbers.  On the HIP path
+        the pairs go H2D as they are and one kernel (csrc/atari_frames.hip) does the max, gray,
+        area resize, rounding, s2d permutation and ring scatter; otherwise its host mirror
+        (``atari_preprocess_exact``) runs first and the frames take the :meth:`append_frames` path."""
+        with self.lock:
+            return self._append_raw_frames_locked(raw)
+
     def insert(self, batch: Dict[str, np.ndarray]) -> np.ndarray:
         """Insert n-step transitions whose S_t/S_tpn payloads are frame seqs (K, C)."""
         with self.lock:
@@ -310,6 +320,30 @@ class GpuReplayShard:
         self.frame_head += n
         return seqs
 
+    def _append_raw_frames_locked(self, raw) -> np.ndarray:
+        if self.frame_shape != (84, 84):
+            raise ValueError(f"raw Atari frames preprocess to 84x84, this ring holds {self.frame_shape} frames")
+        shape = tuple(raw.shape)
+        u8 = torch.uint8 if isinstance(raw, torch.Tensor) else np.uint8
+        if len(shape) != 5 or shape[1:] != RAW_FRAME_SHAPE or raw.dtype != u8:
+            raise ValueError(f"expected uint8 raw frame pairs (n,) + {RAW_FRAME_SHAPE}, got {raw.dtype} {shape}")
+        if not self.use_hip:
+            host = raw.cpu().numpy() if isinstance(raw, torch.Tensor) else raw
+            return self._append_frames_locked(atari_preprocess_exact(host, pooled=False))
+        if isinstance(raw, np.ndarray):
+            raw = self._pinned(raw)            # async H2D from a pinned staging buffer
+        n = raw.shape[0]
+        seqs = self.frame_head + np.arange(n, dtype=np.int64)
+        skip = max(0, n - self.F)  # only the newest F frames survive a wrap
+        src = raw[skip:].to(self.device, non_blocking=True).contiguous()
+        if self._pin_ev is not None and raw.is_pinned():
+            self._pin_ev[self._pin_k].record()
+        start = (self.frame_head + skip) % self.F
+        _lib.check(self.lib.apex_atari_frames(src.data_ptr(), self.frames.data_ptr(), src.shape[0], self.F,
+                                              start, self._stream()), "atari_frames")
+        self.frame_head += n
+        return seqs
+
     def _acquire_pin(self, shape) -> torch.Tensor:
         """The next of two pinned staging buffers of ``shape`` (the copy of its previous
         use must have finished: its event is waited on first).  Refuses while another
@@ -332,15 +366,16 @@ class GpuReplayShard:
         self._pin_used[k] = True
         return self._pin_buf[k]
 
-    def stage_frames(self, n: int) -> Optional[np.ndarray]:
+    def stage_frames(self, n: int, raw: bool = False) -> Optional[np.ndarray]:
         """A pinned host buffer for the next append of ``n`` frames (GPU shards): an env
         that writes its frames straight into it (``step(actions, out=...)``) saves the
         staging copy -- append_frames of exactly that array starts its H2D copy from it.
-        None off the GPU."""
-        if self.device.type != "cuda" or self.frame_shape is None:
+        ``raw``: a buffer of ``n`` raw Atari frame pairs for :meth:`append_raw_frames`
+        (HIP path only: the host mirror reads the env's own array).  None off the GPU."""
+        if self.device.type != "cuda" or self.frame_shape is None or (raw and not self.use_hip):
             return None
         with self.lock:
-            buf = self._acquire_pin((int(n),) + tuple(self.frame_shape))
+            buf = self._acquire_pin((int(n),) + (RAW_FRAME_SHAPE if raw else tuple(self.frame_shape)))
             arr = buf.numpy()
             # one staging slot per shard: the append of this array must come from the same
             # thread before anything else takes a pinned buffer (_acquire_pin checks)

@@ -138,7 +138,8 @@ def _train_frames(cfg: ApexConfig, device, learner_steps: int, comm=None,
         sys.stderr.write(f"warning: Runtime.actor_pipeline={rt.actor_pipeline} > 2 measured far slower on "
                          f"MI355X (actor streams share hardware queues with the learner); 2 is the default\n")
     group = make_gpu_actor_group(cfg, learner, replay, E, rank, world, seed=rt.seed,
-                                 pipeline=int(rt.actor_pipeline) if async_actors else 1)
+                                 pipeline=int(rt.actor_pipeline) if async_actors else 1,
+                                 preprocess=rt.atari_preprocess)
     if ckpt_path and rt.resume and os.path.exists(ckpt_path):
         _restore_actor_rng(group, ckpt_path)
     min_local = max(L.min_replay_mem_size // world, L.replay_sample_size)
