@@ -190,7 +190,7 @@ def _declare(lib: ctypes.CDLL) -> None:
     conv_sigs.declare(lib)
 
 
-ABI_VERSION = 8      # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
+ABI_VERSION = 9     # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
 
 
 def load(build_if_missing: bool = True) -> Optional[ctypes.CDLL]:

@@ -529,20 +529,49 @@ def _splits(Mred: int, target_rows: int, max_rows: int) -> Tuple[int, int]:
     return (Mred + rows - 1) // rows, rows
 
 
+def conv2_wgrad_rows_covers(x_shape, dy_shape, KH: int, stride: int, split: bool, rows: int) -> bool:
+    """Whether the row-resident conv2 weight-gradient kernel (csrc/conv2_wgrad_rows.hip)
+    covers the problem: split-mode conv2 only (y1 [N, 20, 20, 64] against dY2 [N, 9, 9, 64],
+    4 x 4 stride 2), ``rows`` reduction rows per split in whole 64-row steps that fit its
+    row table."""
+    return (bool(split) and KH == 4 and stride == 2 and len(x_shape) == 4 and len(dy_shape) == 4
+            and tuple(x_shape[1:]) == (20, 20, 64) and tuple(dy_shape[1:]) == (9, 9, 64)
+            and x_shape[0] == dy_shape[0] and x_shape[0] > 0
+            and rows > 0 and rows % _WG_ROWS == 0 and rows <= _WG_TBL)
+
+
+def conv2_wgrad_rows_pick(x_shape, dy_shape, KH: int, stride: int, split: bool, rows: int,
+                          force: Optional[bool] = None) -> bool:
+    """The conv2 weight-gradient path: ``force`` (tests) wins, else the row-resident kernel
+    where it covers the problem, ``SW.conv2_wgrad_rows`` is on and the batch has at least
+    ``SW.conv2_wgrad_rows_min`` images.  Forcing it on an uncovered problem is an error."""
+    covers = conv2_wgrad_rows_covers(x_shape, dy_shape, KH, stride, split, rows)
+    if force is not None:
+        if force and not covers:
+            raise ValueError("conv2_wgrad_rows does not cover this problem")
+        return bool(force)
+    return covers and bool(SW.conv2_wgrad_rows) and x_shape[0] >= SW.conv2_wgrad_rows_min
+
+
 def conv_wgrad(lib, ws: Workspace, dy: torch.Tensor, x: torch.Tensor, KH: int, stride: int,
                dw_out: torch.Tensor, db_out: torch.Tensor, target_rows: int = 0, jobs: Optional[list] = None,
-               dy_lo=None, x_lo=None) -> None:
+               dy_lo=None, x_lo=None, rows_kernel: Optional[bool] = None) -> None:
     """dW (OHWI, fp32) and db for an NHWC conv with 64 output channels.  With
     ``jobs``, the split-K reduction is appended there for ``finalize_grads``.
     ``target_rows``: reduction rows per split-K block (0 = tuned default: fewer
     rows for the small 3x3 layer, whose 9 output tiles need more splits (384: two
-    68 KB blocks per CU); 704 for conv2 keeps its 4 x 59 blocks (84 KB LDS each,
-    one per CU) in a single wave on 256 CUs: 3507-3572 -> 3562-3611 steps/s).  Below 256
+    68 KB blocks per CU); 704 for conv2 makes 59 splits at 512 images, a single round on
+    256 CUs for either kernel below: 3507-3572 -> 3562-3611 steps/s).  Below 256
     images (the per-rank rows of a global batch over 4+ ranks) half those rows, so the few
     images still make enough blocks: emulated W = 8 rank step 167.8 / 168.4 / 168.3 ->
     159.9 / 161.5 / 159.6 us, W = 4 ~1 %; at 290 images (W = 2) halving loses 2.5 %
     (profiles/r6_ab_wgrad_rows_small_batch.txt).
-    SW.wg_rows3 / SW.wg_rows2 override for sweeps."""
+    SW.wg_rows3 / SW.wg_rows2 override for sweeps.
+    Split-mode conv2 has two kernels writing the same slabs, bit for bit: the generic
+    implicit GEMM (8 blocks of two taps per split, 4 waves, 144 KB LDS: 8 x 59 blocks at 512
+    images) and the row-resident kernel (csrc/conv2_wgrad_rows.hip: one 8-wave block per
+    (split, kernel row), 4 x 59, each input row staged once).  ``rows_kernel`` forces one
+    (tests); the default is ``conv2_wgrad_rows_pick``."""
     N, OH, OW, Co = dy.shape
     if target_rows <= 0:
         small = N < 256
@@ -557,13 +586,16 @@ def conv_wgrad(lib, ws: Workspace, dy: torch.Tensor, x: torch.Tensor, KH: int, s
     d = _wg_desc(dy=dy.data_ptr(), x=x.data_ptr(), slab=slab.data_ptr(), bias_slab=bslab.data_ptr(), N=N,
                  H=H, W=W, Cin=Cin, OH=OH, OW=OW, KH=KH, KW=KH, stride=stride, mode=1, Co=Co, Kc=Kc, ldd=Co,
                  rows_per_split=rows, Mred=Mred, dy_lo=_lib.ptr(dy_lo), x_lo=_lib.ptr(x_lo))
+    launch, what = lib.apex_conv_wgrad, "conv_wgrad"
+    if conv2_wgrad_rows_pick(x.shape, dy.shape, KH, stride, dy_lo is not None and x_lo is not None, rows,
+                             rows_kernel):
+        launch, what = lib.apex_conv2_wgrad_rows, "conv2_wgrad_rows"   # a missing kernel is an error
     if jobs is not None:   # reduction deferred to one grad_finalize launch
-        _lib.check(lib.apex_conv_wgrad(d, None, None, nsplit, 1.0, _lib.stream_ptr()), "conv_wgrad")
+        _lib.check(launch(d, None, None, nsplit, 1.0, _lib.stream_ptr()), what)
         jobs.append(dict(slab=slab, bslab=bslab, out=dw_out, bout=db_out, n=Co * Kc, nsplit=nsplit, nb=Co,
                          s2dC=0, Kc=Kc, scale=1.0))
         return
-    _lib.check(lib.apex_conv_wgrad(d, dw_out.data_ptr(), db_out.data_ptr(), nsplit, 1.0, _lib.stream_ptr()),
-               "conv_wgrad")
+    _lib.check(launch(d, dw_out.data_ptr(), db_out.data_ptr(), nsplit, 1.0, _lib.stream_ptr()), what)
 
 
 def conv1_wgrad_ring(lib, ws: Workspace, dy: torch.Tensor, ring: torch.Tensor, slots: torch.Tensor,

@@ -77,6 +77,20 @@ class Switches:
     # tuned defaults in ops/conv.py)
     wg_rows3: int = 0
     wg_rows2: int = 0
+    # split-mode conv2 weight gradient on the row-resident kernel (csrc/conv2_wgrad_rows.hip:
+    # every y1 input row staged once per (split, kernel row) workgroup, the same bits as the
+    # generic kernel) for batches of at least conv2_wgrad_rows_min images.  Its grid is half
+    # the generic kernel's, so it pays only where the generic one needs two rounds: isolated
+    # at 512 images 28.8-30.6 vs 29.9-32.1 us (a tie), at 256 images 27.5-28.5 vs 16.6-17.3,
+    # at 74 images 15.5-15.9 vs 9.5-9.7 (profiles/pr4_conv2_wgrad_isolated.txt).  Inside the
+    # 512-row fp32 step, where it ends the backward on the branch, 58.2 vs 61.9 us; 5
+    # interleaved runs each of the parent and this tree: 2,838-2,855 (median 2,850) vs
+    # 2,805-2,827 (2,814) updates/s at 200 / 20 steps, 2,815-2,845 (2,843) vs 2,796-2,813
+    # (2,803) at 20 / 5 (profiles/pr4_ab_conv2_wgrad_rows.txt).  The threshold is the one
+    # size the step was measured at; between 279 images (where the generic grid passes 256
+    # blocks) and 511 nobody has measured
+    conv2_wgrad_rows: bool = True
+    conv2_wgrad_rows_min: int = 512
     # IMPALA weight gradients: workgroups per conv and the partial-slab cap (floats)
     impala_wg_target: int = 512
     impala_slab_cap: int = 8 << 20
