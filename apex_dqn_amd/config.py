@@ -79,6 +79,20 @@ class RuntimeConf:
     rms_decay: float = 0.95
     rms_eps: float = 1.5e-7
     centered_rmsprop: bool = True
+    optimizer: str = "rmsprop"      # "rmsprop" (above) | "adam" (same launches, csrc/rmsprop_common.h OPT_ADAM;
+                                    # reuses the RMSprop state buffers, bias-corrected with t = update index + 1)
+    adam_beta1: float = 0.9
+    adam_beta2: float = 0.999
+    adam_eps: float = 1.5e-4
+    # lr(u), u = updates completed before the current one, evaluated on the device (learner/schedules.py):
+    # lr (u + 1) / warmup while u < lr_warmup_steps, then a linear ramp from lr to lr_end over lr_decay_steps
+    lr_warmup_steps: int = 0
+    lr_decay_steps: int = 0
+    lr_end: Optional[float] = None
+    # IS exponent annealed from Replay_Memory.importance_sampling_exponent to is_beta_end over
+    # is_beta_anneal_steps updates: the batch of update u carries beta(u)
+    is_beta_end: Optional[float] = None
+    is_beta_anneal_steps: int = 0
     grad_clip: float = 40.0
     loss: str = "huber"             # "huber" | "mse" (0.5*delta^2, reference learner.py:48)
     huber_delta: float = 1.0
@@ -249,6 +263,17 @@ class ApexConfig:
                 raise ValueError(f"Runtime.atari_preprocess='device' produces 84x84 frames, got state_shape {ss}")
         if self.Runtime.loss not in ("huber", "mse"):
             raise ValueError("Runtime.loss must be 'huber' or 'mse'")
+        rt = self.Runtime
+        if rt.optimizer not in ("rmsprop", "adam"):
+            raise ValueError(f"Runtime.optimizer must be 'rmsprop' or 'adam', got {rt.optimizer!r}")
+        if int(rt.lr_warmup_steps) < 0 or int(rt.lr_decay_steps) < 0 or int(rt.is_beta_anneal_steps) < 0:
+            raise ValueError("Runtime.lr_warmup_steps, lr_decay_steps and is_beta_anneal_steps must be >= 0")
+        if (rt.lr_end is not None) != (int(rt.lr_decay_steps) > 0):
+            raise ValueError("Runtime.lr_end and Runtime.lr_decay_steps > 0 need each other")
+        if (rt.is_beta_end is not None) != (int(rt.is_beta_anneal_steps) > 0):
+            raise ValueError("Runtime.is_beta_end and Runtime.is_beta_anneal_steps > 0 need each other")
+        if rt.is_beta_end is not None and not rt.use_is_weights:
+            raise ValueError("Runtime.is_beta_end anneals the IS weights: it needs Runtime.use_is_weights")
         net = self.network
         if net in ("nature64", "nature32", "impala") and len(ss) != 3:
             raise ValueError(f"network {net} needs an image state_shape [C,H,W], got {ss}")

@@ -1,4 +1,5 @@
-// Fused multi-tensor centered RMSprop + global grad-norm clip + bf16 pack.
+// Fused multi-tensor centered RMSprop (or Adam: rmsprop_common.h OPT_ADAM) + global
+// grad-norm clip + bf16 pack.
 //
 // Reference learner.py:26 builds torch RMSprop(lr=0.00025/4, weight_decay=0.95,
 // eps=1.5e-7) (decay passed as L2 weight decay, defect A16) and steps 14
@@ -33,6 +34,25 @@ __global__ void __launch_bounds__(256) sqnorm_partial_kernel(const float* __rest
 
 __global__ void __launch_bounds__(256) rmsprop_kernel(RmspropArgs a) { rmsprop_body(a, blockIdx.x, gridDim.x); }
 
+// the step-indexed variants (rmsprop_common.h OPT_RMSPROP_SCHED, OPT_ADAM)
+template <int MODE>
+__global__ void __launch_bounds__(256) opt_sched_kernel(RmspropArgs a) {
+  rmsprop_body<MODE>(a, blockIdx.x, gridDim.x);
+}
+
+static int launch_opt(const RmspropArgs& a, hipStream_t st) {
+  if (((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.v | (uintptr_t)a.m) & 15) return (int)hipErrorInvalidValue;
+  if (((uintptr_t)a.pb | (uintptr_t)a.pb_lo) & 7) return (int)hipErrorInvalidValue;
+  const int mode = opt_mode(a.os);
+  if (mode != OPT_RMSPROP && (a.os.ctr == nullptr || a.os.base == nullptr)) return (int)hipErrorInvalidValue;
+  int nb = (int)((a.n / 4 + 255) / 256);
+  nb = nb < 1 ? 1 : (nb > 2048 ? 2048 : nb);
+  if (mode == OPT_ADAM) opt_sched_kernel<OPT_ADAM><<<nb, 256, 0, st>>>(a);
+  else if (mode == OPT_RMSPROP_SCHED) opt_sched_kernel<OPT_RMSPROP_SCHED><<<nb, 256, 0, st>>>(a);
+  else rmsprop_kernel<<<nb, 256, 0, st>>>(a);
+  APEX_CHECK_LAUNCH();
+}
+
 // fp32 -> bf16 copy; with `lo` also the residual plane (x = y + lo: fp32-accurate mode)
 __global__ void cast_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict__ y, bf16_t* __restrict__ lo,
                                  int64_t n) {
@@ -51,14 +71,10 @@ APEX_EXPORT int apex_grad_sqnorm_partials(const float* g, int64_t n, double* par
 APEX_EXPORT int apex_rmsprop_step(float* p, const float* g, float* v, float* m, bf16_t* pb, int64_t n,
                                   const double* partials, float lr, float alpha, float eps, float clip,
                                   int centered, float* norm_out, bf16_t* pb_lo, const double* wnorm, int wn,
-                                  int wstride, hipStream_t st) {
-  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)v | (uintptr_t)m) & 15) return (int)hipErrorInvalidValue;
-  if (((uintptr_t)pb | (uintptr_t)pb_lo) & 7) return (int)hipErrorInvalidValue;
-  int nb = (int)((n / 4 + 255) / 256);
-  nb = nb < 1 ? 1 : (nb > 2048 ? 2048 : nb);
-  rmsprop_kernel<<<nb, 256, 0, st>>>(RmspropArgs{p, g, v, m, pb, n, partials, NPART, lr, alpha, eps, clip, centered,
-                                                 norm_out, pb_lo, wnorm, wn, wstride, CfFragOut{}});
-  APEX_CHECK_LAUNCH();
+                                  int wstride, OptSched os, hipStream_t st) {
+  return launch_opt(RmspropArgs{p, g, v, m, pb, n, partials, NPART, lr, alpha, eps, clip, centered, norm_out, pb_lo,
+                                wnorm, wn, wstride, CfFragOut{}, nullptr, 0, os},
+                    st);
 }
 
 // the same step with the clip norm taken from ``npart`` producer-written partials
@@ -66,14 +82,10 @@ APEX_EXPORT int apex_rmsprop_step(float* p, const float* g, float* v, float* m, 
 APEX_EXPORT int apex_rmsprop_step_np(float* p, const float* g, float* v, float* m, bf16_t* pb, int64_t n,
                                      const double* partials, int npart, float lr, float alpha, float eps, float clip,
                                      int centered, float* norm_out, bf16_t* pb_lo, const double* wnorm, int wn,
-                                  int wstride, hipStream_t st) {
-  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)v | (uintptr_t)m) & 15) return (int)hipErrorInvalidValue;
-  if (((uintptr_t)pb | (uintptr_t)pb_lo) & 7) return (int)hipErrorInvalidValue;
-  int nb = (int)((n / 4 + 255) / 256);
-  nb = nb < 1 ? 1 : (nb > 2048 ? 2048 : nb);
-  rmsprop_kernel<<<nb, 256, 0, st>>>(RmspropArgs{p, g, v, m, pb, n, partials, npart, lr, alpha, eps, clip, centered,
-                                                 norm_out, pb_lo, wnorm, wn, wstride, CfFragOut{}});
-  APEX_CHECK_LAUNCH();
+                                     int wstride, OptSched os, hipStream_t st) {
+  return launch_opt(RmspropArgs{p, g, v, m, pb, n, partials, npart, lr, alpha, eps, clip, centered, norm_out, pb_lo,
+                                wnorm, wn, wstride, CfFragOut{}, nullptr, 0, os},
+                    st);
 }
 
 APEX_EXPORT int apex_cast_bf16(const float* x, bf16_t* y, int64_t n, bf16_t* lo, hipStream_t st) {

@@ -2,6 +2,11 @@
 // (rmsprop_body), shared by csrc/optimizer.hip (rmsprop_kernel) and by
 // csrc/sumtree.hip (rmsprop_sample_kernel: the optimizer launch also draws the
 // next step's prioritized batch in its first blocks).
+//
+// Compile-time variants of the body (OPT_*): the RMSprop update with the learning rate
+// frozen at capture (the default: its code is the body of before), the same update
+// with a step-indexed learning rate, and Adam.  The last two read the update index
+// from device memory (OptSched), so a replayed graph needs no host round trip.
 #pragma once
 #include "apex_common.h"
 #include "cf_pack.h"
@@ -55,6 +60,63 @@ __device__ __forceinline__ float clip_coef_from_partials(const double* partials,
   return sh[0];
 }
 
+// ------------------------------------------------------ step-indexed schedules
+// The update index inside a replayed graph: the replay's draw counter is bumped once per
+// update by the priority write-back (csrc/sumtree.hip ctr_to_bump), in a launch that
+// precedes the optimizer launch in stream order; `base` is a device word holding the
+// counter's value at update 0 (set at construction / load).  So
+//   counter - base     = updates completed, read at the head of an update (a fresh draw),
+//   counter - base - 1 = u, the updates completed before the current one, read in its
+//                        optimizer launch (whose pre-sample draws update u + 1's batch).
+// The optimizer and sample launches only read the counter.
+// Both schedules are evaluated in fp64 from the integer index and rounded once to fp32;
+// learner/schedules.py is the host mirror (numpy float64, the same operation order: no
+// contraction here), bit for bit.
+__device__ __forceinline__ float sched_lr(int64_t u, double lr0, double lr_end, int64_t warmup, int64_t decay) {
+#pragma clang fp contract(off)
+  double lr = lr0;
+  if (u < warmup) lr = lr0 * (double)(u + 1) / (double)warmup;
+  else if (decay > 0) lr = lr0 + (lr_end - lr0) * fmin(1.0, (double)(u - warmup) / (double)decay);
+  return (float)lr;
+}
+
+// IS exponent of the batch that update u consumes
+__device__ __forceinline__ float sched_beta(int64_t u, double b0, double b_end, int64_t steps) {
+#pragma clang fp contract(off)
+  const double f = steps > 0 ? fmin(1.0, (double)u / (double)steps) : 1.0;
+  return (float)(b0 + (b_end - b0) * f);
+}
+
+// b^t in fp64 by squaring (t an integer: at most 2 x 64 multiplications in a fixed
+// order, which the host mirror repeats exactly)
+__device__ __forceinline__ double pow_u64(double b, uint64_t t) {
+#pragma clang fp contract(off)
+  double r = 1.0;
+  while (t) {
+    if (t & 1) r = r * b;
+    b = b * b;
+    t >>= 1;
+  }
+  return r;
+}
+
+#define OPT_RMSPROP 0        // RMSprop, lr = RmspropArgs.lr
+#define OPT_RMSPROP_SCHED 1  // RMSprop, lr(u)
+#define OPT_ADAM 2           // Adam, lr(u), bias corrections from t = u + 1
+
+struct OptSched {
+  const uint64_t* ctr;   // the replay's draw counter, or null (OPT_RMSPROP)
+  const int64_t* base;   // device word: the counter at update 0
+  int adam;              // 1: Adam (RmspropArgs.eps carries adam_eps; alpha / centered unused)
+  int64_t warmup, decay; // lr schedule (0: off)
+  double lr0, lr_end;
+  double beta1, beta2;
+};
+
+__host__ __device__ inline int opt_mode(const OptSched& s) {
+  return s.adam ? OPT_ADAM : (s.ctr != nullptr ? OPT_RMSPROP_SCHED : OPT_RMSPROP);
+}
+
 struct RmspropArgs {
   float* p;
   const float* g;
@@ -73,9 +135,11 @@ struct RmspropArgs {
   CfFragOut fo;         // the fused forward's online operands in fragment order (w1frag null: off)
   const float* gpre;    // clip norm: a gradient range summed in every block (clip_coef_from_partials), or null
   int64_t npre;
+  OptSched os;          // update index + schedules + Adam constants (all-zero: OPT_RMSPROP)
 };
 
 // one block `bid` of `nblk` (grid-stride over float4 chunks)
+template <int MODE = OPT_RMSPROP>
 __device__ __forceinline__ void rmsprop_body(const RmspropArgs& A_, int bid, int nblk) {
   // no FMA contraction: every inlined copy of the update (steady loop, peeled chunk, the
   // other launches) rounds identically
@@ -87,9 +151,12 @@ __device__ __forceinline__ void rmsprop_body(const RmspropArgs& A_, int bid, int
   bf16_t* __restrict__ pb = A_.pb;
   bf16_t* __restrict__ pbl = A_.pb_lo;
   const int64_t n = A_.n;
-  const float lr = A_.lr, alpha = A_.alpha, eps = A_.eps;
-  const int centered = A_.centered;
-  __shared__ float sh[2];
+  const float alpha = MODE == OPT_ADAM ? (float)A_.os.beta2 : A_.alpha, eps = A_.eps;
+  const int centered = MODE == OPT_ADAM ? 1 : A_.centered;    // (Adam: m is the first moment)
+  // sh[0], sh[1]: clip coefficient and norm; the scheduled variants add sh[2] = lr(u),
+  // sh[3] = 1 - beta1^t, sh[4] = 1 - beta2^t, written by thread 0 ahead of the clip
+  // reduction's barriers
+  __shared__ float sh[MODE == OPT_RMSPROP ? 2 : 5];
   const int64_t n4 = n / 4;
   float4* p4 = reinterpret_cast<float4*>(p);
   const float4* g4 = reinterpret_cast<const float4*>(g);
@@ -107,9 +174,29 @@ __device__ __forceinline__ void rmsprop_body(const RmspropArgs& A_, int bid, int
     gg = g4[i]; pp = p4[i]; vv = v4[i];
     if (centered) mm = m4[i];
   }
+  if constexpr (MODE != OPT_RMSPROP) {
+    if (threadIdx.x == 0) {
+      const OptSched& os = A_.os;
+      int64_t u = (int64_t)os.ctr[0] - os.base[0] - 1;
+      u = u < 0 ? 0 : u;
+      sh[2] = sched_lr(u, os.lr0, os.lr_end, os.warmup, os.decay);
+      if constexpr (MODE == OPT_ADAM) {
+        sh[3] = (float)(1.0 - pow_u64(os.beta1, (uint64_t)u + 1));
+        sh[4] = (float)(1.0 - pow_u64(os.beta2, (uint64_t)u + 1));
+      }
+    }
+  }
   const float coef = clip_coef_from_partials(A_.partials, A_.npart, A_.clip, sh,
                                              is_grad_scale(A_.wnorm, A_.wn, A_.wstride), A_.gpre, A_.npre);
   if (bid == 0 && threadIdx.x == 0 && A_.norm_out) A_.norm_out[0] = sh[1];
+  float lr = A_.lr, c1 = 1.0f, c2 = 1.0f, b1 = 0.f, d1 = 0.f;
+  if constexpr (MODE != OPT_RMSPROP) lr = sh[2];
+  if constexpr (MODE == OPT_ADAM) {
+    c1 = sh[3];
+    c2 = sh[4];
+    b1 = (float)A_.os.beta1;
+    d1 = 1.0f - b1;
+  }
   const float a1 = 1.0f - alpha;
   auto update = [&](int64_t i, const float4 gg, const float4 pp, const float4 vv, const float4 mm, const bool frag) {
     float gx[4] = {gg.x * coef, gg.y * coef, gg.z * coef, gg.w * coef};
@@ -118,13 +205,20 @@ __device__ __forceinline__ void rmsprop_body(const RmspropArgs& A_, int bid, int
     float mx[4] = {mm.x, mm.y, mm.z, mm.w};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      vx[j] = alpha * vx[j] + a1 * gx[j] * gx[j];
-      float var = vx[j];
-      if (centered) {
-        mx[j] = alpha * mx[j] + a1 * gx[j];
-        var = vx[j] - mx[j] * mx[j];
+      if constexpr (MODE == OPT_ADAM) {
+        // m <- b1 m + (1 - b1) g;  v <- b2 v + (1 - b2) g^2;  p -= lr (m / c1) / (sqrt(v / c2) + eps)
+        mx[j] = b1 * mx[j] + d1 * gx[j];
+        vx[j] = alpha * vx[j] + a1 * gx[j] * gx[j];
+        px[j] -= lr * (mx[j] / c1) / (sqrtf(vx[j] / c2) + eps);
+      } else {
+        vx[j] = alpha * vx[j] + a1 * gx[j] * gx[j];
+        float var = vx[j];
+        if (centered) {
+          mx[j] = alpha * mx[j] + a1 * gx[j];
+          var = vx[j] - mx[j] * mx[j];
+        }
+        px[j] -= lr * gx[j] / (sqrtf(fmaxf(var, 0.f)) + eps);
       }
-      px[j] -= lr * gx[j] / (sqrtf(fmaxf(var, 0.f)) + eps);
     }
     p4[i] = make_float4(px[0], px[1], px[2], px[3]);
     v4[i] = make_float4(vx[0], vx[1], vx[2], vx[3]);
@@ -145,7 +239,10 @@ __device__ __forceinline__ void rmsprop_body(const RmspropArgs& A_, int bid, int
   // The first chunk is peeled: the fused forward's operand stores (A_.fo, the launcher
   // checks that w1 / w2 lie within every thread's first chunk) run before the next
   // chunk's loads are issued, so the steady loop keeps 6 waves per SIMD (every block of
-  // the launch resident at once; with the stores inside the loop it held 85 VGPRs)
+  // the launch resident at once; with the stores inside the loop it held 85 VGPRs).
+  // That is the RMSprop instantiations' figure (74 / 75 VGPRs); OPT_ADAM's three divisions
+  // per element hold 86 / 87 VGPRs, 5 waves per SIMD -- the fused launch's 256 blocks of 8
+  // waves are one per CU either way
   if (i < n4) {
     update(i, gg, pp, vv, mm, A_.fo.w1frag != nullptr);
     i += stride;
@@ -168,12 +265,19 @@ __device__ __forceinline__ void rmsprop_body(const RmspropArgs& A_, int bid, int
     float gg = g[i] * coef;
     float vv = alpha * v[i] + a1 * gg * gg, var = vv;
     v[i] = vv;
-    if (centered) {
-      float mm = alpha * m[i] + a1 * gg;
+    float pp;
+    if constexpr (MODE == OPT_ADAM) {
+      const float mm = b1 * m[i] + d1 * gg;
       m[i] = mm;
-      var = vv - mm * mm;
+      pp = p[i] - lr * (mm / c1) / (sqrtf(vv / c2) + eps);
+    } else {
+      if (centered) {
+        float mm = alpha * m[i] + a1 * gg;
+        m[i] = mm;
+        var = vv - mm * mm;
+      }
+      pp = p[i] - lr * gg / (sqrtf(fmaxf(var, 0.f)) + eps);
     }
-    float pp = p[i] - lr * gg / (sqrtf(fmaxf(var, 0.f)) + eps);
     p[i] = pp;
     pb[i] = f32_to_bf16(pp);
     if (pbl != nullptr) pbl[i] = f32_to_bf16(pp - bf16_to_f32(pb[i]));

@@ -264,6 +264,16 @@ static int tree_kfirst(const TreeDesc& t) {
 // all-gathered per-shard statistics: (sum p^alpha, min p^alpha, max IS weight of the
 // shard's rows in the current batch -- written by the head kernel, read by the optimizer)
 #define SHARD_STATS 3
+// Annealed IS exponent: the batch that update u consumes carries beta(u) = beta0 +
+// (beta_end - beta0) min(1, u / steps) (rmsprop_common.h sched_beta).  u = ctr - ubase at
+// the time of the draw: a draw at the head of update u sees u, the pre-sample inside
+// update u - 1's optimizer launch (after that update's counter bump) sees u as well.
+struct BetaSched {
+  const int64_t* ubase;        // device word: the counter at update 0, or null (no schedule)
+  double beta0, beta_end;
+  int64_t steps;
+};
+
 struct SampleArgs {
   TreeDesc t;
   RecordDesc r;
@@ -286,6 +296,7 @@ struct SampleArgs {
   float* out_wscale;           // the batch's W B / M factor (1 unsharded), for the IS batch-max; or null
   int64_t mcap;                // sharded: cap on the global batch M (W B: per-rank batches; the
                                // configured global batch: Runtime.batch_scope = "global")
+  BetaSched bs;                // annealed IS exponent (ubase null: `beta`)
 };
 
 // block `bid` of 4 waves: samples 4 bid .. 4 bid + 3
@@ -295,7 +306,6 @@ __device__ __forceinline__ void tree_sample_body(const SampleArgs& S, int bid) {
   const int B = S.B;
   const uint64_t seed = S.seed;
   const uint64_t* __restrict__ ctr = S.ctr;
-  const float beta = S.beta;
   int64_t* __restrict__ out_idx = S.out_idx;
   float* __restrict__ out_w = S.out_w;
   int32_t* __restrict__ out_gen = S.out_gen;
@@ -378,6 +388,11 @@ __device__ __forceinline__ void tree_sample_body(const SampleArgs& S, int bid) {
     // (p / p_min)^-beta <= 1 (p_min global over the shards in sharded mode), times
     // the global-batch correction
     const float pmin = S.shard_stats != nullptr ? pmin_g : __uint_as_float(t.min_bits[0]);
+    float beta = S.beta;
+    if (S.bs.ubase != nullptr) {
+      const int64_t u = (int64_t)ctr[0] - S.bs.ubase[0];
+      beta = sched_beta(u < 0 ? 0 : u, S.bs.beta0, S.bs.beta_end, S.bs.steps);
+    }
     const float w = (valid && p > 0.f && pmin > 0.f) ? fminf(powf(p / pmin, -beta), 1.0f) * wscale : 0.f;
     out_idx[b] = s;
     out_w[b] = w;
@@ -626,7 +641,7 @@ struct RmsSegs {
   int64_t len[3];
 };
 
-template <int NT, bool SEG>
+template <int NT, bool SEG, int MODE = OPT_RMSPROP>
 __global__ void __launch_bounds__(NT) rmsprop_sample_kernel(RmspropArgs a, SampleArgs s, int nsb, RmsSegs sg) {
   if ((int)blockIdx.x < nsb) {
     tree_sample_body(s, blockIdx.x);
@@ -634,7 +649,7 @@ __global__ void __launch_bounds__(NT) rmsprop_sample_kernel(RmspropArgs a, Sampl
   }
   const int b = blockIdx.x - nsb;
   if constexpr (!SEG) {
-    rmsprop_body(a, b, gridDim.x - nsb);
+    rmsprop_body<MODE>(a, b, gridDim.x - nsb);
   } else {
     int k = 0;
     while (k + 1 < sg.nseg && b >= sg.blk0[k + 1]) ++k;
@@ -651,7 +666,7 @@ __global__ void __launch_bounds__(NT) rmsprop_sample_kernel(RmspropArgs a, Sampl
       t.fo = CfFragOut{};
       t.norm_out = nullptr;
     }
-    rmsprop_body(t, b - sg.blk0[k], sg.blk0[k + 1] - sg.blk0[k]);
+    rmsprop_body<MODE>(t, b - sg.blk0[k], sg.blk0[k + 1] - sg.blk0[k]);
   }
 }
 
@@ -691,7 +706,7 @@ APEX_EXPORT int apex_tree_sample(TreeDesc t, RecordDesc r, int B, uint64_t seed,
                                  int32_t* out_gen, int32_t* out_obs, int32_t* out_nxt, int32_t* out_act,
                                  float* out_rew, float* out_gam, int32_t* out_nxt2, const double* shard_stats,
                                  int shard_rank, int shard_world, uint64_t shard_seed, float* out_wscale,
-                                 int64_t mcap, hipStream_t st) {
+                                 int64_t mcap, BetaSched bs, hipStream_t st) {
   if (B <= 0) return 0;
   if (mcap <= 0) mcap = (int64_t)shard_world * B;
   if (shard_stats != nullptr && (B < 3 || shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world))
@@ -700,7 +715,7 @@ APEX_EXPORT int apex_tree_sample(TreeDesc t, RecordDesc r, int B, uint64_t seed,
   tree_sample_kernel<<<blocks_for(B, waves_per_block), 64 * waves_per_block, 0, st>>>(
       SampleArgs{t, r, B, seed, ctr, beta, out_idx, out_w, out_gen, out_obs, out_nxt, out_act,
                  out_rew, out_gam, out_nxt2, shard_stats, shard_rank, shard_world, shard_seed, out_wscale,
-                 mcap});
+                 mcap, bs});
   APEX_CHECK_LAUNCH();
 }
 
@@ -746,7 +761,7 @@ APEX_EXPORT int apex_fill16(void* p, int64_t n, int nt, hipStream_t st) {
   APEX_CHECK_LAUNCH();
 }
 
-APEX_EXPORT int apex_abi_version() { return 9; }
+APEX_EXPORT int apex_abi_version() { return 10; }
 
 // 1 if this library was built with -DAPEX_DEBUG_BOUNDS
 APEX_EXPORT int apex_debug_bounds_enabled() {
@@ -792,9 +807,12 @@ APEX_EXPORT int apex_rmsprop_sample(float* p, const float* g, float* v, float* m
                                     int64_t* out_idx, float* out_w, int32_t* out_gen, int32_t* out_obs,
                                     int32_t* out_nxt, int32_t* out_act, float* out_rew, float* out_gam,
                                     int32_t* out_nxt2, const double* shard_stats, int shard_rank, int shard_world,
-                                    uint64_t shard_seed, float* out_wscale, int64_t mcap, bf16_t* pb_lo,
-                                    const double* wnorm, int wn, int wstride, CfFragOut fo, const RmsSegs* seg,
-                                    const float* gpre, int64_t npre, hipStream_t st) {
+                                    uint64_t shard_seed, float* out_wscale, int64_t mcap, BetaSched bs,
+                                    bf16_t* pb_lo, const double* wnorm, int wn, int wstride, CfFragOut fo,
+                                    const RmsSegs* seg, const float* gpre, int64_t npre, OptSched os,
+                                    hipStream_t st) {
+  const int mode = opt_mode(os);
+  if (mode != OPT_RMSPROP && (os.ctr == nullptr || os.base == nullptr)) return (int)hipErrorInvalidValue;
   if (mcap <= 0) mcap = (int64_t)shard_world * B;
   if (shard_stats != nullptr && (B < 3 || shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world))
     return (int)hipErrorInvalidValue;
@@ -849,12 +867,20 @@ APEX_EXPORT int apex_rmsprop_sample(float* p, const float* g, float* v, float* m
     return (int)hipErrorInvalidValue;
   if (((uintptr_t)gpre & 15) || npre < 0 || (npre > 0 && gpre == nullptr)) return (int)hipErrorInvalidValue;
   const RmspropArgs ra{p, g, v, m, pb, n, partials, npart, lr, alpha, eps_opt, clip, centered, norm_out, pb_lo,
-                      wnorm, wn, wstride, fo, npre > 0 ? gpre : nullptr, npre};
+                      wnorm, wn, wstride, fo, npre > 0 ? gpre : nullptr, npre, os};
   const SampleArgs sa{t, r, B, seed, ctr, beta, out_idx, out_w, out_gen, out_obs, out_nxt,
                       out_act, out_rew, out_gam, out_nxt2, shard_stats, shard_rank, shard_world, shard_seed,
-                      out_wscale, mcap};
-  if (seg != nullptr) rmsprop_sample_kernel<nt, true><<<sg.blk0[sg.nseg] + nsb, nt, 0, st>>>(ra, sa, nsb, sg);
-  else rmsprop_sample_kernel<nt, false><<<nb + nsb, nt, 0, st>>>(ra, sa, nsb, sg);
+                      out_wscale, mcap, bs};
+  const int grid = (seg != nullptr ? sg.blk0[sg.nseg] : nb) + nsb;
+#define APEX_OPT_LAUNCH(MODE)                                                                          \
+  do {                                                                                                 \
+    if (seg != nullptr) rmsprop_sample_kernel<nt, true, MODE><<<grid, nt, 0, st>>>(ra, sa, nsb, sg);    \
+    else rmsprop_sample_kernel<nt, false, MODE><<<grid, nt, 0, st>>>(ra, sa, nsb, sg);                  \
+  } while (0)
+  if (mode == OPT_ADAM) APEX_OPT_LAUNCH(OPT_ADAM);
+  else if (mode == OPT_RMSPROP_SCHED) APEX_OPT_LAUNCH(OPT_RMSPROP_SCHED);
+  else APEX_OPT_LAUNCH(OPT_RMSPROP);
+#undef APEX_OPT_LAUNCH
   APEX_CHECK_LAUNCH();
 }
 

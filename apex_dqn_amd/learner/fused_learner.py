@@ -15,7 +15,10 @@ Per step (B = local batch), entirely on device, one stream, no host sync:
                                                  prioritized replay), captured in the
                                                  step's HIP graph
   grad-norm clip + centered RMSprop + bf16 pack  ONE launch (csrc/sumtree.hip
-  + the NEXT step's prioritized sample           rmsprop_sample_kernel)
+  + the NEXT step's prioritized sample           rmsprop_sample_kernel; Runtime.optimizer =
+                                                 adam and the lr / IS-exponent schedules are
+                                                 variants of the same launch that read the
+                                                 update index on the device, learner/schedules.py)
 
 Precision (``Runtime.dtype``):
   * ``fp32`` (default, the reference's precision: ``learner.py:37-38`` ``.float()``,
@@ -51,6 +54,7 @@ from ..utils.checkpoint import (adopt_obs_scale, layout_segments, load_checkpoin
                                 save_checkpoint, unpack_flat_state, checkpoint_network)
 from .dp_step import DataParallelStep, Streams
 from .is_norm import IsNormMixin
+from .schedules import StepIndexMixin
 
 
 def _enable_sharding(replay, comm, rt, mcap: int = 0) -> None:
@@ -81,7 +85,7 @@ def dp_layout(cfg: ApexConfig, comm, batch_size: Optional[int] = None, allow_for
     return world, dp, rows, mcap
 
 
-class FusedNatureLearner(IsNormMixin, DataParallelStep):
+class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
     kind = "fused"
 
     def __init__(self, cfg: ApexConfig, device, replay, comm=None, backend: Optional[str] = None,
@@ -255,6 +259,9 @@ class FusedNatureLearner(IsNormMixin, DataParallelStep):
         self._sample_ver = None
         self._setup_frag_out()
         self._fit_rows()          # global batch: rows for the largest shard's share (dp_step.py)
+        # device-resident update index, Runtime.optimizer, lr / IS-exponent schedules
+        # (learner/schedules.py): read inside the captured step, no host round trip
+        self._init_step_index()
         ls = cfg.Learner.load_saved_state
         if ls:
             self.load(ls)
@@ -546,7 +553,7 @@ class FusedNatureLearner(IsNormMixin, DataParallelStep):
                       wnorm=self._wnorm(), **self._lo(pb_lo=self.pbf_lo),
                       **({"frag_out": self._frag_out} if (self._frag_out is not None and nxt is not None) else {}),
                       **({"segs": segs} if segs is not None else {}),
-                      **({"norm_prefix": norm_prefix} if norm_prefix is not None else {}))
+                      **({"norm_prefix": norm_prefix} if norm_prefix is not None else {}), **self._opt_kw())
         if self._presample:
             self._sample_ver = self.replay.version
         self._mark("optimizer")
@@ -994,7 +1001,8 @@ class FusedNatureLearner(IsNormMixin, DataParallelStep):
         self._check_materialized()
         tgt = flat_to_reference_state(self.T, self.c1)
         save_checkpoint(path, self.reference_state_dict(), Q_target_state=tgt,
-                        optimizer_state=pack_flat_state(layout_segments(self.layout), rms_v=self.rms_v, rms_m=self.rms_m),
+                        optimizer_state=pack_flat_state(layout_segments(self.layout), kind=self._opt_kind(),
+                                                        rms_v=self.rms_v, rms_m=self.rms_m),
                         num_q_updates=self.num_q_updates, config=self.cfg.to_dict(),
                         rng={"replay_ctr": int(self.replay.ctr.item()), "replay_seed": int(self.replay.seed)},
                         **(extra or {}))
@@ -1015,10 +1023,13 @@ class FusedNatureLearner(IsNormMixin, DataParallelStep):
             self.sync_target()
         opt = ck.get("optimizer_state")
         unpack_flat_state(opt, layout_segments(self.layout), untagged_network=checkpoint_network(ck),
-                          network=self.cfg.network, rms_v=self.rms_v, rms_m=self.rms_m)
+                          network=self.cfg.network, kind=self._opt_kind(), rms_v=self.rms_v, rms_m=self.rms_m)
         self.num_q_updates = int(ck.get("num_q_updates", 0))
         rng = ck.get("rng")
         if isinstance(rng, dict) and "replay_ctr" in rng:
             self.replay.ctr.fill_(int(rng["replay_ctr"]))
+        self._sync_update_index()
+        if self._presample and (self._opt is not None or self.replay.beta_sched is not None):
+            self._sample_ver = None              # the pre-drawn batch carries another update's IS exponent
         self._last_ckpt = ck
         return True

@@ -31,6 +31,7 @@ import torch
 from ..config import ApexConfig
 from ..models.dueling import build_network
 from ..ops.fused_ops import HipBackend, TorchBackend
+from .schedules import StepIndexMixin
 from ..utils.checkpoint import (adopt_obs_scale, checkpoint_network, load_checkpoint, pack_flat_state, save_checkpoint,
                                 unpack_flat_state)
 from .fused_learner import _enable_sharding, dp_layout
@@ -52,7 +53,7 @@ def _flatten_module(module: torch.nn.Module, device) -> torch.Tensor:
     return flat
 
 
-class GraphLearner:
+class GraphLearner(StepIndexMixin):
     kind = "graph"
 
     def __init__(self, cfg: ApexConfig, device, replay, comm=None, batch_size: Optional[int] = None):
@@ -101,6 +102,7 @@ class GraphLearner:
             replay.gather_shard_stats()
         self.num_q_updates = 0
         self._graphs: Optional[List[torch.cuda.CUDAGraph]] = None
+        self._init_step_index()     # update index, Runtime.optimizer, schedules (learner/schedules.py)
         ls = cfg.Learner.load_saved_state
         if ls:
             self.load(ls)
@@ -139,10 +141,14 @@ class GraphLearner:
 
     def _apply(self) -> None:
         rt = self.rt
+        if self._opt is not None:
+            # the write-back bumps the update index: ahead of an optimizer launch that reads it
+            self.replay.update_priorities(self.S["idx"], self.td_abs, self.S["gen"])
         self.ops.optimizer(self.p32, self.g32, self.rms_v, self.rms_m, self.pbf, rt.lr, rt.rms_decay, rt.rms_eps,
                            rt.grad_clip, rt.centered_rmsprop, self.partials, self.gnorm,
-                           wnorm=(self.wmax, 1, 1) if self._is_bmax else None)
-        self.replay.update_priorities(self.S["idx"], self.td_abs, self.S["gen"])
+                           wnorm=(self.wmax, 1, 1) if self._is_bmax else None, **self._opt_kw())
+        if self._opt is None:
+            self.replay.update_priorities(self.S["idx"], self.td_abs, self.S["gen"])
 
     def _allreduce(self) -> None:
         import torch.distributed as dist
@@ -248,7 +254,8 @@ class GraphLearner:
 
     def save(self, path: str, extra: Optional[Dict] = None) -> None:
         save_checkpoint(path, self.Q.state_dict(), Q_target_state=self.Q_target.state_dict(),
-                        optimizer_state=pack_flat_state(self._segments(), rms_v=self.rms_v, rms_m=self.rms_m),
+                        optimizer_state=pack_flat_state(self._segments(), kind=self._opt_kind(), rms_v=self.rms_v,
+                                                        rms_m=self.rms_m),
                         num_q_updates=self.num_q_updates, config=self.cfg.to_dict(),
                         rng={"replay_ctr": int(self.replay.ctr.item()), "replay_seed": int(self.replay.seed)},
                         **(extra or {}))
@@ -271,9 +278,10 @@ class GraphLearner:
             else:
                 self.sync_target()
             unpack_flat_state(ck.get("optimizer_state"), self._segments(), untagged_network=checkpoint_network(ck),
-                              network=self.cfg.network, rms_v=self.rms_v, rms_m=self.rms_m)
+                              network=self.cfg.network, kind=self._opt_kind(), rms_v=self.rms_v, rms_m=self.rms_m)
         self.num_q_updates = int(ck.get("num_q_updates", 0))
         rng = ck.get("rng")
         if isinstance(rng, dict) and "replay_ctr" in rng:
             self.replay.ctr.fill_(int(rng["replay_ctr"]))
+        self._sync_update_index()
         return True

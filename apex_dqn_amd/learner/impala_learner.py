@@ -43,6 +43,7 @@ from ..utils.checkpoint import (adopt_obs_scale, layout_segments, load_checkpoin
 from ..ops.switches import SW
 from .fused_learner import _enable_sharding, dp_layout
 from .is_norm import IsNormMixin
+from .schedules import StepIndexMixin
 
 CH = (16, 32, 32)
 HIDDEN = 256
@@ -67,7 +68,7 @@ def fc_column_perm(device=None) -> torch.Tensor:
     return k.reshape(-1).to(device)
 
 
-class FusedImpalaLearner(IsNormMixin):
+class FusedImpalaLearner(IsNormMixin, StepIndexMixin):
     kind = "impala"
 
     def __init__(self, cfg: ApexConfig, device, replay, comm=None, backend: Optional[str] = None,
@@ -181,6 +182,7 @@ class FusedImpalaLearner(IsNormMixin):
         if self.world > 1:
             _enable_sharding(replay, comm, self.rt, self.mcap)
             replay.gather_shard_stats()
+        self._init_step_index()     # update index, Runtime.optimizer, schedules (learner/schedules.py)
         ls = cfg.Learner.load_saved_state
         if ls:
             self.load(ls)
@@ -436,7 +438,7 @@ class FusedImpalaLearner(IsNormMixin):
         nxt = (self.replay, self.B, self.S, self.slots[2 * self.B:]) if self._presample else None
         ops.optimizer(self.p32, self.g32, self.rms_v, self.rms_m, self.pbf, rt.lr, rt.rms_decay, rt.rms_eps,
                       rt.grad_clip, rt.centered_rmsprop, self.partials, self.gnorm, sample=nxt, wnorm=self._wnorm(),
-                      **self._lo(pb_lo=self.pbf_lo))
+                      **self._lo(pb_lo=self.pbf_lo), **self._opt_kw())
         if self._presample:
             self._sample_ver = self.replay.version
 
@@ -661,7 +663,8 @@ class FusedImpalaLearner(IsNormMixin):
 
     def save(self, path: str, extra: Optional[Dict] = None) -> None:
         save_checkpoint(path, self.module_state(), Q_target_state=self.module_state(self.T),
-                        optimizer_state=pack_flat_state(layout_segments(self.layout), rms_v=self.rms_v, rms_m=self.rms_m),
+                        optimizer_state=pack_flat_state(layout_segments(self.layout), kind=self._opt_kind(),
+                                                        rms_v=self.rms_v, rms_m=self.rms_m),
                         num_q_updates=self.num_q_updates, config=self.cfg.to_dict(),
                         rng={"replay_ctr": int(self.replay.ctr.item()), "replay_seed": int(self.replay.seed)},
                         **(extra or {}))
@@ -682,9 +685,12 @@ class FusedImpalaLearner(IsNormMixin):
             self.sync_target()
         opt = ck.get("optimizer_state")
         unpack_flat_state(opt, layout_segments(self.layout), untagged_network=checkpoint_network(ck),
-                          network=self.cfg.network, rms_v=self.rms_v, rms_m=self.rms_m)
+                          network=self.cfg.network, kind=self._opt_kind(), rms_v=self.rms_v, rms_m=self.rms_m)
         self.num_q_updates = int(ck.get("num_q_updates", 0))
         rng = ck.get("rng")
         if isinstance(rng, dict) and "replay_ctr" in rng:
             self.replay.ctr.fill_(int(rng["replay_ctr"]))
+        self._sync_update_index()
+        if self._presample and (self._opt is not None or self.replay.beta_sched is not None):
+            self._sample_ver = None              # the pre-drawn batch carries another update's IS exponent
         return True

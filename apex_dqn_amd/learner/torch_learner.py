@@ -21,9 +21,12 @@ from ..config import ApexConfig
 from ..models.dueling import build_network
 from ..utils.checkpoint import adopt_obs_scale, load_checkpoint, save_checkpoint
 from .losses import ddqn_loss
+from .schedules import lr_scheduled, rt_lr
 
 
 def make_optimizer(params, rt) -> torch.optim.Optimizer:
+    if getattr(rt, "optimizer", "rmsprop") == "adam":
+        return torch.optim.Adam(params, lr=rt.lr, betas=(rt.adam_beta1, rt.adam_beta2), eps=rt.adam_eps)
     return torch.optim.RMSprop(params, lr=rt.lr, alpha=rt.rms_decay, eps=rt.rms_eps,
                                centered=rt.centered_rmsprop)
 
@@ -83,6 +86,9 @@ class TorchLearner:
         gnorm = 0.0
         if self.rt.grad_clip and self.rt.grad_clip > 0:
             gnorm = float(torch.nn.utils.clip_grad_norm_(self.Q.parameters(), self.rt.grad_clip))
+        if lr_scheduled(self.rt):
+            for gr in self.optimizer.param_groups:
+                gr["lr"] = rt_lr(self.rt, self.num_q_updates)
         self.optimizer.step()
         self.num_q_updates += 1
         if self.num_q_updates % self.cfg.Learner.q_target_sync_freq == 0:
@@ -105,7 +111,7 @@ class TorchLearner:
         ex: Dict[str, Any] = {}
         if extras:
             ex = dict(Q_target_state=self.Q_target.state_dict(),
-                      optimizer_state=self.optimizer.state_dict(),
+                      optimizer_state=self.optimizer.state_dict(), optimizer_kind=str(self.rt.optimizer),
                       num_q_updates=self.num_q_updates,
                       config=self.cfg.to_dict())
         save_checkpoint(path, self.Q.state_dict(), **ex)
@@ -124,6 +130,11 @@ class TorchLearner:
         else:
             self.sync_target()
         if "optimizer_state" in ck:
-            self.optimizer.load_state_dict(ck["optimizer_state"])
+            saved = str(ck.get("optimizer_kind", "rmsprop"))     # (untagged / older: rmsprop)
+            if saved == self.rt.optimizer:
+                self.optimizer.load_state_dict(ck["optimizer_state"])
+            else:
+                print(f"WARNING: checkpoint optimizer state is {saved} state, this learner runs "
+                      f"{self.rt.optimizer}; optimizer state not restored (starts fresh)")
         self.num_q_updates = int(ck.get("num_q_updates", 0))
         return True

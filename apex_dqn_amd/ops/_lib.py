@@ -70,6 +70,19 @@ class RmsSegs(ctypes.Structure):
     _fields_ = [("nseg", c_i), ("blk0", c_i * 4), ("off", c_i64 * 3), ("len", c_i64 * 3)]
 
 
+class OptSched(ctypes.Structure):
+    """Update index, lr schedule and Adam constants of an optimizer launch (``OptSched``,
+    csrc/rmsprop_common.h); all-zero = RMSprop with the learning rate passed by value."""
+    _fields_ = [("ctr", c_p), ("base", c_p), ("adam", c_i), ("warmup", c_i64), ("decay", c_i64),
+                ("lr0", ctypes.c_double), ("lr_end", ctypes.c_double), ("beta1", ctypes.c_double),
+                ("beta2", ctypes.c_double)]
+
+
+class BetaSched(ctypes.Structure):
+    """Annealed IS exponent of a draw (``BetaSched``, csrc/sumtree.hip); all-zero = off."""
+    _fields_ = [("ubase", c_p), ("beta0", ctypes.c_double), ("beta_end", ctypes.c_double), ("steps", c_i64)]
+
+
 class C2dPack(ctypes.Structure):
     """conv2 weight-fragment pack job riding on another launch (``C2dPackJob``, csrc/conv2_wfrag.h)."""
     _fields_ = [("w", c_p), ("w_lo", c_p), ("out", c_p)]
@@ -136,26 +149,26 @@ _SIGS = {
     "apex_replay_insert": ([TreeDesc, RecordDesc, c_i64, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_p],
                            c_i),
     "apex_tree_sample": ([TreeDesc, RecordDesc, c_i, c_u64, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                          c_p, c_p, c_p, c_i, c_i, c_u64, c_p, c_i64, c_p], c_i),
+                          c_p, c_p, c_p, c_i, c_i, c_u64, c_p, c_i64, BetaSched, c_p], c_i),
     "apex_tree_rebuild": ([TreeDesc, c_p], c_i),
     "apex_gather_frames": ([c_p, c_p, c_i, c_i64, c_i64, c_p, c_p], c_i),
     "apex_debug_bounds_enabled": ([], c_i),
     "apex_debug_errors": ([c_p, c_p, c_i], c_i),
     "apex_grad_sqnorm_partials": ([c_p, c_i64, c_p, c_p], c_i),
     "apex_rmsprop_step": ([c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_f, c_f, c_f, c_f, c_i, c_p, c_p, c_p, c_i, c_i,
-                           c_p], c_i),
+                           OptSched, c_p], c_i),
     "apex_cast_bf16": ([c_p, c_p, c_i64, c_p, c_p], c_i),
     "apex_spin_hold": ([c_i, c_i, c_i, c_p, c_p], c_i),
     "apex_rmsprop_step_np": ([c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i, c_f, c_f, c_f, c_f, c_i, c_p, c_p, c_p,
-                              c_i, c_i, c_p], c_i),
+                              c_i, c_i, OptSched, c_p], c_i),
     "apex_grad_finalize": ([FinalizeDesc, c_p], c_i),
     "apex_norm_total": ([c_p, c_i, c_p, c_p], c_i),
     "apex_ddqn_head": ([c_p, c_p, HeadParams, HeadParams, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p,
                         c_p, c_p, c_p, c_p, c_p, c_i, c_i, HeadLo, HeadPart, C2dPack, IsNorm, c_p], c_i),
     "apex_rmsprop_sample": ([c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i, c_f, c_f, c_f, c_f, c_i, c_p,
                              TreeDesc, RecordDesc, c_i, c_u64, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                             c_p, c_p, c_i, c_i, c_u64, c_p, c_i64, c_p, c_p, c_i, c_i, CfFragOut, c_p, c_p, c_i64,
-                             c_p], c_i),
+                             c_p, c_p, c_i, c_i, c_u64, c_p, c_i64, BetaSched, c_p, c_p, c_i, c_i, CfFragOut, c_p,
+                             c_p, c_i64, OptSched, c_p], c_i),
     "apex_head_wgrad_prio": ([c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, TreeDesc, c_p, c_p, c_p, c_p, c_f, c_f,
                               c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_i64, c_p], c_i),
     "apex_fc_wgrad_head_prio": ([WgradDesc, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, TreeDesc, c_p, c_p, c_p,
@@ -190,7 +203,7 @@ def _declare(lib: ctypes.CDLL) -> None:
     conv_sigs.declare(lib)
 
 
-ABI_VERSION = 9     # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
+ABI_VERSION = 10    # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
 
 
 def load(build_if_missing: bool = True) -> Optional[ctypes.CDLL]:

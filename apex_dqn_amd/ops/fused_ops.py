@@ -21,6 +21,7 @@ from __future__ import annotations
 import ctypes
 from typing import Dict, Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -298,7 +299,7 @@ class TorchBackend:
 
     # ----------------------------------------------------------- optimizer
     def optimizer(self, p32, g32, v, m, pbf, lr, alpha, eps, clip, centered, partials, norm_out, norm_total=None,
-                  sample=None, pb_lo=None, wnorm=None, frag_out=None, segs=None, norm_prefix=None):
+                  sample=None, pb_lo=None, wnorm=None, frag_out=None, segs=None, norm_prefix=None, opt=None):
         """``sample = (replay, B, out, nxt2)``: also draw the next
         batch after the update (the HIP backend fuses it into the optimizer launch).
         ``pb_lo``: split mode, the lo plane of the bf16 copy.  ``wnorm = (stats, n,
@@ -308,16 +309,26 @@ class TorchBackend:
         partials written by the gradient producers) instead of a pass over ``g32``.
         ``segs``: [(offset, length), ...] -- update only these ranges of the flat arrays
         (the sharded data-parallel update; needs ``norm_total``).  ``norm_prefix``: a
-        gradient range whose squares join the partials' sum (summed inside the launch)."""
+        gradient range whose squares join the partials' sum (summed inside the launch).
+        ``opt`` (learner/schedules.py ``OptSpec``): Adam instead of RMSprop (``v`` / ``m`` hold
+        the second / first moment; ``alpha``, ``eps`` and ``centered`` are unused) and / or
+        the step-indexed learning rate, both from the update index on the device."""
         self._optimizer(p32, g32, v, m, pbf, lr, alpha, eps, clip, centered, norm_out, pb_lo, wnorm, norm_total,
-                        segs, norm_prefix)
+                        segs, norm_prefix, opt)
         if sample is not None:
             rp, B, out, nxt2 = sample
             rp.sample(B, out=out, nxt2=nxt2)
 
     def _optimizer(self, p32, g32, v, m, pbf, lr, alpha, eps, clip, centered, norm_out, pb_lo=None, wnorm=None,
-                   norm_total=None, segs=None, norm_prefix=None):
+                   norm_total=None, segs=None, norm_prefix=None, opt=None):
         sc = torch.ones((), dtype=torch.float32, device=g32.device)
+        adam = opt is not None and opt.adam
+        if opt is not None:       # tensor ops only: the index is read on the device
+            lr = opt.lr_tensor().to(g32.device)
+        if adam:
+            c1, c2 = (c.to(g32.device) for c in opt.corrections())
+            b1, b2 = float(np.float32(opt.beta1)), float(np.float32(opt.beta2))
+            d1, d2 = float(np.float32(1) - np.float32(opt.beta1)), float(np.float32(1) - np.float32(opt.beta2))
         if wnorm is not None:     # tensor ops only: no host sync (graph-capturable)
             st, n, stride = wnorm
             mx = st.reshape(-1)[0:n * stride:stride].max().float()
@@ -336,6 +347,12 @@ class TorchBackend:
             r = slice(o, o + n)
             g = g32[r] * (coef * sc)
             vr, mr, pr = v[r], m[r], p32[r]
+            if adam:
+                mr.mul_(b1).add_(d1 * g)
+                vr.mul_(b2).add_(d2 * g * g)
+                pr.sub_(lr * (mr / c1) / ((vr / c2).sqrt() + opt.adam_eps))
+                split_into(pr, pbf[r], None if pb_lo is None else pb_lo[r])
+                continue
             vr.mul_(alpha).add_((1 - alpha) * g * g)
             if centered:
                 mr.mul_(alpha).add_((1 - alpha) * g)
@@ -610,13 +627,27 @@ class HipBackend(TorchBackend):
                                             ctr.data_ptr(), q_out.data_ptr(), a_out.data_ptr(),
                                             P["wv"].numel(), _lib.ptr(H_lo), _lib.stream_ptr()), "actor_head")
 
+    @staticmethod
+    def _opt_sched(opt) -> "_lib.OptSched":
+        """``OptSched`` of an ``OptSpec`` (all-zero for None: RMSprop, lr by value)."""
+        os_ = _lib.OptSched()
+        if opt is not None:
+            os_.ctr, os_.base, os_.adam = opt.ctr.data_ptr(), opt.base.data_ptr(), int(opt.adam)
+            os_.warmup, os_.decay = int(opt.warmup), int(opt.decay)
+            os_.lr0, os_.lr_end = float(opt.lr), float(opt.lr if opt.lr_end is None else opt.lr_end)
+            os_.beta1, os_.beta2 = float(opt.beta1), float(opt.beta2)
+        return os_
+
     def optimizer(self, p32, g32, v, m, pbf, lr, alpha, eps, clip, centered, partials, norm_out, norm_total=None,
-                  sample=None, pb_lo=None, wnorm=None, frag_out=None, segs=None, norm_prefix=None) -> bool:
+                  sample=None, pb_lo=None, wnorm=None, frag_out=None, segs=None, norm_prefix=None, opt=None) -> bool:
         """``frag_out`` (ops/conv.py conv12_frag_out): the launch also stores the updated
         w1 / w2 in the fused forward's fragment order.  Returns whether it did (the fused
         optimizer + sample launch only).  ``segs``: the ranges to update (the sharded DP
         update: one launch, csrc/sumtree.hip ``RmsSegs``)."""
         n = p32.numel()
+        osd = self._opt_sched(opt)
+        if opt is not None and opt.adam:
+            eps = opt.adam_eps        # (RmspropArgs.eps carries Adam's epsilon)
         if segs is not None:
             if norm_total is None:
                 raise ValueError("a sharded update needs the clip norm's partials (norm_total)")
@@ -649,13 +680,14 @@ class HipBackend(TorchBackend):
                 p32.data_ptr(), g32.data_ptr(), v.data_ptr(), m.data_ptr(), pbf.data_ptr(), n, part.data_ptr(), npart,
                 float(lr), float(alpha), float(eps), float(clip), int(centered), norm_out.data_ptr(),
                 *rp.sample_launch_args(B, out, nxt2), lo, *wn, frag_out if frag_out is not None else _lib.CfFragOut(),
-                segp, _lib.ptr(norm_prefix), 0 if norm_prefix is None else norm_prefix.numel(), st), "rmsprop_sample")
+                segp, _lib.ptr(norm_prefix), 0 if norm_prefix is None else norm_prefix.numel(), osd, st),
+                "rmsprop_sample")
             return frag_out is not None
         if norm_prefix is not None:
             raise ValueError("norm_prefix runs in the fused optimizer + sample launch")
         if sample is not None:
             self.optimizer(p32, g32, v, m, pbf, lr, alpha, eps, clip, centered, partials, norm_out, norm_total,
-                           pb_lo=pb_lo, wnorm=wnorm)
+                           pb_lo=pb_lo, wnorm=wnorm, opt=opt)
             rp, B, out, nxt2 = sample
             rp.sample(B, out=out, nxt2=nxt2)
             return
@@ -664,13 +696,13 @@ class HipBackend(TorchBackend):
             _lib.check(self.lib.apex_rmsprop_step_np(p32.data_ptr(), g32.data_ptr(), v.data_ptr(), m.data_ptr(),
                                                      pbf.data_ptr(), n, part.data_ptr(), npart, float(lr),
                                                      float(alpha), float(eps), float(clip), int(centered),
-                                                     norm_out.data_ptr(), lo, *wn, st), "rmsprop_np")
+                                                     norm_out.data_ptr(), lo, *wn, osd, st), "rmsprop_np")
             return
         _lib.check(self.lib.apex_grad_sqnorm_partials(g32.data_ptr(), n, partials.data_ptr(), st), "sqnorm")
         _lib.check(self.lib.apex_rmsprop_step(p32.data_ptr(), g32.data_ptr(), v.data_ptr(), m.data_ptr(),
                                               pbf.data_ptr(), n, partials.data_ptr(), float(lr), float(alpha),
                                               float(eps), float(clip), int(centered), norm_out.data_ptr(), lo, *wn,
-                                              st),
+                                              osd, st),
                    "rmsprop")
 
     def _pack_args(self, dst: torch.Tensor, segs):

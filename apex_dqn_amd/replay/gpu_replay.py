@@ -197,6 +197,33 @@ class GpuReplayShard:
         self.shard_mcap = 0     # cap on a draw's global batch M (0: W x the per-rank batch)
         self.local_stats = None
         self.shard_stats = None
+        self.beta_sched = None  # (base, beta_end, steps): annealed IS exponent (set_beta_schedule)
+
+    # ------------------------------------------------------------ IS exponent
+    def set_beta_schedule(self, base: Optional[torch.Tensor], beta_end: Optional[float] = None, steps: int = 0) -> None:
+        """Anneal the IS exponent from ``beta`` to ``beta_end`` over ``steps`` learner updates:
+        a draw uses beta(u), u = ``ctr`` - ``base`` at the time of the draw (``base``: the
+        learner's int64 device word holding the counter's value at update 0; the learner's
+        priority write-back bumps ``ctr`` once per update, so a draw at the head of update u
+        and the pre-sample inside update u - 1's optimizer launch both see u;
+        learner/schedules.py ``beta_at``).  ``base`` None: constant ``beta``."""
+        self.beta_sched = None if (base is None or beta_end is None) else (base, float(beta_end), int(steps))
+
+    def _beta_sched_arg(self) -> "_lib.BetaSched":
+        bs = _lib.BetaSched()
+        if self.beta_sched is not None:
+            base, end, steps = self.beta_sched
+            bs.ubase, bs.beta0, bs.beta_end, bs.steps = base.data_ptr(), float(self.beta), end, steps
+        return bs
+
+    def beta_tensor(self) -> torch.Tensor:
+        """The IS exponent of a draw made now, as an fp32 tensor (tensor operations only)."""
+        if self.beta_sched is None:
+            return torch.tensor(self.beta, dtype=torch.float32, device=self.device)
+        base, end, steps = self.beta_sched
+        u = (self.ctr.reshape(-1)[0] - base.reshape(-1)[0]).clamp_min(0).double()
+        f = torch.clamp(u / float(steps), max=1.0) if steps > 0 else torch.ones_like(u)
+        return (torch.full_like(u, self.beta) + (end - self.beta) * f).float()
 
     # -------------------------------------------------------------- sharding
     def enable_sharding(self, rank: int, world: int, shard_seed: int, group=None, mcap: int = 0) -> None:
@@ -480,8 +507,14 @@ class GpuReplayShard:
             idx[empty] = nz[-1] if nz.numel() else 0
         p = leaf[idx].float()
         vt = torch.from_numpy(valid)
-        w = torch.where(vt & (p > 0) & (pmin > 0), (p / max(pmin, 1e-38)).pow(-self.beta).clamp(max=1.0),
-                        torch.zeros_like(p)) * wscale
+        if self.beta_sched is None:
+            w = torch.where(vt & (p > 0) & (pmin > 0), (p / max(pmin, 1e-38)).pow(-self.beta).clamp(max=1.0),
+                            torch.zeros_like(p)) * wscale
+        else:
+            # the annealed exponent stays a device tensor (no read-back of the update index)
+            ok = (vt & (p > 0) & (pmin > 0)).to(d)
+            ratio = (p / max(pmin, 1e-38)).to(d)
+            w = torch.where(ok, ratio.pow(-self.beta_tensor()).clamp(max=1.0), torch.zeros_like(ratio)) * wscale
         idx = idx.to(d)
         out["idx"].copy_(idx)
         out["weights"].copy_(w.float())
@@ -504,7 +537,7 @@ class GpuReplayShard:
                 out["idx"].data_ptr(), out["weights"].data_ptr(), out["gen"].data_ptr(), out["obs"].data_ptr(),
                 out["nxt"].data_ptr(), out["act"].data_ptr(), out["rew"].data_ptr(), out["gam"].data_ptr(),
                 _lib.ptr(nxt2), _lib.ptr(self.shard_stats), self.shard_rank, self.shard_world, self.shard_seed,
-                _lib.ptr(out.get("wscale")), int(self.shard_mcap))
+                _lib.ptr(out.get("wscale")), int(self.shard_mcap), self._beta_sched_arg())
 
     def alloc_sample_buffers(self, B: int) -> Dict[str, torch.Tensor]:
         d = self.device

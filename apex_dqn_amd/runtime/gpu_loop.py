@@ -370,6 +370,7 @@ def _log(metrics, learner, group, replay, st: "_LoopState", rt, world: int, devi
     metrics.log("learner", step=n, loss=m["loss"], td_abs=m["td_abs_mean"], grad_norm=m["grad_norm"],
                 is_weight_mean=m.get("is_weight_mean", float(learner.S["weights"].mean())),
                 valid_rows=m.get("valid_rows", learner.B),
+                **(learner.schedule_metrics() if hasattr(learner, "schedule_metrics") else {}),
                 learner_kind=getattr(learner, "kind", "fused"),
                 replay=replay.size(), actor_steps=st.actor_steps, inserted=group.inserted,
                 episodes=len(eps_list),

@@ -29,6 +29,7 @@ import torch
 from ..actors.actor_group import ActorGroup, HostFrameStore
 from ..config import ApexConfig
 from ..envs.vector_envs import make_vec_env
+from ..learner.schedules import rt_lr
 from ..learner.torch_learner import TorchLearner
 from ..models.dueling import build_network
 from ..replay.host_replay import PrioritizedReplay
@@ -86,7 +87,9 @@ def train_inline(cfg: ApexConfig, learner_steps: int, device="cpu",
                 replay.remove_to_fit()
             if metrics is not None and learner.num_q_updates % cfg.Runtime.log_every == 0:
                 metrics.log("learner", step=learner.num_q_updates, loss=out["loss"],
-                            replay=replay.size(), grad_norm=out["grad_norm"])
+                            replay=replay.size(), grad_norm=out["grad_norm"],
+                            lr=rt_lr(cfg.Runtime, learner.num_q_updates - 1),
+                            is_beta=float(cfg.Replay_Memory.importance_sampling_exponent))
             ck = cfg.Runtime
             if ck.ckpt_dir and ck.ckpt_freq and learner.num_q_updates % ck.ckpt_freq == 0:
                 learner.save(os.path.join(ck.ckpt_dir, "checkpoint.pt"))
@@ -197,7 +200,9 @@ def train_multiprocess(cfg: ApexConfig, learner_steps: int, num_procs: Optional[
                 replay.remove_to_fit()
             if metrics is not None and learner.num_q_updates % cfg.Runtime.log_every == 0:
                 metrics.log("learner", step=learner.num_q_updates, loss=out["loss"],
-                            replay=replay.size(), restarts=restarts)
+                            replay=replay.size(), restarts=restarts,
+                            lr=rt_lr(cfg.Runtime, learner.num_q_updates - 1),
+                            is_beta=float(cfg.Replay_Memory.importance_sampling_exponent))
     finally:
         stop_evt.set()
         for p in procs:

@@ -38,20 +38,28 @@ def load_checkpoint(path: str) -> Optional[Dict[str, Any]]:
         return None
 
 
-def pack_flat_state(segments: Segments, **flats: torch.Tensor) -> Dict[str, Any]:
+def pack_flat_state(segments: Segments, kind: Optional[str] = None, **flats: torch.Tensor) -> Dict[str, Any]:
     """Per-parameter state kept in a flat buffer (RMSprop's ``rms_v`` / ``rms_m``), saved
     per named segment with the layout it came from: a later engine whose flat layout
     orders or pads the segments differently still restores every value to its parameter
-    (:func:`unpack_flat_state`)."""
+    (:func:`unpack_flat_state`).  ``kind``: the update rule the state belongs to
+    (``Runtime.optimizer``: Adam keeps its moments in the same buffers)."""
     out: Dict[str, Any] = {"layout": [[str(n), int(o), int(k)] for n, o, k in segments]}
+    if kind is not None:
+        out["kind"] = str(kind)
     for key, flat in flats.items():
         f = flat.detach().cpu()
         out[key] = {n: f[o:o + k].clone() for n, o, k in segments}
     return out
 
 
+def optimizer_state_kind(opt: Any) -> str:
+    """The update rule a saved optimizer state belongs to (untagged / older: ``rmsprop``)."""
+    return str(opt.get("kind", "rmsprop")) if isinstance(opt, dict) else "rmsprop"
+
+
 def unpack_flat_state(opt: Any, segments: Segments, untagged_network: Optional[str] = None,
-                      network: Optional[str] = None, **dsts: torch.Tensor) -> bool:
+                      network: Optional[str] = None, kind: Optional[str] = None, **dsts: torch.Tensor) -> bool:
     """Restore :func:`pack_flat_state` output into the flat buffers ``dsts`` of the current
     layout ``segments``.  State whose segments do not match by name and size is refused
     (returns False, with a warning, buffers untouched): the caller then starts the optimizer
@@ -63,8 +71,17 @@ def unpack_flat_state(opt: Any, segments: Segments, untagged_network: Optional[s
     current flat buffer's length: this engine's flat layout (``models/flat_params.py``
     nature segments and their padding) has not changed since, so the vector is the buffer.
     Dropping it instead would restart centered RMSprop at v = m = 0 -- a several-times
-    larger step on every parameter in mid-training."""
+    larger step on every parameter in mid-training.
+
+    ``kind``: the current update rule.  State saved by another rule (its ``kind`` tag;
+    none = ``rmsprop``) is not restored: the same buffers would mean other statistics."""
     if not isinstance(opt, dict) or not dsts:
+        return False
+    if kind is not None and optimizer_state_kind(opt) != kind:
+        print(f"WARNING: checkpoint optimizer state is {optimizer_state_kind(opt)} state, this learner runs "
+              f"{kind}; optimizer state not restored (starts fresh)")
+        for dst in dsts.values():
+            dst.zero_()
         return False
     if "layout" not in opt:
         raw = all(isinstance(opt.get(key), torch.Tensor) and opt[key].numel() == dst.numel()
