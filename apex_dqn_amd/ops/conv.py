@@ -445,6 +445,47 @@ def conv3_dgrad_img(lib, dy: torch.Tensor, w3: torch.Tensor, mask: torch.Tensor,
     _lib.check(lib.apex_conv3_dgrad_img(d, int(grid), _lib.stream_ptr()), "conv3_dgrad_img")
 
 
+def conv3_dgrad_img_split_covers(dy_shape, w_shape, out_shape, split: bool) -> bool:
+    """Whether the split-mode image-resident conv3 data gradient
+    (csrc/conv3_dgrad_img_split.hip) covers the problem: hi + lo planes, 64 -> 64 channels,
+    3x3 / stride 1, 7x7 -> 9x9."""
+    N = dy_shape[0]
+    return bool(split) and N >= 1 and tuple(dy_shape) == (N, 7, 7, 64) and tuple(w_shape) == (64, 3, 3, 64) and \
+        tuple(out_shape) == (N, 9, 9, 64)
+
+
+def conv3_dgrad_img_split_pick(dy_shape, w_shape, out_shape, split: bool, force: Optional[bool] = None) -> bool:
+    """The split conv3 data gradient's kernel: the image-resident one (True) where it
+    covers the problem, ``SW.conv3_dgrad_img_split`` is on and the batch has at least
+    ``SW.conv3_dgrad_img_split_min`` images; the generic implicit GEMM otherwise.  ``force``
+    (tests, microbenchmarks) overrides the switch and the threshold, not the coverage."""
+    covers = conv3_dgrad_img_split_covers(dy_shape, w_shape, out_shape, split)
+    if force is not None:
+        if force and not covers:
+            raise ValueError("conv3_dgrad_img_split does not cover this problem")
+        return bool(force)
+    return covers and bool(SW.conv3_dgrad_img_split) and dy_shape[0] >= SW.conv3_dgrad_img_split_min
+
+
+def conv3_dgrad_img_split(lib, dy: torch.Tensor, dy_lo: torch.Tensor, w3: torch.Tensor, w_lo: torch.Tensor,
+                          mask: torch.Tensor, out: torch.Tensor, out_lo: torch.Tensor, grid: int = 0) -> None:
+    """Split-mode conv3 data gradient on the image-resident kernel
+    (csrc/conv3_dgrad_img_split.hip): eight waves own 16-channel x 48-pixel output tiles over
+    the full K with the hi + lo weight fragments in registers, dY3 hi / lo in LDS; the same
+    bits as the generic kernel's two planes.  ``grid``: workgroups (0: 256), capped to N."""
+    from .conv_sigs import Conv3DgradSplitDesc
+    N = dy.shape[0]
+    for t in (dy, dy_lo, w3, w_lo, mask, out, out_lo):
+        assert t.is_contiguous() and t.dtype == torch.bfloat16
+    assert dy_lo.shape == dy.shape and w_lo.shape == w3.shape and out_lo.shape == out.shape == mask.shape
+    d = Conv3DgradSplitDesc()
+    d.dy, d.dy_lo, d.w, d.w_lo = dy.data_ptr(), dy_lo.data_ptr(), w3.data_ptr(), w_lo.data_ptr()
+    d.mask, d.dx, d.dx_lo, d.N = mask.data_ptr(), out.data_ptr(), out_lo.data_ptr(), N
+    d.H, d.W, d.Cout = int(dy.shape[1]), int(dy.shape[2]), int(dy.shape[3])
+    d.Cin, d.KH, d.KW, d.stride = int(w3.shape[3]), int(w3.shape[1]), int(w3.shape[2]), 1
+    _lib.check(lib.apex_conv3_dgrad_img_split(d, int(grid), _lib.stream_ptr()), "conv3_dgrad_img_split")
+
+
 def conv3_dgrad(lib, dy: torch.Tensor, w3: torch.Tensor, mask: torch.Tensor, out: torch.Tensor, dy_lo=None,
                 w_lo=None, out_lo=None) -> None:
     """dX2 (9x9) from dY3 (7x7): full correlation with the flipped 3x3 weights, read
@@ -453,6 +494,9 @@ def conv3_dgrad(lib, dy: torch.Tensor, w3: torch.Tensor, mask: torch.Tensor, out
     assert w3.shape == (64, 3, 3, 64)
     if SW.conv3_dgrad_img and dy_lo is None and hasattr(lib, "apex_conv3_dgrad_img"):
         conv3_dgrad_img(lib, dy, w3, mask, out)
+        return
+    if conv3_dgrad_img_split_pick(dy.shape, w3.shape, out.shape, dy_lo is not None):
+        conv3_dgrad_img_split(lib, dy, dy_lo, w3, w_lo, mask, out, out_lo)   # a missing kernel is an error
         return
     d = _conv_desc(x=dy.data_ptr(), w=w3.data_ptr(), y=out.data_ptr(), mask=mask.data_ptr(), N=N, H=7, W=7,
                    Cin=64, OH=9, OW=9, Cout=64, KH=3, KW=3, stride=1, pad=2, mode=1, K=576,

@@ -51,6 +51,14 @@ class Conv3DgradImgDesc(ctypes.Structure):
     _fields_ = [("dy", c_p), ("w", c_p), ("mask", c_p), ("dx", c_p), ("N", c_i)]
 
 
+class Conv3DgradSplitDesc(ctypes.Structure):
+    """Split-mode image-resident conv3 data gradient (mirrors ``Conv3DgradSplitDesc`` in
+    csrc/conv3_dgrad_img_split.hip)."""
+    _fields_ = [("dy", c_p), ("dy_lo", c_p), ("w", c_p), ("w_lo", c_p), ("mask", c_p), ("dx", c_p),
+                ("dx_lo", c_p), ("N", c_i), ("H", c_i), ("W", c_i), ("Cout", c_i), ("Cin", c_i), ("KH", c_i),
+                ("KW", c_i), ("stride", c_i)]
+
+
 def declare(lib: ctypes.CDLL) -> None:
     from ._lib import ConvDesc, WgradDesc
     sigs = {
@@ -59,6 +67,7 @@ def declare(lib: ctypes.CDLL) -> None:
         "apex_conv12_pack": ([Conv12Desc, c_p], c_i),
         "apex_conv2_dgrad_img": ([Conv2DgradImgDesc, c_i, c_p], c_i),
         "apex_conv3_dgrad_img": ([Conv3DgradImgDesc, c_i, c_p], c_i),
+        "apex_conv3_dgrad_img_split": ([Conv3DgradSplitDesc, c_i, c_p], c_i),
         "apex_conv21_bwd_fused": ([Conv21BwdDesc, c_i, c_p], c_i),
         "apex_conv_fwd": ([ConvDesc, c_p], c_i),
         "apex_fc_gemm128": ([ConvDesc, c_p, c_i64, c_i, c_i, c_i, C2dPackJob, c_p], c_i),

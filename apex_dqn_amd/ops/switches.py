@@ -43,6 +43,20 @@ class Switches:
     # image-resident conv3 / conv2 data gradients (csrc/conv2_img.hip)
     conv3_dgrad_img: bool = True
     conv2_dgrad_img: bool = True
+    # split-mode conv3 data gradient on the image-resident kernel
+    # (csrc/conv3_dgrad_img_split.hip, the same bits as the generic implicit GEMM) for batches
+    # of at least conv3_dgrad_img_split_min images.  Isolated, 7 interleaved repeats of 50
+    # launches: 13.5-14.2 vs 21.0-21.9 us at 512 images, 8.9-9.5 vs 12.0-12.7 at 256, 8.3-8.6
+    # vs 10.2-10.6 at 146, 7.9-8.0 vs 9.9-10.1 at 74 (profiles/pr6_conv3_dgrad_isolated.txt).
+    # Inside the 512-row fp32 step 13.5 vs 22.8 us, and conv21_bwd_fused starts 18.5 instead of
+    # 27.4 us after it; 5 interleaved runs each of the parent and this tree: 2,928-2,967
+    # (median 2,950) vs 2,884-2,910 (2,894) updates/s at 200 / 20 steps, 2,932-2,967 (2,943) vs
+    # 2,876-2,917 (2,890) at 20 / 5 (profiles/pr6_ab_conv3_dgrad_img.txt).  Emulated rank
+    # steps, forced on vs off, 3 runs each: W = 8 (74 rows) 154.0-154.9 vs 158.6-161.1 us, W = 4
+    # (146 rows) 190.3-191.5 vs 192.3-195.6.  The threshold is the smallest size measured;
+    # below 74 images nobody has measured, so those keep the generic kernel
+    conv3_dgrad_img_split: bool = True
+    conv3_dgrad_img_split_min: int = 74
     # split conv2 data gradient: one workgroup per (image, stride-parity class) up to this
     # many images (0: never), per image above it
     conv2_dgrad_cls_max: int = 256
