@@ -267,8 +267,19 @@ class GpuActorGroup:
                 ops.conv_fwd(self.y2, Pb["w3"], P["b3"], 1, self.y3)
             ops.fc_fwd(self.y3.reshape(E, 3136), Pb["wfc"], P["bfc"], self.h, **ks)
         heads = {k: P[k] for k in ("wv", "bv", "wa", "ba")}
-        ops.actor_head(self.h, heads, self.eps, self.ctr, self.seed, self.q, self.act, H_lo=self.h_lo)
+        self._actor_head(self.h, heads, self.h_lo)
         self.ctr += 1
+
+    def _actor_head(self, h, heads, h_lo) -> None:
+        """q + epsilon-greedy draw into ``self.q`` / ``self.act``: the dueling head, or with a
+        distributional learner (``learner.N`` atoms) the expected q of its C51 head."""
+        n = int(getattr(self.learner, "N", 1))
+        if n >= 2:
+            rt = self.cfg.Runtime
+            self.ops.c51_actor_head(h, heads, self.eps, self.ctr, self.seed, n, rt.v_min, rt.v_max, self.q, self.act,
+                                    H_lo=h_lo)
+        else:
+            self.ops.actor_head(h, heads, self.eps, self.ctr, self.seed, self.q, self.act, H_lo=h_lo)
 
     def step(self) -> int:
         """One env step for all E envs; returns the number of transitions inserted."""
@@ -478,7 +489,7 @@ class ImpalaActorGroup(GpuActorGroup):
         self.slots.copy_(torch.from_numpy((payload % self.replay.F).astype(np.int32)), non_blocking=True)
         h = self.learner.trunk_forward(self.slots, self.ps, self.bufs)
         heads = {k: self.ps["V"][k] for k in ("wv", "bv", "wa", "ba")}
-        self.ops.actor_head(h, heads, self.eps, self.ctr, self.seed, self.q, self.act, H_lo=self.bufs.get("h_lo"))
+        self._actor_head(h, heads, self.bufs.get("h_lo"))
         self.ctr += 1
         self.q_host.copy_(self.q, non_blocking=True)
         self.a_host.copy_(self.act, non_blocking=True)

@@ -96,6 +96,13 @@ class RuntimeConf:
     grad_clip: float = 40.0
     loss: str = "huber"             # "huber" | "mse" (0.5*delta^2, reference learner.py:48)
     huber_delta: float = 1.0
+    # distributional (C51) dueling head: num_atoms >= 2 atoms on the support [v_min, v_max]; the loss is the
+    # cross-entropy against the projected n-step target distribution (loss / huber_delta do not apply), the
+    # priority stays |E[target] - E[q]| (learner/losses.py c51_loss).  1 = the scalar head.  Single-rank
+    # NatureCNN (csrc/c51_head.hip) and the torch learners (mlp); not IMPALA, the DP step or the graph learner
+    num_atoms: int = 1
+    v_min: float = -10.0
+    v_max: float = 10.0
     priority_eps: float = 1e-6      # priority floor: leaves hold (|delta| + priority_eps)^alpha
     use_is_weights: bool = True
     is_normalise: str = "batch_max"  # IS weights (N P(i))^-beta divided by their max over the sampled batch
@@ -275,6 +282,17 @@ class ApexConfig:
         if rt.is_beta_end is not None and not rt.use_is_weights:
             raise ValueError("Runtime.is_beta_end anneals the IS weights: it needs Runtime.use_is_weights")
         net = self.network
+        na = rt.num_atoms
+        if isinstance(na, bool) or not isinstance(na, int) or not (na == 1 or 2 <= na <= 64):
+            raise ValueError(f"Runtime.num_atoms must be 1 or an integer in [2, 64] (one lane per atom), got {na!r}")
+        if not float(rt.v_min) < float(rt.v_max):
+            raise ValueError(f"Runtime.v_min must be below Runtime.v_max, got {rt.v_min} / {rt.v_max}")
+        if na >= 2:
+            if net not in ("nature64", "nature32", "mlp"):
+                raise ValueError(f"Runtime.num_atoms={na} needs network nature64, nature32 or mlp, got {net!r}")
+            if int(rt.world_size) > 1 or rt.force_dp:
+                raise ValueError(f"Runtime.num_atoms={na} runs on a single rank: the data-parallel step "
+                                 f"(world_size > 1, force_dp) has no distributional head")
         if net in ("nature64", "nature32", "impala") and len(ss) != 3:
             raise ValueError(f"network {net} needs an image state_shape [C,H,W], got {ss}")
         if net in ("nature64", "nature32") and tuple(ss[1:]) != (84, 84):
@@ -285,6 +303,15 @@ class ApexConfig:
         if self.Runtime.network != "auto":
             return self.Runtime.network
         return "nature64" if len(self.env_conf.state_shape) == 3 else "mlp"
+
+    @property
+    def distributional(self) -> bool:
+        return int(self.Runtime.num_atoms) >= 2
+
+    def head_kw(self) -> Dict[str, Any]:
+        """The dueling modules' head arguments (models/dueling.py)."""
+        rt = self.Runtime
+        return dict(num_atoms=int(rt.num_atoms), v_min=float(rt.v_min), v_max=float(rt.v_max))
 
     @property
     def env_backend(self) -> str:

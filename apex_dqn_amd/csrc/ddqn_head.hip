@@ -22,17 +22,6 @@
 #include "head_common.h"
 #include "conv2_wfrag.h"
 
-// Batch-max IS normalisation (Runtime.is_normalise = "batch_max"): block 0's second
-// wave also leaves m = max_b isw[b] / wscale -- the largest (p / p_min)^-beta of the
-// batch, the sampler's W B / M factor taken out -- for the optimizer, which scales the
-// gradient by 1 / m (csrc/rmsprop_common.h is_grad_scale).  With DP `out` is this
-// rank's slot of the shard statistics that are all-gathered later in the step.
-struct IsNorm {
-  const float* wscale;   // sampler's W B / M (null: 1)
-  double* out;           // null: off
-  unsigned long long* valid_count;   // DP: += rows of this batch the rank drew (weight > 0); or null
-};
-
 // hp.part != null: the fc forward's split-K epilogue runs inside (head_common.h
 // load_row_part); blocks >= B run the conv2 weight-fragment pack job (pk.out != null)
 // that otherwise rides on that epilogue's launch.
@@ -69,7 +58,11 @@ __global__ void __launch_bounds__(192) ddqn_head_kernel(
   }
 }
 
-__global__ void __launch_bounds__(512) head_wgrad_kernel(HeadWgArgs h) { head_wgrad_body(h, blockIdx.x, blockIdx.y); }
+// (h.NV >= 2: the wide head of csrc/c51_head.hip, blockIdx.x = row tile)
+__global__ void __launch_bounds__(512) head_wgrad_kernel(HeadWgArgs h) {
+  if (h.NV >= 2) head_wgrad_wide_body(h, blockIdx.x, blockIdx.y, blockIdx.x * gridDim.y + blockIdx.y);
+  else head_wgrad_body(h, blockIdx.x, blockIdx.y);
+}
 
 APEX_EXPORT int apex_ddqn_head(const bf16_t* Hon, const bf16_t* Htg, HeadParams Pon, HeadParams Ptg,
                                const int32_t* act, const float* rew, const float* gam, const float* isw,
@@ -103,11 +96,15 @@ APEX_EXPORT int apex_ddqn_head(const bf16_t* Hon, const bf16_t* Htg, HeadParams 
   APEX_CHECK_LAUNCH();
 }
 
+// nv >= 2: nv value rows and A advantage rows (the distributional head: dhead [B, nv + A])
 APEX_EXPORT int apex_head_wgrad(const bf16_t* Hon, const float* dhead, int B, int A, float* gwv, float* gbv,
-                                float* gwa, float* gba, int hidden, const bf16_t* Hon_lo, hipStream_t st) {
-  if (hidden != 512 && hidden != 256) return (int)hipErrorInvalidValue;
-  dim3 grid(A + 1, hidden / 64);
-  head_wgrad_kernel<<<grid, 512, 0, st>>>(HeadWgArgs{Hon, dhead, B, A, gwv, gbv, gwa, gba, hidden, Hon_lo});
+                                float* gwa, float* gba, int hidden, const bf16_t* Hon_lo, int nv, double* norm_part,
+                                hipStream_t st) {
+  if ((hidden != 512 && hidden != 256) || nv < 1 || A < 1 || B < 1) return (int)hipErrorInvalidValue;
+  if (norm_part != nullptr && nv < 2) return (int)hipErrorInvalidValue;    // (the wide head's partials only)
+  dim3 grid(nv >= 2 ? head_wgrad_wide_tiles(nv, A) : A + 1, hidden / 64);
+  head_wgrad_kernel<<<grid, 512, 0, st>>>(HeadWgArgs{Hon, dhead, B, A, gwv, gbv, gwa, gba, hidden, Hon_lo, nv,
+                                                     norm_part});
   APEX_CHECK_LAUNCH();
 }
 

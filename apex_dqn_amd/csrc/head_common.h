@@ -23,6 +23,17 @@ struct HeadLo {
   bf16_t* dH;
 };
 
+// Batch-max IS normalisation (Runtime.is_normalise = "batch_max"): block 0's second
+// wave also leaves m = max_b isw[b] / wscale -- the largest (p / p_min)^-beta of the
+// batch, the sampler's W B / M factor taken out -- for the optimizer, which scales the
+// gradient by 1 / m (csrc/rmsprop_common.h is_grad_scale).  With DP `out` is this
+// rank's slot of the shard statistics that are all-gathered later in the step.
+struct IsNorm {
+  const float* wscale;   // sampler's W B / M (null: 1)
+  double* out;           // null: off
+  unsigned long long* valid_count;   // DP: += rows of this batch the rank drew (weight > 0); or null
+};
+
 // NPL consecutive fp32 weights (16-B aligned: NPL is 4 or 8) as float4 loads
 template <int NPL>
 __device__ __forceinline__ void load_w(const float* __restrict__ p, float* w) {
@@ -441,6 +452,10 @@ struct HeadWgArgs {
   float* gba;
   int HS;
   const bf16_t* Hon_lo;      // split mode: lo plane of Hon (else null)
+  int NV;                    // value rows (0 / 1: the scalar head).  N >= 2 atoms (csrc/c51_head.hip): dhead
+                             // [B, NV + A] with A = the advantage rows (actions x atoms), gwv [NV][HS], gbv
+                             // [NV], gwa [A][HS], gba [A] -- head_wgrad_wide_body
+  double* norm_part;         // wide head: one squared-norm partial per block of what it stores (or null)
 };
 
 // block (j, chunk): any multiple of 64 threads up to 1024 (waves split the rows)
@@ -487,5 +502,78 @@ __device__ __forceinline__ void head_wgrad_body(const HeadWgArgs& h, int j, int 
       if (q < nw) sb += red[q][64];
     if (j == 0) h.gbv[0] += sb;
     else h.gba[j - 1] += sb;
+  }
+}
+
+// The same gradients for a wide head (NV value rows + A advantage rows, the distributional
+// head's (A + 1) x N outputs): a block takes HWG_JT rows of one stream and one 64-column
+// chunk, so each activation it loads feeds HWG_JT products instead of one; the waves split
+// the batch rows, their partials meet in LDS and are added in wave order (no atomics).
+// Row tiles never straddle the value / advantage boundary: tiles [0, tv) are value rows,
+// tv = ceil(NV / HWG_JT), the rest advantage rows.  block (tile, chunk): up to 8 waves.
+#define HWG_JT 8
+__host__ __device__ __forceinline__ int head_wgrad_wide_tiles(int NV, int A) {
+  return (NV + HWG_JT - 1) / HWG_JT + (A + HWG_JT - 1) / HWG_JT;
+}
+
+// (`slot`: the block's index among the wide blocks, its place in h.norm_part)
+__device__ __forceinline__ void head_wgrad_wide_body(const HeadWgArgs& h, int tile, int chunk, int slot) {
+  const bf16_t* __restrict__ Hon = h.Hon;
+  const bf16_t* __restrict__ Hlo = h.Hon_lo;
+  const float* __restrict__ dhead = h.dhead;
+  const int B = h.B, A = h.A, HS = h.HS, NV = h.NV, J = NV + A;
+  __shared__ float redw[8][HWG_JT][65];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int tv = (NV + HWG_JT - 1) / HWG_JT;
+  const bool val = tile < tv;
+  const int j0 = val ? tile * HWG_JT : NV + (tile - tv) * HWG_JT;   // first dhead column of the tile
+  const int jend = val ? NV : J;
+  const int k = chunk * 64 + lane;
+  const int col = (val ? 0 : HS) + k;
+  float acc[HWG_JT], accb[HWG_JT];
+#pragma unroll
+  for (int t = 0; t < HWG_JT; ++t) acc[t] = accb[t] = 0.f;
+#pragma unroll 4
+  for (int b = w; b < B; b += nw) {
+    const int64_t o = (int64_t)b * 2 * HS + col;
+    float x = bf16_to_f32(Hon[o]);
+    if (Hlo != nullptr) x += bf16_to_f32(Hlo[o]);
+    const float* __restrict__ dr = dhead + (int64_t)b * J + j0;
+#pragma unroll
+    for (int t = 0; t < HWG_JT; ++t) {
+      const float d = j0 + t < jend ? dr[t] : 0.f;
+      acc[t] += d * x;
+      accb[t] += d;
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < HWG_JT; ++t) {
+    redw[w][t][lane] = acc[t];
+    if (lane == 0) redw[w][t][64] = accb[t];
+  }
+  __syncthreads();
+  if (w != 0) return;
+  double ss = 0.0;      // squares of what this block stores (the region was zeroed: it stores s, sb)
+#pragma unroll
+  for (int t = 0; t < HWG_JT; ++t) {
+    const int j = j0 + t;
+    if (j >= jend) break;
+    float s = 0.f, sb = 0.f;
+    for (int q = 0; q < nw; ++q) {
+      s += redw[q][t][lane];
+      sb += redw[q][t][64];
+    }
+    if (val) h.gwv[(int64_t)j * HS + k] += s;
+    else h.gwa[(int64_t)(j - NV) * HS + k] += s;
+    ss += (double)s * (double)s;
+    if (lane == 0 && chunk == 0) {
+      if (val) h.gbv[j] += sb;
+      else h.gba[j - NV] += sb;
+      ss += (double)sb * (double)sb;
+    }
+  }
+  if (h.norm_part != nullptr) {
+    ss = wave_sum(ss);
+    if (lane == 0) h.norm_part[slot] = ss;
   }
 }

@@ -599,7 +599,8 @@ __global__ void __launch_bounds__(512) head_wgrad_prio_kernel(HeadWgArgs hw, Tre
     return;
   }
   const int b = blockIdx.x - 1, nch = hw.HS / 64;
-  head_wgrad_body(hw, b / nch, b - (b / nch) * nch);
+  if (hw.NV >= 2) head_wgrad_wide_body(hw, b / nch, b - (b / nch) * nch, b);   // (row tile, chunk, slot)
+  else head_wgrad_body(hw, b / nch, b - (b / nch) * nch);
 }
 
 // fc weight gradient + head weight gradient + priority write-back in ONE launch
@@ -761,7 +762,7 @@ APEX_EXPORT int apex_fill16(void* p, int64_t n, int nt, hipStream_t st) {
   APEX_CHECK_LAUNCH();
 }
 
-APEX_EXPORT int apex_abi_version() { return 10; }
+APEX_EXPORT int apex_abi_version() { return 11; }
 
 // 1 if this library was built with -DAPEX_DEBUG_BOUNDS
 APEX_EXPORT int apex_debug_bounds_enabled() {
@@ -890,11 +891,13 @@ APEX_EXPORT int apex_head_wgrad_prio(const bf16_t* Hon, const float* dhead, int 
                                      float alpha, float eps, uint64_t* ctr_to_bump, const bf16_t* Hon_lo,
                                      double* stats_out, const uint16_t* const* psrc, const int64_t* pld,
                                      const int* pcols, int pnseg, int prows, uint16_t* pdst, int64_t pdld,
-                                     hipStream_t st) {
+                                     int nv, double* norm_part, hipStream_t st) {
+  if (norm_part != nullptr && nv < 2) return (int)hipErrorInvalidValue;    // (the wide head's partials only)
   // the single-block tree update holds TU_MAXR items per thread
-  if ((hidden != 512 && hidden != 256) || B < 1 || B > 1024 || B > TU_MAXR * 512 || idx == nullptr)
+  if ((hidden != 512 && hidden != 256) || B < 1 || B > 1024 || B > TU_MAXR * 512 || idx == nullptr || nv < 1 || A < 1)
     return (int)hipErrorInvalidValue;
-  const int nhw = (A + 1) * (hidden / 64);
+  // (nv >= 2: the distributional head's nv value rows + A advantage rows, head_wgrad_wide_body)
+  const int nhw = (nv >= 2 ? head_wgrad_wide_tiles(nv, A) : A + 1) * (hidden / 64);
   // optional row pack in the same launch (pnseg > 0): up to 256 tail blocks
   PackRows pk{};
   int npk = 0;
@@ -906,7 +909,7 @@ APEX_EXPORT int apex_head_wgrad_prio(const bf16_t* Hon, const float* dhead, int 
     npk = npk > 256 ? 256 : npk;
   }
   head_wgrad_prio_kernel<<<1 + nhw + npk, 512, 0, st>>>(
-      HeadWgArgs{Hon, dhead, B, A, gwv, gbv, gwa, gba, hidden, Hon_lo},
+      HeadWgArgs{Hon, dhead, B, A, gwv, gbv, gwa, gba, hidden, Hon_lo, nv, norm_part},
       TreeUpdArgs{t, idx, td, gen_expect, gen, ctr_to_bump, alpha, eps, B, tree_kfirst(t), stats_out}, pk, nhw, npk);
   APEX_CHECK_LAUNCH();
 }

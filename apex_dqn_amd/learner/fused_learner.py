@@ -4,7 +4,10 @@ Per step (B = local batch), entirely on device, one stream, no host sync:
 
   online fwd on 2B rows, target fwd on B rows    conv1_s2d (reads the uint8 replay ring
                                                  by slot) / conv2 / conv3 / fc
-  DDQN target + Huber*IS loss + |delta| + dH     csrc/ddqn_head.hip
+  DDQN target + Huber*IS loss + |delta| + dH     csrc/ddqn_head.hip (Runtime.num_atoms >= 2:
+                                                 csrc/c51_head.hip, projected cross-entropy,
+                                                 then head wgrad + write-back and fc wgrad as
+                                                 two launches on the backward's branch)
   fc wgrad + head wgrad + priority write-back    ONE launch (csrc/sumtree.hip
   (generation-checked, last writer wins)         fc_wgrad_head_prio_kernel)
   backward: fc, conv3, conv2 dgrad+wgrad, conv1  csrc/conv_mfma.hip, conv2_img.hip,
@@ -100,6 +103,11 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         # B = the rows this rank computes: replay_sample_size, or with a global-batch DP
         # step (Runtime.batch_scope) its share of the global draw plus slack (dp_layout)
         self.world, self._dp, self.B, self.mcap = dp_layout(cfg, comm, batch_size)
+        # distributional (C51) head: N atoms per action (csrc/c51_head.hip); 1 = the scalar head
+        self.N = int(self.rt.num_atoms)
+        if self.N >= 2 and self._dp:
+            raise ValueError(f"Runtime.num_atoms={self.N}: the distributional head runs on a single rank, not in "
+                             f"the data-parallel step (world > 1, Runtime.force_dp, the emulated world)")
         if self.rt.dtype not in ("fp32", "bf16"):
             raise ValueError("Runtime.dtype must be fp32 or bf16")
         self.precision = self.rt.dtype
@@ -125,7 +133,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         # (the torch backend emulates the split kernel's contract: ops.conv12_fwd)
         self._c12 = self.split or (backend == "hip" and self.ops._conv12_native() and SW.conv12_bf16)
         d = self.device
-        self.layout = FlatLayout(nature_segments(self.C, self.A, 64))
+        self.layout = FlatLayout(nature_segments(self.C, self.A, 64, self.N))
         n = self.layout.numel
         self.p32 = torch.zeros(n, dtype=torch.float32, device=d)
         # bf16 compute copies [hi | lo] of the online / target parameters (lo: split mode)
@@ -148,7 +156,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         self.Pl = self.layout.views(self.pbf_lo) if self.split else None
         self.Tl = self.layout.views(self.tbf_lo) if self.split else None
         # random init identical in distribution to the reference module (torch default init)
-        init = DuellingDQN((self.C, 84, 84), self.A, conv1_channels=self.c1)
+        init = DuellingDQN((self.C, 84, 84), self.A, conv1_channels=self.c1, **cfg.head_kw())
         reference_state_to_flat(init.state_dict(), {k: v for k, v in self.P.items()})
         if comm is not None and comm.world_size > 1:
             comm.broadcast_flat(self.p32)
@@ -247,7 +255,9 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         self._dp_setup()
         # the fc layer's split-K epilogue runs inside the head launch (ops.fc_fwd defer_head;
         # SW.fc_epi_in_head = False keeps the separate epilogue launch)
-        self._defer_fc_epilogue = SW.fc_epi_in_head
+        # (the distributional head reads h: the separate epilogue launch, which then also
+        # carries the conv2 fragment pack job)
+        self._defer_fc_epilogue = SW.fc_epi_in_head and self.N == 1
         # next-batch pre-sampling: the batch of step t+1 is drawn at the end of step t,
         # after the priority write-back -- on the HIP backend inside the optimizer launch
         # (its first blocks run the sampler: csrc/sumtree.hip rmsprop_sample_kernel), so
@@ -326,7 +336,8 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         self.dY3, self.dY3_lo = act(B, 7, 7, 64)
         self.dY2, self.dY2_lo = act(B, 9, 9, 64)
         self.dY1, self.dY1_lo = act(B, 20, 20, 64)
-        self.dhead = torch.zeros(B, self.A + 1, dtype=torch.float32, device=d)
+        # [d value | d advantage]; N atoms each with the distributional head (N + a N + i)
+        self.dhead = torch.zeros(B, (self.A + 1) * self.N, dtype=torch.float32, device=d)
         self.td_abs = torch.zeros(B, dtype=torch.float32, device=d)
         self.loss_b = torch.zeros(B, dtype=torch.float32, device=d)
         self.partials = torch.zeros(1024, dtype=torch.float64, device=d)
@@ -337,8 +348,11 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         self.gnorm = torch.zeros(1, dtype=torch.float32, device=d)
         # head-gradient region (zeroed by the head kernel, accumulated by head_wgrad)
         o0 = self.layout.offsets["wv"]
-        o1 = self.layout.offsets["ba"] + self.A
+        o1 = self.layout.offsets["ba"] + self.A * self.N
         self.g_head_region = self.g32[o0:o1]
+        # its share of the producer-summed clip norm: summed by one finalize block (the scalar
+        # head's 2.5 K values), or by the wide head weight gradient's own blocks (N >= 2)
+        self._head_norm_range = self.g_head_region if self.N == 1 else None
 
     def _lo(self, **kw) -> Dict[str, Any]:
         """Split-mode keyword arguments of an op (empty in bf16 / plain fp32 mode)."""
@@ -434,10 +448,17 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         self._mark("forward")
         isw = S["weights"] if self._isw else None
         sp = self.split
-        ops.head(self.h[:2 * B], self.h[2 * B:], self._head_params(self.P), self._head_params(self.T), S["act"],
-                 S["rew"], S["gam"], isw, rt.loss == "huber", rt.huber_delta, 1.0 / (B * self.world),
-                 self.td_abs, self.loss_b, self.dH, self.dhead, zero=self.g_head_region,
-                 isn=self._isn(), **self._lo(lo=sp and (self.h_lo[:2 * B], self.h_lo[2 * B:], self.dH_lo)))
+        if self.N >= 2:
+            # categorical projection + cross-entropy (Runtime.loss / huber_delta do not apply)
+            ops.c51_head(self.h[:2 * B], self.h[2 * B:], self._head_params(self.P), self._head_params(self.T),
+                         S["act"], S["rew"], S["gam"], isw, self.N, rt.v_min, rt.v_max, 1.0 / (B * self.world),
+                         self.td_abs, self.loss_b, self.dH, self.dhead, zero=self.g_head_region, isn=self._isn(),
+                         **self._lo(lo=sp and (self.h_lo[:2 * B], self.h_lo[2 * B:], self.dH_lo)))
+        else:
+            ops.head(self.h[:2 * B], self.h[2 * B:], self._head_params(self.P), self._head_params(self.T), S["act"],
+                     S["rew"], S["gam"], isw, rt.loss == "huber", rt.huber_delta, 1.0 / (B * self.world),
+                     self.td_abs, self.loss_b, self.dH, self.dhead, zero=self.g_head_region,
+                     isn=self._isn(), **self._lo(lo=sp and (self.h_lo[:2 * B], self.h_lo[2 * B:], self.dH_lo)))
         self._mark("head")
         prio = (self.replay, S["idx"], S["gen"], self.td_abs)
         if self._branched or self._dp:
@@ -489,7 +510,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         # region's norm partials, then conv1): the same norm-partial slots, so the two
         # schedules give bit-identical updates
         fuse = self._fuse_norm
-        n1 = ops.finalize_grads(jobs, self.g_head_region if fuse else None,
+        n1 = ops.finalize_grads(jobs, self._head_norm_range if fuse else None,
                                 dict(part=self.norm_part, slot0=self._fc_slots) if fuse else None)
         n2 = ops.finalize_grads(jobs1, None, dict(part=self.norm_part, slot0=n1) if fuse else None)
         self._npart = n2 if fuse else 0
@@ -583,6 +604,10 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         # 74 rows lose (4,264 / 4,214 vs 4,367 / 4,403; 6,077 vs 6,415),
         # profiles/r4_ab_fc_wgrad_main.txt
         fc_main = SW.fc_wgrad_main == "on" or (SW.fc_wgrad_main == "auto" and sp and B >= 256)
+        if self.N >= 2 and SW.fc_wgrad_main != "on":
+            # the distributional head's weight gradient and the fc weight gradient are two
+            # launches that do not fill the chip: on the branch, beside the data-gradient chain
+            fc_main = False
         if not fc_main:
             ev = torch.cuda.Event()
             ev.record(main)
@@ -612,7 +637,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         with torch.cuda.stream(side):
             # conv3 / conv2 split-K reductions (+ the head region's norm partials) on the
             # branch, beside conv1's weight gradient
-            n_side = ops.finalize_grads(jobs, self.g_head_region if fuse else None,
+            n_side = ops.finalize_grads(jobs, self._head_norm_range if fuse else None,
                                         dict(part=self.norm_part, slot0=self._fc_slots) if fuse else None)
         n_main = ops.finalize_grads(jobs1, None, dict(part=self.norm_part, slot0=n_side) if fuse else None)
         main.wait_stream(side)
@@ -983,7 +1008,8 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         """Greedy-evaluation helper: q for a (N, C, 84, 84) uint8 batch (fp32 module,
         scaled by ``Runtime.obs_scale`` as the learner's conv1 is)."""
         sd = self.reference_state_dict()
-        net = DuellingDQN((self.C, 84, 84), self.A, conv1_channels=self.c1, obs_scale=self.rt.obs_scale)
+        net = DuellingDQN((self.C, 84, 84), self.A, conv1_channels=self.c1, obs_scale=self.rt.obs_scale,
+                          **self.cfg.head_kw())
         net = net.to(self.device)
         net.load_state_dict(sd)
         with torch.no_grad():

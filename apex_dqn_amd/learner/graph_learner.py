@@ -59,6 +59,9 @@ class GraphLearner(StepIndexMixin):
     def __init__(self, cfg: ApexConfig, device, replay, comm=None, batch_size: Optional[int] = None):
         self.cfg = cfg
         self.rt = cfg.Runtime
+        if int(self.rt.num_atoms) != 1:
+            raise ValueError(f"Runtime.num_atoms={self.rt.num_atoms}: the graph learner (Runtime.use_hip_kernels = "
+                             f"false on the GPU) has no distributional head; run the HIP kernels or num_atoms = 1")
         self.device = torch.device(device)
         self.replay = replay
         self.comm = comm

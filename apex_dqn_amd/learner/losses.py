@@ -26,6 +26,53 @@ def ddqn_targets(q_online_next: torch.Tensor, q_target_next: torch.Tensor,
     return R + Gamma * q_target_next.gather(1, a_star).squeeze(1)
 
 
+def c51_project(p_next: torch.Tensor, R: torch.Tensor, Gamma: torch.Tensor, v_min: float,
+                v_max: float) -> torch.Tensor:
+    """Categorical projection of the n-step target ``R + Gamma z`` onto the support
+    z_i = v_min + i delta (N atoms): ``m_i = sum_j p'_j max(0, 1 - |b_j - i|)`` with
+    ``b_j = (clamp(R + Gamma z_j, v_min, v_max) - v_min) / delta`` -- the usual floor / ceil
+    split written as a gather (deterministic, continuous in b, no scatter), summed in
+    increasing j.  Gamma = 0 (terminal) needs no special case; sum_i m_i = 1.  Computes in
+    ``p_next``'s dtype (fp64 inputs: the tests' reference).  p_next [B, N] -> m [B, N]."""
+    N = p_next.shape[-1]
+    dt = p_next.dtype
+    delta = (float(v_max) - float(v_min)) / (N - 1)
+    idx = torch.arange(N, dtype=dt, device=p_next.device)
+    z = float(v_min) + idx * delta
+    tz = (R.to(dt)[:, None] + Gamma.to(dt)[:, None] * z[None, :]).clamp(float(v_min), float(v_max))
+    b = (tz - float(v_min)) / delta
+    m = torch.zeros_like(p_next)
+    for j in range(N):        # fixed order: the kernels' sum
+        m = m + p_next[:, j:j + 1] * (1.0 - (b[:, j:j + 1] - idx[None, :]).abs()).clamp_min(0.0)
+    return m
+
+
+def c51_loss(logp_t: torch.Tensor, q_online_next: torch.Tensor, p_target_next: torch.Tensor,
+             A: torch.Tensor, R: torch.Tensor, Gamma: torch.Tensor, v_min: float, v_max: float,
+             weights: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Distributional double-DQN loss.  ``logp_t`` [B, A, N]: log p(S_t) of the online net;
+    ``q_online_next`` [B, A]: its expected q at S_{t+n} (picks a*, first maximum);
+    ``p_target_next`` [B, A, N]: the target net's probabilities at S_{t+n}.  Returns (mean
+    over the batch of -w sum_i m_i log p(S_t)[a, i], |sum_i m_i z_i - q(S_t)[a]| per sample):
+    the priority is the absolute TD error of the expectations, on the scale of the actors'
+    initial priorities, not the KL."""
+    B, _, N = logp_t.shape
+    dt = logp_t.dtype
+    ar = torch.arange(B, device=logp_t.device)
+    with torch.no_grad():
+        a_star = q_online_next.argmax(dim=1)
+        m = c51_project(p_target_next[ar, a_star].to(dt), R, Gamma, v_min, v_max)
+        delta = (float(v_max) - float(v_min)) / (N - 1)
+        z = float(v_min) + torch.arange(N, dtype=dt, device=logp_t.device) * delta
+    lp = logp_t[ar, A.long().view(-1)]
+    per = -(m * lp).sum(-1)
+    if weights is not None:
+        per = per * weights.to(dt)
+    with torch.no_grad():
+        td = ((m * z).sum(-1) - (lp.exp() * z).sum(-1)).abs()
+    return per.mean(), td
+
+
 def ddqn_loss(q_online_t: torch.Tensor, q_online_next: torch.Tensor,
               q_target_next: torch.Tensor, A: torch.Tensor, R: torch.Tensor,
               Gamma: torch.Tensor, weights: torch.Tensor = None, loss: str = "huber",

@@ -20,7 +20,7 @@ import torch
 from ..config import ApexConfig
 from ..models.dueling import build_network
 from ..utils.checkpoint import adopt_obs_scale, load_checkpoint, save_checkpoint
-from .losses import ddqn_loss
+from .losses import c51_loss, ddqn_loss
 from .schedules import lr_scheduled, rt_lr
 
 
@@ -39,7 +39,7 @@ class TorchLearner:
         self.comm = comm
         shape = cfg.env_conf.state_shape
         self.Q = build_network(cfg.network, shape, cfg.env_conf.action_dim,
-                               obs_scale=self.rt.obs_scale).to(self.device)
+                               obs_scale=self.rt.obs_scale, **cfg.head_kw()).to(self.device)
         if comm is not None and comm.world_size > 1:
             comm.broadcast_module(self.Q)
         self.Q_target = copy.deepcopy(self.Q)
@@ -71,6 +71,13 @@ class TorchLearner:
         G = self._to(batch["Gamma"], torch.float32)
         w = self._to(batch["weights"], torch.float32) if (
             self.rt.use_is_weights and "weights" in batch) else None
+        if self.cfg.distributional:
+            # C51: cross-entropy against the projected target distribution (learner/losses.py)
+            with torch.no_grad():
+                q_next_online = self.Q(S_tpn)[2]
+                p_next_target = self.Q_target.log_probs(S_tpn).exp()
+            return c51_loss(self.Q.log_probs(S_t), q_next_online, p_next_target, A, R, G,
+                            self.rt.v_min, self.rt.v_max, w)
         with torch.no_grad():
             q_next_online = self.Q(S_tpn)[2]
             q_next_target = self.Q_target(S_tpn)[2]

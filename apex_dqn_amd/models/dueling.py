@@ -30,6 +30,43 @@ def dueling_combine(value: torch.Tensor, adv: torch.Tensor) -> torch.Tensor:
     return value + adv - adv.mean(dim=1, keepdim=True)
 
 
+class _C51Head:
+    """Distributional (C51) dueling head shared by the modules that take ``num_atoms``:
+    the value head has N outputs, the advantage head A N (row a N + i = action a, atom i),
+    the dueling combine runs per atom and q is the expectation over the fixed support
+    z_i = v_min + i (v_max - v_min) / (N - 1).  N = 1: the scalar head."""
+
+    def _init_head(self, hidden: int, num_atoms: int, v_min: float, v_max: float) -> None:
+        self.num_atoms = int(num_atoms)
+        self.v_min, self.v_max = float(v_min), float(v_max)
+        self.value = nn.Linear(hidden, self.num_atoms)
+        self.advantage = nn.Linear(hidden, self.action_dim * self.num_atoms)
+        if self.num_atoms > 1:
+            self.register_buffer("support", c51_support(self.num_atoms, self.v_min, self.v_max), persistent=False)
+
+    def _head(self, hv: torch.Tensor, ha: torch.Tensor):
+        value, advantage = self.value(hv), self.advantage(ha)
+        if self.num_atoms == 1:
+            return value, advantage, dueling_combine(value, advantage), None
+        logp = c51_log_probs(value, advantage, self.action_dim)
+        q = (logp.exp() * self.support.to(logp.dtype)).sum(-1)
+        return value, advantage, q, logp
+
+
+def c51_support(num_atoms: int, v_min: float, v_max: float, dtype=torch.float32) -> torch.Tensor:
+    """z_i = v_min + i (v_max - v_min) / (N - 1), evaluated in fp64 and rounded to ``dtype``."""
+    delta = (float(v_max) - float(v_min)) / (int(num_atoms) - 1)
+    return (float(v_min) + torch.arange(int(num_atoms), dtype=torch.float64) * delta).to(dtype)
+
+
+def c51_log_probs(value: torch.Tensor, advantage: torch.Tensor, action_dim: int) -> torch.Tensor:
+    """[B, A, N] log-probabilities: per-atom dueling combine, log-softmax over the atoms."""
+    B, N = value.shape
+    adv = advantage.reshape(B, action_dim, N)
+    logits = value[:, None, :] + adv - adv.mean(dim=1, keepdim=True)
+    return F.log_softmax(logits, dim=-1)
+
+
 class _ObsScale(nn.Module):
     def __init__(self, scale: float):
         super().__init__()
@@ -41,7 +78,7 @@ class _ObsScale(nn.Module):
         return x.float() if not x.is_floating_point() else x
 
 
-class DuellingDQN(nn.Module):
+class DuellingDQN(nn.Module, _C51Head):
     """Dueling NatureCNN: 3 conv + two 512-wide streams + value/advantage heads.
 
     ``conv1_channels`` = 64 matches the reference checkpoint layout
@@ -51,7 +88,8 @@ class DuellingDQN(nn.Module):
     """
 
     def __init__(self, state_shape: Sequence[int], action_dim: int,
-                 conv1_channels: int = 64, obs_scale: float = 1.0 / 255.0):
+                 conv1_channels: int = 64, obs_scale: float = 1.0 / 255.0,
+                 num_atoms: int = 1, v_min: float = -10.0, v_max: float = 10.0):
         super().__init__()
         self.input_shape = tuple(state_shape)
         self.action_dim = int(action_dim)
@@ -63,8 +101,7 @@ class DuellingDQN(nn.Module):
         self.layer3 = nn.Sequential(nn.Conv2d(64, 64, 3, stride=1), nn.ReLU())
         self.value_stream_layer = nn.Sequential(nn.Linear(64 * 7 * 7, 512), nn.ReLU())
         self.advantage_stream_layer = nn.Sequential(nn.Linear(64 * 7 * 7, 512), nn.ReLU())
-        self.value = nn.Linear(512, 1)
-        self.advantage = nn.Linear(512, self.action_dim)
+        self._init_head(512, num_atoms, v_min, v_max)
 
     def features(self, x: torch.Tensor) -> torch.Tensor:
         x = self.pre(x)
@@ -73,15 +110,19 @@ class DuellingDQN(nn.Module):
 
     def forward(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         h = self.features(x)
-        value = self.value(self.value_stream_layer(h))
-        advantage = self.advantage(self.advantage_stream_layer(h))
-        return value, advantage, dueling_combine(value, advantage)
+        return self._head(self.value_stream_layer(h), self.advantage_stream_layer(h))[:3]
+
+    def log_probs(self, x: torch.Tensor) -> torch.Tensor:
+        """[B, A, N] log-probabilities of the value distribution (``num_atoms`` >= 2)."""
+        h = self.features(x)
+        return self._head(self.value_stream_layer(h), self.advantage_stream_layer(h))[3]
 
 
-class MLPDuellingDQN(nn.Module):
+class MLPDuellingDQN(nn.Module, _C51Head):
     """Dueling MLP for low-dimensional states (CartPole config)."""
 
-    def __init__(self, state_shape: Sequence[int], action_dim: int, hidden: int = 128):
+    def __init__(self, state_shape: Sequence[int], action_dim: int, hidden: int = 128,
+                 num_atoms: int = 1, v_min: float = -10.0, v_max: float = 10.0):
         super().__init__()
         d = int(state_shape[0]) if len(state_shape) == 1 else int(torch.tensor(state_shape).prod())
         self.input_shape = tuple(state_shape)
@@ -89,14 +130,16 @@ class MLPDuellingDQN(nn.Module):
         self.layer1 = nn.Sequential(nn.Linear(d, hidden), nn.ReLU())
         self.value_stream_layer = nn.Sequential(nn.Linear(hidden, hidden), nn.ReLU())
         self.advantage_stream_layer = nn.Sequential(nn.Linear(hidden, hidden), nn.ReLU())
-        self.value = nn.Linear(hidden, 1)
-        self.advantage = nn.Linear(hidden, self.action_dim)
+        self._init_head(hidden, num_atoms, v_min, v_max)
 
     def forward(self, x: torch.Tensor):
         h = self.layer1(x.float().reshape(x.shape[0], -1))
-        value = self.value(self.value_stream_layer(h))
-        advantage = self.advantage(self.advantage_stream_layer(h))
-        return value, advantage, dueling_combine(value, advantage)
+        return self._head(self.value_stream_layer(h), self.advantage_stream_layer(h))[:3]
+
+    def log_probs(self, x: torch.Tensor) -> torch.Tensor:
+        """[B, A, N] log-probabilities of the value distribution (``num_atoms`` >= 2)."""
+        h = self.layer1(x.float().reshape(x.shape[0], -1))
+        return self._head(self.value_stream_layer(h), self.advantage_stream_layer(h))[3]
 
 
 class _ResBlock(nn.Module):
@@ -163,14 +206,18 @@ class ImpalaDuellingDQN(nn.Module):
 
 
 def build_network(kind: str, state_shape: Sequence[int], action_dim: int,
-                  obs_scale: float = 1.0 / 255.0) -> nn.Module:
+                  obs_scale: float = 1.0 / 255.0, num_atoms: int = 1, v_min: float = -10.0,
+                  v_max: float = 10.0) -> nn.Module:
+    head = dict(num_atoms=num_atoms, v_min=v_min, v_max=v_max)
     if kind == "nature64":
-        return DuellingDQN(state_shape, action_dim, conv1_channels=64, obs_scale=obs_scale)
+        return DuellingDQN(state_shape, action_dim, conv1_channels=64, obs_scale=obs_scale, **head)
     if kind == "nature32":
-        return DuellingDQN(state_shape, action_dim, conv1_channels=32, obs_scale=obs_scale)
+        return DuellingDQN(state_shape, action_dim, conv1_channels=32, obs_scale=obs_scale, **head)
     if kind == "mlp":
-        return MLPDuellingDQN(state_shape, action_dim)
+        return MLPDuellingDQN(state_shape, action_dim, **head)
     if kind == "impala":
+        if int(num_atoms) != 1:
+            raise ValueError("Runtime.num_atoms >= 2: the impala network has no distributional head")
         return ImpalaDuellingDQN(state_shape, action_dim, obs_scale=obs_scale)
     raise ValueError(f"unknown network kind {kind!r}")
 

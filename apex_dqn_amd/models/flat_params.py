@@ -20,17 +20,20 @@ import torch
 ALIGN = 64  # elements (256 B): every segment starts 16-B aligned for dwordx4 access
 
 
-def nature_segments(C: int, A: int, c1: int = 64) -> List[Tuple[str, Tuple[int, ...]]]:
+def nature_segments(C: int, A: int, c1: int = 64, num_atoms: int = 1) -> List[Tuple[str, Tuple[int, ...]]]:
     """Flat order: the small tensors (convs, heads) first, the 3.2 M-parameter fc layer
     last, so the fc weights are one contiguous suffix: the data-parallel exchange treats
     [0, wfc) and [wfc, end) as its two buckets and the single-rank step updates the fc
-    suffix early (learner/fused_learner.py)."""
+    suffix early (learner/fused_learner.py).  ``num_atoms`` N >= 2 (the distributional
+    head): wv (N, 512), bv (N,), wa (A N, 512) with row a N + i = action a, atom i, ba (A N,)."""
+    N = int(num_atoms)
+    heads = [("wv", (512,)), ("bv", (1,)), ("wa", (A, 512)), ("ba", (A,))] if N == 1 else \
+        [("wv", (N, 512)), ("bv", (N,)), ("wa", (A * N, 512)), ("ba", (A * N,))]
     return [
         ("w1", (c1, C, 8, 8)), ("b1", (c1,)),
         ("w2", (64, 4, 4, c1)), ("b2", (64,)),
         ("w3", (64, 3, 3, 64)), ("b3", (64,)),
-        ("wv", (512,)), ("bv", (1,)),
-        ("wa", (A, 512)), ("ba", (A,)),
+        *heads,
         ("wfc", (1024, 3136)), ("bfc", (1024,)),
     ]
 
@@ -81,7 +84,7 @@ def flat_to_reference_state(v: Dict[str, torch.Tensor], c1: int = 64) -> "Ordere
     sd["value_stream_layer.0.bias"] = v["bfc"][:512].clone()
     sd["advantage_stream_layer.0.weight"] = fc_cols_to_chw(v["wfc"][512:]).contiguous()
     sd["advantage_stream_layer.0.bias"] = v["bfc"][512:].clone()
-    sd["value.weight"] = v["wv"].view(1, 512).clone()
+    sd["value.weight"] = v["wv"].reshape(-1, 512).clone()
     sd["value.bias"] = v["bv"].clone()
     sd["advantage.weight"] = v["wa"].clone()
     sd["advantage.bias"] = v["ba"].clone()
@@ -100,6 +103,12 @@ def reference_state_to_flat(sd: Dict[str, torch.Tensor], v: Dict[str, torch.Tens
         return w.reshape(-1, 64, 7, 7).permute(0, 2, 3, 1).reshape(w.shape[0], 3136)
 
     with torch.no_grad():
+        # (checked before anything is copied: a mismatch leaves the views untouched)
+        for k, name in (("wv", "value.weight"), ("bv", "value.bias"), ("wa", "advantage.weight"),
+                        ("ba", "advantage.bias")):
+            if sd[name].numel() != v[k].numel():
+                raise ValueError(f"{name} has shape {tuple(sd[name].shape)}, this layout holds {tuple(v[k].shape)}: "
+                                 f"the head's atom count differs (Runtime.num_atoms) or the action count does")
         c1 = sd["layer1.0.weight"].shape[0]
         if c1 != v["w1"].shape[0]:
             for k in ("w1", "b1", "w2"):
@@ -114,7 +123,7 @@ def reference_state_to_flat(sd: Dict[str, torch.Tensor], v: Dict[str, torch.Tens
         v["bfc"][:512].copy_(sd["value_stream_layer.0.bias"])
         v["wfc"][512:].copy_(fc_cols_to_hwc(sd["advantage_stream_layer.0.weight"]))
         v["bfc"][512:].copy_(sd["advantage_stream_layer.0.bias"])
-        v["wv"].copy_(sd["value.weight"].reshape(512))
+        v["wv"].copy_(sd["value.weight"].reshape(v["wv"].shape))
         v["bv"].copy_(sd["value.bias"])
         v["wa"].copy_(sd["advantage.weight"])
         v["ba"].copy_(sd["advantage.bias"])

@@ -57,6 +57,14 @@ class IsNorm(ctypes.Structure):
     _fields_ = [("wscale", c_p), ("out", c_p), ("valid_count", c_p)]
 
 
+class C51Args(ctypes.Structure):
+    """Arguments of the distributional head kernel (``C51Args``, csrc/c51_head.hip)."""
+    _fields_ = [("Hon", c_p), ("Htg", c_p), ("Pon", HeadParams), ("Ptg", HeadParams), ("act", c_p), ("rew", c_p),
+                ("gam", c_p), ("isw", c_p), ("B", c_i), ("A", c_i), ("N", c_i), ("hidden", c_i), ("vmin", c_f),
+                ("vmax", c_f), ("grad_scale", c_f), ("td_abs", c_p), ("loss", c_p), ("q_out", c_p), ("dH", c_p),
+                ("dhead", c_p), ("zero_ptr", c_p), ("zero_n", c_i), ("lo", HeadLo), ("isn", IsNorm)]
+
+
 class CfFragOut(ctypes.Structure):
     """The optimizer's stores of the fused forward's online operands (``CfFragOut``,
     csrc/cf_pack.h); all-zero = off."""
@@ -170,10 +178,12 @@ _SIGS = {
                              c_p, c_p, c_i, c_i, c_u64, c_p, c_i64, BetaSched, c_p, c_p, c_i, c_i, CfFragOut, c_p,
                              c_p, c_i64, OptSched, c_p], c_i),
     "apex_head_wgrad_prio": ([c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, TreeDesc, c_p, c_p, c_p, c_p, c_f, c_f,
-                              c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_i64, c_p], c_i),
+                              c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_i64, c_i, c_p, c_p], c_i),
     "apex_fc_wgrad_head_prio": ([WgradDesc, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, TreeDesc, c_p, c_p, c_p,
                                  c_p, c_f, c_f, c_p, c_p, c_p, c_p], c_i),
-    "apex_head_wgrad": ([c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p], c_i),
+    "apex_head_wgrad": ([c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p], c_i),
+    "apex_c51_head": ([C51Args, c_p], c_i),
+    "apex_c51_actor_head": ([c_p, HeadParams, c_i, c_i, c_i, c_f, c_f, c_p, c_u64, c_p, c_p, c_p, c_i, c_p, c_p], c_i),
     "apex_actor_head": ([c_p, HeadParams, c_i, c_i, c_p, c_u64, c_p, c_p, c_p, c_i, c_p, c_p], c_i),
     "apex_conv1_s2d_fwd": ([Conv1S2DDesc, c_i, c_p], c_i),
     "apex_conv1_wgrad_img": ([Conv1WgDesc, c_i, c_p], c_i),
@@ -203,7 +213,7 @@ def _declare(lib: ctypes.CDLL) -> None:
     conv_sigs.declare(lib)
 
 
-ABI_VERSION = 10    # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
+ABI_VERSION = 11    # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
 
 
 def load(build_if_missing: bool = True) -> Optional[ctypes.CDLL]:

@@ -176,6 +176,11 @@ class TorchBackend:
             q_out.copy_(q_t)
         if zero is not None:
             zero.zero_()
+        self._is_norm_stats(isn, w)
+
+    @staticmethod
+    def _is_norm_stats(isn, w) -> None:
+        """The head's batch-max IS statistic (``isn`` of :meth:`head`) from the weights ``w``."""
         if isn is not None:
             if isn[1] is not None:   # tensor ops only: no host sync (graph-capturable)
                 ws = isn[0].reshape(-1)[0].double() if isn[0] is not None else torch.ones((), dtype=torch.float64,
@@ -186,16 +191,104 @@ class TorchBackend:
             if len(isn) > 2 and isn[2] is not None:
                 isn[2].add_((w > 0).sum())
 
+    # ------------------------------------------------- distributional (C51) head
+    @staticmethod
+    def _c51_logp(h, P, A: int, N: int, dt):
+        """[rows, A, N] log-probabilities and [rows, A] expected q of stream activations ``h``:
+        per-atom dueling combine, log-softmax over the atoms (max-subtracted)."""
+        HS = P["wv"].shape[-1]
+        v = h[:, :HS] @ P["wv"].to(dt).reshape(N, HS).t() + P["bv"].to(dt)
+        a = (h[:, HS:] @ P["wa"].to(dt).t() + P["ba"].to(dt)).reshape(-1, A, N)
+        return torch.log_softmax(v[:, None, :] + a - a.mean(1, keepdim=True), dim=-1)
+
+    def c51_head(self, Hon, Htg, Pon: Dict[str, torch.Tensor], Ptg: Dict[str, torch.Tensor], act, rew, gam, isw,
+                 num_atoms: int, v_min: float, v_max: float, grad_scale: float, td_abs, loss, dH, dhead,
+                 q_out=None, zero: Optional[torch.Tensor] = None, lo=None, isn=None):
+        """The distributional counterpart of :meth:`head` (the oracle of csrc/c51_head.hip
+        ``c51_head_kernel``): head weights ``wv (N, HS)``, ``bv (N,)``, ``wa (A N, HS)``, ``ba
+        (A N,)``; loss = -w sum_i m_i log p(S_t)[a, i] with m the projected target
+        distribution of the double-DQN action (learner/losses.py ``c51_project``), td_abs =
+        |sum_i m_i z_i - q(S_t)[a]|, ``dhead [B, (A + 1) N]`` (value atoms, then action a's
+        atoms at N + a N), ``q_out`` the expected q(S_t).  Computes in the head weights'
+        dtype when that is fp64 (the tests' reference), else fp32."""
+        from ..learner.losses import c51_project
+        B, N = act.shape[0], int(num_atoms)
+        A = Pon["wa"].shape[0] // N
+        dt = torch.float64 if Pon["wv"].dtype == torch.float64 else torch.float32
+        HS = Pon["wv"].shape[-1]
+
+        def joined(hi, l):
+            return hi.to(dt) if l is None else hi.to(dt) + l.to(dt)
+
+        Hon = joined(Hon, None if lo is None else lo[0])
+        Htg = joined(Htg, None if lo is None else lo[1])
+        delta = (float(v_max) - float(v_min)) / (N - 1)
+        z = float(v_min) + torch.arange(N, dtype=dt, device=Hon.device) * delta
+        ar = torch.arange(B, device=Hon.device)
+        lp_t = self._c51_logp(Hon[:B], Pon, A, N, dt)
+        q_t = (lp_t.exp() * z).sum(-1)
+        q_n = (self._c51_logp(Hon[B:2 * B], Pon, A, N, dt).exp() * z).sum(-1)
+        a_star = q_n.argmax(1)
+        p_g = self._c51_logp(Htg[:B], Ptg, A, N, dt)[ar, a_star].exp()
+        m = c51_project(p_g, rew, gam, v_min, v_max)
+        lp = lp_t[ar, act.long()]
+        p = lp.exp()
+        w = isw.to(dt) if isw is not None else torch.ones(B, dtype=dt, device=Hon.device)
+        td_abs.copy_(((m * z).sum(-1) - (p * z).sum(-1)).abs())
+        loss.copy_(-w * (m * lp).sum(-1))
+        g = w[:, None] * (p - m) * grad_scale                      # d loss / d logits of (a_b, .)
+        onehot = torch.nn.functional.one_hot(act.long(), A).to(dt)
+        dadv = g[:, None, :] * (onehot - 1.0 / A)[:, :, None]      # [B, A, N]
+        dhead[:, :N] = g
+        dhead[:, N:] = dadv.reshape(B, A * N)
+        dv = g @ Pon["wv"].to(dt).reshape(N, HS)
+        da = dadv.reshape(B, A * N) @ Pon["wa"].to(dt)
+        dh = torch.cat([dv, da], 1) * (Hon[:B] > 0).to(dt)
+        split_into(dh, dH, None if lo is None else lo[2])
+        if q_out is not None:
+            q_out.copy_(q_t)
+        if zero is not None:
+            zero.zero_()
+        self._is_norm_stats(isn, w.float())
+
+    def c51_actor_head(self, H, P, eps, ctr, seed, num_atoms: int, v_min: float, v_max: float, q_out, a_out,
+                       H_lo=None):
+        """Expected q of the distributional head + epsilon-greedy per row (the oracle of
+        csrc/c51_head.hip ``c51_actor_head_kernel``)."""
+        N = int(num_atoms)
+        dt = torch.float64 if P["wv"].dtype == torch.float64 else torch.float32
+        h = H.to(dt) if H_lo is None else H.to(dt) + H_lo.to(dt)
+        E, A = q_out.shape
+        delta = (float(v_max) - float(v_min)) / (N - 1)
+        z = float(v_min) + torch.arange(N, dtype=dt, device=h.device) * delta
+        q = (self._c51_logp(h, P, A, N, dt).exp() * z).sum(-1)
+        q_out.copy_(q)
+        gen = torch.Generator(device="cpu").manual_seed(int(seed) * 1000003 + int(ctr.item()))
+        u = torch.rand(E, generator=gen).to(q.device)
+        r = torch.randint(0, A, (E,), generator=gen).to(q.device)
+        a_out.copy_(torch.where(u < eps.to(q.device), r, q.argmax(1)).to(a_out.dtype))
+
     def head_wgrad(self, Hon, dhead, g: Dict[str, torch.Tensor], prio=None, Hon_lo=None, pack=None):
         """``prio = (replay, idx, gen, td_abs)``: also write the batch's priorities back
         (the HIP backend runs it as one extra block of the same launch).  ``pack = (dst,
         segs)``: also the :meth:`pack_rows` of the DP step's factor rows (HIP: tail blocks
-        of the same launch)."""
+        of the same launch).  ``g["wv"]`` of shape (N, HS): N value rows (the distributional
+        head; ``dhead [B, N + A N]``)."""
         if pack is not None:
             self.pack_rows(*pack)
         if prio is not None:
             prio[0].update_priorities(prio[1], prio[3], prio[2])
         B = dhead.shape[0]
+        if g["wv"].dim() == 2:
+            NV, HS = g["wv"].shape
+            dt = g["wv"].dtype
+            h = Hon[:B].to(dt) if Hon_lo is None else Hon[:B].to(dt) + Hon_lo[:B].to(dt)
+            dh = dhead.to(dt)
+            g["wv"].add_(dh[:, :NV].t() @ h[:, :HS])
+            g["bv"].add_(dh[:, :NV].sum(0))
+            g["wa"].add_(dh[:, NV:].t() @ h[:, HS:])
+            g["ba"].add_(dh[:, NV:].sum(0))
+            return
         HS = g["wv"].numel()
         h = join(Hon[:B], None if Hon_lo is None else Hon_lo[:B])
         g["wv"].add_(dhead[:, 0] @ h[:, :HS])
@@ -392,7 +485,7 @@ class HipBackend(TorchBackend):
         super().__init__(dtype)
         self.lib = _lib.require_kernels()
         self.native_conv = native_conv and hasattr(self.lib, "apex_conv_fwd")
-        self.kernels = ["replay", "head", "head_wgrad", "optimizer", "actor_head"]
+        self.kernels = ["replay", "head", "head_wgrad", "optimizer", "actor_head", "c51_head", "c51_actor_head"]
         if self.native_conv:
             self.kernels += ["conv_fwd", "conv_dgrad", "conv_wgrad", "fc_fwd", "fc_bwd"]
         self.ws = C.Workspace()
@@ -507,13 +600,19 @@ class HipBackend(TorchBackend):
 
     def fc_head_wgrad(self, dh, x, dw_out, db_out, Hon, dhead, g_head, prio, norm=None, dh_lo=None, x_lo=None,
                       Hon_lo=None) -> int:
-        if self.native_conv and prio is not None and prio[0].use_hip:
+        # (the distributional head's wide weight gradient does not ride in the fused launch: the
+        # head weight gradient + priority write-back launch, then the fc weight gradient)
+        if self.native_conv and prio is not None and prio[0].use_hip and g_head["bv"].numel() == 1:
             rp, idx, gen, td = prio
             r = C.dense_wgrad_head_prio(self.lib, dh, x.reshape(x.shape[0], -1), dw_out, db_out, norm, Hon, dhead,
                                         g_head, rp, idx, gen, td, dy_lo=dh_lo,
                                         x_lo=None if x_lo is None else x_lo.reshape(x.shape[0], -1), Hon_lo=Hon_lo)
             if r is not None:
                 return r
+        if self.native_conv and norm is not None and g_head["bv"].numel() > 1:
+            # the wide head's blocks leave their own squared-norm partials, the fc partials follow
+            nh = self.head_wgrad(Hon, dhead, g_head, prio=prio, Hon_lo=Hon_lo, norm=norm)
+            return nh + self.fc_wgrad(dh, x, dw_out, db_out, norm=(norm[0], int(norm[1]) + nh), dh_lo=dh_lo, x_lo=x_lo)
         return super().fc_head_wgrad(dh, x, dw_out, db_out, Hon, dhead, g_head, prio, norm, dh_lo, x_lo, Hon_lo)
 
     def finalize_grads(self, jobs, norm_range=None, norm=None) -> int:
@@ -602,24 +701,62 @@ class HipBackend(TorchBackend):
             isn_s.valid_count = _lib.ptr(isn[2]) if len(isn) > 2 else None
         _lib.check(self.lib.apex_ddqn_head(*args, hl, hp, pk, isn_s, _lib.stream_ptr()), "ddqn_head")
 
-    def head_wgrad(self, Hon, dhead, g, prio=None, Hon_lo=None, pack=None):
-        B, A1 = dhead.shape
+    def c51_head(self, Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, v_min, v_max, grad_scale, td_abs, loss,
+                 dH, dhead, q_out=None, zero=None, lo=None, isn=None):
+        """csrc/c51_head.hip ``c51_head_kernel`` (reads h: the fc epilogue is not deferred)."""
+        assert getattr(self, "_fc_part", None) is None, "the distributional head reads h: fc epilogue deferred"
+        N = int(num_atoms)
+        a = _lib.C51Args()
+        a.Hon, a.Htg, a.Pon, a.Ptg = Hon.data_ptr(), Htg.data_ptr(), self._hp(Pon), self._hp(Ptg)
+        a.act, a.rew, a.gam, a.isw = act.data_ptr(), rew.data_ptr(), gam.data_ptr(), _lib.ptr(isw)
+        a.B, a.A, a.N, a.hidden = act.shape[0], Pon["wa"].shape[0] // N, N, Pon["wv"].shape[-1]
+        a.vmin, a.vmax, a.grad_scale = float(v_min), float(v_max), float(grad_scale)
+        a.td_abs, a.loss, a.q_out = td_abs.data_ptr(), loss.data_ptr(), _lib.ptr(q_out)
+        a.dH, a.dhead = dH.data_ptr(), dhead.data_ptr()
+        a.zero_ptr, a.zero_n = _lib.ptr(zero), 0 if zero is None else zero.numel()
+        a.lo = _lib.head_lo(*(lo if lo is not None else (None, None, None)))
+        if isn is not None:
+            a.isn.wscale, a.isn.out = _lib.ptr(isn[0]), _lib.ptr(isn[1])
+            a.isn.valid_count = _lib.ptr(isn[2]) if len(isn) > 2 else None
+        assert dhead.shape == (a.B, (a.A + 1) * N) and dhead.is_contiguous()
+        _lib.check(self.lib.apex_c51_head(a, _lib.stream_ptr()), "c51_head")
+
+    def c51_actor_head(self, H, P, eps, ctr, seed, num_atoms, v_min, v_max, q_out, a_out, H_lo=None):
+        E, A = q_out.shape
+        _lib.check(self.lib.apex_c51_actor_head(H.data_ptr(), self._hp(P), E, A, int(num_atoms), float(v_min),
+                                                float(v_max), eps.data_ptr(), int(seed), ctr.data_ptr(),
+                                                q_out.data_ptr(), a_out.data_ptr(), P["wv"].shape[-1],
+                                                _lib.ptr(H_lo), _lib.stream_ptr()), "c51_actor_head")
+
+    def head_wgrad(self, Hon, dhead, g, prio=None, Hon_lo=None, pack=None, norm=None) -> int:
+        """``norm = (partials, slot0)`` (the distributional head only): every block also leaves
+        the squared norm of what it stores; returns the slots written."""
+        B, J = dhead.shape
+        nv = g["bv"].numel()          # value rows: 1, or the distributional head's atoms
+        hidden = g["wv"].shape[-1]
+        npart, nslots = None, 0
+        if norm is not None:
+            assert nv >= 2
+            nslots = (-(-nv // 8) + -(-(J - nv) // 8)) * (hidden // 64)       # csrc/head_common.h HWG_JT
+            npart = norm[0].data_ptr() + 8 * int(norm[1])
+            assert int(norm[1]) + nslots <= norm[0].numel() and norm[0].dtype == torch.float64
         if prio is not None and prio[0].use_hip and B <= 1024:
             rp, idx, gen, td = prio
             pk = self._pack_args(*pack) if pack is not None else (None, None, None, 0, 0, None, 0)
             _lib.check(self.lib.apex_head_wgrad_prio(
-                Hon.data_ptr(), dhead.data_ptr(), B, A1 - 1, g["wv"].data_ptr(), g["bv"].data_ptr(),
-                g["wa"].data_ptr(), g["ba"].data_ptr(), g["wv"].numel(), rp.tree_desc(), idx.data_ptr(),
+                Hon.data_ptr(), dhead.data_ptr(), B, J - nv, g["wv"].data_ptr(), g["bv"].data_ptr(),
+                g["wa"].data_ptr(), g["ba"].data_ptr(), hidden, rp.tree_desc(), idx.data_ptr(),
                 td.data_ptr(), _lib.ptr(gen), rp.gen.data_ptr(), rp.alpha, rp.eps, rp.ctr.data_ptr(),
-                _lib.ptr(Hon_lo), _lib.ptr(rp.local_stats), *pk, _lib.stream_ptr()), "head_wgrad_prio")
-            return
+                _lib.ptr(Hon_lo), _lib.ptr(rp.local_stats), *pk, nv, npart, _lib.stream_ptr()), "head_wgrad_prio")
+            return nslots
         if pack is not None:
             self.pack_rows(*pack)
         if prio is not None:
             prio[0].update_priorities(prio[1], prio[3], prio[2])
-        _lib.check(self.lib.apex_head_wgrad(Hon.data_ptr(), dhead.data_ptr(), B, A1 - 1, g["wv"].data_ptr(),
+        _lib.check(self.lib.apex_head_wgrad(Hon.data_ptr(), dhead.data_ptr(), B, J - nv, g["wv"].data_ptr(),
                                             g["bv"].data_ptr(), g["wa"].data_ptr(), g["ba"].data_ptr(),
-                                            g["wv"].numel(), _lib.ptr(Hon_lo), _lib.stream_ptr()), "head_wgrad")
+                                            hidden, _lib.ptr(Hon_lo), nv, npart, _lib.stream_ptr()), "head_wgrad")
+        return nslots
 
     def actor_head(self, H, P, eps, ctr, seed, q_out, a_out, H_lo=None):
         E, A = q_out.shape

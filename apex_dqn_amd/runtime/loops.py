@@ -106,7 +106,7 @@ def _actor_proc(rank_id: int, cfg_dict: Dict[str, Any], num_envs: int, offset: i
     cfg = ApexConfig.from_dict(cfg_dict)
     group = _make_group(cfg, num_envs, offset, total, cfg.Runtime.seed)
     net = build_network(cfg.network, cfg.env_conf.state_shape, cfg.env_conf.action_dim,
-                        obs_scale=cfg.Runtime.obs_scale).eval()
+                        obs_scale=cfg.Runtime.obs_scale, **cfg.head_kw()).eval()
     ver, sd = shared.read(-1)
     if sd is not None:
         net.load_state_dict(sd)
