@@ -31,6 +31,14 @@ the reference's ``soft_capacity`` (``replay.py:71-80``).
 On CPU (tests) the same class runs a torch implementation with identical
 semantics (exact recompute instead of fp64 deltas; the same counter-based
 uniforms as the kernel, so the global draw is bit-identical).
+
+Running minimum (the p_min of the IS weights, :meth:`min_leaf`): the kernels fold every
+positive leaf value they write into one ``atomicMin`` word, so between two
+:meth:`rebuild` calls it is a LOWER bound of the minimum over the live leaves -- equal
+to it until the minimum leaf is overwritten with a larger value or evicted, too small
+(never too large, never zero) from then on, which only pushes the max-normalised IS
+weights below their exact value.  ``rebuild()`` recomputes it exactly.  The CPU path
+recomputes the minimum on every mutation and is always exact.
 """
 from __future__ import annotations
 
@@ -136,6 +144,9 @@ class GpuReplayShard:
                  frame_shape=(84, 84), alpha: float = 0.6, beta: float = 0.4, eps: float = 1e-6,
                  device: torch.device = torch.device("cuda"), seed: int = 0, use_hip: Optional[bool] = None):
         self.device = torch.device(device)
+        if int(capacity) < 2:
+            # one leaf: no internal level (L == 0), so no kernel would ever write the root
+            raise ValueError("replay capacity must be at least 2")
         self.cap = int(capacity)
         self.soft_capacity = int(min(soft_capacity, capacity))
         self.F = int(frame_capacity)
