@@ -272,9 +272,12 @@ class GpuActorGroup:
 
     def _actor_head(self, h, heads, h_lo) -> None:
         """q + epsilon-greedy draw into ``self.q`` / ``self.act``: the dueling head, or with a
-        distributional learner (``learner.N`` atoms) the expected q of its C51 head."""
+        distributional learner (``learner.N`` atoms) the expected q of its C51 head or the mean of
+        its quantile head (``Runtime.dist_head``)."""
         n = int(getattr(self.learner, "N", 1))
-        if n >= 2:
+        if n >= 2 and self.cfg.quantile:
+            self.ops.qr_actor_head(h, heads, self.eps, self.ctr, self.seed, n, self.q, self.act, H_lo=h_lo)
+        elif n >= 2:
             rt = self.cfg.Runtime
             self.ops.c51_actor_head(h, heads, self.eps, self.ctr, self.seed, n, rt.v_min, rt.v_max, self.q, self.act,
                                     H_lo=h_lo)

@@ -103,6 +103,11 @@ class RuntimeConf:
     num_atoms: int = 1
     v_min: float = -10.0
     v_max: float = 10.0
+    # the distributional head's kind, read only when num_atoms >= 2: "categorical" (C51, above) or "quantile"
+    # (QR-DQN, csrc/qr_head.hip): num_atoms quantiles per action at tau_i = (2 i + 1) / (2 N), the quantile Huber
+    # loss with kappa = huber_delta (> 0; loss does not apply), no support (v_min / v_max are ignored), the same
+    # priority and the same refusals (learner/losses.py quantile_huber_loss)
+    dist_head: str = "categorical"
     priority_eps: float = 1e-6      # priority floor: leaves hold (|delta| + priority_eps)^alpha
     use_is_weights: bool = True
     is_normalise: str = "batch_max"  # IS weights (N P(i))^-beta divided by their max over the sampled batch
@@ -287,6 +292,14 @@ class ApexConfig:
             raise ValueError(f"Runtime.num_atoms must be 1 or an integer in [2, 64] (one lane per atom), got {na!r}")
         if not float(rt.v_min) < float(rt.v_max):
             raise ValueError(f"Runtime.v_min must be below Runtime.v_max, got {rt.v_min} / {rt.v_max}")
+        if rt.dist_head not in ("categorical", "quantile"):
+            raise ValueError(f"Runtime.dist_head must be 'categorical' or 'quantile', got {rt.dist_head!r}")
+        if na == 1 and rt.dist_head != "categorical":
+            raise ValueError(f"Runtime.dist_head={rt.dist_head!r} needs Runtime.num_atoms >= 2 (the scalar head has "
+                             f"no distribution)")
+        if na >= 2 and rt.dist_head == "quantile" and not float(rt.huber_delta) > 0.0:
+            raise ValueError(f"Runtime.dist_head='quantile' needs Runtime.huber_delta > 0 (the quantile Huber loss's "
+                             f"kappa), got {rt.huber_delta}")
         if na >= 2:
             if net not in ("nature64", "nature32", "mlp"):
                 raise ValueError(f"Runtime.num_atoms={na} needs network nature64, nature32 or mlp, got {net!r}")
@@ -311,7 +324,13 @@ class ApexConfig:
     def head_kw(self) -> Dict[str, Any]:
         """The dueling modules' head arguments (models/dueling.py)."""
         rt = self.Runtime
-        return dict(num_atoms=int(rt.num_atoms), v_min=float(rt.v_min), v_max=float(rt.v_max))
+        return dict(num_atoms=int(rt.num_atoms), v_min=float(rt.v_min), v_max=float(rt.v_max),
+                    dist_head=str(rt.dist_head))
+
+    @property
+    def quantile(self) -> bool:
+        """The distributional head is the quantile-regression one (Runtime.dist_head)."""
+        return self.distributional and self.Runtime.dist_head == "quantile"
 
     @property
     def env_backend(self) -> str:

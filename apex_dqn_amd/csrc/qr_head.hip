@@ -1,0 +1,192 @@
+// Quantile-regression (QR-DQN) dueling head for the NatureCNN learner: the distributional
+// head of Runtime.dist_head = "quantile" (Runtime.num_atoms = N quantiles per action, one
+// lane per quantile, 2 <= N <= 64).  No support: nothing to clamp onto.
+//
+// Head weights exactly as csrc/c51_head.hip reads them: wv [N][HS], bv [N], wa [A N][HS]
+// (row a N + i = action a, quantile i), ba [A N]; HS = 512.  kappa = Runtime.huber_delta > 0.
+//
+//   theta[a,i] = v[i] + adv[a,i] - mean_a' adv[a',i]         (dueling mean per quantile)
+//   q[a]       = (1/N) sum_i theta[a,i],   tau_i = (2 i + 1) / (2 N)
+//   a*         = argmax_a q_online(S_t+n) (first maximum)
+//   T_j        = R + G theta_target(S_t+n)[a*,j]             (G = 0 at terminals: T_j = R)
+//   u_ij       = T_j - theta(S_t)[a_b,i]
+//   L(u)       = u^2 / 2 if |u| <= kappa, else kappa (|u| - kappa / 2)
+//   loss_b     = w_b sum_i (1/N) sum_j |tau_i - 1{u_ij < 0}| L(u_ij) / kappa
+//   g_i        = -w_b grad_scale (1/N) sum_j |tau_i - 1{u_ij < 0}| clamp(u_ij, -kappa, kappa) / kappa
+//                (the j-sums in increasing j; the i-sum a wave sum)
+//   d v[i] = g_i,  d adv[a,i] = g_i ([a = a_b] - 1/A)  -> dhead [B][(A + 1) N]
+//   td_abs_b   = |(1/N) sum_j T_j - q(S_t)[a_b]| = |R + G q_target[a*] - q[a_b]|
+//   dH         = dhead . W, masked by the stream ReLUs (bf16, or hi / lo planes)
+//
+// qr_head_kernel: one block of DIST_NT threads per DIST_SPB samples.  Staging the
+// activation rows, the logits and dH (phases 0, 1 and 3) are csrc/dist_head.h's, shared
+// with the categorical head; phase 2 is this head's own:
+//   2. Wave s finishes sample s with lane = quantile.  The three theta rows come from the
+//      LDS logits; q per action is one wave sum; a* is made wave-uniform; each lane keeps
+//      its T_j, and the j loop reads lane j of it (j is wave-uniform: a lane read, no
+//      shuffle) while every lane accumulates its own quantile's loss and gradient.  Lanes
+//      >= N hold theta = T = 0 and add exact zeros to the wave sums; a sample past the
+//      batch stores nothing.
+// Nothing depends on the order blocks run in (no float atomics).
+//
+// qr_actor_head_kernel: one wave per env row, the logits as in phase 1 with the row in
+// registers, q = the mean of theta per action and the epsilon-greedy draw of
+// actor_head_kernel (same counter-RNG words).
+#include "dist_head.h"
+
+struct QRArgs {
+  const bf16_t* Hon;    // [2B][2 HS]
+  const bf16_t* Htg;    // [B][2 HS]
+  HeadParams Pon, Ptg;
+  const int32_t* act;
+  const float* rew;
+  const float* gam;
+  const float* isw;     // null: weights off
+  int B, A, N, hidden;
+  float kappa, grad_scale;
+  float* td_abs;
+  float* loss;
+  float* q_out;         // [B][A] q(S_t) = mean of the quantiles, or null
+  bf16_t* dH;           // [B][2 HS]
+  float* dhead;         // [B][(A + 1) N]
+  float* zero_ptr;      // head-gradient region zeroed for the head weight gradient
+  int zero_n;
+  HeadLo lo;
+  IsNorm isn;
+};
+
+// this lane's quantile of action a (0 in a lane past N)
+__device__ __forceinline__ float qr_theta(const DistRow& r, int a, int N, int lane) {
+  return lane < N ? r.v + (r.L[N + a * N + lane] + r.ba[a * N + lane]) - r.mean : 0.f;
+}
+
+__global__ void __launch_bounds__(DIST_NT) qr_head_kernel(QRArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float qr_smem[];
+  constexpr int HS = DIST_HS, ROW = 2 * HS, SPB = DIST_SPB, NR = 3 * SPB;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int B = a.B, A = a.A, N = a.N, AN = A * N, J = N + AN;
+  const int Jp = (J + 3) & ~3;
+  float* Hs = qr_smem;                   // [NR][ROW]: rows s (S_t), SPB + s (online S_t+n), 2 SPB + s (target)
+  float* Ls = qr_smem + NR * ROW;        // [NR][Jp] logits (no biases); rows s later hold the dhead rows
+  const int b0 = blockIdx.x * SPB;
+  const bool split = a.lo.Hon != nullptr;
+
+  dist_head_side(a, tid, lane, wv);
+  dist_head_stage(a, Hs, b0, tid, split);
+  __syncthreads();
+  dist_head_logits(a, Hs, Ls, Jp, lane, wv);
+  __syncthreads();
+
+  // ---- phase 2: wave s finishes sample s (lane = quantile)
+  if (wv < SPB) {
+    const int s = wv;
+    const bool live = b0 + s < B;
+    const int b = min(b0 + s, B - 1);
+    const bool valid = lane < N;
+    const float invN = 1.0f / (float)N;
+    const int a_b = a.act[b];
+    const float rew_b = a.rew[b], gam_b = a.gam[b];
+    const float w_b = a.isw != nullptr ? a.isw[b] : 1.f;
+    const float kappa = a.kappa;
+    // double DQN: a* from the online net at S_t+n (first maximum wins)
+    int astar = 0;
+    {
+      const DistRow rn = dist_row(Ls + (SPB + s) * Jp, a.Pon, A, N, lane);
+      float best = -3.4e38f;
+      for (int j = 0; j < A; ++j) {
+        const float q = wave_sum_dpp(qr_theta(rn, j, N, lane)) * invN;
+        if (q > best) { best = q; astar = j; }
+      }
+      astar = __builtin_amdgcn_readfirstlane(astar);
+    }
+    // the target samples: lane j holds T_j
+    float T;
+    {
+      const DistRow rg = dist_row(Ls + (2 * SPB + s) * Jp, a.Ptg, A, N, lane);
+      T = valid ? rew_b + gam_b * qr_theta(rg, astar, N, lane) : 0.f;
+    }
+    // S_t: q of every action, the taken action's quantiles
+    float th_sa = 0.f, q_sa = 0.f;
+    {
+      const DistRow rt = dist_row(Ls + s * Jp, a.Pon, A, N, lane);
+      for (int j = 0; j < A; ++j) {
+        const float th = qr_theta(rt, j, N, lane);
+        const float q = wave_sum_dpp(th) * invN;
+        if (a.q_out != nullptr && live && lane == 0) a.q_out[(int64_t)b * A + j] = q;
+        if (j == a_b) { th_sa = th; q_sa = q; }
+      }
+    }
+    // this lane's quantile against every target sample, in increasing j
+    const float tau = (2.f * (float)lane + 1.f) / (2.f * (float)N);
+    float rho = 0.f, c = 0.f;
+    for (int j = 0; j < N; ++j) {
+      const float Tj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(T), j));
+      const float u = Tj - th_sa;
+      const float au = fabsf(u);
+      const float wgt = fabsf(tau - (u < 0.f ? 1.f : 0.f));
+      rho += wgt * (au <= kappa ? 0.5f * u * u : kappa * (au - 0.5f * kappa));
+      c += wgt * fminf(fmaxf(u, -kappa), kappa);
+    }
+    const float sc = invN / kappa;
+    const float ls = wave_sum_dpp(valid ? rho * sc : 0.f);
+    const float et = wave_sum_dpp(T) * invN;
+    const float g = valid ? -w_b * a.grad_scale * (c * sc) : 0.f;
+    if (live && lane == 0) {
+      a.td_abs[b] = fabsf(et - q_sa);
+      a.loss[b] = w_b * ls;
+    }
+    // the dhead row: to memory, and into LDS (over the consumed S_t logits) for phase 3
+    dist_head_store_dhead(g, live, valid, a_b, A, N, lane, Ls + s * Jp, a.dhead + (int64_t)b * J);
+  }
+  __syncthreads();
+
+  dist_head_dh(a, Hs, Ls, Jp, b0, tid, split);
+}
+
+APEX_EXPORT int apex_qr_head(QRArgs a, hipStream_t st) {
+  size_t lds = 0;
+  if (!dist_head_args_ok(a, &lds) || !(a.kappa > 0.f)) return (int)hipErrorInvalidValue;
+  const int grid = (a.B + DIST_SPB - 1) / DIST_SPB;
+  qr_head_kernel<<<grid, DIST_NT, lds, st>>>(a);
+  APEX_CHECK_LAUNCH();
+}
+
+// Actor side: q = mean of the quantiles + epsilon-greedy, one wave per env row (four per
+// block; a wave past E repeats the last row and stores nothing).
+__global__ void __launch_bounds__(256) qr_actor_head_kernel(const bf16_t* __restrict__ H, HeadParams P, int E, int A,
+                                                            int N, const float* __restrict__ eps, uint64_t seed,
+                                                            const uint64_t* __restrict__ ctr,
+                                                            float* __restrict__ q_out, int32_t* __restrict__ a_out,
+                                                            const bf16_t* __restrict__ H_lo) {
+  extern __shared__ __attribute__((aligned(16))) float qr_smem[];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int AN = A * N, J = N + AN, Jp = (J + 3) & ~3;
+  const int e_raw = blockIdx.x * 4 + wv;
+  const bool live = e_raw < E;
+  const int e = min(e_raw, E - 1);
+  float* L = qr_smem + wv * Jp;
+  dist_actor_logits(H, H_lo, P, e, A, N, lane, L);
+  __syncthreads();
+  const float invN = 1.0f / (float)N;
+  const DistRow r = dist_row(L, P, A, N, lane);
+  int best = 0;
+  float bq = -3.4e38f;
+  for (int j = 0; j < A; ++j) {
+    const float q = wave_sum_dpp(qr_theta(r, j, N, lane)) * invN;
+    if (q > bq) { bq = q; best = j; }
+    if (live && lane == 0) q_out[(int64_t)e * A + j] = q;
+  }
+  if (live && lane == 0) dist_actor_draw(best, e, A, eps, seed, ctr, a_out);
+}
+
+APEX_EXPORT int apex_qr_actor_head(const bf16_t* H, HeadParams P, int E, int A, int N, const float* eps, uint64_t seed,
+                                   const uint64_t* ctr, float* q_out, int32_t* a_out, int hidden,
+                                   const bf16_t* H_lo, hipStream_t st) {
+  if (A < 1 || A > HEAD_MAXA || E < 1 || N < 2 || N > 64 || hidden != DIST_HS) return (int)hipErrorInvalidValue;
+  if ((((uintptr_t)P.wv | (uintptr_t)P.wa) & 15) || (((uintptr_t)H | (uintptr_t)H_lo) & 7))
+    return (int)hipErrorInvalidValue;
+  const int J = (A + 1) * N, Jp = (J + 3) & ~3;
+  qr_actor_head_kernel<<<(E + 3) / 4, 256, (size_t)4 * Jp * sizeof(float), st>>>(H, P, E, A, N, eps, seed, ctr, q_out,
+                                                                                 a_out, H_lo);
+  APEX_CHECK_LAUNCH();
+}

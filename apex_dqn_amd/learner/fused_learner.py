@@ -6,6 +6,7 @@ Per step (B = local batch), entirely on device, one stream, no host sync:
                                                  by slot) / conv2 / conv3 / fc
   DDQN target + Huber*IS loss + |delta| + dH     csrc/ddqn_head.hip (Runtime.num_atoms >= 2:
                                                  csrc/c51_head.hip, projected cross-entropy,
+                                                 or csrc/qr_head.hip, quantile Huber loss,
                                                  then head wgrad + write-back and fc wgrad as
                                                  two launches on the backward's branch)
   fc wgrad + head wgrad + priority write-back    ONE launch (csrc/sumtree.hip
@@ -53,7 +54,7 @@ from ..models.flat_params import (FlatLayout, flat_to_reference_state, nature_se
                                   reference_state_to_flat)
 from ..ops.fused_ops import HipBackend, TorchBackend, split_into
 from ..ops.switches import SW
-from ..utils.checkpoint import (adopt_obs_scale, layout_segments, load_checkpoint, pack_flat_state,
+from ..utils.checkpoint import (adopt_obs_scale, check_dist_head, layout_segments, load_checkpoint, pack_flat_state,
                                 save_checkpoint, unpack_flat_state, checkpoint_network)
 from .dp_step import DataParallelStep, Streams
 from .is_norm import IsNormMixin
@@ -105,6 +106,8 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         self.world, self._dp, self.B, self.mcap = dp_layout(cfg, comm, batch_size)
         # distributional (C51) head: N atoms per action (csrc/c51_head.hip); 1 = the scalar head
         self.N = int(self.rt.num_atoms)
+        # its kind: categorical (csrc/c51_head.hip) or quantile regression (csrc/qr_head.hip)
+        self.quantile = cfg.quantile
         if self.N >= 2 and self._dp:
             raise ValueError(f"Runtime.num_atoms={self.N}: the distributional head runs on a single rank, not in "
                              f"the data-parallel step (world > 1, Runtime.force_dp, the emulated world)")
@@ -448,7 +451,14 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         self._mark("forward")
         isw = S["weights"] if self._isw else None
         sp = self.split
-        if self.N >= 2:
+        if self.N >= 2 and self.quantile:
+            # quantile regression: the quantile Huber loss, kappa = huber_delta (Runtime.loss, v_min / v_max
+            # do not apply)
+            ops.qr_head(self.h[:2 * B], self.h[2 * B:], self._head_params(self.P), self._head_params(self.T),
+                        S["act"], S["rew"], S["gam"], isw, self.N, rt.huber_delta, 1.0 / (B * self.world),
+                        self.td_abs, self.loss_b, self.dH, self.dhead, zero=self.g_head_region, isn=self._isn(),
+                        **self._lo(lo=sp and (self.h_lo[:2 * B], self.h_lo[2 * B:], self.dH_lo)))
+        elif self.N >= 2:
             # categorical projection + cross-entropy (Runtime.loss / huber_delta do not apply)
             ops.c51_head(self.h[:2 * B], self.h[2 * B:], self._head_params(self.P), self._head_params(self.T),
                          S["act"], S["rew"], S["gam"], isw, self.N, rt.v_min, rt.v_max, 1.0 / (B * self.world),
@@ -1037,6 +1047,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         ck = load_checkpoint(path)
         if ck is None:
             return False
+        check_dist_head(ck, self.rt)
         if adopt_obs_scale(ck, self.rt):
             self._graphs = self._multi = None    # the input scale is a kernel argument: recapture
             self._setup_frag_out()               # (and folded into the conv1 operands)

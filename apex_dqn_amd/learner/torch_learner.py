@@ -19,8 +19,8 @@ import torch
 
 from ..config import ApexConfig
 from ..models.dueling import build_network
-from ..utils.checkpoint import adopt_obs_scale, load_checkpoint, save_checkpoint
-from .losses import c51_loss, ddqn_loss
+from ..utils.checkpoint import adopt_obs_scale, check_dist_head, load_checkpoint, save_checkpoint
+from .losses import c51_loss, ddqn_loss, quantile_huber_loss
 from .schedules import lr_scheduled, rt_lr
 
 
@@ -71,6 +71,13 @@ class TorchLearner:
         G = self._to(batch["Gamma"], torch.float32)
         w = self._to(batch["weights"], torch.float32) if (
             self.rt.use_is_weights and "weights" in batch) else None
+        if self.cfg.quantile:
+            # QR-DQN: quantile Huber loss against the target net's quantiles (learner/losses.py)
+            with torch.no_grad():
+                q_next_online = self.Q(S_tpn)[2]
+                th_next_target = self.Q_target.quantiles(S_tpn)
+            return quantile_huber_loss(self.Q.quantiles(S_t), q_next_online, th_next_target, A, R, G,
+                                       self.rt.huber_delta, w)
         if self.cfg.distributional:
             # C51: cross-entropy against the projected target distribution (learner/losses.py)
             with torch.no_grad():
@@ -127,6 +134,7 @@ class TorchLearner:
         ck = load_checkpoint(path)
         if ck is None:
             return False
+        check_dist_head(ck, self.rt)
         if adopt_obs_scale(ck, self.rt):
             for net in (self.Q, self.Q_target):
                 if hasattr(net, "pre"):

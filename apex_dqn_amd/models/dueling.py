@@ -34,20 +34,33 @@ class _C51Head:
     """Distributional (C51) dueling head shared by the modules that take ``num_atoms``:
     the value head has N outputs, the advantage head A N (row a N + i = action a, atom i),
     the dueling combine runs per atom and q is the expectation over the fixed support
-    z_i = v_min + i (v_max - v_min) / (N - 1).  N = 1: the scalar head."""
+    z_i = v_min + i (v_max - v_min) / (N - 1).  N = 1: the scalar head.
 
-    def _init_head(self, hidden: int, num_atoms: int, v_min: float, v_max: float) -> None:
+    ``dist_head = "quantile"`` (QR-DQN): the same weights, keys and shapes, read as N
+    quantiles per action, theta[a, i] = v[i] + adv[a, i] - mean_a' adv[a', i] at tau_i =
+    (2 i + 1) / (2 N); q is their mean; no support buffer (v_min / v_max are ignored)."""
+
+    def _init_head(self, hidden: int, num_atoms: int, v_min: float, v_max: float,
+                   dist_head: str = "categorical") -> None:
+        if dist_head not in ("categorical", "quantile"):
+            raise ValueError(f"dist_head must be 'categorical' or 'quantile', got {dist_head!r}")
         self.num_atoms = int(num_atoms)
+        self.dist_head = dist_head if self.num_atoms > 1 else "categorical"
         self.v_min, self.v_max = float(v_min), float(v_max)
         self.value = nn.Linear(hidden, self.num_atoms)
         self.advantage = nn.Linear(hidden, self.action_dim * self.num_atoms)
-        if self.num_atoms > 1:
+        if self.num_atoms > 1 and self.dist_head == "categorical":
             self.register_buffer("support", c51_support(self.num_atoms, self.v_min, self.v_max), persistent=False)
 
     def _head(self, hv: torch.Tensor, ha: torch.Tensor):
+        """(value, advantage, q, dist): dist = [B, A, N] log-probabilities (categorical) or
+        quantiles (quantile); None for the scalar head."""
         value, advantage = self.value(hv), self.advantage(ha)
         if self.num_atoms == 1:
             return value, advantage, dueling_combine(value, advantage), None
+        if self.dist_head == "quantile":
+            theta = dueling_quantiles(value, advantage, self.action_dim)
+            return value, advantage, theta.mean(-1), theta
         logp = c51_log_probs(value, advantage, self.action_dim)
         q = (logp.exp() * self.support.to(logp.dtype)).sum(-1)
         return value, advantage, q, logp
@@ -65,6 +78,14 @@ def c51_log_probs(value: torch.Tensor, advantage: torch.Tensor, action_dim: int)
     adv = advantage.reshape(B, action_dim, N)
     logits = value[:, None, :] + adv - adv.mean(dim=1, keepdim=True)
     return F.log_softmax(logits, dim=-1)
+
+
+def dueling_quantiles(value: torch.Tensor, advantage: torch.Tensor, action_dim: int) -> torch.Tensor:
+    """[B, A, N] quantiles theta[a, i] = v[i] + adv[a, i] - mean_a' adv[a', i] (the dueling
+    mean per quantile)."""
+    B, N = value.shape
+    adv = advantage.reshape(B, action_dim, N)
+    return value[:, None, :] + adv - adv.mean(dim=1, keepdim=True)
 
 
 class _ObsScale(nn.Module):
@@ -89,7 +110,8 @@ class DuellingDQN(nn.Module, _C51Head):
 
     def __init__(self, state_shape: Sequence[int], action_dim: int,
                  conv1_channels: int = 64, obs_scale: float = 1.0 / 255.0,
-                 num_atoms: int = 1, v_min: float = -10.0, v_max: float = 10.0):
+                 num_atoms: int = 1, v_min: float = -10.0, v_max: float = 10.0,
+                 dist_head: str = "categorical"):
         super().__init__()
         self.input_shape = tuple(state_shape)
         self.action_dim = int(action_dim)
@@ -101,7 +123,7 @@ class DuellingDQN(nn.Module, _C51Head):
         self.layer3 = nn.Sequential(nn.Conv2d(64, 64, 3, stride=1), nn.ReLU())
         self.value_stream_layer = nn.Sequential(nn.Linear(64 * 7 * 7, 512), nn.ReLU())
         self.advantage_stream_layer = nn.Sequential(nn.Linear(64 * 7 * 7, 512), nn.ReLU())
-        self._init_head(512, num_atoms, v_min, v_max)
+        self._init_head(512, num_atoms, v_min, v_max, dist_head)
 
     def features(self, x: torch.Tensor) -> torch.Tensor:
         x = self.pre(x)
@@ -114,6 +136,13 @@ class DuellingDQN(nn.Module, _C51Head):
 
     def log_probs(self, x: torch.Tensor) -> torch.Tensor:
         """[B, A, N] log-probabilities of the value distribution (``num_atoms`` >= 2)."""
+        assert self.dist_head == "categorical" and self.num_atoms > 1
+        h = self.features(x)
+        return self._head(self.value_stream_layer(h), self.advantage_stream_layer(h))[3]
+
+    def quantiles(self, x: torch.Tensor) -> torch.Tensor:
+        """[B, A, N] quantiles of the value distribution (``dist_head = "quantile"``)."""
+        assert self.dist_head == "quantile"
         h = self.features(x)
         return self._head(self.value_stream_layer(h), self.advantage_stream_layer(h))[3]
 
@@ -122,7 +151,8 @@ class MLPDuellingDQN(nn.Module, _C51Head):
     """Dueling MLP for low-dimensional states (CartPole config)."""
 
     def __init__(self, state_shape: Sequence[int], action_dim: int, hidden: int = 128,
-                 num_atoms: int = 1, v_min: float = -10.0, v_max: float = 10.0):
+                 num_atoms: int = 1, v_min: float = -10.0, v_max: float = 10.0,
+                 dist_head: str = "categorical"):
         super().__init__()
         d = int(state_shape[0]) if len(state_shape) == 1 else int(torch.tensor(state_shape).prod())
         self.input_shape = tuple(state_shape)
@@ -130,7 +160,7 @@ class MLPDuellingDQN(nn.Module, _C51Head):
         self.layer1 = nn.Sequential(nn.Linear(d, hidden), nn.ReLU())
         self.value_stream_layer = nn.Sequential(nn.Linear(hidden, hidden), nn.ReLU())
         self.advantage_stream_layer = nn.Sequential(nn.Linear(hidden, hidden), nn.ReLU())
-        self._init_head(hidden, num_atoms, v_min, v_max)
+        self._init_head(hidden, num_atoms, v_min, v_max, dist_head)
 
     def forward(self, x: torch.Tensor):
         h = self.layer1(x.float().reshape(x.shape[0], -1))
@@ -138,6 +168,13 @@ class MLPDuellingDQN(nn.Module, _C51Head):
 
     def log_probs(self, x: torch.Tensor) -> torch.Tensor:
         """[B, A, N] log-probabilities of the value distribution (``num_atoms`` >= 2)."""
+        assert self.dist_head == "categorical" and self.num_atoms > 1
+        h = self.layer1(x.float().reshape(x.shape[0], -1))
+        return self._head(self.value_stream_layer(h), self.advantage_stream_layer(h))[3]
+
+    def quantiles(self, x: torch.Tensor) -> torch.Tensor:
+        """[B, A, N] quantiles of the value distribution (``dist_head = "quantile"``)."""
+        assert self.dist_head == "quantile"
         h = self.layer1(x.float().reshape(x.shape[0], -1))
         return self._head(self.value_stream_layer(h), self.advantage_stream_layer(h))[3]
 
@@ -207,8 +244,8 @@ class ImpalaDuellingDQN(nn.Module):
 
 def build_network(kind: str, state_shape: Sequence[int], action_dim: int,
                   obs_scale: float = 1.0 / 255.0, num_atoms: int = 1, v_min: float = -10.0,
-                  v_max: float = 10.0) -> nn.Module:
-    head = dict(num_atoms=num_atoms, v_min=v_min, v_max=v_max)
+                  v_max: float = 10.0, dist_head: str = "categorical") -> nn.Module:
+    head = dict(num_atoms=num_atoms, v_min=v_min, v_max=v_max, dist_head=dist_head)
     if kind == "nature64":
         return DuellingDQN(state_shape, action_dim, conv1_channels=64, obs_scale=obs_scale, **head)
     if kind == "nature32":

@@ -65,6 +65,15 @@ class C51Args(ctypes.Structure):
                 ("dhead", c_p), ("zero_ptr", c_p), ("zero_n", c_i), ("lo", HeadLo), ("isn", IsNorm)]
 
 
+class QRArgs(ctypes.Structure):
+    """Arguments of the quantile-regression head kernel (``QRArgs``, csrc/qr_head.hip): ``C51Args`` with
+    ``kappa`` in the place of the support."""
+    _fields_ = [("Hon", c_p), ("Htg", c_p), ("Pon", HeadParams), ("Ptg", HeadParams), ("act", c_p), ("rew", c_p),
+                ("gam", c_p), ("isw", c_p), ("B", c_i), ("A", c_i), ("N", c_i), ("hidden", c_i), ("kappa", c_f),
+                ("grad_scale", c_f), ("td_abs", c_p), ("loss", c_p), ("q_out", c_p), ("dH", c_p),
+                ("dhead", c_p), ("zero_ptr", c_p), ("zero_n", c_i), ("lo", HeadLo), ("isn", IsNorm)]
+
+
 class CfFragOut(ctypes.Structure):
     """The optimizer's stores of the fused forward's online operands (``CfFragOut``,
     csrc/cf_pack.h); all-zero = off."""
@@ -184,6 +193,8 @@ _SIGS = {
     "apex_head_wgrad": ([c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p], c_i),
     "apex_c51_head": ([C51Args, c_p], c_i),
     "apex_c51_actor_head": ([c_p, HeadParams, c_i, c_i, c_i, c_f, c_f, c_p, c_u64, c_p, c_p, c_p, c_i, c_p, c_p], c_i),
+    "apex_qr_head": ([QRArgs, c_p], c_i),
+    "apex_qr_actor_head": ([c_p, HeadParams, c_i, c_i, c_i, c_p, c_u64, c_p, c_p, c_p, c_i, c_p, c_p], c_i),
     "apex_actor_head": ([c_p, HeadParams, c_i, c_i, c_p, c_u64, c_p, c_p, c_p, c_i, c_p, c_p], c_i),
     "apex_conv1_s2d_fwd": ([Conv1S2DDesc, c_i, c_p], c_i),
     "apex_conv1_wgrad_img": ([Conv1WgDesc, c_i, c_p], c_i),
@@ -213,7 +224,7 @@ def _declare(lib: ctypes.CDLL) -> None:
     conv_sigs.declare(lib)
 
 
-ABI_VERSION = 11    # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
+ABI_VERSION = 12    # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
 
 
 def load(build_if_missing: bool = True) -> Optional[ctypes.CDLL]:

@@ -268,6 +268,78 @@ class TorchBackend:
         r = torch.randint(0, A, (E,), generator=gen).to(q.device)
         a_out.copy_(torch.where(u < eps.to(q.device), r, q.argmax(1)).to(a_out.dtype))
 
+    # ------------------------------------------- quantile-regression (QR-DQN) head
+    @staticmethod
+    def _qr_theta(h, P, A: int, N: int, dt):
+        """[rows, A, N] quantiles of stream activations ``h``: theta[a, i] = v[i] + adv[a, i] -
+        mean_a' adv[a', i] (the dueling mean per quantile)."""
+        HS = P["wv"].shape[-1]
+        v = h[:, :HS] @ P["wv"].to(dt).reshape(N, HS).t() + P["bv"].to(dt)
+        a = (h[:, HS:] @ P["wa"].to(dt).t() + P["ba"].to(dt)).reshape(-1, A, N)
+        return v[:, None, :] + a - a.mean(1, keepdim=True)
+
+    def qr_head(self, Hon, Htg, Pon: Dict[str, torch.Tensor], Ptg: Dict[str, torch.Tensor], act, rew, gam, isw,
+                num_atoms: int, kappa: float, grad_scale: float, td_abs, loss, dH, dhead,
+                q_out=None, zero: Optional[torch.Tensor] = None, lo=None, isn=None):
+        """The quantile-regression counterpart of :meth:`c51_head` (the oracle of
+        csrc/qr_head.hip ``qr_head_kernel``), the same head weights read as N quantiles per
+        action: T_j = R + Gamma theta_target(S_t+n)[a*, j] with a* the online net's double-DQN
+        action (q = mean of the quantiles), loss = w sum_i rho_i and g = -w grad_scale c
+        (learner/losses.py ``quantile_huber_terms``, kappa > 0), td_abs = |mean_j T_j -
+        q(S_t)[a]|, ``dhead`` / ``dH`` / ``q_out`` laid out as :meth:`c51_head`'s.  Computes in
+        the head weights' dtype when that is fp64 (the tests' reference), else fp32."""
+        from ..learner.losses import quantile_huber_terms
+        B, N = act.shape[0], int(num_atoms)
+        A = Pon["wa"].shape[0] // N
+        dt = torch.float64 if Pon["wv"].dtype == torch.float64 else torch.float32
+        HS = Pon["wv"].shape[-1]
+        if not float(kappa) > 0.0:
+            raise ValueError(f"qr_head: kappa must be > 0, got {kappa}")
+
+        def joined(hi, l):
+            return hi.to(dt) if l is None else hi.to(dt) + l.to(dt)
+
+        Hon = joined(Hon, None if lo is None else lo[0])
+        Htg = joined(Htg, None if lo is None else lo[1])
+        ar = torch.arange(B, device=Hon.device)
+        th_t = self._qr_theta(Hon[:B], Pon, A, N, dt)
+        q_t = th_t.mean(-1)
+        a_star = self._qr_theta(Hon[B:2 * B], Pon, A, N, dt).mean(-1).argmax(1)
+        T = rew.to(dt)[:, None] + gam.to(dt)[:, None] * self._qr_theta(Htg[:B], Ptg, A, N, dt)[ar, a_star]
+        th = th_t[ar, act.long()]
+        rho, c = quantile_huber_terms(th, T, kappa)
+        w = isw.to(dt) if isw is not None else torch.ones(B, dtype=dt, device=Hon.device)
+        td_abs.copy_((T.mean(-1) - th.mean(-1)).abs())
+        loss.copy_(w * rho.sum(-1))
+        g = -w[:, None] * grad_scale * c                           # d loss / d theta of (a_b, .)
+        onehot = torch.nn.functional.one_hot(act.long(), A).to(dt)
+        dadv = g[:, None, :] * (onehot - 1.0 / A)[:, :, None]      # [B, A, N]
+        dhead[:, :N] = g
+        dhead[:, N:] = dadv.reshape(B, A * N)
+        dv = g @ Pon["wv"].to(dt).reshape(N, HS)
+        da = dadv.reshape(B, A * N) @ Pon["wa"].to(dt)
+        dh = torch.cat([dv, da], 1) * (Hon[:B] > 0).to(dt)
+        split_into(dh, dH, None if lo is None else lo[2])
+        if q_out is not None:
+            q_out.copy_(q_t)
+        if zero is not None:
+            zero.zero_()
+        self._is_norm_stats(isn, w.float())
+
+    def qr_actor_head(self, H, P, eps, ctr, seed, num_atoms: int, q_out, a_out, H_lo=None):
+        """q = mean of the quantiles + epsilon-greedy per row (the oracle of csrc/qr_head.hip
+        ``qr_actor_head_kernel``)."""
+        N = int(num_atoms)
+        dt = torch.float64 if P["wv"].dtype == torch.float64 else torch.float32
+        h = H.to(dt) if H_lo is None else H.to(dt) + H_lo.to(dt)
+        E, A = q_out.shape
+        q = self._qr_theta(h, P, A, N, dt).mean(-1)
+        q_out.copy_(q)
+        gen = torch.Generator(device="cpu").manual_seed(int(seed) * 1000003 + int(ctr.item()))
+        u = torch.rand(E, generator=gen).to(q.device)
+        r = torch.randint(0, A, (E,), generator=gen).to(q.device)
+        a_out.copy_(torch.where(u < eps.to(q.device), r, q.argmax(1)).to(a_out.dtype))
+
     def head_wgrad(self, Hon, dhead, g: Dict[str, torch.Tensor], prio=None, Hon_lo=None, pack=None):
         """``prio = (replay, idx, gen, td_abs)``: also write the batch's priorities back
         (the HIP backend runs it as one extra block of the same launch).  ``pack = (dst,
@@ -485,7 +557,8 @@ class HipBackend(TorchBackend):
         super().__init__(dtype)
         self.lib = _lib.require_kernels()
         self.native_conv = native_conv and hasattr(self.lib, "apex_conv_fwd")
-        self.kernels = ["replay", "head", "head_wgrad", "optimizer", "actor_head", "c51_head", "c51_actor_head"]
+        self.kernels = ["replay", "head", "head_wgrad", "optimizer", "actor_head", "c51_head", "c51_actor_head", "qr_head",
+                        "qr_actor_head"]
         if self.native_conv:
             self.kernels += ["conv_fwd", "conv_dgrad", "conv_wgrad", "fc_fwd", "fc_bwd"]
         self.ws = C.Workspace()
@@ -727,6 +800,32 @@ class HipBackend(TorchBackend):
                                                 float(v_max), eps.data_ptr(), int(seed), ctr.data_ptr(),
                                                 q_out.data_ptr(), a_out.data_ptr(), P["wv"].shape[-1],
                                                 _lib.ptr(H_lo), _lib.stream_ptr()), "c51_actor_head")
+
+    def qr_head(self, Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, kappa, grad_scale, td_abs, loss,
+                dH, dhead, q_out=None, zero=None, lo=None, isn=None):
+        """csrc/qr_head.hip ``qr_head_kernel`` (reads h: the fc epilogue is not deferred)."""
+        assert getattr(self, "_fc_part", None) is None, "the distributional head reads h: fc epilogue deferred"
+        N = int(num_atoms)
+        a = _lib.QRArgs()
+        a.Hon, a.Htg, a.Pon, a.Ptg = Hon.data_ptr(), Htg.data_ptr(), self._hp(Pon), self._hp(Ptg)
+        a.act, a.rew, a.gam, a.isw = act.data_ptr(), rew.data_ptr(), gam.data_ptr(), _lib.ptr(isw)
+        a.B, a.A, a.N, a.hidden = act.shape[0], Pon["wa"].shape[0] // N, N, Pon["wv"].shape[-1]
+        a.kappa, a.grad_scale = float(kappa), float(grad_scale)
+        a.td_abs, a.loss, a.q_out = td_abs.data_ptr(), loss.data_ptr(), _lib.ptr(q_out)
+        a.dH, a.dhead = dH.data_ptr(), dhead.data_ptr()
+        a.zero_ptr, a.zero_n = _lib.ptr(zero), 0 if zero is None else zero.numel()
+        a.lo = _lib.head_lo(*(lo if lo is not None else (None, None, None)))
+        if isn is not None:
+            a.isn.wscale, a.isn.out = _lib.ptr(isn[0]), _lib.ptr(isn[1])
+            a.isn.valid_count = _lib.ptr(isn[2]) if len(isn) > 2 else None
+        assert dhead.shape == (a.B, (a.A + 1) * N) and dhead.is_contiguous()
+        _lib.check(self.lib.apex_qr_head(a, _lib.stream_ptr()), "qr_head")
+
+    def qr_actor_head(self, H, P, eps, ctr, seed, num_atoms, q_out, a_out, H_lo=None):
+        E, A = q_out.shape
+        _lib.check(self.lib.apex_qr_actor_head(H.data_ptr(), self._hp(P), E, A, int(num_atoms), eps.data_ptr(),
+                                               int(seed), ctr.data_ptr(), q_out.data_ptr(), a_out.data_ptr(),
+                                               P["wv"].shape[-1], _lib.ptr(H_lo), _lib.stream_ptr()), "qr_actor_head")
 
     def head_wgrad(self, Hon, dhead, g, prio=None, Hon_lo=None, pack=None, norm=None) -> int:
         """``norm = (partials, slot0)`` (the distributional head only): every block also leaves

@@ -121,6 +121,24 @@ def checkpoint_network(ck: Dict[str, Any]) -> Optional[str]:
     return str(net)
 
 
+def check_dist_head(ck: Dict[str, Any], runtime_conf) -> None:
+    """Refuse a checkpoint whose saved config names the other distributional head kind: at
+    the same ``num_atoms`` the categorical and the quantile head have the same keys and
+    shapes, but the numbers mean different things (logits / quantiles).  A checkpoint without
+    a config (reference format) or with the scalar head is not judged here."""
+    c = ck.get("config") if isinstance(ck, dict) else None
+    if not isinstance(c, dict):
+        return
+    rt = c.get("Runtime") or {}
+    if int(rt.get("num_atoms", 1)) < 2 or int(runtime_conf.num_atoms) < 2:
+        return
+    saved = str(rt.get("dist_head", "categorical"))
+    if saved != str(runtime_conf.dist_head):
+        raise ValueError(f"the checkpoint was saved with Runtime.dist_head={saved!r}, this learner runs "
+                         f"Runtime.dist_head={runtime_conf.dist_head!r}: the head weights have the same shapes "
+                         f"but another meaning")
+
+
 def layout_segments(layout) -> List[Tuple[str, int, int]]:
     """Segments of a ``models.flat_params.FlatLayout``."""
     out = []
