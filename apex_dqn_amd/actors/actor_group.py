@@ -78,6 +78,9 @@ class ActorGroup:
         self.builder = make_nstep_builder(self.E, n, gamma, obs_shape, obs_dtype,
                                     env_id_offset=global_actor_offset)
         self.t = 0
+        # noisy layers (learner/noisy.py actor_noise_hook): called with the inference-call index
+        # before every batched policy call; one draw serves all envs of the call
+        self.noise_hook: Optional[Callable[[int], None]] = None
         self.episodes = []   # (env_id, ep_len, ep_return)
         self._cur = None
 
@@ -128,6 +131,8 @@ class ActorGroup:
     def step(self, policy: Callable) -> None:
         if self._cur is None:
             self.reset()
+        if self.noise_hook is not None:
+            self.noise_hook(self.t)
         q = policy(self.observation(self.payload))
         if isinstance(q, torch.Tensor):
             q = q.float().cpu().numpy()

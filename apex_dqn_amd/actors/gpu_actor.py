@@ -57,8 +57,11 @@ from .nstep import make_nstep_builder
 
 
 class GpuActorGroup:
+    noisy = False     # (the groups of learners without noisy layers never set it)
+
     def __init__(self, cfg, learner, replay, env, num_envs: int, global_offset: int = 0,
-                 total_actors: Optional[int] = None, seed: int = 0, rank: int = 0, world: int = 1):
+                 total_actors: Optional[int] = None, seed: int = 0, rank: int = 0, world: int = 1,
+                 group: int = 0):
         self.cfg = cfg
         self.learner = learner
         self.replay = replay
@@ -104,6 +107,23 @@ class GpuActorGroup:
         self.P = learner.layout.views(self.p32)
         self.Pb = learner.layout.views(self.pbf)
         self.Pl = learner.layout.views(self._pbf_all[n:]) if self.split else None
+        # noisy layers (learner/noisy.py): the slot above holds mu and sigma; the group owns shadow
+        # buffers for its effective fc / head parameters, composed on the actor stream inside the
+        # (captured) inference with stream s = 2 + group and the draw index ctr // resample -- ctr
+        # is the epsilon draw's call counter, so one draw serves all envs of a batched call
+        self.noisy = bool(getattr(learner, "noisy", False))
+        if self.noisy:
+            from ..learner.noisy import NoisyPlan, actor_stream, noise_seed
+            nm = learner.mu_layout.numel
+            self._e32 = torch.zeros(nm, dtype=torch.float32, device=d)
+            self._ebf = torch.zeros((2 if self.split else 1) * nm, dtype=ad, device=d)
+            self.xi = torch.zeros(1, learner.xi.shape[1], dtype=torch.float32, device=d)
+            self.EP = learner.mu_layout.views(self._e32)
+            self.EPb = learner.mu_layout.views(self._ebf[:nm])
+            self.EPl = learner.mu_layout.views(self._ebf[nm:]) if self.split else None
+            self._nz = NoisyPlan(A=self.A, N=int(learner.N), offsets=dict(learner.layout.offsets),
+                                 seed=noise_seed(cfg.Runtime.seed), ctr=self.ctr, base=None,
+                                 every=int(cfg.Runtime.noisy_actor_resample), stream0=actor_stream(group))
         self.builder = make_nstep_builder(self.E, a.num_steps, a.gamma, (self.C,), np.int64, env_id_offset=global_offset)
         self.global_offset = global_offset
         self.payload: Optional[np.ndarray] = None
@@ -220,7 +240,13 @@ class GpuActorGroup:
         self.slots.copy_(sl, non_blocking=True)
         if self._use_graph():
             if getattr(self, "_graph", None) is None:
+                c0 = self.ctr.clone() if self.noisy else None
                 self._policy_kernels()            # warm: kernel library, workspaces
+                if c0 is not None:
+                    # noisy layers: the counter is the draw's call index (u = ctr // resample),
+                    # so the warm run does not count (without them the counter only keys the
+                    # epsilon draws and keeps its sequence of before)
+                    self.ctr.copy_(c0)
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, stream=self.stream, capture_error_mode="thread_local"):
                     self._policy_kernels()
@@ -256,17 +282,23 @@ class GpuActorGroup:
         # (SW.actor_fc_ksplit: the actors' fc forward with few K splits -- a throughput job
         # beside the learner, where the chip-filling split's partial planes cost HBM traffic)
         ks = dict(ksplit=SW.actor_fc_ksplit) if SW.actor_fc_ksplit > 0 else {}
+        F, Fb, Fl = P, Pb, Pl          # where the fc layer and the heads read their parameters
+        if self.noisy:
+            nm = self._e32.numel()
+            ops.noisy_compose(self._nz, [(self.p32, self._e32, self._ebf[:nm], self._ebf[nm:] if self.split else None)],
+                              self.xi)
+            F, Fb, Fl = self.EP, self.EPb, self.EPl
         if self.split:
             if c3 is None:
                 ops.conv_fwd(self.y2, Pb["w3"], P["b3"], 1, self.y3, x_lo=self.y2_lo, w_lo=Pl["w3"],
                              out_lo=self.y3_lo)
-            ops.fc_fwd(self.y3.reshape(E, 3136), Pb["wfc"], P["bfc"], self.h, x_lo=self.y3_lo.reshape(E, 3136),
-                       w_lo=Pl["wfc"], out_lo=self.h_lo, **ks)
+            ops.fc_fwd(self.y3.reshape(E, 3136), Fb["wfc"], F["bfc"], self.h, x_lo=self.y3_lo.reshape(E, 3136),
+                       w_lo=Fl["wfc"], out_lo=self.h_lo, **ks)
         else:
             if c3 is None:
                 ops.conv_fwd(self.y2, Pb["w3"], P["b3"], 1, self.y3)
-            ops.fc_fwd(self.y3.reshape(E, 3136), Pb["wfc"], P["bfc"], self.h, **ks)
-        heads = {k: P[k] for k in ("wv", "bv", "wa", "ba")}
+            ops.fc_fwd(self.y3.reshape(E, 3136), Fb["wfc"], F["bfc"], self.h, **ks)
+        heads = {k: F[k] for k in ("wv", "bv", "wa", "ba")}
         self._actor_head(self.h, heads, self.h_lo)
         self.ctr += 1
 
@@ -516,7 +548,7 @@ def make_gpu_actor_group(cfg, learner, replay, num_envs: int, rank: int = 0, wor
             env = make_vec_env(cfg.env_backend, cfg.env_conf.name, h, cfg.env_conf.action_dim,
                                seed=seed + 1000 * rank + 100003 * k, preprocess=pre)
             g = GpuActorGroup(cfg, learner, replay, env, h, global_offset=rank * num_envs + k * h,
-                              total_actors=total, seed=seed + rank, rank=rank, world=world)
+                              total_actors=total, seed=seed + rank, rank=rank, world=world, group=k)
             g.eps = torch.tensor(eps_all[k * h:(k + 1) * h], dtype=torch.float32, device=learner.device)
             groups.append(g)
         return PipelinedActorGroups(groups)

@@ -108,6 +108,14 @@ class RuntimeConf:
     # loss with kappa = huber_delta (> 0; loss does not apply), no support (v_min / v_max are ignored), the same
     # priority and the same refusals (learner/losses.py quantile_huber_loss)
     dist_head: str = "categorical"
+    # factorised NoisyNet fc and head layers (Fortunato et al. 2018; learner/noisy.py, csrc/noisy.hip): the two
+    # stream layers and the two heads carry W = mu + sigma * (xi_out (x) xi_in), one draw per update for the online
+    # net and one for the target net, one per noisy_actor_resample batched inference calls for an actor group;
+    # sigma starts at noisy_sigma0 / sqrt(fan-in).  Single-rank NatureCNN with any head kind and the torch
+    # learners (mlp); not IMPALA, the DP step or the graph learner.  The epsilon ladder is not touched
+    noisy: bool = False
+    noisy_sigma0: float = 0.5
+    noisy_actor_resample: int = 1
     priority_eps: float = 1e-6      # priority floor: leaves hold (|delta| + priority_eps)^alpha
     use_is_weights: bool = True
     is_normalise: str = "batch_max"  # IS weights (N P(i))^-beta divided by their max over the sampled batch
@@ -306,6 +314,21 @@ class ApexConfig:
             if int(rt.world_size) > 1 or rt.force_dp:
                 raise ValueError(f"Runtime.num_atoms={na} runs on a single rank: the data-parallel step "
                                  f"(world_size > 1, force_dp) has no distributional head")
+        if not isinstance(rt.noisy, bool):
+            raise ValueError(f"Runtime.noisy must be true or false, got {rt.noisy!r}")
+        if not float(rt.noisy_sigma0) > 0.0:
+            raise ValueError(f"Runtime.noisy_sigma0 (Runtime.noisy's initial sigma scale) must be > 0, got "
+                             f"{rt.noisy_sigma0}")
+        nr = rt.noisy_actor_resample
+        if isinstance(nr, bool) or not isinstance(nr, int) or nr < 1:
+            raise ValueError(f"Runtime.noisy_actor_resample (Runtime.noisy's inference calls per actor draw) must "
+                             f"be an integer >= 1, got {nr!r}")
+        if rt.noisy:
+            if net not in ("nature64", "nature32", "mlp"):
+                raise ValueError(f"Runtime.noisy needs network nature64, nature32 or mlp, got {net!r}")
+            if int(rt.world_size) > 1 or rt.force_dp:
+                raise ValueError("Runtime.noisy runs on a single rank: the data-parallel step (world_size > 1, "
+                                 "force_dp) has no noisy layers")
         if net in ("nature64", "nature32", "impala") and len(ss) != 3:
             raise ValueError(f"network {net} needs an image state_shape [C,H,W], got {ss}")
         if net in ("nature64", "nature32") and tuple(ss[1:]) != (84, 84):
@@ -324,8 +347,11 @@ class ApexConfig:
     def head_kw(self) -> Dict[str, Any]:
         """The dueling modules' head arguments (models/dueling.py)."""
         rt = self.Runtime
-        return dict(num_atoms=int(rt.num_atoms), v_min=float(rt.v_min), v_max=float(rt.v_max),
-                    dist_head=str(rt.dist_head))
+        kw = dict(num_atoms=int(rt.num_atoms), v_min=float(rt.v_min), v_max=float(rt.v_max),
+                  dist_head=str(rt.dist_head))
+        if rt.noisy:       # (only then: the non-noisy call is the one of before)
+            kw.update(noisy=True, noisy_sigma0=float(rt.noisy_sigma0))
+        return kw
 
     @property
     def quantile(self) -> bool:

@@ -54,8 +54,8 @@ from ..models.flat_params import (FlatLayout, flat_to_reference_state, nature_se
                                   reference_state_to_flat)
 from ..ops.fused_ops import HipBackend, TorchBackend, split_into
 from ..ops.switches import SW
-from ..utils.checkpoint import (adopt_obs_scale, check_dist_head, layout_segments, load_checkpoint, pack_flat_state,
-                                save_checkpoint, unpack_flat_state, checkpoint_network)
+from ..utils.checkpoint import (adopt_obs_scale, check_dist_head, check_noisy, layout_segments, load_checkpoint,
+                                pack_flat_state, save_checkpoint, unpack_flat_state, checkpoint_network)
 from .dp_step import DataParallelStep, Streams
 from .is_norm import IsNormMixin
 from .schedules import StepIndexMixin
@@ -111,6 +111,12 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         if self.N >= 2 and self._dp:
             raise ValueError(f"Runtime.num_atoms={self.N}: the distributional head runs on a single rank, not in "
                              f"the data-parallel step (world > 1, Runtime.force_dp, the emulated world)")
+        # factorised NoisyNet fc and head layers (learner/noisy.py, csrc/noisy.hip): sigma segments in the
+        # flat buffers, effective weights composed into shadow buffers at the head of every update
+        self.noisy = bool(self.rt.noisy)
+        if self.noisy and self._dp:
+            raise ValueError("Runtime.noisy: the noisy layers run on a single rank, not in the data-parallel step "
+                             "(world > 1, Runtime.force_dp, the emulated world)")
         if self.rt.dtype not in ("fp32", "bf16"):
             raise ValueError("Runtime.dtype must be fp32 or bf16")
         self.precision = self.rt.dtype
@@ -136,7 +142,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         # (the torch backend emulates the split kernel's contract: ops.conv12_fwd)
         self._c12 = self.split or (backend == "hip" and self.ops._conv12_native() and SW.conv12_bf16)
         d = self.device
-        self.layout = FlatLayout(nature_segments(self.C, self.A, 64, self.N))
+        self.layout = FlatLayout(nature_segments(self.C, self.A, 64, self.N, noisy=self.noisy))
         n = self.layout.numel
         self.p32 = torch.zeros(n, dtype=torch.float32, device=d)
         # bf16 compute copies [hi | lo] of the online / target parameters (lo: split mode)
@@ -158,6 +164,9 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         self.Tb = self.layout.views(self.tbf)
         self.Pl = self.layout.views(self.pbf_lo) if self.split else None
         self.Tl = self.layout.views(self.tbf_lo) if self.split else None
+        self._nz = None          # the noisy layers' plan, set once the update index exists (_init_noisy)
+        if self.noisy:
+            self._alloc_noisy()
         # random init identical in distribution to the reference module (torch default init)
         init = DuellingDQN((self.C, 84, 84), self.A, conv1_channels=self.c1, **cfg.head_kw())
         reference_state_to_flat(init.state_dict(), {k: v for k, v in self.P.items()})
@@ -209,7 +218,12 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         # producer-summed clip norm: the fc wgrad epilogue and the grad_finalize blocks
         # write squared-norm partials of the values they store, the optimizer launch sums
         # them.  With DP the norm is of the all-reduced gradient: the optimizer's own pass.
-        self._fuse_norm = not self._dp and self.ops.name == "hip" and getattr(self.ops, "native_conv", False)
+        # (noisy layers: the sigma gradients join after the producers, so the optimizer's own pass
+        # over g32 sums the norm, as in the DP step; the default path's partial slots are untouched.
+        # With the sigma-gradient blocks as one more producer the step measured the same within
+        # its spread, profiles/pr11_ab_noisy_sigma_norm_partials_rejected.txt)
+        self._fuse_norm = not self._dp and self.ops.name == "hip" and getattr(self.ops, "native_conv", False) \
+            and not self.noisy
         # DP: the rank-local replay shards form ONE prioritized replay (replay/gpu_replay.py
         # enable_sharding): every step all-gathers the shards' (sum p^alpha, min p^alpha)
         # right after the priority write-back and the next batch is one global draw,
@@ -275,6 +289,8 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         # device-resident update index, Runtime.optimizer, lr / IS-exponent schedules
         # (learner/schedules.py): read inside the captured step, no host round trip
         self._init_step_index()
+        if self.noisy:
+            self._init_noisy()
         ls = cfg.Learner.load_saved_state
         if ls:
             self.load(ls)
@@ -304,6 +320,72 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         if getattr(self, "_frag_out", None) is not None:
             c1, c2 = self._conv12_weights()
             self.ops.conv12_pack(c1, c2, self.rt.obs_scale, sets=1, c3=self._conv3_weights())
+        self._noisy_compose()
+
+    # ------------------------------------------------------- noisy layers
+    def _alloc_noisy(self) -> None:
+        """Shadow buffers of the mu layout for the effective parameters of both nets (row 0
+        online, row 1 target): fp32 (head weights, noisy biases) and the bf16 operand planes
+        [hi | lo] of ``wfc``; the draw buffer ``xi`` [2, K padded]."""
+        from .noisy import xi_offsets
+        d = self.device
+        self.mu_layout = FlatLayout(nature_segments(self.C, self.A, 64, self.N))
+        nm = self.mu_layout.numel
+        assert all(self.layout.offsets[k] == o for k, o in self.mu_layout.offsets.items())
+        self._e32 = torch.zeros(2, nm, dtype=torch.float32, device=d)
+        self._ebf = torch.zeros(2, (2 if self.split else 1) * nm, dtype=self.act_dtype, device=d)
+        K = xi_offsets(self.A, self.N)["K"]
+        self.xi = torch.zeros(2, (K + 63) // 64 * 64, dtype=torch.float32, device=d)
+        views = self.mu_layout.views
+        self.EP, self.ET = views(self._e32[0]), views(self._e32[1])
+        self.EPb, self.ETb = views(self._ebf[0, :nm]), views(self._ebf[1, :nm])
+        self.EPl = views(self._ebf[0, nm:]) if self.split else None
+        self.ETl = views(self._ebf[1, nm:]) if self.split else None
+
+    def _init_noisy(self) -> None:
+        from .noisy import NoisyPlan, noise_seed
+        # u = replay.ctr - upd_base: the updates completed, read at the head of an update
+        self._nz = NoisyPlan(A=self.A, N=self.N, offsets=dict(self.layout.offsets), seed=noise_seed(self.rt.seed),
+                             ctr=self.replay.ctr, base=self.upd_base, every=1, stream0=0)
+        self._noisy_compose()
+
+    def _noisy_nets(self):
+        nm = self.mu_layout.numel
+        lo = (lambda k: self._ebf[k, nm:]) if self.split else (lambda k: None)
+        return [(self.p32, self._e32[0], self._ebf[0, :nm], lo(0)), (self.t32, self._e32[1], self._ebf[1, :nm], lo(1))]
+
+    def _noisy_compose(self, fc32=None) -> None:
+        """Effective parameters of both nets for the update the device's index names (draws
+        s = 0 online, s = 1 target): one launch at the head of every update, and eagerly after
+        the weights changed outside a step.  ``fc32``: (online, target) fp32 outputs of the
+        effective ``wfc`` (tests)."""
+        if getattr(self, "_nz", None) is not None:
+            self.ops.noisy_compose(self._nz, self._noisy_nets(), self.xi, fc32=fc32)
+
+    def _noisy_compose_step(self) -> None:
+        """The compose at the head of an update, on the main stream (this update's draws, the
+        index read on the device).  (On the branch stream beside the conv forward, joined before
+        the fc forward, the step lost 25 us: +82-89 against +58-62 us per update fp32, +77-82
+        against +58 bf16 -- the co-running conv forward stretches by more than the compose
+        takes, profiles/pr11_ab_noisy_compose_branch_rejected.txt.)"""
+        if self.noisy:
+            self._noisy_compose()
+
+    def _noisy_sigma_grad(self) -> None:
+        """G[sigma] from G[mu] and the online draw, once the fc and head weight gradients are
+        final (same stream, behind them) and before the optimizer."""
+        if self.noisy:
+            self.ops.noisy_sigma_grad(self._nz, self.g32, self.xi[0])
+
+    def _fc_weights(self):
+        """(online wfc, its lo plane, online bfc, target wfc, its lo plane, target bfc) the fc
+        kernels read: the parameters' bf16 copies, or the noisy layers' shadows."""
+        sp = self.split
+        if self.noisy:
+            return (self.EPb["wfc"], sp and self.EPl["wfc"], self.EP["bfc"],
+                    self.ETb["wfc"], sp and self.ETl["wfc"], self.ET["bfc"])
+        return (self.Pb["wfc"], sp and self.Pl["wfc"], self.P["bfc"],
+                self.Tb["wfc"], sp and self.Tl["wfc"], self.T["bfc"])
 
     def _backend_name(self) -> str:
         try:
@@ -399,10 +481,11 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             ops.conv_fwd(self.y2, Pb["w3"], P["b3"], 1, self.y3, Tb["w3"], T["b3"], 2 * B,
                          **self._lo(x_lo=self.y2_lo, w_lo=sp and Pl["w3"], w2_lo=sp and Tl["w3"], out_lo=self.y3_lo))
         self._wait_params()       # sharded DP update: the last update's fc rows (learner/dp_step.py)
-        ops.fc_fwd(self.y3.reshape(n, 3136), Pb["wfc"], P["bfc"], self.h, Tb["wfc"], T["bfc"], 2 * B,
+        wfc, wfc_lo, bfc, wfc_t, wfc_t_lo, bfc_t = self._fc_weights()
+        ops.fc_fwd(self.y3.reshape(n, 3136), wfc, bfc, self.h, wfc_t, bfc_t, 2 * B,
                    c2d=(Pb["w2"], Pl["w2"] if sp else None), defer_head=defer_head,
-                   **self._lo(x_lo=sp and self.y3_lo.reshape(n, 3136), w_lo=sp and Pl["wfc"],
-                              w2_lo=sp and Tl["wfc"], out_lo=self.h_lo))
+                   **self._lo(x_lo=sp and self.y3_lo.reshape(n, 3136), w_lo=wfc_lo,
+                              w2_lo=wfc_t_lo, out_lo=self.h_lo))
 
     def _conv12_weights(self):
         P, T, Pb, Tb, Pl, Tl = self.P, self.T, self.Pb, self.Tb, self.Pl, self.Tl
@@ -424,8 +507,11 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             c1, c2 = self._conv12_weights()
             self.ops.conv12_pack(c1, c2, self.rt.obs_scale, sets=2, c3=self._conv3_weights())
             self._tgt_packed = True
+        self._noisy_compose()
 
     def _head_params(self, V):
+        if self.noisy and (V is self.P or V is self.T):     # the effective head parameters of that net
+            V = self.EP if V is self.P else self.ET
         return {k: V[k] for k in ("wv", "bv", "wa", "ba")}
 
     # ---------------------------------------------------------------- step
@@ -446,6 +532,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             self._sample()
         S = self.S
         self._mark("sample")
+        self._noisy_compose_step()
         # conv1 reads the uint8 frame stacks straight from the replay ring by slot
         self.forward_all(defer_head=self._defer_fc_epilogue)
         self._mark("forward")
@@ -480,6 +567,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
                                            self.dhead, self.G, prio, norm=nrm,
                                            **self._lo(dh_lo=self.dH_lo, x_lo=sp and self.y3_lo[:B],
                                                       Hon_lo=self.h_lo))
+        self._noisy_sigma_grad()
         if self._comm_bf16:
             cut = self.layout.offsets["wfc"]
             self.gcomm[cut:].copy_(self.g32[cut:])
@@ -502,8 +590,9 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         B, rt, ops, G, Pb, Pl = self.B, self.rt, self.ops, self.G, self.Pb, self.Pl
         sp = self.split
         jobs = []    # split-K reductions of conv3 / conv2, finalised at the end
-        ops.fc_dgrad(self.dH, self.y3[:B], Pb["wfc"], self.dY3,
-                     **self._lo(dh_lo=self.dH_lo, w_lo=sp and Pl["wfc"], dx_lo=self.dY3_lo))
+        wfc, wfc_lo = self._fc_weights()[:2]
+        ops.fc_dgrad(self.dH, self.y3[:B], wfc, self.dY3,
+                     **self._lo(dh_lo=self.dH_lo, w_lo=wfc_lo, dx_lo=self.dY3_lo))
         if after_first is not None:
             after_first()
         ops.conv_wgrad(self.dY3, self.y2[:B], 3, 1, G["w3"], G["b3"], jobs=jobs,
@@ -621,8 +710,9 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         if not fc_main:
             ev = torch.cuda.Event()
             ev.record(main)
-        ops.fc_dgrad(self.dH, self.y3[:B], Pb["wfc"], self.dY3,
-                     **self._lo(dh_lo=self.dH_lo, w_lo=sp and Pl["wfc"], dx_lo=self.dY3_lo))
+        wfc, wfc_lo = self._fc_weights()[:2]
+        ops.fc_dgrad(self.dH, self.y3[:B], wfc, self.dY3,
+                     **self._lo(dh_lo=self.dH_lo, w_lo=wfc_lo, dx_lo=self.dY3_lo))
         if fc_main:
             # fc dgrad and the fc weight gradient back to back on the main stream, each on
             # the whole chip; the branch forks after them (its first wait, conv3's wgrad)
@@ -631,6 +721,9 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             side.wait_event(ev)
             with torch.cuda.stream(side):
                 fc_wgrad()
+                # noisy layers: the sigma gradients right behind the fc / head weight gradients
+                # on the branch, which has slack beside the data-gradient chain
+                self._noisy_sigma_grad()
         # (conv3's weight gradient after conv1's on the main stream, where the chain has
         # slack at 512 rows: 2,674 / 2,668 vs 2,677 / 2,675 fp32, 4,271 / 4,312 vs 4,388 /
         # 4,489 bf16, 6,078 / 6,056 vs 6,478 / 6,437 at 74 rows -- the co-running kernels
@@ -640,6 +733,10 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         # it; else the pair, conv1's weight gradient enqueued after the branch's conv2 wgrad
         fuse21 = ops.conv21_fused_ok(self.dY2, self.slots[:B], **self._lo(dy2_lo=self.dY2_lo, w2_lo=sp and Pl["w2"]))
         self._conv32_branched(main, side, jobs, jobs1=jobs1 if fuse21 else None)
+        if fc_main and self.noisy:
+            # (the branch has waited for the main stream past the fc weight gradient by now)
+            with torch.cuda.stream(side):
+                self._noisy_sigma_grad()
         if not fuse21:
             ops.conv1_wgrad_ring(self.dY1, self.replay.frames, self.slots[:B], self.frames, rt.obs_scale, G["w1"],
                                  G["b1"], jobs=jobs1, **self._lo(dy_lo=self.dY1_lo))
@@ -1012,7 +1109,10 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
 
     # ------------------------------------------------------------ metrics
     def last_metrics(self) -> Dict[str, float]:
-        return self._is_metrics()
+        m = self._is_metrics()
+        if self.noisy:     # mean |sigma| of the fc weight sigma (the metrics above synced already)
+            m["noisy_sigma_mean"] = float(self.P["swfc"].abs().mean())
+        return m
 
     def q_values(self, frames_u8: torch.Tensor) -> torch.Tensor:
         """Greedy-evaluation helper: q for a (N, C, 84, 84) uint8 batch (fp32 module,
@@ -1048,6 +1148,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         if ck is None:
             return False
         check_dist_head(ck, self.rt)
+        check_noisy(ck, self.rt)
         if adopt_obs_scale(ck, self.rt):
             self._graphs = self._multi = None    # the input scale is a kernel argument: recapture
             self._setup_frag_out()               # (and folded into the conv1 operands)
@@ -1066,6 +1167,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         if isinstance(rng, dict) and "replay_ctr" in rng:
             self.replay.ctr.fill_(int(rng["replay_ctr"]))
         self._sync_update_index()
+        self._noisy_compose()                    # (the draws of the restored update index)
         if self._presample and (self._opt is not None or self.replay.beta_sched is not None):
             self._sample_ver = None              # the pre-drawn batch carries another update's IS exponent
         self._last_ckpt = ck

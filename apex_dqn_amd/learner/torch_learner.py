@@ -19,7 +19,7 @@ import torch
 
 from ..config import ApexConfig
 from ..models.dueling import build_network
-from ..utils.checkpoint import adopt_obs_scale, check_dist_head, load_checkpoint, save_checkpoint
+from ..utils.checkpoint import adopt_obs_scale, check_dist_head, check_noisy, load_checkpoint, save_checkpoint
 from .losses import c51_loss, ddqn_loss, quantile_huber_loss
 from .schedules import lr_scheduled, rt_lr
 
@@ -112,7 +112,17 @@ class TorchLearner:
     def sync_target(self) -> None:
         self.Q_target.load_state_dict(self.Q.state_dict())
 
+    def set_update_noise(self) -> None:
+        """Noisy layers: the draws of update ``num_q_updates`` -- the online net's (s = 0, both
+        its S_t and S_t+n rows) and the target net's (s = 1); the fused learner's convention
+        (learner/noisy.py), so both see the same noise."""
+        if self.rt.noisy:
+            from .noisy import set_module_noise
+            set_module_noise(self.Q, self.rt.seed, self.num_q_updates, 0)
+            set_module_noise(self.Q_target, self.rt.seed, self.num_q_updates, 1)
+
     def step(self, batch: Dict[str, Any]) -> Dict[str, Any]:
+        self.set_update_noise()
         loss, td = self.compute_loss_and_priorities(batch)
         gnorm = self.update_Q(loss)
         return {"loss": float(loss.detach()), "td_abs": td.cpu().numpy(), "grad_norm": gnorm}
@@ -135,6 +145,7 @@ class TorchLearner:
         if ck is None:
             return False
         check_dist_head(ck, self.rt)
+        check_noisy(ck, self.rt)
         if adopt_obs_scale(ck, self.rt):
             for net in (self.Q, self.Q_target):
                 if hasattr(net, "pre"):

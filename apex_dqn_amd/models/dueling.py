@@ -30,6 +30,44 @@ def dueling_combine(value: torch.Tensor, adv: torch.Tensor) -> torch.Tensor:
     return value + adv - adv.mean(dim=1, keepdim=True)
 
 
+class NoisyLinear(nn.Module):
+    """Linear layer with factorised Gaussian noise (Fortunato et al. 2018):
+    W = mu_w + sigma_w * (xi_out (x) xi_in), b = mu_b + sigma_b * xi_out.  ``weight`` / ``bias``
+    keep ``nn.Linear``'s names, shapes and default init (U(-1/sqrt(p), 1/sqrt(p)), p the
+    fan-in) and hold mu; ``weight_sigma`` / ``bias_sigma`` start at sigma0 / sqrt(p).  The
+    noise is injected (:meth:`set_noise`; learner/noisy.py ``noise_vectors``), never drawn
+    here: the learner, the oracle and the kernels see one draw.  No noise set = zero noise."""
+
+    def __init__(self, in_features: int, out_features: int, sigma0: float = 0.5):
+        super().__init__()
+        self.in_features, self.out_features = int(in_features), int(out_features)
+        lin = nn.Linear(self.in_features, self.out_features)     # (the same RNG use as the plain layer)
+        self.weight = nn.Parameter(lin.weight.detach().clone())
+        self.bias = nn.Parameter(lin.bias.detach().clone())
+        s = float(sigma0) / float(self.in_features) ** 0.5
+        self.weight_sigma = nn.Parameter(torch.full((self.out_features, self.in_features), s))
+        self.bias_sigma = nn.Parameter(torch.full((self.out_features,), s))
+        self.register_buffer("xi_in", torch.zeros(self.in_features), persistent=False)
+        self.register_buffer("xi_out", torch.zeros(self.out_features), persistent=False)
+
+    def set_noise(self, xi_out: torch.Tensor, xi_in: torch.Tensor) -> None:
+        with torch.no_grad():
+            self.xi_out.copy_(xi_out.reshape(-1).to(self.xi_out.dtype))
+            self.xi_in.copy_(xi_in.reshape(-1).to(self.xi_in.dtype))
+
+    def effective(self):
+        w = self.weight + self.weight_sigma * torch.outer(self.xi_out, self.xi_in)
+        return w, self.bias + self.bias_sigma * self.xi_out
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        w, b = self.effective()
+        return F.linear(x, w, b)
+
+
+def _linear(p: int, rows: int, noisy: bool, sigma0: float) -> nn.Module:
+    return NoisyLinear(p, rows, sigma0) if noisy else nn.Linear(p, rows)
+
+
 class _C51Head:
     """Distributional (C51) dueling head shared by the modules that take ``num_atoms``:
     the value head has N outputs, the advantage head A N (row a N + i = action a, atom i),
@@ -41,16 +79,36 @@ class _C51Head:
     (2 i + 1) / (2 N); q is their mean; no support buffer (v_min / v_max are ignored)."""
 
     def _init_head(self, hidden: int, num_atoms: int, v_min: float, v_max: float,
-                   dist_head: str = "categorical") -> None:
+                   dist_head: str = "categorical", noisy: bool = False, sigma0: float = 0.5) -> None:
         if dist_head not in ("categorical", "quantile"):
             raise ValueError(f"dist_head must be 'categorical' or 'quantile', got {dist_head!r}")
         self.num_atoms = int(num_atoms)
         self.dist_head = dist_head if self.num_atoms > 1 else "categorical"
         self.v_min, self.v_max = float(v_min), float(v_max)
-        self.value = nn.Linear(hidden, self.num_atoms)
-        self.advantage = nn.Linear(hidden, self.action_dim * self.num_atoms)
+        self.noisy = bool(noisy)
+        self.value = _linear(hidden, self.num_atoms, self.noisy, sigma0)
+        self.advantage = _linear(hidden, self.action_dim * self.num_atoms, self.noisy, sigma0)
         if self.num_atoms > 1 and self.dist_head == "categorical":
             self.register_buffer("support", c51_support(self.num_atoms, self.v_min, self.v_max), persistent=False)
+
+    def set_noise(self, v) -> None:
+        """Inject one network draw (learner/noisy.py ``noise_vectors``: ``fc_in_v``, ``fc_in_a``,
+        ``fc_out``, ``v_in``, ``a_in``, ``v_out``, ``a_out``) into the four noisy layers.  The
+        stream layers' xi_in comes in the engine's h, w, c column order (models/flat_params.py)
+        and is permuted to this module's c, h, w order; an MLP's columns are used as given."""
+        assert self.noisy, "set_noise on a network without noisy layers"
+        lv, la = self.value_stream_layer[0], self.advantage_stream_layer[0]
+        h = lv.out_features
+
+        def cols(x):
+            if x.numel() == 3136 and len(self.input_shape) == 3:
+                return x.reshape(7, 7, 64).permute(2, 0, 1).reshape(-1)
+            return x
+
+        lv.set_noise(v["fc_out"][:h], cols(v["fc_in_v"]))
+        la.set_noise(v["fc_out"][h:], cols(v["fc_in_a"]))
+        self.value.set_noise(v["v_out"], v["v_in"])
+        self.advantage.set_noise(v["a_out"], v["a_in"])
 
     def _head(self, hv: torch.Tensor, ha: torch.Tensor):
         """(value, advantage, q, dist): dist = [B, A, N] log-probabilities (categorical) or
@@ -111,7 +169,7 @@ class DuellingDQN(nn.Module, _C51Head):
     def __init__(self, state_shape: Sequence[int], action_dim: int,
                  conv1_channels: int = 64, obs_scale: float = 1.0 / 255.0,
                  num_atoms: int = 1, v_min: float = -10.0, v_max: float = 10.0,
-                 dist_head: str = "categorical"):
+                 dist_head: str = "categorical", noisy: bool = False, noisy_sigma0: float = 0.5):
         super().__init__()
         self.input_shape = tuple(state_shape)
         self.action_dim = int(action_dim)
@@ -121,9 +179,9 @@ class DuellingDQN(nn.Module, _C51Head):
         self.layer1 = nn.Sequential(nn.Conv2d(c, c1, 8, stride=4), nn.ReLU())
         self.layer2 = nn.Sequential(nn.Conv2d(c1, 64, 4, stride=2), nn.ReLU())
         self.layer3 = nn.Sequential(nn.Conv2d(64, 64, 3, stride=1), nn.ReLU())
-        self.value_stream_layer = nn.Sequential(nn.Linear(64 * 7 * 7, 512), nn.ReLU())
-        self.advantage_stream_layer = nn.Sequential(nn.Linear(64 * 7 * 7, 512), nn.ReLU())
-        self._init_head(512, num_atoms, v_min, v_max, dist_head)
+        self.value_stream_layer = nn.Sequential(_linear(64 * 7 * 7, 512, noisy, noisy_sigma0), nn.ReLU())
+        self.advantage_stream_layer = nn.Sequential(_linear(64 * 7 * 7, 512, noisy, noisy_sigma0), nn.ReLU())
+        self._init_head(512, num_atoms, v_min, v_max, dist_head, noisy, noisy_sigma0)
 
     def features(self, x: torch.Tensor) -> torch.Tensor:
         x = self.pre(x)
@@ -152,15 +210,15 @@ class MLPDuellingDQN(nn.Module, _C51Head):
 
     def __init__(self, state_shape: Sequence[int], action_dim: int, hidden: int = 128,
                  num_atoms: int = 1, v_min: float = -10.0, v_max: float = 10.0,
-                 dist_head: str = "categorical"):
+                 dist_head: str = "categorical", noisy: bool = False, noisy_sigma0: float = 0.5):
         super().__init__()
         d = int(state_shape[0]) if len(state_shape) == 1 else int(torch.tensor(state_shape).prod())
         self.input_shape = tuple(state_shape)
         self.action_dim = int(action_dim)
         self.layer1 = nn.Sequential(nn.Linear(d, hidden), nn.ReLU())
-        self.value_stream_layer = nn.Sequential(nn.Linear(hidden, hidden), nn.ReLU())
-        self.advantage_stream_layer = nn.Sequential(nn.Linear(hidden, hidden), nn.ReLU())
-        self._init_head(hidden, num_atoms, v_min, v_max, dist_head)
+        self.value_stream_layer = nn.Sequential(_linear(hidden, hidden, noisy, noisy_sigma0), nn.ReLU())
+        self.advantage_stream_layer = nn.Sequential(_linear(hidden, hidden, noisy, noisy_sigma0), nn.ReLU())
+        self._init_head(hidden, num_atoms, v_min, v_max, dist_head, noisy, noisy_sigma0)
 
     def forward(self, x: torch.Tensor):
         h = self.layer1(x.float().reshape(x.shape[0], -1))
@@ -244,8 +302,10 @@ class ImpalaDuellingDQN(nn.Module):
 
 def build_network(kind: str, state_shape: Sequence[int], action_dim: int,
                   obs_scale: float = 1.0 / 255.0, num_atoms: int = 1, v_min: float = -10.0,
-                  v_max: float = 10.0, dist_head: str = "categorical") -> nn.Module:
-    head = dict(num_atoms=num_atoms, v_min=v_min, v_max=v_max, dist_head=dist_head)
+                  v_max: float = 10.0, dist_head: str = "categorical", noisy: bool = False,
+                  noisy_sigma0: float = 0.5) -> nn.Module:
+    head = dict(num_atoms=num_atoms, v_min=v_min, v_max=v_max, dist_head=dist_head, noisy=noisy,
+                noisy_sigma0=noisy_sigma0)
     if kind == "nature64":
         return DuellingDQN(state_shape, action_dim, conv1_channels=64, obs_scale=obs_scale, **head)
     if kind == "nature32":
@@ -255,6 +315,8 @@ def build_network(kind: str, state_shape: Sequence[int], action_dim: int,
     if kind == "impala":
         if int(num_atoms) != 1:
             raise ValueError("Runtime.num_atoms >= 2: the impala network has no distributional head")
+        if noisy:
+            raise ValueError("Runtime.noisy: the impala network has no noisy layers")
         return ImpalaDuellingDQN(state_shape, action_dim, obs_scale=obs_scale)
     raise ValueError(f"unknown network kind {kind!r}")
 
@@ -266,3 +328,5 @@ REFERENCE_KEYS = (
     "advantage_stream_layer.0.weight", "advantage_stream_layer.0.bias",
     "value.weight", "value.bias", "advantage.weight", "advantage.bias",
 )
+NOISY_LAYERS = ("value_stream_layer.0", "advantage_stream_layer.0", "value", "advantage")
+SIGMA_KEYS = tuple(f"{l}.{p}_sigma" for l in NOISY_LAYERS for p in ("weight", "bias"))

@@ -20,22 +20,33 @@ import torch
 ALIGN = 64  # elements (256 B): every segment starts 16-B aligned for dwordx4 access
 
 
-def nature_segments(C: int, A: int, c1: int = 64, num_atoms: int = 1) -> List[Tuple[str, Tuple[int, ...]]]:
+SIGMA_SEGMENTS = (("swv", "wv"), ("sbv", "bv"), ("swa", "wa"), ("sba", "ba"), ("swfc", "wfc"), ("sbfc", "bfc"))
+
+
+def nature_segments(C: int, A: int, c1: int = 64, num_atoms: int = 1,
+                    noisy: bool = False) -> List[Tuple[str, Tuple[int, ...]]]:
     """Flat order: the small tensors (convs, heads) first, the 3.2 M-parameter fc layer
     last, so the fc weights are one contiguous suffix: the data-parallel exchange treats
     [0, wfc) and [wfc, end) as its two buckets and the single-rank step updates the fc
     suffix early (learner/fused_learner.py).  ``num_atoms`` N >= 2 (the distributional
-    head): wv (N, 512), bv (N,), wa (A N, 512) with row a N + i = action a, atom i, ba (A N,)."""
+    head): wv (N, 512), bv (N,), wa (A N, 512) with row a N + i = action a, atom i, ba (A N,).
+    ``noisy`` (factorised NoisyNet fc and head layers, learner/noisy.py): the sigma segments
+    swv, sbv, swa, sba, swfc, sbfc with the shapes of their mu segments follow the fc layer,
+    so every other segment keeps its offset."""
     N = int(num_atoms)
     heads = [("wv", (512,)), ("bv", (1,)), ("wa", (A, 512)), ("ba", (A,))] if N == 1 else \
         [("wv", (N, 512)), ("bv", (N,)), ("wa", (A * N, 512)), ("ba", (A * N,))]
-    return [
+    segs = [
         ("w1", (c1, C, 8, 8)), ("b1", (c1,)),
         ("w2", (64, 4, 4, c1)), ("b2", (64,)),
         ("w3", (64, 3, 3, 64)), ("b3", (64,)),
         *heads,
         ("wfc", (1024, 3136)), ("bfc", (1024,)),
     ]
+    if noisy:
+        shapes = dict(segs)
+        segs += [(s, shapes[m]) for s, m in SIGMA_SEGMENTS]
+    return segs
 
 
 class FlatLayout:
@@ -88,6 +99,15 @@ def flat_to_reference_state(v: Dict[str, torch.Tensor], c1: int = 64) -> "Ordere
     sd["value.bias"] = v["bv"].clone()
     sd["advantage.weight"] = v["wa"].clone()
     sd["advantage.bias"] = v["ba"].clone()
+    if "swfc" in v:       # noisy layers: the sigma segments, the fc sigma permuted as the fc weight
+        sd["value_stream_layer.0.weight_sigma"] = fc_cols_to_chw(v["swfc"][:512]).contiguous()
+        sd["value_stream_layer.0.bias_sigma"] = v["sbfc"][:512].clone()
+        sd["advantage_stream_layer.0.weight_sigma"] = fc_cols_to_chw(v["swfc"][512:]).contiguous()
+        sd["advantage_stream_layer.0.bias_sigma"] = v["sbfc"][512:].clone()
+        sd["value.weight_sigma"] = v["swv"].reshape(-1, 512).clone()
+        sd["value.bias_sigma"] = v["sbv"].clone()
+        sd["advantage.weight_sigma"] = v["swa"].clone()
+        sd["advantage.bias_sigma"] = v["sba"].clone()
     return OrderedDict((k, t.detach().float().cpu()) for k, t in sd.items())
 
 
@@ -104,6 +124,11 @@ def reference_state_to_flat(sd: Dict[str, torch.Tensor], v: Dict[str, torch.Tens
 
     with torch.no_grad():
         # (checked before anything is copied: a mismatch leaves the views untouched)
+        has_sigma = any(k.endswith("_sigma") for k in sd)
+        if has_sigma != ("swfc" in v):
+            raise ValueError("the state has " + ("" if has_sigma else "no ") + "noisy-layer sigma keys (*_sigma) and "
+                             "this layout holds " + ("none" if has_sigma else "them") + ": Runtime.noisy differs "
+                             "(a reference checkpoint has no sigma)")
         for k, name in (("wv", "value.weight"), ("bv", "value.bias"), ("wa", "advantage.weight"),
                         ("ba", "advantage.bias")):
             if sd[name].numel() != v[k].numel():
@@ -127,3 +152,12 @@ def reference_state_to_flat(sd: Dict[str, torch.Tensor], v: Dict[str, torch.Tens
         v["bv"].copy_(sd["value.bias"])
         v["wa"].copy_(sd["advantage.weight"])
         v["ba"].copy_(sd["advantage.bias"])
+        if has_sigma:
+            v["swfc"][:512].copy_(fc_cols_to_hwc(sd["value_stream_layer.0.weight_sigma"]))
+            v["sbfc"][:512].copy_(sd["value_stream_layer.0.bias_sigma"])
+            v["swfc"][512:].copy_(fc_cols_to_hwc(sd["advantage_stream_layer.0.weight_sigma"]))
+            v["sbfc"][512:].copy_(sd["advantage_stream_layer.0.bias_sigma"])
+            v["swv"].copy_(sd["value.weight_sigma"].reshape(v["swv"].shape))
+            v["sbv"].copy_(sd["value.bias_sigma"])
+            v["swa"].copy_(sd["advantage.weight_sigma"])
+            v["sba"].copy_(sd["advantage.bias_sigma"])

@@ -74,6 +74,24 @@ class QRArgs(ctypes.Structure):
                 ("dhead", c_p), ("zero_ptr", c_p), ("zero_n", c_i), ("lo", HeadLo), ("isn", IsNorm)]
 
 
+class NoisyNet(ctypes.Structure):
+    """One network of a noisy compose launch (``NoisyNet``, csrc/noisy.hip)."""
+    _fields_ = [("p", c_p), ("e32", c_p), ("ehi", c_p), ("elo", c_p), ("fc32", c_p), ("xi", c_p)]
+
+
+class NoisyArgs(ctypes.Structure):
+    """Arguments of ``noisy_compose_kernel`` (``NoisyArgs``, csrc/noisy.hip)."""
+    _fields_ = [("net", NoisyNet * 2), ("nnets", c_i), ("A", c_i), ("N", c_i), ("stream0", c_i), ("mu", c_i64 * 6),
+                ("sg", c_i64 * 6), ("seed", c_u64), ("ctr", c_p), ("base", c_p), ("every", c_i64), ("n_p", c_i64),
+                ("n_e", c_i64)]
+
+
+class NoisyGradArgs(ctypes.Structure):
+    """Arguments of ``noisy_sigma_grad_kernel`` (``NoisyGradArgs``, csrc/noisy.hip)."""
+    _fields_ = [("g", c_p), ("xi", c_p), ("A", c_i), ("N", c_i), ("mu", c_i64 * 6), ("sg", c_i64 * 6),
+                ("n_g", c_i64)]
+
+
 class CfFragOut(ctypes.Structure):
     """The optimizer's stores of the fused forward's online operands (``CfFragOut``,
     csrc/cf_pack.h); all-zero = off."""
@@ -206,6 +224,9 @@ _SIGS = {
     "apex_pack_rows": ([c_p, c_p, c_p, c_i, c_i, c_p, c_i64, c_p], c_i),
     "apex_sqnorm_ranges": ([c_p, c_i64, c_p, c_i64, c_p, c_i, c_p], c_i),
     "apex_copy_segments": ([c_i, c_p, c_p, c_p, c_p], c_i),
+    "apex_noisy_xi_len": ([c_i, c_i], c_i),
+    "apex_noisy_compose": ([NoisyArgs, c_p], c_i),
+    "apex_noisy_sigma_grad": ([NoisyGradArgs, c_p], c_i),
 }
 
 _LIB: Optional[ctypes.CDLL] = None

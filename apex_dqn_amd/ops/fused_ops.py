@@ -531,6 +531,46 @@ class TorchBackend:
     def gather_frames(self, replay, slots, out):
         replay.gather_frames(slots, out)
 
+    # ------------------------------------------------------- noisy layers
+    def noisy_compose(self, plan, nets, xi, fc32=None, xi_in=None) -> None:
+        """Effective parameters of the noisy fc and head layers (learner/noisy.py; the oracle of
+        csrc/noisy.hip ``noisy_compose_kernel``).  ``plan``: a ``NoisyPlan``; ``nets``: [(flat
+        parameters with mu and sigma segments, fp32 shadow, bf16 shadow hi, lo or None), ...],
+        net i drawing with stream ``plan.stream0 + i`` at the index ``plan.index()``; the shadows
+        have the mu layout and get W = mu + sigma (xi_out (x) xi_in), evaluated in fp64 and
+        rounded to fp32: heads and noisy biases into the fp32 shadow, ``wfc`` split into hi (+
+        lo).  ``xi`` [len(nets), >= K] receives the draws (fp32, which is what enters W);
+        ``fc32``: per net an optional (1024, 3136) fp32 output of the effective ``wfc``;
+        ``xi_in`` (tests): these draws instead of the mirror's."""
+        from ..learner import noisy as NZ
+        K = plan.K
+        u = plan.index() if xi_in is None else 0
+        for i, (p, e32, ehi, elo) in enumerate(nets):
+            if xi_in is None:
+                xi[i, :K].copy_(NZ.noise_vectors(plan.seed, u, plan.stream0 + i, plan.A, plan.N)["xi"])
+            else:
+                xi[i, :K].copy_(xi_in[i, :K])
+            v = NZ.split_xi(xi[i].double(), plan.A, plan.N)
+            for name in NZ.MU:
+                mu = plan.seg(p, name).double()
+                w = (mu + plan.seg(p, NZ.SIGMA[name]).double() * NZ.outer(v, name, mu.shape).to(mu.device)).float()
+                if name == "wfc":
+                    split_into(w, plan.seg(ehi, name), None if elo is None else plan.seg(elo, name))
+                    if fc32 is not None and fc32[i] is not None:
+                        fc32[i].copy_(w)
+                else:
+                    plan.seg(e32, name).copy_(w)
+
+    def noisy_sigma_grad(self, plan, g32, xi) -> None:
+        """G[sigma] = G[mu] * xi_out (x) xi_in for the six noisy segments of the flat gradient,
+        from the draw ``xi`` (K values, the online net's); the product in fp64, rounded once
+        (the oracle of csrc/noisy.hip ``noisy_sigma_grad_kernel``)."""
+        from ..learner import noisy as NZ
+        v = NZ.split_xi(xi.reshape(-1).double(), plan.A, plan.N)
+        for name in NZ.MU:
+            gm = plan.seg(g32, name).double()
+            plan.seg(g32, NZ.SIGMA[name]).copy_((gm * NZ.outer(v, name, gm.shape).to(gm.device)).float())
+
     # ------------------------------------------- data-parallel gradient factors
     def pack_rows(self, dst: torch.Tensor, segs) -> None:
         """dst[:, c0:c0 + n] = seg for the 2-D ``segs`` laid side by side (same row count)."""
@@ -558,7 +598,7 @@ class HipBackend(TorchBackend):
         self.lib = _lib.require_kernels()
         self.native_conv = native_conv and hasattr(self.lib, "apex_conv_fwd")
         self.kernels = ["replay", "head", "head_wgrad", "optimizer", "actor_head", "c51_head", "c51_actor_head", "qr_head",
-                        "qr_actor_head"]
+                        "qr_actor_head", "noisy_compose", "noisy_sigma_grad"]
         if self.native_conv:
             self.kernels += ["conv_fwd", "conv_dgrad", "conv_wgrad", "fc_fwd", "fc_bwd"]
         self.ws = C.Workspace()
@@ -972,6 +1012,46 @@ class HipBackend(TorchBackend):
         _lib.check(self.lib.apex_sqnorm_ranges(a.data_ptr(), a.numel(), _lib.ptr(b), 0 if b is None else b.numel(),
                                                partials.data_ptr(), int(nblk), _lib.stream_ptr()), "sqnorm_ranges")
         return int(nblk)
+
+    @staticmethod
+    def _noisy_offsets(plan, mu, sg) -> None:
+        from ..learner import noisy as NZ
+        for k, name in enumerate(NZ.MU):
+            mu[k], sg[k] = int(plan.offsets[name]), int(plan.offsets[NZ.SIGMA[name]])
+
+    def noisy_compose(self, plan, nets, xi, fc32=None, xi_in=None) -> None:
+        """csrc/noisy.hip ``noisy_compose_kernel``: all nets in one launch; the draw index is
+        read on the device."""
+        if xi_in is not None:
+            return super().noisy_compose(plan, nets, xi, fc32, xi_in)
+        a = _lib.NoisyArgs()
+        a.nnets, a.A, a.N, a.stream0 = len(nets), int(plan.A), int(plan.N), int(plan.stream0)
+        assert 1 <= a.nnets <= 2 and xi.dtype == torch.float32 and xi.shape[0] >= a.nnets and xi.shape[1] >= plan.K \
+            and xi.stride(1) == 1 and xi.stride(0) % 4 == 0
+        self._noisy_offsets(plan, a.mu, a.sg)
+        a.seed, a.ctr, a.base, a.every = int(plan.seed), plan.ctr.data_ptr(), _lib.ptr(plan.base), int(plan.every)
+        assert plan.ctr.dtype == torch.int64 and (plan.base is None or plan.base.dtype == torch.int64)
+        a.n_p = min(int(p.numel()) for p, _, _, _ in nets)
+        a.n_e = min(min(int(e.numel()), int(h.numel()), int(h.numel() if l is None else l.numel()))
+                    for _, e, h, l in nets)
+        for i, (p, e32, ehi, elo) in enumerate(nets):
+            assert p.dtype == torch.float32 and e32.dtype == torch.float32 and ehi.dtype == torch.bfloat16 \
+                and (elo is None or elo.dtype == torch.bfloat16)
+            n = a.net[i]
+            n.p, n.e32, n.ehi, n.elo, n.xi = p.data_ptr(), e32.data_ptr(), ehi.data_ptr(), _lib.ptr(elo), \
+                xi[i].data_ptr()
+            f = None if fc32 is None else fc32[i]
+            assert f is None or (f.dtype == torch.float32 and f.is_contiguous() and f.numel() == 1024 * 3136)
+            n.fc32 = _lib.ptr(f)
+        _lib.check(self.lib.apex_noisy_compose(a, _lib.stream_ptr()), "noisy_compose")
+
+    def noisy_sigma_grad(self, plan, g32, xi) -> None:
+        """csrc/noisy.hip ``noisy_sigma_grad_kernel``."""
+        a = _lib.NoisyGradArgs()
+        assert g32.dtype == torch.float32 and xi.dtype == torch.float32 and xi.numel() >= plan.K and xi.is_contiguous()
+        a.g, a.xi, a.A, a.N, a.n_g = g32.data_ptr(), xi.data_ptr(), int(plan.A), int(plan.N), int(g32.numel())
+        self._noisy_offsets(plan, a.mu, a.sg)
+        _lib.check(self.lib.apex_noisy_sigma_grad(a, _lib.stream_ptr()), "noisy_sigma_grad")
 
     def cast_bf16(self, x32, hi, lo=None) -> None:
         """hi = bf16(x32) (and lo = bf16(x32 - hi)) with one kernel."""

@@ -139,6 +139,19 @@ def check_dist_head(ck: Dict[str, Any], runtime_conf) -> None:
                          f"but another meaning")
 
 
+def check_noisy(ck: Dict[str, Any], runtime_conf) -> None:
+    """Refuse a checkpoint whose ``Q_state`` has noisy-layer sigma keys (``*_sigma``) when the
+    learner has none, and the reverse (a reference checkpoint never has them): before anything
+    is copied."""
+    qs = ck.get("Q_state") if isinstance(ck, dict) else None
+    if not isinstance(qs, dict):
+        return
+    has = any(str(k).endswith("_sigma") for k in qs)
+    if has != bool(runtime_conf.noisy):
+        raise ValueError(f"the checkpoint has {'' if has else 'no '}noisy-layer sigma keys (*_sigma), this learner "
+                         f"runs Runtime.noisy={bool(runtime_conf.noisy)}")
+
+
 def layout_segments(layout) -> List[Tuple[str, int, int]]:
     """Segments of a ``models.flat_params.FlatLayout``."""
     out = []

@@ -18,7 +18,8 @@ CSRC = os.path.join(ROOT, "apex_dqn_amd", "csrc")
 HOT = ["conv12_fused_kernel", "conv2_dgrad_img", "conv3_dgrad_img", "igemm_dma_kernel", "igemm_wgrad_kernel",
        "conv2_wgrad_rows_kernel",
        "fc_gemm128_kernel", "conv1_wgrad_img_kernel", "conv21_bwd_fused_kernel", "fc_wgrad_head_prio_kernel", "rmsprop_sample_kernel",
-       "grad_finalize_kernel", "actor_head_kernel", "c51_head_kernel", "qr_head_kernel", "head_wgrad_prio_kernel", "sconv_", "resblock_", "maxpool_bwd"]
+       "grad_finalize_kernel", "actor_head_kernel", "c51_head_kernel", "qr_head_kernel", "head_wgrad_prio_kernel",
+       "noisy_compose_kernel", "noisy_sigma_grad_kernel", "sconv_", "resblock_", "maxpool_bwd"]
 
 
 def usage(path):
