@@ -116,6 +116,15 @@ class RuntimeConf:
     noisy: bool = False
     noisy_sigma0: float = 0.5
     noisy_actor_resample: int = 1
+    # Munchausen-DQN target for the scalar head (Vieillard et al. 2020; learner/losses.py munchausen_loss,
+    # csrc/mdqn_head.hip): T = R + alpha clamp(tau ln pi(a | Q_target(S_t)), clip, 0) + Gamma * the target net's
+    # soft value at S_t+n, pi = softmax(Q_target / tau); no online argmax.  The forward runs the online net on
+    # S_t only and the target net on S_t+n and S_t.  Single-rank NatureCNN and the torch learners (mlp), with or
+    # without Runtime.noisy; not the distributional heads, IMPALA, the DP step or the graph learner
+    munchausen: bool = False
+    munchausen_alpha: float = 0.9
+    munchausen_tau: float = 0.03
+    munchausen_clip: float = -1.0
     priority_eps: float = 1e-6      # priority floor: leaves hold (|delta| + priority_eps)^alpha
     use_is_weights: bool = True
     is_normalise: str = "batch_max"  # IS weights (N P(i))^-beta divided by their max over the sampled batch
@@ -329,6 +338,26 @@ class ApexConfig:
             if int(rt.world_size) > 1 or rt.force_dp:
                 raise ValueError("Runtime.noisy runs on a single rank: the data-parallel step (world_size > 1, "
                                  "force_dp) has no noisy layers")
+        if not isinstance(rt.munchausen, bool):
+            raise ValueError(f"Runtime.munchausen must be true or false, got {rt.munchausen!r}")
+        if not 0.0 <= float(rt.munchausen_alpha) <= 1.0:
+            raise ValueError(f"Runtime.munchausen_alpha (the bonus scale) must be in [0, 1], got "
+                             f"{rt.munchausen_alpha}")
+        if not float(rt.munchausen_tau) > 0.0:
+            raise ValueError(f"Runtime.munchausen_tau (the softmax temperature) must be > 0, got "
+                             f"{rt.munchausen_tau}")
+        if not float(rt.munchausen_clip) < 0.0:
+            raise ValueError(f"Runtime.munchausen_clip (the lower clip of tau ln pi) must be < 0, got "
+                             f"{rt.munchausen_clip}")
+        if rt.munchausen:
+            if na >= 2:
+                raise ValueError(f"Runtime.munchausen is a target of the scalar head: Runtime.num_atoms={na} "
+                                 f"(a distributional head) is not supported")
+            if net not in ("nature64", "nature32", "mlp"):
+                raise ValueError(f"Runtime.munchausen needs network nature64, nature32 or mlp, got {net!r}")
+            if int(rt.world_size) > 1 or rt.force_dp:
+                raise ValueError("Runtime.munchausen runs on a single rank: the data-parallel step (world_size > 1, "
+                                 "force_dp) has no Munchausen target")
         if net in ("nature64", "nature32", "impala") and len(ss) != 3:
             raise ValueError(f"network {net} needs an image state_shape [C,H,W], got {ss}")
         if net in ("nature64", "nature32") and tuple(ss[1:]) != (84, 84):
@@ -352,6 +381,11 @@ class ApexConfig:
         if rt.noisy:       # (only then: the non-noisy call is the one of before)
             kw.update(noisy=True, noisy_sigma0=float(rt.noisy_sigma0))
         return kw
+
+    def munchausen_kw(self) -> Dict[str, float]:
+        """(alpha, tau, clip) of the Munchausen target (learner/losses.py munchausen_loss)."""
+        rt = self.Runtime
+        return dict(alpha=float(rt.munchausen_alpha), tau=float(rt.munchausen_tau), clip=float(rt.munchausen_clip))
 
     @property
     def quantile(self) -> bool:

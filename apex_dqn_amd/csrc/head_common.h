@@ -282,16 +282,29 @@ __device__ __forceinline__ void head_q(const HeadParams& P, int A, int lane, flo
     if (j < A) q[j] = v + part[j + 1] - amean;
 }
 
+// Munchausen-DQN target (csrc/mdqn_head.hip): T = rew + alpha clamp(tau ln pi(a | g0), clip, 0) + gam vsoft(g1),
+// pi = softmax(g / tau), g0 / g1 the target net's q at S_t / S_t+n
+struct MdqnTarget {
+  float alpha, tau, clip;
+  float* aux;            // [B, 2] (bonus, vsoft) per sample, or null
+};
+
 // One block of three waves per sample (blockIdx.x = b).  Returns true in wave 0,
 // which finishes the sample and holds |delta| (wave-uniform) in *ad_out.
-template <int HS, int MAXA = HEAD_MAXA>
+// MDQN (mdqn_head_kernel; `mt` non-null): Hon [B] holds the online S_t rows only and Htg [2B] the target net's
+// rows, [0, B) = S_t+n (wave 1) and [B, 2B) = S_t (wave 2); wave 0 forms the Munchausen target from the two
+// target q-vectors instead of the double-DQN one and runs the same loss / dhead / dH tail.  Every MDQN
+// difference is an `if constexpr`: the default instantiation compiles to the code of before (its ISA is
+// compared with the parent's, docs/PERF_NOTES.md).  The deferred fc epilogue (hp.part) is not laid out for the
+// MDQN row plan: apex_mdqn_head refuses it.
+template <int HS, int MAXA = HEAD_MAXA, bool MDQN = false>
 __device__ __forceinline__ bool ddqn_head_body(
     const bf16_t* __restrict__ Hon, const bf16_t* __restrict__ Htg, HeadParams Pon, HeadParams Ptg,
     const int32_t* __restrict__ act, const float* __restrict__ rew, const float* __restrict__ gam,
     const float* __restrict__ isw, int B, int A, int huber, float kappa, float grad_scale,
     float* __restrict__ td_abs, float* __restrict__ loss, float* __restrict__ q_out,
     bf16_t* __restrict__ dH, float* __restrict__ dhead, float* __restrict__ zero_ptr, int zero_n,
-    float* ad_out, HeadLo lo, const HeadPart& hp) {
+    float* ad_out, HeadLo lo, const HeadPart& hp, const MdqnTarget* mt = nullptr) {
   __shared__ float qs[2][MAXA];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int b = blockIdx.x;
@@ -334,6 +347,9 @@ __device__ __forceinline__ bool ddqn_head_body(
     if (hp.part != nullptr) {
       load_row_part<HS>(hp, wv == 1 ? B + b : hp.two_b + b, lane, hv_x, ha_x, false);
       head_q<HS, MAXA>(wv == 1 ? Pon : Ptg, A, lane, q, hv_x, ha_x);
+    } else if constexpr (MDQN) {
+      const int64_t r = (int64_t)(wv == 1 ? b : B + b) * ROW;
+      head_row<HS, MAXA>(Htg + r, split ? lo.Htg + r : nullptr, Ptg, A, lane, q, hv_x, ha_x);
     } else if (wv == 1)
       head_row<HS, MAXA>(Hon + (int64_t)(B + b) * ROW, split ? lo.Hon + (int64_t)(B + b) * ROW : nullptr, Pon, A, lane, q,
                    hv_x, ha_x);
@@ -363,7 +379,37 @@ __device__ __forceinline__ bool ddqn_head_body(
     }
   }
   (void)astar;
-  const float G = rew_b + gam_b * qg_star;
+  float G = rew_b + gam_b * qg_star;
+  if constexpr (MDQN) {
+    // q_n = g1 (target net, S_t+n), q_g = g0 (target net, S_t): wave-uniform values, no shuffles; every exponent
+    // is max-subtracted (no overflow, underflow to 0 is the correct limit); accurate expf / logf
+    float m1 = -3.4e38f, m0 = -3.4e38f, g0a = 0.f;
+#pragma unroll
+    for (int j = 0; j < MAXA; ++j) {
+      if (j < A) {
+        m1 = fmaxf(m1, q_n[j]);
+        m0 = fmaxf(m0, q_g[j]);
+        if (j == a_b) g0a = q_g[j];
+      }
+    }
+    const float tau = mt->tau;
+    float s1 = 0.f, s0 = 0.f;
+#pragma unroll
+    for (int j = 0; j < MAXA; ++j) {
+      if (j < A) {
+        s1 += expf((q_n[j] - m1) / tau);
+        s0 += expf((q_g[j] - m0) / tau);
+      }
+    }
+    const float tlp = (g0a - m0) - tau * logf(s0);                   // tau ln pi(a_b | g0) <= 0
+    const float bonus = mt->alpha * fminf(fmaxf(tlp, mt->clip), 0.f);
+    const float vsoft = m1 + tau * logf(s1);
+    G = rew_b + bonus + gam_b * vsoft;
+    if (mt->aux != nullptr && lane == 0) {
+      mt->aux[2 * (int64_t)b] = bonus;
+      mt->aux[2 * (int64_t)b + 1] = vsoft;
+    }
+  }
   const float delta = G - q_sa;
   const float ad = fabsf(delta);
   float l, dl;

@@ -1,0 +1,96 @@
+// Fused dueling heads + Munchausen-DQN target (Vieillard, Pietquin, Geist 2020) + Huber/IS loss +
+// priorities + head backward: the scalar head of csrc/ddqn_head.hip with another target.  One block
+// of three waves per sample, each wave evaluating one 2*HS-wide activation row:
+//   wave 0  online net at S_t      (q_on, keeps the weights the backward needs)
+//   wave 1  target net at S_t+n    (g1)
+//   wave 2  target net at S_t      (g0)
+// The q-vectors meet in LDS; wave 0 forms, with pi = softmax(g / tau) and every exponent max-subtracted
+// (no overflow; a term that underflows to 0 is the correct limit),
+//   tau ln pi(a | g0) = (g0[a] - max g0) - tau ln sum_a' exp((g0[a'] - max g0) / tau)
+//   bonus = alpha clamp(tau ln pi(a | g0), clip, 0)
+//   vsoft = max g1 + tau ln sum_a' exp((g1[a'] - max g1) / tau)     (= E_pi[g1 - tau ln pi(. | g1)])
+//   T     = rew + bonus + gam vsoft,   delta = T - q_on[a]
+// and runs the scalar head's own loss / dhead / dH tail (head_common.h ddqn_head_body<.., MDQN = true>).  There is no
+// online argmax: the target is detached, the gradient flows through q_on[a] only.  learner/losses.py
+// munchausen_loss is the definition, TorchBackend.mdqn_head the oracle.
+//
+// Inputs (per sample b of the batch B):
+//   Hon  [B, 2 HS]   bf16  online stream activations of S_t; cols [0, HS) value, [HS, 2 HS) advantage
+//   Htg  [2B, 2 HS]  bf16  target stream activations: rows [0, B) = S_t+n, rows [B, 2B) = S_t
+//   lo.Hon / lo.Htg / lo.dH: the lo planes in split (fp32-accurate) mode, else null
+// Outputs: td_abs[B], loss[B], q_out[B, A] (optional), aux[B, 2] = (bonus, vsoft) (optional),
+// dH[B, 2 HS], dhead[B, 1 + A]; the side duties of ddqn_head_kernel (head-gradient zeroing, IsNorm).
+#include "head_common.h"
+
+struct MdqnArgs {
+  const bf16_t* Hon;
+  const bf16_t* Htg;
+  HeadParams Pon, Ptg;
+  const int32_t* act;
+  const float* rew;
+  const float* gam;
+  const float* isw;      // IS weights, or null (1)
+  int B, A, huber, hidden;
+  float kappa, alpha, tau, clip, grad_scale;
+  float* td_abs;
+  float* loss;
+  float* q_out;          // or null
+  float* aux;            // [B, 2] (bonus, vsoft), or null
+  bf16_t* dH;
+  float* dhead;
+  float* zero_ptr;       // head-gradient region to zero (or null)
+  int zero_n;
+  HeadLo lo;
+  IsNorm isn;
+  HeadPart hp;           // must be all null: the deferred fc epilogue is not taken (see mdqn_head_kernel)
+};
+
+// ddqn_head_body<HS, MAXA, true> (head_common.h) with the side job of ddqn_head_kernel's second wave.  The body
+// is instantiated with its HeadPart argument taken from the launch arguments, as ddqn_head_kernel does, although
+// the launcher only lets a null one through: with both of the body's forward paths present hipcc compiles wave
+// 0's head_q as it does in ddqn_head_kernel, and q_out is bit-equal to that kernel's (with the path folded away
+// two products of the value stream's dot product contract differently, one unit in the last place of q).
+template <int HS, int MAXA>
+__global__ void __launch_bounds__(192) mdqn_head_kernel(MdqnArgs a) {
+  float ad;
+  const MdqnTarget mt{a.alpha, a.tau, a.clip, a.aux};
+  const bool w0 = ddqn_head_body<HS, MAXA, true>(a.Hon, a.Htg, a.Pon, a.Ptg, a.act, a.rew, a.gam, a.isw, a.B, a.A, a.huber,
+                                                 a.kappa, a.grad_scale, a.td_abs, a.loss, a.q_out, a.dH, a.dhead, a.zero_ptr,
+                                                 a.zero_n, &ad, a.lo, a.hp, &mt);
+  // batch-max IS normalisation: block 0's second wave (csrc/ddqn_head.hip, same semantics)
+  if (!w0 && (a.isn.out != nullptr || a.isn.valid_count != nullptr) && blockIdx.x == 0 && (threadIdx.x >> 6) == 1) {
+    float m = 0.f;
+    int nv = 0;
+    for (int i = threadIdx.x & 63; i < a.B; i += 64) {
+      m = fmaxf(m, a.isw[i]);
+      nv += a.isw[i] > 0.f ? 1 : 0;
+    }
+    m = wave_max(m);
+    nv = wave_sum(nv);
+    if ((threadIdx.x & 63) == 0) {
+      const float ws = a.isn.wscale != nullptr ? a.isn.wscale[0] : 1.f;
+      if (a.isn.out != nullptr) a.isn.out[0] = ws > 0.f ? (double)m / (double)ws : 0.0;
+      if (a.isn.valid_count != nullptr) atomicAdd(a.isn.valid_count, (unsigned long long)nv);
+    }
+  }
+}
+
+APEX_EXPORT int apex_mdqn_head(MdqnArgs a, hipStream_t st) {
+  if (a.A < 1 || a.A > HEAD_MAXA || a.B < 1 || a.hidden != 512) return (int)hipErrorInvalidValue;
+  if (!(a.tau > 0.f) || !(a.clip < 0.f) || !(a.alpha >= 0.f && a.alpha <= 1.f)) return (int)hipErrorInvalidValue;
+  if (a.Hon == nullptr || a.Htg == nullptr || a.act == nullptr || a.rew == nullptr || a.gam == nullptr ||
+      a.td_abs == nullptr || a.loss == nullptr || a.dH == nullptr || a.dhead == nullptr)
+    return (int)hipErrorInvalidValue;
+  if ((a.isn.out != nullptr || a.isn.valid_count != nullptr) && a.isw == nullptr) return (int)hipErrorInvalidValue;
+  if (a.lo.Hon != nullptr && (a.lo.Htg == nullptr || a.lo.dH == nullptr)) return (int)hipErrorInvalidValue;
+  if (a.zero_ptr != nullptr && a.zero_n < 0) return (int)hipErrorInvalidValue;
+  if (a.hp.part != nullptr || a.hp.hon != nullptr || a.hp.hon_lo != nullptr) return (int)hipErrorInvalidValue;
+  // 16-byte row loads / stores and float4 weight loads
+  if (((uintptr_t)a.Hon | (uintptr_t)a.Htg | (uintptr_t)a.dH | (uintptr_t)a.lo.Hon | (uintptr_t)a.lo.Htg |
+       (uintptr_t)a.lo.dH | (uintptr_t)a.Pon.wv | (uintptr_t)a.Pon.wa | (uintptr_t)a.Ptg.wv | (uintptr_t)a.Ptg.wa) & 15)
+    return (int)hipErrorInvalidValue;
+  // the q arrays in registers: 8 actions keep the kernel free of scratch (as ddqn_head_kernel)
+  if (a.A <= 8) mdqn_head_kernel<512, 8><<<a.B, 192, 0, st>>>(a);
+  else mdqn_head_kernel<512, HEAD_MAXA><<<a.B, 192, 0, st>>>(a);
+  APEX_CHECK_LAUNCH();
+}

@@ -290,6 +290,7 @@ struct SampleArgs {
   float* out_rew;
   float* out_gam;
   int32_t* out_nxt2;
+  int32_t* out_obs2;            // the S_t slots a second time (the Munchausen step's third row block), or null
   const double* shard_stats;   // sharded mode: [W][SHARD_STATS] (total, min p, batch IS max) per shard, or null
   int shard_rank, shard_world;
   uint64_t shard_seed;         // common to all ranks (the local `seed` is per shard)
@@ -315,6 +316,7 @@ __device__ __forceinline__ void tree_sample_body(const SampleArgs& S, int bid) {
   float* __restrict__ out_rew = S.out_rew;
   float* __restrict__ out_gam = S.out_gam;
   int32_t* __restrict__ out_nxt2 = S.out_nxt2;
+  int32_t* __restrict__ out_obs2 = S.out_obs2;
   const int lane = threadIdx.x & 63;
   const int b = (bid * blockDim.x + threadIdx.x) >> 6;
   if (b >= B) return;
@@ -403,7 +405,9 @@ __device__ __forceinline__ void tree_sample_body(const SampleArgs& S, int bid) {
     out_gam[b] = r.gam[s];
   }
   for (int c = lane; c < r.C; c += 64) {
-    out_obs[(int64_t)b * r.C + c] = r.obs[s * r.C + c];
+    const int32_t ov = r.obs[s * r.C + c];
+    out_obs[(int64_t)b * r.C + c] = ov;
+    if (out_obs2) out_obs2[(int64_t)b * r.C + c] = ov;
     const int32_t nv = r.nxt[s * r.C + c];
     out_nxt[(int64_t)b * r.C + c] = nv;
     if (out_nxt2) out_nxt2[(int64_t)b * r.C + c] = nv;
@@ -705,9 +709,9 @@ APEX_EXPORT int apex_replay_insert(TreeDesc t, RecordDesc r, int64_t start, int 
 APEX_EXPORT int apex_tree_sample(TreeDesc t, RecordDesc r, int B, uint64_t seed, const uint64_t* ctr,
                                  float beta, int64_t* out_idx, float* out_w,
                                  int32_t* out_gen, int32_t* out_obs, int32_t* out_nxt, int32_t* out_act,
-                                 float* out_rew, float* out_gam, int32_t* out_nxt2, const double* shard_stats,
-                                 int shard_rank, int shard_world, uint64_t shard_seed, float* out_wscale,
-                                 int64_t mcap, BetaSched bs, hipStream_t st) {
+                                 float* out_rew, float* out_gam, int32_t* out_nxt2, int32_t* out_obs2,
+                                 const double* shard_stats, int shard_rank, int shard_world, uint64_t shard_seed,
+                                 float* out_wscale, int64_t mcap, BetaSched bs, hipStream_t st) {
   if (B <= 0) return 0;
   if (mcap <= 0) mcap = (int64_t)shard_world * B;
   if (shard_stats != nullptr && (B < 3 || shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world))
@@ -715,8 +719,8 @@ APEX_EXPORT int apex_tree_sample(TreeDesc t, RecordDesc r, int B, uint64_t seed,
   const int waves_per_block = 4;
   tree_sample_kernel<<<blocks_for(B, waves_per_block), 64 * waves_per_block, 0, st>>>(
       SampleArgs{t, r, B, seed, ctr, beta, out_idx, out_w, out_gen, out_obs, out_nxt, out_act,
-                 out_rew, out_gam, out_nxt2, shard_stats, shard_rank, shard_world, shard_seed, out_wscale,
-                 mcap, bs});
+                 out_rew, out_gam, out_nxt2, out_obs2, shard_stats, shard_rank, shard_world, shard_seed,
+                 out_wscale, mcap, bs});
   APEX_CHECK_LAUNCH();
 }
 
@@ -762,7 +766,7 @@ APEX_EXPORT int apex_fill16(void* p, int64_t n, int nt, hipStream_t st) {
   APEX_CHECK_LAUNCH();
 }
 
-APEX_EXPORT int apex_abi_version() { return 12; }
+APEX_EXPORT int apex_abi_version() { return 13; }
 
 // 1 if this library was built with -DAPEX_DEBUG_BOUNDS
 APEX_EXPORT int apex_debug_bounds_enabled() {
@@ -807,9 +811,9 @@ APEX_EXPORT int apex_rmsprop_sample(float* p, const float* g, float* v, float* m
                                     uint64_t seed, const uint64_t* ctr, float beta,
                                     int64_t* out_idx, float* out_w, int32_t* out_gen, int32_t* out_obs,
                                     int32_t* out_nxt, int32_t* out_act, float* out_rew, float* out_gam,
-                                    int32_t* out_nxt2, const double* shard_stats, int shard_rank, int shard_world,
-                                    uint64_t shard_seed, float* out_wscale, int64_t mcap, BetaSched bs,
-                                    bf16_t* pb_lo, const double* wnorm, int wn, int wstride, CfFragOut fo,
+                                    int32_t* out_nxt2, int32_t* out_obs2, const double* shard_stats, int shard_rank,
+                                    int shard_world, uint64_t shard_seed, float* out_wscale, int64_t mcap,
+                                    BetaSched bs, bf16_t* pb_lo, const double* wnorm, int wn, int wstride, CfFragOut fo,
                                     const RmsSegs* seg, const float* gpre, int64_t npre, OptSched os,
                                     hipStream_t st) {
   const int mode = opt_mode(os);
@@ -870,8 +874,8 @@ APEX_EXPORT int apex_rmsprop_sample(float* p, const float* g, float* v, float* m
   const RmspropArgs ra{p, g, v, m, pb, n, partials, npart, lr, alpha, eps_opt, clip, centered, norm_out, pb_lo,
                       wnorm, wn, wstride, fo, npre > 0 ? gpre : nullptr, npre, os};
   const SampleArgs sa{t, r, B, seed, ctr, beta, out_idx, out_w, out_gen, out_obs, out_nxt,
-                      out_act, out_rew, out_gam, out_nxt2, shard_stats, shard_rank, shard_world, shard_seed,
-                      out_wscale, mcap, bs};
+                      out_act, out_rew, out_gam, out_nxt2, out_obs2, shard_stats, shard_rank, shard_world,
+                      shard_seed, out_wscale, mcap, bs};
   const int grid = (seg != nullptr ? sg.blk0[sg.nseg] : nb) + nsb;
 #define APEX_OPT_LAUNCH(MODE)                                                                          \
   do {                                                                                                 \

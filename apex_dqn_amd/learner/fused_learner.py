@@ -4,7 +4,10 @@ Per step (B = local batch), entirely on device, one stream, no host sync:
 
   online fwd on 2B rows, target fwd on B rows    conv1_s2d (reads the uint8 replay ring
                                                  by slot) / conv2 / conv3 / fc
-  DDQN target + Huber*IS loss + |delta| + dH     csrc/ddqn_head.hip (Runtime.num_atoms >= 2:
+  DDQN target + Huber*IS loss + |delta| + dH     csrc/ddqn_head.hip (Runtime.munchausen: the online
+                                                 net on B rows, the target net on 2B, and the
+                                                 Munchausen target, csrc/mdqn_head.hip;
+                                                 Runtime.num_atoms >= 2:
                                                  csrc/c51_head.hip, projected cross-entropy,
                                                  or csrc/qr_head.hip, quantile Huber loss,
                                                  then head wgrad + write-back and fc wgrad as
@@ -117,6 +120,14 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         if self.noisy and self._dp:
             raise ValueError("Runtime.noisy: the noisy layers run on a single rank, not in the data-parallel step "
                              "(world > 1, Runtime.force_dp, the emulated world)")
+        # Munchausen-DQN target of the scalar head (csrc/mdqn_head.hip): rows [0, B) online S_t, [B, 2B) target
+        # S_t+n, [2B, 3B) target S_t -- the forward's weight set switches at row B (_rows_first)
+        self.munchausen = bool(self.rt.munchausen)
+        if self.munchausen and self.N >= 2:
+            raise ValueError(f"Runtime.munchausen is a target of the scalar head, not of Runtime.num_atoms={self.N}")
+        if self.munchausen and self._dp:
+            raise ValueError("Runtime.munchausen: the Munchausen target runs on a single rank, not in the "
+                             "data-parallel step (world > 1, Runtime.force_dp, the emulated world)")
         if self.rt.dtype not in ("fp32", "bf16"):
             raise ValueError("Runtime.dtype must be fp32 or bf16")
         self.precision = self.rt.dtype
@@ -274,7 +285,9 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         # SW.fc_epi_in_head = False keeps the separate epilogue launch)
         # (the distributional head reads h: the separate epilogue launch, which then also
         # carries the conv2 fragment pack job)
-        self._defer_fc_epilogue = SW.fc_epi_in_head and self.N == 1
+        # (the Munchausen head reads h too: with the weight set switched at row B the fc forward keeps its
+        # own epilogue, ops.fc_fwd)
+        self._defer_fc_epilogue = SW.fc_epi_in_head and self.N == 1 and not self.munchausen
         # next-batch pre-sampling: the batch of step t+1 is drawn at the end of step t,
         # after the priority write-back -- on the HIP backend inside the optimizer launch
         # (its first blocks run the sampler: csrc/sumtree.hip rmsprop_sample_kernel), so
@@ -401,6 +414,8 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         # rows [0,B) = S_t, [B,2B) = S_{t+n} (online net), [2B,3B) = S_{t+n} (target net):
         # every forward layer is ONE launch over 3B images with the weight set
         # switched at row 2B (block-uniform)
+        # (Runtime.munchausen: [0,B) = S_t (online net), [B,2B) = S_{t+n}, [2B,3B) = S_t (both target net),
+        # switched at row B: _rows_first)
         self.S = self.replay.alloc_sample_buffers(B)
         self.slots = torch.zeros(3 * B, C, dtype=torch.int32, device=d)
         self.S["obs"] = self.slots[:B]
@@ -425,6 +440,8 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         self.dhead = torch.zeros(B, (self.A + 1) * self.N, dtype=torch.float32, device=d)
         self.td_abs = torch.zeros(B, dtype=torch.float32, device=d)
         self.loss_b = torch.zeros(B, dtype=torch.float32, device=d)
+        # Munchausen target: (bonus, soft value) per row, for the metrics
+        self.mdqn_aux = torch.zeros(B, 2, dtype=torch.float32, device=d) if self.munchausen else None
         self.partials = torch.zeros(1024, dtype=torch.float64, device=d)
         # single rank, HIP: the clip norm is summed by the gradient producers (fc wgrad
         # epilogue + grad_finalize blocks) instead of a separate pass over g32
@@ -449,15 +466,20 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         """conv3 inside the fused conv1 -> conv2 launch (small launches only, SW.conv123_max_images)."""
         return bool(self._c12) and 0 < 3 * self.B <= SW.conv123_max_images
 
+    @property
+    def _rows_first(self) -> int:
+        """The first row of the target net in the 3B-row forward: 2B, or B with the Munchausen target."""
+        return self.B if self.munchausen else 2 * self.B
+
     def forward_all(self, defer_head: bool = False) -> None:
-        """Online net on rows [0,2B), target net on rows [2B,3B): one launch per layer.
+        """Online net on rows [0,2B), target net on rows [2B,3B) (``_rows_first``): one launch per layer.
         bf16 weights (Pb / Tb, + Pl / Tl lo planes in split mode), fp32 biases (P / T).
         ``defer_head``: the fc layer's split-K epilogue may be left to the step's head
         launch (which then writes h rows [0, B) only)."""
         ops, rt, B = self.ops, self.rt, self.B
         Pb, P, Tb, T, Pl, Tl = self.Pb, self.P, self.Tb, self.T, self.Pl, self.Tl
         sp = self.split
-        n = 3 * B
+        n, r1 = 3 * B, self._rows_first
         # c2f: conv2's weights packed for its forward in the same launch (csrc/conv2_wfrag.h)
         if self._c12:
             # conv1 -> conv2 in one launch, y1 kept in LDS; only the S_t rows' y1 (the
@@ -469,20 +491,20 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             # conv3 in the same launch from y2 in LDS (SW.conv123_fused)
             c3 = self._conv3_weights() if self._conv123 else None
             ops.conv12_fwd(self.replay.frames, self.slots, self.frames, rt.obs_scale, self.y1, self.y1_lo, self.y2,
-                           self.y2_lo, c1, c2, rows_first=2 * B, copy_n=B,
+                           self.y2_lo, c1, c2, rows_first=r1, copy_n=B,
                            pack_sets=online | (0 if self._tgt_packed else 2), c3=c3, y3=self.y3, y3_lo=self.y3_lo)
         else:
             c2f = (Pb["w2"], None, Tb["w2"], None)
             ops.conv1_fwd_ring(self.replay.frames, self.slots, self.frames, Pb["w1"], P["b1"], rt.obs_scale, self.y1,
-                               Tb["w1"], T["b1"], 2 * B, c2f=c2f)
-            ops.conv_fwd(self.y1, Pb["w2"], P["b2"], 2, self.y2, Tb["w2"], T["b2"], 2 * B)
+                               Tb["w1"], T["b1"], r1, c2f=c2f)
+            ops.conv_fwd(self.y1, Pb["w2"], P["b2"], 2, self.y2, Tb["w2"], T["b2"], r1)
         self._issue_params()      # sharded DP update: a deferred fc-row all-gather (learner/dp_step.py)
         if not self._conv123:
-            ops.conv_fwd(self.y2, Pb["w3"], P["b3"], 1, self.y3, Tb["w3"], T["b3"], 2 * B,
+            ops.conv_fwd(self.y2, Pb["w3"], P["b3"], 1, self.y3, Tb["w3"], T["b3"], r1,
                          **self._lo(x_lo=self.y2_lo, w_lo=sp and Pl["w3"], w2_lo=sp and Tl["w3"], out_lo=self.y3_lo))
         self._wait_params()       # sharded DP update: the last update's fc rows (learner/dp_step.py)
         wfc, wfc_lo, bfc, wfc_t, wfc_t_lo, bfc_t = self._fc_weights()
-        ops.fc_fwd(self.y3.reshape(n, 3136), wfc, bfc, self.h, wfc_t, bfc_t, 2 * B,
+        ops.fc_fwd(self.y3.reshape(n, 3136), wfc, bfc, self.h, wfc_t, bfc_t, r1,
                    c2d=(Pb["w2"], Pl["w2"] if sp else None), defer_head=defer_head,
                    **self._lo(x_lo=sp and self.y3_lo.reshape(n, 3136), w_lo=wfc_lo,
                               w2_lo=wfc_t_lo, out_lo=self.h_lo))
@@ -538,7 +560,15 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         self._mark("forward")
         isw = S["weights"] if self._isw else None
         sp = self.split
-        if self.N >= 2 and self.quantile:
+        if self.munchausen:
+            # Munchausen target: online S_t rows, target S_t+n and S_t rows (csrc/mdqn_head.hip)
+            mk = self.cfg.munchausen_kw()
+            ops.mdqn_head(self.h[:B], self.h[B:], self._head_params(self.P), self._head_params(self.T), S["act"],
+                          S["rew"], S["gam"], isw, rt.loss == "huber", rt.huber_delta, mk["alpha"], mk["tau"],
+                          mk["clip"], 1.0 / (B * self.world), self.td_abs, self.loss_b, self.dH, self.dhead,
+                          aux=self.mdqn_aux, zero=self.g_head_region, isn=self._isn(),
+                          **self._lo(lo=sp and (self.h_lo[:B], self.h_lo[B:], self.dH_lo)))
+        elif self.N >= 2 and self.quantile:
             # quantile regression: the quantile Huber loss, kappa = huber_delta (Runtime.loss, v_min / v_max
             # do not apply)
             ops.qr_head(self.h[:2 * B], self.h[2 * B:], self._head_params(self.P), self._head_params(self.T),
@@ -575,9 +605,16 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
 
     def _sample(self) -> None:
         """The sampler writes idx / IS weights / records and the frame-ring slots of
-        S_t, S_{t+n} (twice: online and target rows) into the step's buffers."""
-        self.replay.sample(self.B, out=self.S, nxt2=self.slots[2 * self.B:])
+        S_t, S_{t+n} (twice: online and target rows) into the step's buffers.  Munchausen row plan: S_t
+        twice (online and target rows), S_{t+n} once."""
+        self.replay.sample(self.B, out=self.S, **self._slots2())
         self._sample_ver = self.replay.version
+
+    def _slots2(self) -> Dict[str, torch.Tensor]:
+        """The sampler's destination for the third row block ``slots[2B:]``: the S_{t+n} slots a second time,
+        or with the Munchausen target the S_t slots."""
+        third = self.slots[2 * self.B:]
+        return dict(obs2=third) if self.munchausen else dict(nxt2=third)
 
     def _seg2(self, after_first=None) -> None:
         """fc dgrad + conv backward (with DP, all of it overlaps the fc/heads bucket
@@ -665,7 +702,8 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             self.g32.copy_(self.gcomm)
         # with pre-sampling the optimizer launch also draws step t+1's batch (every
         # read of this step's sample buffers is behind us)
-        nxt = (self.replay, self.B, self.S, self.slots[2 * self.B:]) if self._presample else None
+        s2 = self._slots2()
+        nxt = (self.replay, self.B, self.S, s2.get("nxt2"), s2.get("obs2")) if self._presample else None
         ops.optimizer(self.p32, self.g32, self.rms_v, self.rms_m, self.pbf, rt.lr, rt.rms_decay, rt.rms_eps,
                       rt.grad_clip, rt.centered_rmsprop, self.partials, self.gnorm,
                       norm_total=(self.norm_part, self._npart) if self._fuse_norm else
@@ -1112,6 +1150,9 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         m = self._is_metrics()
         if self.noisy:     # mean |sigma| of the fc weight sigma (the metrics above synced already)
             m["noisy_sigma_mean"] = float(self.P["swfc"].abs().mean())
+        if self.munchausen:     # the last update's mean bonus (<= 0) and mean soft value of S_t+n
+            mean = self.mdqn_aux.double().mean(0)
+            m["munchausen_bonus_mean"], m["soft_value_mean"] = float(mean[0]), float(mean[1])
         return m
 
     def q_values(self, frames_u8: torch.Tensor) -> torch.Tensor:

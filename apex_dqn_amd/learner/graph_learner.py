@@ -62,6 +62,9 @@ class GraphLearner(StepIndexMixin):
         if int(self.rt.num_atoms) != 1:
             raise ValueError(f"Runtime.num_atoms={self.rt.num_atoms}: the graph learner (Runtime.use_hip_kernels = "
                              f"false on the GPU) has no distributional head; run the HIP kernels or num_atoms = 1")
+        if self.rt.munchausen:
+            raise ValueError("Runtime.munchausen: the graph learner (Runtime.use_hip_kernels = false on the GPU) has "
+                             "no Munchausen target; run the HIP kernels or munchausen = false")
         if self.rt.noisy:
             raise ValueError("Runtime.noisy: the graph learner (Runtime.use_hip_kernels = false on the GPU) has no "
                              "noisy layers; run the HIP kernels or noisy = false")

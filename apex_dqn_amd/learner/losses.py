@@ -123,6 +123,54 @@ def quantile_huber_loss(theta_t: torch.Tensor, q_online_next: torch.Tensor, thet
     return per.mean(), td
 
 
+def tau_log_policy(g: torch.Tensor, tau: float) -> torch.Tensor:
+    """tau ln softmax(g / tau) over the last axis, max-subtracted: (g - max g) - tau ln sum exp((g - max g) /
+    tau).  Cannot overflow; a term that underflows to 0 is the correct limit."""
+    c = g - g.max(dim=-1, keepdim=True).values
+    return c - float(tau) * torch.log(torch.exp(c / float(tau)).sum(dim=-1, keepdim=True))
+
+
+def munchausen_targets(q_target_t: torch.Tensor, q_target_next: torch.Tensor, A: torch.Tensor, R: torch.Tensor,
+                       Gamma: torch.Tensor, alpha: float, tau: float,
+                       clip: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(T, bonus, vsoft) of the Munchausen-DQN target, each [B], in ``q_target_t``'s dtype:
+
+        bonus = alpha clamp(tau ln pi(a | g0), clip, 0)            g0 = Q_target(S_t)
+        vsoft = sum_a' pi(a' | g1) (g1[a'] - tau ln pi(a' | g1))   g1 = Q_target(S_t+n)
+        T     = R + bonus + Gamma vsoft
+
+    pi = softmax(g / tau).  vsoft is evaluated as the expectation (analytically max g1 + tau ln sum exp((g1 -
+    max g1) / tau), the form the kernel uses).  Gamma = 0 at terminals needs no special case; with n-step
+    returns the bonus is paid on the first transition only."""
+    dt = q_target_t.dtype
+    g0, g1 = q_target_t, q_target_next.to(dt)
+    tl0 = tau_log_policy(g0, tau).gather(1, A.long().view(-1, 1)).squeeze(1)
+    bonus = float(alpha) * tl0.clamp(float(clip), 0.0)
+    tl1 = tau_log_policy(g1, tau)
+    vsoft = ((tl1 / float(tau)).exp() * (g1 - tl1)).sum(-1)
+    return R.to(dt) + bonus + Gamma.to(dt) * vsoft, bonus, vsoft
+
+
+def munchausen_loss(q_t: torch.Tensor, q_target_t: torch.Tensor, q_target_next: torch.Tensor, A: torch.Tensor,
+                    R: torch.Tensor, Gamma: torch.Tensor, w: torch.Tensor = None, alpha: float = 0.9,
+                    tau: float = 0.03, clip: float = -1.0, loss: str = "huber",
+                    kappa: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Munchausen-DQN loss (Vieillard, Pietquin, Geist 2020) of the scalar head: ``q_t`` [B, A] the online
+    net at S_t, ``q_target_t`` / ``q_target_next`` the target net at S_t / S_t+n.  delta = T - q_t[a] with T
+    of :func:`munchausen_targets` (no online argmax: this is not double DQN), the Huber or 0.5 delta^2 loss
+    weighted by ``w``; the gradient flows through q_t[a] only.  Returns (scalar loss, |delta| per sample) as
+    :func:`ddqn_loss`; computes in ``q_t``'s dtype (fp64 inputs: the tests' reference)."""
+    dt = q_t.dtype
+    with torch.no_grad():
+        T = munchausen_targets(q_target_t.to(dt), q_target_next.to(dt), A, R, Gamma, alpha, tau, clip)[0]
+    q_sa = q_t.gather(1, A.long().view(-1, 1)).squeeze(1)
+    delta = T - q_sa
+    per = huber(delta, kappa) if loss == "huber" else 0.5 * delta * delta
+    if w is not None:
+        per = per * w.to(dt)
+    return per.mean(), delta.detach().abs()
+
+
 def ddqn_loss(q_online_t: torch.Tensor, q_online_next: torch.Tensor,
               q_target_next: torch.Tensor, A: torch.Tensor, R: torch.Tensor,
               Gamma: torch.Tensor, weights: torch.Tensor = None, loss: str = "huber",

@@ -20,7 +20,7 @@ import torch
 from ..config import ApexConfig
 from ..models.dueling import build_network
 from ..utils.checkpoint import adopt_obs_scale, check_dist_head, check_noisy, load_checkpoint, save_checkpoint
-from .losses import c51_loss, ddqn_loss, quantile_huber_loss
+from .losses import c51_loss, ddqn_loss, munchausen_loss, munchausen_targets, quantile_huber_loss
 from .schedules import lr_scheduled, rt_lr
 
 
@@ -85,6 +85,16 @@ class TorchLearner:
                 p_next_target = self.Q_target.log_probs(S_tpn).exp()
             return c51_loss(self.Q.log_probs(S_t), q_next_online, p_next_target, A, R, G,
                             self.rt.v_min, self.rt.v_max, w)
+        if self.rt.munchausen:
+            # Munchausen-DQN: the target net at S_t and S_t+n, no online argmax (learner/losses.py)
+            with torch.no_grad():
+                g0 = self.Q_target(S_t)[2]
+                g1 = self.Q_target(S_tpn)[2]
+                kw = self.cfg.munchausen_kw()
+                _, bonus, vsoft = munchausen_targets(g0, g1, A, R, G, **kw)
+                self._mdqn = (float(bonus.mean()), float(vsoft.mean()))
+            return munchausen_loss(self.Q(S_t)[2], g0, g1, A, R, G, w, loss=self.rt.loss,
+                                   kappa=self.rt.huber_delta, **kw)
         with torch.no_grad():
             q_next_online = self.Q(S_tpn)[2]
             q_next_target = self.Q_target(S_tpn)[2]
@@ -125,7 +135,15 @@ class TorchLearner:
         self.set_update_noise()
         loss, td = self.compute_loss_and_priorities(batch)
         gnorm = self.update_Q(loss)
-        return {"loss": float(loss.detach()), "td_abs": td.cpu().numpy(), "grad_norm": gnorm}
+        out = {"loss": float(loss.detach()), "td_abs": td.cpu().numpy(), "grad_norm": gnorm}
+        out.update(self.last_metrics())
+        return out
+
+    def last_metrics(self) -> Dict[str, float]:
+        """Munchausen target: the last update's mean bonus and mean soft value (else empty)."""
+        if not self.rt.munchausen or getattr(self, "_mdqn", None) is None:
+            return {}
+        return {"munchausen_bonus_mean": self._mdqn[0], "soft_value_mean": self._mdqn[1]}
 
     # --------------------------------------------------------- params
     def state_dict_for_actors(self) -> Dict[str, torch.Tensor]:

@@ -74,6 +74,15 @@ class QRArgs(ctypes.Structure):
                 ("dhead", c_p), ("zero_ptr", c_p), ("zero_n", c_i), ("lo", HeadLo), ("isn", IsNorm)]
 
 
+class MdqnArgs(ctypes.Structure):
+    """Arguments of the Munchausen head kernel (``MdqnArgs``, csrc/mdqn_head.hip)."""
+    _fields_ = [("Hon", c_p), ("Htg", c_p), ("Pon", HeadParams), ("Ptg", HeadParams), ("act", c_p), ("rew", c_p),
+                ("gam", c_p), ("isw", c_p), ("B", c_i), ("A", c_i), ("huber", c_i), ("hidden", c_i), ("kappa", c_f),
+                ("alpha", c_f), ("tau", c_f), ("clip", c_f), ("grad_scale", c_f), ("td_abs", c_p), ("loss", c_p),
+                ("q_out", c_p), ("aux", c_p), ("dH", c_p), ("dhead", c_p), ("zero_ptr", c_p), ("zero_n", c_i),
+                ("lo", HeadLo), ("isn", IsNorm), ("hp", HeadPart)]
+
+
 class NoisyNet(ctypes.Structure):
     """One network of a noisy compose launch (``NoisyNet``, csrc/noisy.hip)."""
     _fields_ = [("p", c_p), ("e32", c_p), ("ehi", c_p), ("elo", c_p), ("fc32", c_p), ("xi", c_p)]
@@ -184,7 +193,7 @@ _SIGS = {
     "apex_replay_insert": ([TreeDesc, RecordDesc, c_i64, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_p],
                            c_i),
     "apex_tree_sample": ([TreeDesc, RecordDesc, c_i, c_u64, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                          c_p, c_p, c_p, c_i, c_i, c_u64, c_p, c_i64, BetaSched, c_p], c_i),
+                          c_p, c_p, c_p, c_p, c_i, c_i, c_u64, c_p, c_i64, BetaSched, c_p], c_i),
     "apex_tree_rebuild": ([TreeDesc, c_p], c_i),
     "apex_gather_frames": ([c_p, c_p, c_i, c_i64, c_i64, c_p, c_p], c_i),
     "apex_debug_bounds_enabled": ([], c_i),
@@ -202,7 +211,7 @@ _SIGS = {
                         c_p, c_p, c_p, c_p, c_p, c_i, c_i, HeadLo, HeadPart, C2dPack, IsNorm, c_p], c_i),
     "apex_rmsprop_sample": ([c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i, c_f, c_f, c_f, c_f, c_i, c_p,
                              TreeDesc, RecordDesc, c_i, c_u64, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                             c_p, c_p, c_i, c_i, c_u64, c_p, c_i64, BetaSched, c_p, c_p, c_i, c_i, CfFragOut, c_p,
+                             c_p, c_p, c_p, c_i, c_i, c_u64, c_p, c_i64, BetaSched, c_p, c_p, c_i, c_i, CfFragOut, c_p,
                              c_p, c_i64, OptSched, c_p], c_i),
     "apex_head_wgrad_prio": ([c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, TreeDesc, c_p, c_p, c_p, c_p, c_f, c_f,
                               c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_i64, c_i, c_p, c_p], c_i),
@@ -212,6 +221,7 @@ _SIGS = {
     "apex_c51_head": ([C51Args, c_p], c_i),
     "apex_c51_actor_head": ([c_p, HeadParams, c_i, c_i, c_i, c_f, c_f, c_p, c_u64, c_p, c_p, c_p, c_i, c_p, c_p], c_i),
     "apex_qr_head": ([QRArgs, c_p], c_i),
+    "apex_mdqn_head": ([MdqnArgs, c_p], c_i),
     "apex_qr_actor_head": ([c_p, HeadParams, c_i, c_i, c_i, c_p, c_u64, c_p, c_p, c_p, c_i, c_p, c_p], c_i),
     "apex_actor_head": ([c_p, HeadParams, c_i, c_i, c_p, c_u64, c_p, c_p, c_p, c_i, c_p, c_p], c_i),
     "apex_conv1_s2d_fwd": ([Conv1S2DDesc, c_i, c_p], c_i),
@@ -245,7 +255,7 @@ def _declare(lib: ctypes.CDLL) -> None:
     conv_sigs.declare(lib)
 
 
-ABI_VERSION = 12    # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
+ABI_VERSION = 13    # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
 
 
 def load(build_if_missing: bool = True) -> Optional[ctypes.CDLL]:

@@ -42,6 +42,11 @@ def split_into(v: torch.Tensor, hi: torch.Tensor, lo: Optional[torch.Tensor]) ->
         lo.copy_((v.reshape(hi.shape).float() - hi.float()))
 
 
+def _sample5(sample):
+    """``(replay, B, out, nxt2, obs2)`` of an optimizer call's ``sample`` (``obs2`` optional)."""
+    return tuple(sample) + (None,) * (5 - len(sample))
+
+
 class TorchBackend:
     name = "torch"
 
@@ -174,6 +179,72 @@ class TorchBackend:
         split_into(dh, dH, None if lo is None else lo[2])
         if q_out is not None:
             q_out.copy_(q_t)
+        if zero is not None:
+            zero.zero_()
+        self._is_norm_stats(isn, w)
+
+    def mdqn_head(self, Hon, Htg, Pon: Dict[str, torch.Tensor], Ptg: Dict[str, torch.Tensor], act, rew, gam, isw,
+                  huber: bool, kappa: float, alpha: float, tau: float, clip: float, grad_scale: float, td_abs, loss,
+                  dH, dhead, q_out=None, aux=None, zero: Optional[torch.Tensor] = None, lo=None, isn=None):
+        """The scalar head with the Munchausen-DQN target (csrc/mdqn_head.hip; learner/losses.py
+        munchausen_loss is the definition).  ``Hon`` [B, 2 HS]: the online net at S_t; ``Htg`` [2B, 2 HS]:
+        the target net, rows [0, B) at S_t+n (g1) and rows [B, 2B) at S_t (g0).  T = rew + alpha clamp(tau ln
+        pi(a | g0), clip, 0) + gam (max g1 + tau ln sum exp((g1 - max g1) / tau)), delta = T - q_on[a]; loss,
+        priority, ``dhead`` and ``dH`` as :meth:`head`.  ``aux`` [B, 2] fp32 (optional) receives (bonus, soft
+        value) per row; ``lo``, ``zero`` and ``isn`` as :meth:`head`."""
+        B = act.shape[0]
+        A = Pon["wa"].shape[0]
+        assert Hon.shape[0] == B and Htg.shape[0] == 2 * B
+        dt = Hon.dtype if Hon.dtype == torch.float64 else torch.float32     # (fp64 inputs: the tests' reference)
+
+        def joined(hi, l):
+            return hi.to(dt) if l is None else hi.to(dt) + l.to(dt)
+
+        Hon = joined(Hon, None if lo is None else lo[0])
+        Htg = joined(Htg, None if lo is None else lo[1])
+        HS = Pon["wv"].numel()
+
+        def q_of(h, P):
+            v = h[:, :HS] @ P["wv"].to(dt) + P["bv"].to(dt)
+            a = h[:, HS:] @ P["wa"].to(dt).t() + P["ba"].to(dt)
+            return v[:, None] + a - a.mean(1, keepdim=True)
+
+        q_t = q_of(Hon, Pon)
+        g1 = q_of(Htg[:B], Ptg)
+        g0 = q_of(Htg[B:], Ptg)
+        tau, alpha, clip = float(tau), float(alpha), float(clip)
+        c0 = g0 - g0.max(1, keepdim=True).values
+        tl0 = c0.gather(1, act.long()[:, None]).squeeze(1) - tau * torch.log(torch.exp(c0 / tau).sum(1))
+        bonus = alpha * tl0.clamp(clip, 0.0)
+        m1 = g1.max(1).values
+        vsoft = m1 + tau * torch.log(torch.exp((g1 - m1[:, None]) / tau).sum(1))
+        G = rew.to(dt) + bonus + gam.to(dt) * vsoft
+        q_sa = q_t.gather(1, act.long()[:, None]).squeeze(1)
+        delta = G - q_sa
+        ad = delta.abs()
+        if huber:
+            lval = torch.where(ad <= kappa, 0.5 * delta * delta, kappa * (ad - 0.5 * kappa))
+            dl = torch.where(ad <= kappa, delta, kappa * delta.sign())
+        else:
+            lval = 0.5 * delta * delta
+            dl = delta
+        w = isw.to(dt) if isw is not None else torch.ones_like(delta)
+        dq = -w * dl * grad_scale
+        td_abs.copy_(ad)
+        loss.copy_(w * lval)
+        onehot = torch.nn.functional.one_hot(act.long(), A).to(dt)
+        dadv = dq[:, None] * (onehot - 1.0 / A)
+        dhead[:, 0] = dq
+        dhead[:, 1:] = dadv
+        dv = dq[:, None] * Pon["wv"].to(dt)[None, :]
+        da = dadv @ Pon["wa"].to(dt)
+        dh = torch.cat([dv, da], 1) * (Hon > 0).to(dt)
+        split_into(dh, dH, None if lo is None else lo[2])
+        if q_out is not None:
+            q_out.copy_(q_t)
+        if aux is not None:
+            aux[:, 0] = bonus
+            aux[:, 1] = vsoft
         if zero is not None:
             zero.zero_()
         self._is_norm_stats(isn, w)
@@ -465,8 +536,9 @@ class TorchBackend:
     # ----------------------------------------------------------- optimizer
     def optimizer(self, p32, g32, v, m, pbf, lr, alpha, eps, clip, centered, partials, norm_out, norm_total=None,
                   sample=None, pb_lo=None, wnorm=None, frag_out=None, segs=None, norm_prefix=None, opt=None):
-        """``sample = (replay, B, out, nxt2)``: also draw the next
-        batch after the update (the HIP backend fuses it into the optimizer launch).
+        """``sample = (replay, B, out, nxt2[, obs2])``: also draw the next
+        batch after the update (the HIP backend fuses it into the optimizer launch; ``obs2``: the
+        sampler's second copy of the S_t slots, the Munchausen row plan).
         ``pb_lo``: split mode, the lo plane of the bf16 copy.  ``wnorm = (stats, n,
         stride)``: batch-max IS normalisation, the gradient is divided by the largest of
         the n per-rank maxima ``stats[k * stride]`` (csrc/rmsprop_common.h is_grad_scale).
@@ -481,8 +553,8 @@ class TorchBackend:
         self._optimizer(p32, g32, v, m, pbf, lr, alpha, eps, clip, centered, norm_out, pb_lo, wnorm, norm_total,
                         segs, norm_prefix, opt)
         if sample is not None:
-            rp, B, out, nxt2 = sample
-            rp.sample(B, out=out, nxt2=nxt2)
+            rp, B, out, nxt2, obs2 = _sample5(sample)
+            rp.sample(B, out=out, nxt2=nxt2, **({} if obs2 is None else {"obs2": obs2}))
 
     def _optimizer(self, p32, g32, v, m, pbf, lr, alpha, eps, clip, centered, norm_out, pb_lo=None, wnorm=None,
                    norm_total=None, segs=None, norm_prefix=None, opt=None):
@@ -598,7 +670,7 @@ class HipBackend(TorchBackend):
         self.lib = _lib.require_kernels()
         self.native_conv = native_conv and hasattr(self.lib, "apex_conv_fwd")
         self.kernels = ["replay", "head", "head_wgrad", "optimizer", "actor_head", "c51_head", "c51_actor_head", "qr_head",
-                        "qr_actor_head", "noisy_compose", "noisy_sigma_grad"]
+                        "qr_actor_head", "noisy_compose", "noisy_sigma_grad", "mdqn_head"]
         if self.native_conv:
             self.kernels += ["conv_fwd", "conv_dgrad", "conv_wgrad", "fc_fwd", "fc_bwd"]
         self.ws = C.Workspace()
@@ -814,6 +886,30 @@ class HipBackend(TorchBackend):
             isn_s.valid_count = _lib.ptr(isn[2]) if len(isn) > 2 else None
         _lib.check(self.lib.apex_ddqn_head(*args, hl, hp, pk, isn_s, _lib.stream_ptr()), "ddqn_head")
 
+    def mdqn_head(self, Hon, Htg, Pon, Ptg, act, rew, gam, isw, huber, kappa, alpha, tau, clip, grad_scale, td_abs,
+                  loss, dH, dhead, q_out=None, aux=None, zero=None, lo=None, isn=None):
+        """csrc/mdqn_head.hip ``mdqn_head_kernel`` (reads h: with the weight set switched at row B the fc
+        forward never defers its epilogue)."""
+        assert getattr(self, "_fc_part", None) is None, "the Munchausen head reads h: fc epilogue deferred"
+        a = _lib.MdqnArgs()
+        a.Hon, a.Htg, a.Pon, a.Ptg = Hon.data_ptr(), Htg.data_ptr(), self._hp(Pon), self._hp(Ptg)
+        a.act, a.rew, a.gam, a.isw = act.data_ptr(), rew.data_ptr(), gam.data_ptr(), _lib.ptr(isw)
+        a.B, a.A, a.huber, a.hidden = act.shape[0], Pon["wa"].shape[0], int(huber), Pon["wv"].numel()
+        a.kappa, a.alpha, a.tau, a.clip, a.grad_scale = float(kappa), float(alpha), float(tau), float(clip), \
+            float(grad_scale)
+        a.td_abs, a.loss, a.q_out, a.aux = td_abs.data_ptr(), loss.data_ptr(), _lib.ptr(q_out), _lib.ptr(aux)
+        a.dH, a.dhead = dH.data_ptr(), dhead.data_ptr()
+        a.zero_ptr, a.zero_n = _lib.ptr(zero), 0 if zero is None else zero.numel()
+        a.lo = _lib.head_lo(*(lo if lo is not None else (None, None, None)))
+        if isn is not None:
+            a.isn.wscale, a.isn.out = _lib.ptr(isn[0]), _lib.ptr(isn[1])
+            a.isn.valid_count = _lib.ptr(isn[2]) if len(isn) > 2 else None
+        assert Hon.shape[0] == a.B and Htg.shape[0] == 2 * a.B and Hon.is_contiguous() and Htg.is_contiguous()
+        assert dhead.shape == (a.B, a.A + 1) and dhead.is_contiguous() and dH.is_contiguous()
+        assert aux is None or (aux.shape == (a.B, 2) and aux.dtype == torch.float32 and aux.is_contiguous())
+        assert q_out is None or (q_out.shape == (a.B, a.A) and q_out.is_contiguous())
+        _lib.check(self.lib.apex_mdqn_head(a, _lib.stream_ptr()), "mdqn_head")
+
     def c51_head(self, Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, v_min, v_max, grad_scale, td_abs, loss,
                  dH, dhead, q_out=None, zero=None, lo=None, isn=None):
         """csrc/c51_head.hip ``c51_head_kernel`` (reads h: the fc epilogue is not deferred)."""
@@ -944,7 +1040,7 @@ class HipBackend(TorchBackend):
             raise ValueError("frag_out needs the fused optimizer + sample launch (a HIP replay)")
         if sample is not None and sample[0].use_hip:
             # the next batch's draw rides in the optimizer launch (csrc/sumtree.hip: rmsprop_sample_kernel)
-            rp, B, out, nxt2 = sample
+            rp, B, out, nxt2, obs2 = _sample5(sample)
             if norm_total is None:
                 _lib.check(self.lib.apex_grad_sqnorm_partials(g32.data_ptr(), n, partials.data_ptr(), st), "sqnorm")
                 part, npart = partials, partials.numel()
@@ -955,7 +1051,8 @@ class HipBackend(TorchBackend):
             _lib.check(self.lib.apex_rmsprop_sample(
                 p32.data_ptr(), g32.data_ptr(), v.data_ptr(), m.data_ptr(), pbf.data_ptr(), n, part.data_ptr(), npart,
                 float(lr), float(alpha), float(eps), float(clip), int(centered), norm_out.data_ptr(),
-                *rp.sample_launch_args(B, out, nxt2), lo, *wn, frag_out if frag_out is not None else _lib.CfFragOut(),
+                *rp.sample_launch_args(B, out, nxt2, obs2), lo, *wn,
+                frag_out if frag_out is not None else _lib.CfFragOut(),
                 segp, _lib.ptr(norm_prefix), 0 if norm_prefix is None else norm_prefix.numel(), osd, st),
                 "rmsprop_sample")
             return frag_out is not None
@@ -964,8 +1061,8 @@ class HipBackend(TorchBackend):
         if sample is not None:
             self.optimizer(p32, g32, v, m, pbf, lr, alpha, eps, clip, centered, partials, norm_out, norm_total,
                            pb_lo=pb_lo, wnorm=wnorm, opt=opt)
-            rp, B, out, nxt2 = sample
-            rp.sample(B, out=out, nxt2=nxt2)
+            rp, B, out, nxt2, obs2 = _sample5(sample)
+            rp.sample(B, out=out, nxt2=nxt2, **({} if obs2 is None else {"obs2": obs2}))
             return
         if norm_total is not None:   # squared norm already summed by the gradient producers
             part, npart = norm_total if isinstance(norm_total, tuple) else (norm_total, 1)

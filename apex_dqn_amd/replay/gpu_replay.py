@@ -478,13 +478,14 @@ class GpuReplayShard:
 
     # ------------------------------------------------------------- sampling
     def sample(self, B: int, out: Optional[Dict[str, torch.Tensor]] = None,
-               nxt2: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+               nxt2: Optional[torch.Tensor] = None, obs2: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """Stratified proportional sample of B slots; IS weights max-normalised
         (globally over the shards once :meth:`enable_sharding` ran: then rows whose
         global draw fell in another shard carry weight 0 and generation -1).
 
         ``out`` (preallocated tensors) makes the call graph-capturable; ``nxt2``
-        receives a second copy of the S_{t+n} frame slots (target-network rows).
+        receives a second copy of the S_{t+n} frame slots (target-network rows), ``obs2``
+        one of the S_t frame slots (the Munchausen step's target rows at S_t).
         """
         d = self.device
         if out is None:
@@ -492,7 +493,7 @@ class GpuReplayShard:
         if self.sharded and B < 3:
             raise ValueError("sharded sampling needs B >= 3")
         if self.use_hip:
-            _lib.check(self.lib.apex_tree_sample(*self.sample_launch_args(B, out, nxt2), self._stream()),
+            _lib.check(self.lib.apex_tree_sample(*self.sample_launch_args(B, out, nxt2, obs2), self._stream()),
                        "tree_sample")
             return out
         leaf = self.leaf.double().cpu()
@@ -539,16 +540,19 @@ class GpuReplayShard:
             out["wscale"].fill_(wscale)
         if nxt2 is not None:
             nxt2.copy_(out["nxt"])
+        if obs2 is not None:
+            obs2.copy_(out["obs"])
         return out
 
-    def sample_launch_args(self, B: int, out: Dict[str, torch.Tensor], nxt2: Optional[torch.Tensor] = None) -> tuple:
+    def sample_launch_args(self, B: int, out: Dict[str, torch.Tensor], nxt2: Optional[torch.Tensor] = None,
+                           obs2: Optional[torch.Tensor] = None) -> tuple:
         """The tree_sample arguments (TreeDesc .. shard_seed) of :meth:`sample`, for
         kernels that draw the batch inside another launch (``apex_rmsprop_sample``)."""
         return (self.tree_desc(), self.record_desc(), B, self.seed, self.ctr.data_ptr(), self.beta,
                 out["idx"].data_ptr(), out["weights"].data_ptr(), out["gen"].data_ptr(), out["obs"].data_ptr(),
                 out["nxt"].data_ptr(), out["act"].data_ptr(), out["rew"].data_ptr(), out["gam"].data_ptr(),
-                _lib.ptr(nxt2), _lib.ptr(self.shard_stats), self.shard_rank, self.shard_world, self.shard_seed,
-                _lib.ptr(out.get("wscale")), int(self.shard_mcap), self._beta_sched_arg())
+                _lib.ptr(nxt2), _lib.ptr(obs2), _lib.ptr(self.shard_stats), self.shard_rank, self.shard_world,
+                self.shard_seed, _lib.ptr(out.get("wscale")), int(self.shard_mcap), self._beta_sched_arg())
 
     def alloc_sample_buffers(self, B: int) -> Dict[str, torch.Tensor]:
         d = self.device
