@@ -58,6 +58,7 @@ from .nstep import make_nstep_builder
 
 class GpuActorGroup:
     noisy = False     # (the groups of learners without noisy layers never set it)
+    implicit = False  # (nor the implicit quantile head's)
 
     def __init__(self, cfg, learner, replay, env, num_envs: int, global_offset: int = 0,
                  total_actors: Optional[int] = None, seed: int = 0, rank: int = 0, world: int = 1,
@@ -111,6 +112,13 @@ class GpuActorGroup:
         # buffers for its effective fc / head parameters, composed on the actor stream inside the
         # (captured) inference with stream s = 2 + group and the draw index ctr // resample -- ctr
         # is the epsilon draw's call counter, so one draw serves all envs of a batched call
+        # implicit quantile head (learner/iqn.py): the slot above carries wtau / btau; K fractions per env row
+        # and inference call, drawn in the head kernel with stream s = 2 + group and the call counter ctr
+        self.implicit = bool(getattr(learner, "implicit", False))
+        if self.implicit:
+            from ..learner.iqn import iqn_seed
+            from ..learner.noisy import actor_stream
+            self._iqn = (iqn_seed(cfg.Runtime.seed), actor_stream(group), int(cfg.Runtime.iqn_actor_samples))
         self.noisy = bool(getattr(learner, "noisy", False))
         if self.noisy:
             from ..learner.noisy import NoisyPlan, actor_stream, noise_seed
@@ -307,7 +315,12 @@ class GpuActorGroup:
         distributional learner (``learner.N`` atoms) the expected q of its C51 head or the mean of
         its quantile head (``Runtime.dist_head``)."""
         n = int(getattr(self.learner, "N", 1))
-        if n >= 2 and self.cfg.quantile:
+        if self.implicit:
+            seed_q, stream, K = self._iqn
+            emb = {"wtau": self.P["wtau"], "btau": self.P["btau"]}
+            self.ops.iqn_actor_head(h, heads, emb, self.eps, self.ctr, self.seed, seed_q, self.ctr, stream, K, False,
+                                    self.q, self.act, H_lo=h_lo)
+        elif n >= 2 and self.cfg.quantile:
             self.ops.qr_actor_head(h, heads, self.eps, self.ctr, self.seed, n, self.q, self.act, H_lo=h_lo)
         elif n >= 2:
             rt = self.cfg.Runtime

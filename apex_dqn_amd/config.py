@@ -108,6 +108,11 @@ class RuntimeConf:
     # loss with kappa = huber_delta (> 0; loss does not apply), no support (v_min / v_max are ignored), the same
     # priority and the same refusals (learner/losses.py quantile_huber_loss)
     dist_head: str = "categorical"
+    # "implicit" (IQN, csrc/iqn_head.hip): num_atoms = N tau samples per state in the loss (N and N' of the paper),
+    # the head at the scalar head's shapes gated by a 64-cosine embedding of tau after the fc layer; the quantile
+    # head's loss with sampled fractions (learner/losses.py iqn_loss, learner/iqn.py the draws' mirror).
+    # iqn_actor_samples = K: the samples behind the actors' and the greedy evaluation's q
+    iqn_actor_samples: int = 32
     # factorised NoisyNet fc and head layers (Fortunato et al. 2018; learner/noisy.py, csrc/noisy.hip): the two
     # stream layers and the two heads carry W = mu + sigma * (xi_out (x) xi_in), one draw per update for the online
     # net and one for the target net, one per noisy_actor_resample batched inference calls for an actor group;
@@ -309,14 +314,24 @@ class ApexConfig:
             raise ValueError(f"Runtime.num_atoms must be 1 or an integer in [2, 64] (one lane per atom), got {na!r}")
         if not float(rt.v_min) < float(rt.v_max):
             raise ValueError(f"Runtime.v_min must be below Runtime.v_max, got {rt.v_min} / {rt.v_max}")
-        if rt.dist_head not in ("categorical", "quantile"):
-            raise ValueError(f"Runtime.dist_head must be 'categorical' or 'quantile', got {rt.dist_head!r}")
+        if rt.dist_head not in ("categorical", "quantile", "implicit"):
+            raise ValueError(f"Runtime.dist_head must be 'categorical', 'quantile' or 'implicit', got {rt.dist_head!r}")
+        ks = rt.iqn_actor_samples
+        if isinstance(ks, bool) or not isinstance(ks, int) or not 1 <= ks <= 64:
+            raise ValueError(f"Runtime.iqn_actor_samples must be an integer in [1, 64] (one lane per sample), got {ks!r}")
         if na == 1 and rt.dist_head != "categorical":
             raise ValueError(f"Runtime.dist_head={rt.dist_head!r} needs Runtime.num_atoms >= 2 (the scalar head has "
                              f"no distribution)")
-        if na >= 2 and rt.dist_head == "quantile" and not float(rt.huber_delta) > 0.0:
-            raise ValueError(f"Runtime.dist_head='quantile' needs Runtime.huber_delta > 0 (the quantile Huber loss's "
-                             f"kappa), got {rt.huber_delta}")
+        if na >= 2 and rt.dist_head in ("quantile", "implicit") and not float(rt.huber_delta) > 0.0:
+            raise ValueError(f"Runtime.dist_head={rt.dist_head!r} needs Runtime.huber_delta > 0 (the quantile Huber "
+                             f"loss's kappa), got {rt.huber_delta}")
+        if na >= 2 and rt.dist_head == "implicit":
+            if rt.noisy is True:
+                raise ValueError("Runtime.noisy with Runtime.dist_head='implicit' is not built: the noisy layers "
+                                 "compose the categorical and quantile heads only")
+            if rt.munchausen is True:
+                raise ValueError("Runtime.munchausen with Runtime.dist_head='implicit' (M-IQN) is not built: the "
+                                 "Munchausen target is the scalar head's")
         if na >= 2:
             if net not in ("nature64", "nature32", "mlp"):
                 raise ValueError(f"Runtime.num_atoms={na} needs network nature64, nature32 or mlp, got {net!r}")
@@ -378,6 +393,8 @@ class ApexConfig:
         rt = self.Runtime
         kw = dict(num_atoms=int(rt.num_atoms), v_min=float(rt.v_min), v_max=float(rt.v_max),
                   dist_head=str(rt.dist_head))
+        if self.implicit:  # (only then: the other heads' call is the one of before)
+            kw.update(iqn_actor_samples=int(rt.iqn_actor_samples))
         if rt.noisy:       # (only then: the non-noisy call is the one of before)
             kw.update(noisy=True, noisy_sigma0=float(rt.noisy_sigma0))
         return kw
@@ -391,6 +408,11 @@ class ApexConfig:
     def quantile(self) -> bool:
         """The distributional head is the quantile-regression one (Runtime.dist_head)."""
         return self.distributional and self.Runtime.dist_head == "quantile"
+
+    @property
+    def implicit(self) -> bool:
+        """The distributional head is the implicit quantile one (Runtime.dist_head)."""
+        return self.distributional and self.Runtime.dist_head == "implicit"
 
     @property
     def env_backend(self) -> str:

@@ -18,6 +18,7 @@
 #include "igemm_wgrad.h"
 #include "rmsprop_common.h"
 #include "pack_rows.h"
+#include "iqn_wgrad.h"
 
 // Bounds-checking debug build (SURVEY §5.2 "race / bounds detection"): built as a
 // separate library with -DAPEX_DEBUG_BOUNDS and selected by APEX_DEBUG_BOUNDS=1.
@@ -607,6 +608,20 @@ __global__ void __launch_bounds__(512) head_wgrad_prio_kernel(HeadWgArgs hw, Tre
   else head_wgrad_body(hw, b / nch, b - (b / nch) * nch);
 }
 
+// The implicit quantile head's weight gradients (csrc/iqn_wgrad.h) + priority write-back in one launch, in the place
+// of head_wgrad_prio_kernel: block 0 the single-block tree update (`prio`; without it the blocks start at 0).
+__global__ void __launch_bounds__(512) iqn_wgrad_prio_kernel(IqnWgArgs hw, TreeUpdArgs tu, int prio) {
+  if (prio && blockIdx.x == 0) {
+    tree_update_block(tu);
+    return;
+  }
+  iqn_wgrad_body(hw, (int)blockIdx.x - prio);
+}
+
+__global__ void __launch_bounds__(256) iqn_wgrad_reduce_kernel(IqnWgArgs hw) {
+  iqn_wgrad_reduce_body(hw, blockIdx.x * 256 + threadIdx.x);
+}
+
 // fc weight gradient + head weight gradient + priority write-back in ONE launch
 // (all three only need the head kernel's outputs).  Block 0: the single-block tree
 // update (the latency-bound long pole, dispatched first); blocks 1..nhw: head
@@ -915,6 +930,32 @@ APEX_EXPORT int apex_head_wgrad_prio(const bf16_t* Hon, const float* dhead, int 
   head_wgrad_prio_kernel<<<1 + nhw + npk, 512, 0, st>>>(
       HeadWgArgs{Hon, dhead, B, A, gwv, gbv, gwa, gba, hidden, Hon_lo, nv, norm_part},
       TreeUpdArgs{t, idx, td, gen_expect, gen, ctr_to_bump, alpha, eps, B, tree_kfirst(t), stats_out}, pk, nhw, npk);
+  APEX_CHECK_LAUNCH();
+}
+
+APEX_EXPORT int apex_iqn_wgrad_part_floats() { return IQN_WG_S * (2 * DIST_HS * IQN_E + 2 * DIST_HS); }
+
+// without the priority write-back (tests, benchmarks)
+APEX_EXPORT int apex_iqn_wgrad(IqnWgArgs h, hipStream_t st) {
+  if (!iqn_wgrad_args_ok(h)) return (int)hipErrorInvalidValue;
+  iqn_wgrad_prio_kernel<<<iqn_wgrad_blocks(h.A), 512, 0, st>>>(h, TreeUpdArgs{}, 0);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  iqn_wgrad_reduce_kernel<<<(2 * DIST_HS * IQN_E + 2 * DIST_HS + 255) / 256, 256, 0, st>>>(h);
+  APEX_CHECK_LAUNCH();
+}
+
+APEX_EXPORT int apex_iqn_wgrad_prio(IqnWgArgs h, TreeDesc t, const int64_t* idx, const float* td,
+                                    const int32_t* gen_expect, const int32_t* gen, float alpha, float eps,
+                                    uint64_t* ctr_to_bump, double* stats_out, hipStream_t st) {
+  // the single-block tree update holds TU_MAXR items per thread
+  if (!iqn_wgrad_args_ok(h) || h.B > 1024 || h.B > TU_MAXR * 512 || idx == nullptr || td == nullptr)
+    return (int)hipErrorInvalidValue;
+  iqn_wgrad_prio_kernel<<<1 + iqn_wgrad_blocks(h.A), 512, 0, st>>>(
+      h, TreeUpdArgs{t, idx, td, gen_expect, gen, ctr_to_bump, alpha, eps, h.B, tree_kfirst(t), stats_out}, 1);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  iqn_wgrad_reduce_kernel<<<(2 * DIST_HS * IQN_E + 2 * DIST_HS + 255) / 256, 256, 0, st>>>(h);
   APEX_CHECK_LAUNCH();
 }
 

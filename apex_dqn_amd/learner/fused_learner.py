@@ -111,6 +111,10 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         self.N = int(self.rt.num_atoms)
         # its kind: categorical (csrc/c51_head.hip) or quantile regression (csrc/qr_head.hip)
         self.quantile = cfg.quantile
+        # implicit quantile head (csrc/iqn_head.hip): N tau samples per state in the loss, the head weights at
+        # the scalar head's shapes (Nh = 1) and the embedding wtau / btau behind the fc layer in the flat layout
+        self.implicit = cfg.implicit
+        self.Nh = 1 if self.implicit else self.N
         if self.N >= 2 and self._dp:
             raise ValueError(f"Runtime.num_atoms={self.N}: the distributional head runs on a single rank, not in "
                              f"the data-parallel step (world > 1, Runtime.force_dp, the emulated world)")
@@ -153,7 +157,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         # (the torch backend emulates the split kernel's contract: ops.conv12_fwd)
         self._c12 = self.split or (backend == "hip" and self.ops._conv12_native() and SW.conv12_bf16)
         d = self.device
-        self.layout = FlatLayout(nature_segments(self.C, self.A, 64, self.N, noisy=self.noisy))
+        self.layout = FlatLayout(nature_segments(self.C, self.A, 64, self.Nh, noisy=self.noisy, implicit=self.implicit))
         n = self.layout.numel
         self.p32 = torch.zeros(n, dtype=torch.float32, device=d)
         # bf16 compute copies [hi | lo] of the online / target parameters (lo: split mode)
@@ -234,7 +238,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         # With the sigma-gradient blocks as one more producer the step measured the same within
         # its spread, profiles/pr11_ab_noisy_sigma_norm_partials_rejected.txt)
         self._fuse_norm = not self._dp and self.ops.name == "hip" and getattr(self.ops, "native_conv", False) \
-            and not self.noisy
+            and not self.noisy and not self.implicit
         # DP: the rank-local replay shards form ONE prioritized replay (replay/gpu_replay.py
         # enable_sharding): every step all-gathers the shards' (sum p^alpha, min p^alpha)
         # right after the priority write-back and the next batch is one global draw,
@@ -450,7 +454,13 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         self.gnorm = torch.zeros(1, dtype=torch.float32, device=d)
         # head-gradient region (zeroed by the head kernel, accumulated by head_wgrad)
         o0 = self.layout.offsets["wv"]
-        o1 = self.layout.offsets["ba"] + self.A * self.N
+        o1 = self.layout.offsets["ba"] + self.A * self.Nh
+        if self.implicit:
+            # what iqn_head leaves for iqn_wgrad (set 0), the fractions of the last update, the draws' seed
+            from .iqn import iqn_seed
+            self.iqn_ws = self.ops.iqn_workspace(B, self.N, d)
+            self.tau_out = torch.zeros(B, 3, self.N, dtype=torch.float32, device=d)
+            self._seed_q = iqn_seed(self.rt.seed)
         self.g_head_region = self.g32[o0:o1]
         # its share of the producer-summed clip norm: summed by one finalize block (the scalar
         # head's 2.5 K values), or by the wide head weight gradient's own blocks (N >= 2)
@@ -531,6 +541,22 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             self._tgt_packed = True
         self._noisy_compose()
 
+    @staticmethod
+    def _embed(V):
+        return {"wtau": V["wtau"], "btau": V["btau"]}
+
+    def _iqn_weight_grads(self, prio) -> None:
+        """The implicit head's weight-gradient launches in the place of the wide head's: G[wv, bv, wa, ba, wtau,
+        btau] from what iqn_head left with the priority write-back as block 0 of the same launch (it bumps the draw
+        counter: after the head read it) and the small reduce of G[wtau]'s split partials, then the fc weight gradient.  The clip norm is the optimizer's own pass
+        over g32 (as with noisy layers)."""
+        sp, B, G = self.split, self.B, self.G
+        self.ops.iqn_wgrad(self.S["act"], self.iqn_ws, {k: G[k] for k in ("wv", "bv", "wa", "ba", "wtau", "btau")},
+                           prio=prio)
+        self.ops.fc_wgrad(self.dH, self.y3[:B], G["wfc"], G["bfc"],
+                          **self._lo(dh_lo=self.dH_lo, x_lo=sp and self.y3_lo[:B]))
+        self._fc_slots = 0
+
     def _head_params(self, V):
         if self.noisy and (V is self.P or V is self.T):     # the effective head parameters of that net
             V = self.EP if V is self.P else self.ET
@@ -568,6 +594,15 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
                           mk["clip"], 1.0 / (B * self.world), self.td_abs, self.loss_b, self.dH, self.dhead,
                           aux=self.mdqn_aux, zero=self.g_head_region, isn=self._isn(),
                           **self._lo(lo=sp and (self.h_lo[:B], self.h_lo[B:], self.dH_lo)))
+        elif self.implicit:
+            # implicit quantiles: the quantile Huber loss at fractions drawn for this update (the index read on
+            # the device: replay.ctr - upd_base, as the noisy layers' compose reads it)
+            ops.iqn_head(self.h[:2 * B], self.h[2 * B:], self._head_params(self.P), self._head_params(self.T),
+                         self._embed(self.P), self._embed(self.T), S["act"], S["rew"], S["gam"], isw, self.N,
+                         rt.huber_delta, 1.0 / (B * self.world), self._seed_q, self.replay.ctr, self.upd_base,
+                         self.td_abs, self.loss_b, self.dH, self.dhead, self.iqn_ws, tau_out=self.tau_out,
+                         zero=self.g_head_region, isn=self._isn(),
+                         **self._lo(lo=sp and (self.h_lo[:2 * B], self.h_lo[2 * B:], self.dH_lo)))
         elif self.N >= 2 and self.quantile:
             # quantile regression: the quantile Huber loss, kappa = huber_delta (Runtime.loss, v_min / v_max
             # do not apply)
@@ -593,10 +628,13 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         # fc wgrad + head wgrad + priority write-back: one launch on the HIP backend
         # (csrc/sumtree.hip fc_wgrad_head_prio_kernel)
         nrm = (self.norm_part, 0) if self._fuse_norm else None
-        self._fc_slots = ops.fc_head_wgrad(self.dH, self.y3[:B], self.G["wfc"], self.G["bfc"], self.h,
-                                           self.dhead, self.G, prio, norm=nrm,
-                                           **self._lo(dh_lo=self.dH_lo, x_lo=sp and self.y3_lo[:B],
-                                                      Hon_lo=self.h_lo))
+        if self.implicit:
+            self._iqn_weight_grads(prio)
+        else:
+            self._fc_slots = ops.fc_head_wgrad(self.dH, self.y3[:B], self.G["wfc"], self.G["bfc"], self.h,
+                                               self.dhead, self.G, prio, norm=nrm,
+                                               **self._lo(dh_lo=self.dH_lo, x_lo=sp and self.y3_lo[:B],
+                                                          Hon_lo=self.h_lo))
         self._noisy_sigma_grad()
         if self._comm_bf16:
             cut = self.layout.offsets["wfc"]
@@ -732,6 +770,8 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         nrm = (self.norm_part, 0) if self._fuse_norm else None
 
         def fc_wgrad():
+            if self.implicit:
+                return self._iqn_weight_grads(prio)
             self._fc_slots = ops.fc_head_wgrad(self.dH, self.y3[:B], G["wfc"], G["bfc"], self.h, self.dhead, G,
                                                prio, norm=nrm,
                                                **self._lo(dh_lo=self.dH_lo, x_lo=sp and self.y3_lo[:B],

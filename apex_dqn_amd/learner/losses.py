@@ -73,9 +73,11 @@ def c51_loss(logp_t: torch.Tensor, q_online_next: torch.Tensor, p_target_next: t
     return per.mean(), td
 
 
-def quantile_huber_terms(theta: torch.Tensor, T: torch.Tensor, kappa: float) -> Tuple[torch.Tensor, torch.Tensor]:
+def quantile_huber_terms(theta: torch.Tensor, T: torch.Tensor, kappa: float,
+                         tau: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """The quantile Huber loss of N quantiles ``theta`` [B, N] at tau_i = (2 i + 1) / (2 N)
-    against N target samples ``T`` [B, N], u_ij = T_j - theta_i:
+    (or at the given fractions ``tau`` [B, N]: the implicit quantile head's sampled ones)
+    against N target samples ``T`` [B, N'], u_ij = T_j - theta_i:
 
         rho[b, i] = (1/N) sum_j |tau_i - 1{u_ij < 0}| L_kappa(u_ij) / kappa
         c[b, i]   = (1/N) sum_j |tau_i - 1{u_ij < 0}| clamp(u_ij, -kappa, kappa) / kappa
@@ -83,10 +85,13 @@ def quantile_huber_terms(theta: torch.Tensor, T: torch.Tensor, kappa: float) -> 
     so d (sum_i rho) / d theta_i = -c_i.  The j-sums run in increasing j (a fixed-order loop:
     the kernel's order); computes in ``theta``'s dtype.  ``rho`` carries theta's autograd
     graph, ``c`` is detached."""
-    N = theta.shape[-1]
+    N = T.shape[-1]
     dt = theta.dtype
     kappa = float(kappa)
-    tau = ((2.0 * torch.arange(N, dtype=dt, device=theta.device) + 1.0) / (2.0 * N))[None, :]
+    if tau is None:
+        tau = ((2.0 * torch.arange(N, dtype=dt, device=theta.device) + 1.0) / (2.0 * N))[None, :]
+    else:
+        tau = tau.to(dt)
     rho = torch.zeros_like(theta)
     c = torch.zeros_like(theta)
     for j in range(N):        # fixed order: the kernels' sum
@@ -116,6 +121,30 @@ def quantile_huber_loss(theta_t: torch.Tensor, q_online_next: torch.Tensor, thet
         T = R.to(dt)[:, None] + Gamma.to(dt)[:, None] * theta_target_next[ar, a_star].to(dt)
     th = theta_t[ar, A.long().view(-1)]
     per = quantile_huber_terms(th, T, kappa)[0].sum(-1)
+    if weights is not None:
+        per = per * weights.to(dt)
+    with torch.no_grad():
+        td = (T.mean(-1) - th.mean(-1)).abs()
+    return per.mean(), td
+
+
+def iqn_loss(theta_t: torch.Tensor, tau_t: torch.Tensor, q_online_next: torch.Tensor,
+             theta_target_next: torch.Tensor, A: torch.Tensor, R: torch.Tensor, Gamma: torch.Tensor, kappa: float,
+             weights: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Implicit quantile (IQN) double-DQN loss: :func:`quantile_huber_loss` with sampled
+    fractions.  ``theta_t`` [B, A, N]: the online net at S_t evaluated at ``tau_t`` [B, N];
+    ``q_online_next`` [B, A]: its q at S_{t+n} (the mean over its own tau set), which picks a*
+    (first maximum); ``theta_target_next`` [B, A, N']: the target net at S_{t+n} at its own
+    tau set (the fractions of the target samples do not enter the loss).  Returns (mean over
+    the batch of w sum_i rho_i, |mean_j T_j - mean_i theta_i| per sample)."""
+    B = theta_t.shape[0]
+    dt = theta_t.dtype
+    ar = torch.arange(B, device=theta_t.device)
+    with torch.no_grad():
+        a_star = q_online_next.argmax(dim=1)
+        T = R.to(dt)[:, None] + Gamma.to(dt)[:, None] * theta_target_next[ar, a_star].to(dt)
+    th = theta_t[ar, A.long().view(-1)]
+    per = quantile_huber_terms(th, T, kappa, tau_t)[0].sum(-1)
     if weights is not None:
         per = per * weights.to(dt)
     with torch.no_grad():

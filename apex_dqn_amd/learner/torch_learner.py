@@ -71,6 +71,19 @@ class TorchLearner:
         G = self._to(batch["Gamma"], torch.float32)
         w = self._to(batch["weights"], torch.float32) if (
             self.rt.use_is_weights and "weights" in batch) else None
+        if self.cfg.implicit:
+            # IQN: the quantile Huber loss at sampled fractions, three sets per row drawn by the fused learner's
+            # convention (learner/iqn.py: update index = num_q_updates), so both see the same fractions
+            from .iqn import iqn_seed, learner_taus
+            from .losses import iqn_loss
+            taus = learner_taus(iqn_seed(self.rt.seed), self.num_q_updates, S_t.shape[0],
+                                int(self.rt.num_atoms)).to(self.device)
+            self.last_taus = taus
+            with torch.no_grad():
+                q_next_online = self.Q.quantiles_at(S_tpn, taus[:, 1]).mean(-1)
+                th_next_target = self.Q_target.quantiles_at(S_tpn, taus[:, 2])
+            return iqn_loss(self.Q.quantiles_at(S_t, taus[:, 0]), taus[:, 0], q_next_online, th_next_target, A, R, G,
+                            self.rt.huber_delta, w)
         if self.cfg.quantile:
             # QR-DQN: quantile Huber loss against the target net's quantiles (learner/losses.py)
             with torch.no_grad():

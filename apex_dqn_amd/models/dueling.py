@@ -79,15 +79,28 @@ class _C51Head:
     (2 i + 1) / (2 N); q is their mean; no support buffer (v_min / v_max are ignored)."""
 
     def _init_head(self, hidden: int, num_atoms: int, v_min: float, v_max: float,
-                   dist_head: str = "categorical", noisy: bool = False, sigma0: float = 0.5) -> None:
-        if dist_head not in ("categorical", "quantile"):
-            raise ValueError(f"dist_head must be 'categorical' or 'quantile', got {dist_head!r}")
+                   dist_head: str = "categorical", noisy: bool = False, sigma0: float = 0.5,
+                   iqn_actor_samples: int = 32) -> None:
+        if dist_head not in ("categorical", "quantile", "implicit"):
+            raise ValueError(f"dist_head must be 'categorical', 'quantile' or 'implicit', got {dist_head!r}")
         self.num_atoms = int(num_atoms)
         self.dist_head = dist_head if self.num_atoms > 1 else "categorical"
         self.v_min, self.v_max = float(v_min), float(v_max)
         self.noisy = bool(noisy)
-        self.value = _linear(hidden, self.num_atoms, self.noisy, sigma0)
-        self.advantage = _linear(hidden, self.action_dim * self.num_atoms, self.noisy, sigma0)
+        self.implicit = self.dist_head == "implicit"
+        if self.implicit and self.noisy:
+            raise ValueError("dist_head 'implicit' has no noisy layers")
+        # implicit (IQN): the heads at the scalar head's shapes; num_atoms is the loss's sample count only
+        rows = 1 if self.implicit else self.num_atoms
+        self.value = _linear(hidden, rows, self.noisy, sigma0)
+        self.advantage = _linear(hidden, self.action_dim * rows, self.noisy, sigma0)
+        if self.implicit:
+            # the cosine embedding of tau (64 cosines, the paper's n) gating both stream activations
+            self.tau_embed = nn.Linear(64, 2 * hidden)
+            self.iqn_actor_samples = int(iqn_actor_samples)
+            # (seed_q, counter word) of the next forward's K fractions per row, set by an actor group's hook
+            # (learner/iqn.py actor_tau_hook); None: the greedy evaluation's midpoints
+            self.iqn_draw = None
         if self.num_atoms > 1 and self.dist_head == "categorical":
             self.register_buffer("support", c51_support(self.num_atoms, self.v_min, self.v_max), persistent=False)
 
@@ -113,6 +126,16 @@ class _C51Head:
     def _head(self, hv: torch.Tensor, ha: torch.Tensor):
         """(value, advantage, q, dist): dist = [B, A, N] log-probabilities (categorical) or
         quantiles (quantile); None for the scalar head."""
+        if self.implicit:
+            # q = the mean over K fractions: an actor's draws (row e of the call, index e 64 + k), or for the
+            # greedy evaluation the midpoints tau_k = (2 k + 1) / (2 K)
+            from ..learner.iqn import midpoint_taus, stream_taus
+            if self.iqn_draw is not None:
+                tau = stream_taus(self.iqn_draw[0], self.iqn_draw[1], hv.shape[0], self.iqn_actor_samples).to(hv.device)
+            else:
+                tau = midpoint_taus(self.iqn_actor_samples).to(hv.device)[None, :].expand(hv.shape[0], -1)
+            theta, v, adv = self._theta_at(hv, ha, tau)
+            return v.mean(1, keepdim=True), adv.mean(1), theta.mean(-1), theta
         value, advantage = self.value(hv), self.advantage(ha)
         if self.num_atoms == 1:
             return value, advantage, dueling_combine(value, advantage), None
@@ -122,6 +145,23 @@ class _C51Head:
         logp = c51_log_probs(value, advantage, self.action_dim)
         q = (logp.exp() * self.support.to(logp.dtype)).sum(-1)
         return value, advantage, q, logp
+
+    def _theta_at(self, hv: torch.Tensor, ha: torch.Tensor, tau: torch.Tensor):
+        """theta [rows, A, n], v [rows, n], adv [rows, n, A] at the fractions ``tau`` [rows, n]: c_i = cos(pi i
+        tau) (fp64 at the given tau, then cast), phi = relu(We c + be), x = h * phi, v = wv . x[:H] + bv, adv_a
+        = wa[a] . x[H:] + ba[a], theta[a] = v + adv_a - mean_a' adv_a'."""
+        from ..learner.iqn import cos_features
+        H = hv.shape[-1]
+        phi = F.relu(self.tau_embed(cos_features(tau, hv.dtype).to(hv.device)))
+        v = self.value(hv[:, None, :] * phi[..., :H]).squeeze(-1)
+        adv = self.advantage(ha[:, None, :] * phi[..., H:])
+        theta = v[..., None] + adv - adv.mean(-1, keepdim=True)
+        return theta.transpose(1, 2), v, adv
+
+    def quantiles_at(self, x: torch.Tensor, tau: torch.Tensor) -> torch.Tensor:
+        """[rows, A, n] quantile values of the implicit head at the fractions ``tau`` [rows, n]."""
+        assert self.implicit
+        return self._theta_at(*self.streams(x), tau)[0]
 
 
 def c51_support(num_atoms: int, v_min: float, v_max: float, dtype=torch.float32) -> torch.Tensor:
@@ -169,7 +209,8 @@ class DuellingDQN(nn.Module, _C51Head):
     def __init__(self, state_shape: Sequence[int], action_dim: int,
                  conv1_channels: int = 64, obs_scale: float = 1.0 / 255.0,
                  num_atoms: int = 1, v_min: float = -10.0, v_max: float = 10.0,
-                 dist_head: str = "categorical", noisy: bool = False, noisy_sigma0: float = 0.5):
+                 dist_head: str = "categorical", noisy: bool = False, noisy_sigma0: float = 0.5,
+                 iqn_actor_samples: int = 32):
         super().__init__()
         self.input_shape = tuple(state_shape)
         self.action_dim = int(action_dim)
@@ -181,7 +222,11 @@ class DuellingDQN(nn.Module, _C51Head):
         self.layer3 = nn.Sequential(nn.Conv2d(64, 64, 3, stride=1), nn.ReLU())
         self.value_stream_layer = nn.Sequential(_linear(64 * 7 * 7, 512, noisy, noisy_sigma0), nn.ReLU())
         self.advantage_stream_layer = nn.Sequential(_linear(64 * 7 * 7, 512, noisy, noisy_sigma0), nn.ReLU())
-        self._init_head(512, num_atoms, v_min, v_max, dist_head, noisy, noisy_sigma0)
+        self._init_head(512, num_atoms, v_min, v_max, dist_head, noisy, noisy_sigma0, iqn_actor_samples)
+
+    def streams(self, x: torch.Tensor):
+        h = self.features(x)
+        return self.value_stream_layer(h), self.advantage_stream_layer(h)
 
     def features(self, x: torch.Tensor) -> torch.Tensor:
         x = self.pre(x)
@@ -210,7 +255,8 @@ class MLPDuellingDQN(nn.Module, _C51Head):
 
     def __init__(self, state_shape: Sequence[int], action_dim: int, hidden: int = 128,
                  num_atoms: int = 1, v_min: float = -10.0, v_max: float = 10.0,
-                 dist_head: str = "categorical", noisy: bool = False, noisy_sigma0: float = 0.5):
+                 dist_head: str = "categorical", noisy: bool = False, noisy_sigma0: float = 0.5,
+                 iqn_actor_samples: int = 32):
         super().__init__()
         d = int(state_shape[0]) if len(state_shape) == 1 else int(torch.tensor(state_shape).prod())
         self.input_shape = tuple(state_shape)
@@ -218,7 +264,11 @@ class MLPDuellingDQN(nn.Module, _C51Head):
         self.layer1 = nn.Sequential(nn.Linear(d, hidden), nn.ReLU())
         self.value_stream_layer = nn.Sequential(_linear(hidden, hidden, noisy, noisy_sigma0), nn.ReLU())
         self.advantage_stream_layer = nn.Sequential(_linear(hidden, hidden, noisy, noisy_sigma0), nn.ReLU())
-        self._init_head(hidden, num_atoms, v_min, v_max, dist_head, noisy, noisy_sigma0)
+        self._init_head(hidden, num_atoms, v_min, v_max, dist_head, noisy, noisy_sigma0, iqn_actor_samples)
+
+    def streams(self, x: torch.Tensor):
+        h = self.layer1(x.float().reshape(x.shape[0], -1))
+        return self.value_stream_layer(h), self.advantage_stream_layer(h)
 
     def forward(self, x: torch.Tensor):
         h = self.layer1(x.float().reshape(x.shape[0], -1))
@@ -303,9 +353,9 @@ class ImpalaDuellingDQN(nn.Module):
 def build_network(kind: str, state_shape: Sequence[int], action_dim: int,
                   obs_scale: float = 1.0 / 255.0, num_atoms: int = 1, v_min: float = -10.0,
                   v_max: float = 10.0, dist_head: str = "categorical", noisy: bool = False,
-                  noisy_sigma0: float = 0.5) -> nn.Module:
+                  noisy_sigma0: float = 0.5, iqn_actor_samples: int = 32) -> nn.Module:
     head = dict(num_atoms=num_atoms, v_min=v_min, v_max=v_max, dist_head=dist_head, noisy=noisy,
-                noisy_sigma0=noisy_sigma0)
+                noisy_sigma0=noisy_sigma0, iqn_actor_samples=iqn_actor_samples)
     if kind == "nature64":
         return DuellingDQN(state_shape, action_dim, conv1_channels=64, obs_scale=obs_scale, **head)
     if kind == "nature32":

@@ -24,7 +24,7 @@ SIGMA_SEGMENTS = (("swv", "wv"), ("sbv", "bv"), ("swa", "wa"), ("sba", "ba"), ("
 
 
 def nature_segments(C: int, A: int, c1: int = 64, num_atoms: int = 1,
-                    noisy: bool = False) -> List[Tuple[str, Tuple[int, ...]]]:
+                    noisy: bool = False, implicit: bool = False) -> List[Tuple[str, Tuple[int, ...]]]:
     """Flat order: the small tensors (convs, heads) first, the 3.2 M-parameter fc layer
     last, so the fc weights are one contiguous suffix: the data-parallel exchange treats
     [0, wfc) and [wfc, end) as its two buckets and the single-rank step updates the fc
@@ -32,7 +32,9 @@ def nature_segments(C: int, A: int, c1: int = 64, num_atoms: int = 1,
     head): wv (N, 512), bv (N,), wa (A N, 512) with row a N + i = action a, atom i, ba (A N,).
     ``noisy`` (factorised NoisyNet fc and head layers, learner/noisy.py): the sigma segments
     swv, sbv, swa, sba, swfc, sbfc with the shapes of their mu segments follow the fc layer,
-    so every other segment keeps its offset."""
+    so every other segment keeps its offset.  ``implicit`` (the implicit quantile head: pass
+    ``num_atoms`` = 1, its heads have the scalar head's shapes): the embedding ``wtau`` (1024, 64),
+    ``btau`` (1024,) follows the fc layer in the same way."""
     N = int(num_atoms)
     heads = [("wv", (512,)), ("bv", (1,)), ("wa", (A, 512)), ("ba", (A,))] if N == 1 else \
         [("wv", (N, 512)), ("bv", (N,)), ("wa", (A * N, 512)), ("ba", (A * N,))]
@@ -46,6 +48,8 @@ def nature_segments(C: int, A: int, c1: int = 64, num_atoms: int = 1,
     if noisy:
         shapes = dict(segs)
         segs += [(s, shapes[m]) for s, m in SIGMA_SEGMENTS]
+    if implicit:
+        segs += [("wtau", (1024, 64)), ("btau", (1024,))]
     return segs
 
 
@@ -108,6 +112,9 @@ def flat_to_reference_state(v: Dict[str, torch.Tensor], c1: int = 64) -> "Ordere
         sd["value.bias_sigma"] = v["sbv"].clone()
         sd["advantage.weight_sigma"] = v["swa"].clone()
         sd["advantage.bias_sigma"] = v["sba"].clone()
+    if "wtau" in v:       # implicit quantile head: the cosine embedding (rows in h's column order)
+        sd["tau_embed.weight"] = v["wtau"].clone()
+        sd["tau_embed.bias"] = v["btau"].clone()
     return OrderedDict((k, t.detach().float().cpu()) for k, t in sd.items())
 
 
@@ -129,6 +136,10 @@ def reference_state_to_flat(sd: Dict[str, torch.Tensor], v: Dict[str, torch.Tens
             raise ValueError("the state has " + ("" if has_sigma else "no ") + "noisy-layer sigma keys (*_sigma) and "
                              "this layout holds " + ("none" if has_sigma else "them") + ": Runtime.noisy differs "
                              "(a reference checkpoint has no sigma)")
+        has_tau = "tau_embed.weight" in sd
+        if has_tau != ("wtau" in v):
+            raise ValueError("the state has " + ("" if has_tau else "no ") + "implicit quantile embedding (tau_embed.*) "
+                             "and this layout holds " + ("none" if has_tau else "one") + ": Runtime.dist_head differs")
         for k, name in (("wv", "value.weight"), ("bv", "value.bias"), ("wa", "advantage.weight"),
                         ("ba", "advantage.bias")):
             if sd[name].numel() != v[k].numel():
@@ -152,6 +163,9 @@ def reference_state_to_flat(sd: Dict[str, torch.Tensor], v: Dict[str, torch.Tens
         v["bv"].copy_(sd["value.bias"])
         v["wa"].copy_(sd["advantage.weight"])
         v["ba"].copy_(sd["advantage.bias"])
+        if has_tau:
+            v["wtau"].copy_(sd["tau_embed.weight"])
+            v["btau"].copy_(sd["tau_embed.bias"])
         if has_sigma:
             v["swfc"][:512].copy_(fc_cols_to_hwc(sd["value_stream_layer.0.weight_sigma"]))
             v["sbfc"][:512].copy_(sd["value_stream_layer.0.bias_sigma"])

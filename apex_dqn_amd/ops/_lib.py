@@ -74,6 +74,35 @@ class QRArgs(ctypes.Structure):
                 ("dhead", c_p), ("zero_ptr", c_p), ("zero_n", c_i), ("lo", HeadLo), ("isn", IsNorm)]
 
 
+class IqnEmbed(ctypes.Structure):
+    """The cosine embedding of one net (``IqnEmbed``, csrc/iqn_head.hip): ``We (2 HS, 64)``, ``be (2 HS,)``."""
+    _fields_ = [("w", c_p), ("b", c_p)]
+
+
+class IqnArgs(ctypes.Structure):
+    """Arguments of the implicit quantile head kernel (``IqnArgs``, csrc/iqn_head.hip)."""
+    _fields_ = [("Hon", c_p), ("Htg", c_p), ("Pon", HeadParams), ("Ptg", HeadParams), ("Eon", IqnEmbed),
+                ("Etg", IqnEmbed), ("act", c_p), ("rew", c_p), ("gam", c_p), ("isw", c_p), ("B", c_i), ("A", c_i),
+                ("N", c_i), ("hidden", c_i), ("kappa", c_f), ("grad_scale", c_f), ("seed_q", c_u64), ("ctr", c_p),
+                ("base", c_p), ("td_abs", c_p), ("loss", c_p), ("q_out", c_p), ("tau_out", c_p), ("dH", c_p),
+                ("dhead", c_p), ("dpre", c_p), ("cosT", c_p), ("xg", c_p), ("gsum", c_p), ("zero_ptr", c_p),
+                ("zero_n", c_i), ("lo", HeadLo), ("isn", IsNorm), ("max_blocks", c_i)]
+
+
+class IqnWgArgs(ctypes.Structure):
+    """Arguments of ``iqn_wgrad_prio_kernel`` (``IqnWgArgs``, csrc/iqn_wgrad.h; launched from csrc/sumtree.hip)."""
+    _fields_ = [("dpre", c_p), ("cosT", c_p), ("xg", c_p), ("gsum", c_p), ("act", c_p), ("B", c_i), ("A", c_i),
+                ("N", c_i), ("gwv", c_p), ("gbv", c_p), ("gwa", c_p), ("gba", c_p), ("gwtau", c_p), ("gbtau", c_p),
+                ("part", c_p)]
+
+
+class IqnActorArgs(ctypes.Structure):
+    """Arguments of ``iqn_actor_head_kernel`` (``IqnActorArgs``, csrc/iqn_head.hip)."""
+    _fields_ = [("H", c_p), ("H_lo", c_p), ("P", HeadParams), ("Em", IqnEmbed), ("E", c_i), ("A", c_i), ("K", c_i),
+                ("hidden", c_i), ("midpoint", c_i), ("eps", c_p), ("seed", c_u64), ("ctr", c_p), ("seed_q", c_u64),
+                ("tau_ctr", c_p), ("stream", c_i), ("q_out", c_p), ("a_out", c_p), ("tau_out", c_p)]
+
+
 class MdqnArgs(ctypes.Structure):
     """Arguments of the Munchausen head kernel (``MdqnArgs``, csrc/mdqn_head.hip)."""
     _fields_ = [("Hon", c_p), ("Htg", c_p), ("Pon", HeadParams), ("Ptg", HeadParams), ("act", c_p), ("rew", c_p),
@@ -222,6 +251,11 @@ _SIGS = {
     "apex_c51_actor_head": ([c_p, HeadParams, c_i, c_i, c_i, c_f, c_f, c_p, c_u64, c_p, c_p, c_p, c_i, c_p, c_p], c_i),
     "apex_qr_head": ([QRArgs, c_p], c_i),
     "apex_mdqn_head": ([MdqnArgs, c_p], c_i),
+    "apex_iqn_head": ([IqnArgs, c_p], c_i),
+    "apex_iqn_wgrad": ([IqnWgArgs, c_p], c_i),
+    "apex_iqn_wgrad_part_floats": ([], c_i),
+    "apex_iqn_wgrad_prio": ([IqnWgArgs, TreeDesc, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p], c_i),
+    "apex_iqn_actor_head": ([IqnActorArgs, c_p], c_i),
     "apex_qr_actor_head": ([c_p, HeadParams, c_i, c_i, c_i, c_p, c_u64, c_p, c_p, c_p, c_i, c_p, c_p], c_i),
     "apex_actor_head": ([c_p, HeadParams, c_i, c_i, c_p, c_u64, c_p, c_p, c_p, c_i, c_p, c_p], c_i),
     "apex_conv1_s2d_fwd": ([Conv1S2DDesc, c_i, c_p], c_i),

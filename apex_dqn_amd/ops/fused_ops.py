@@ -411,6 +411,141 @@ class TorchBackend:
         r = torch.randint(0, A, (E,), generator=gen).to(q.device)
         a_out.copy_(torch.where(u < eps.to(q.device), r, q.argmax(1)).to(a_out.dtype))
 
+    # ------------------------------------------------- implicit quantile (IQN) head
+    @staticmethod
+    def _iqn_theta(h, P, E, tau, dt):
+        """theta [rows, A, n] and pre [rows, n, 2 HS] of stream activations ``h`` at the
+        fractions ``tau`` [rows, n] (fp32): c = cos(pi i tau) (fp64 at the fp32 tau, then
+        cast), pre = We c + be, x = h * relu(pre), v = wv . x[:HS] + bv, adv_a = wa[a] .
+        x[HS:] + ba[a], theta[a] = v + adv_a - mean_a' adv_a'.  ``P``: the scalar head's
+        shapes; ``E``: ``wtau (2 HS, 64)``, ``btau (2 HS,)``."""
+        from ..learner.iqn import cos_features
+        HS = P["wv"].shape[-1]
+        cf = cos_features(tau, dt)
+        pre = cf @ E["wtau"].to(dt).t() + E["btau"].to(dt)
+        x = h[:, None, :] * torch.relu(pre)
+        v = x[..., :HS] @ P["wv"].to(dt).reshape(HS) + P["bv"].to(dt).reshape(())
+        adv = x[..., HS:] @ P["wa"].to(dt).t() + P["ba"].to(dt)
+        th = v[..., None] + adv - adv.mean(-1, keepdim=True)
+        return th.transpose(1, 2), pre, cf
+
+    @staticmethod
+    def iqn_workspace(B: int, N: int, device, dtype=torch.float32) -> Dict[str, torch.Tensor]:
+        """What :meth:`iqn_head` leaves for :meth:`iqn_wgrad` (set 0 only): ``dpre [B, N, 2 HS]``,
+        ``cos [B, N, 64]``, ``xg [B, 2 HS]`` = sum_k g_k x_k and ``gsum [B]`` = sum_k g_k."""
+        z = lambda *s: torch.zeros(*s, device=device, dtype=dtype)      # noqa: E731
+        return {"dpre": z(B, N, 1024), "cos": z(B, N, 64), "xg": z(B, 1024), "gsum": z(B)}
+
+    @staticmethod
+    def _iqn_update_index(ctr, base) -> int:
+        u = int(ctr.reshape(-1)[0].item()) - (0 if base is None else int(base.reshape(-1)[0].item()))
+        return max(u, 0)
+
+    def iqn_head(self, Hon, Htg, Pon: Dict[str, torch.Tensor], Ptg: Dict[str, torch.Tensor],
+                 Eon: Dict[str, torch.Tensor], Etg: Dict[str, torch.Tensor], act, rew, gam, isw, num_samples: int,
+                 kappa: float, grad_scale: float, seed_q: int, ctr, base, td_abs, loss, dH, dhead, ws, q_out=None,
+                 tau_out=None, zero: Optional[torch.Tensor] = None, lo=None, isn=None, max_blocks=None):
+        """The implicit quantile counterpart of :meth:`qr_head` (the oracle of csrc/iqn_head.hip
+        ``iqn_head_kernel``): the scalar head's weights ``P`` gated by the cosine embedding
+        ``E`` (:meth:`_iqn_theta`) at three tau sets of N fractions per sample, drawn by the
+        mirror learner/iqn.py ``learner_taus`` at update u = ctr - base: set 0 the online net at
+        S_t, set 1 the online net at S_t+n (a* = first maximum of the mean), set 2 the target
+        net at S_t+n (T_j).  loss, g, td_abs and ``dhead [B, (A + 1) N]`` as :meth:`qr_head`
+        with tau_i of set 0; ``dH`` = [h > 0] sum_k phi_k dx_k; ``ws`` (:meth:`iqn_workspace`)
+        receives what :meth:`iqn_wgrad` needs; ``tau_out [B, 3, N]`` the fractions used."""
+        from ..learner.iqn import learner_taus
+        from ..learner.losses import quantile_huber_terms
+        B, N = act.shape[0], int(num_samples)
+        A = Pon["wa"].shape[0]
+        dt = torch.float64 if Pon["wv"].dtype == torch.float64 else torch.float32
+        HS = Pon["wv"].shape[-1]
+        if not float(kappa) > 0.0:
+            raise ValueError(f"iqn_head: kappa must be > 0, got {kappa}")
+
+        def joined(hi, l):
+            return hi.to(dt) if l is None else hi.to(dt) + l.to(dt)
+
+        Hon = joined(Hon, None if lo is None else lo[0])
+        Htg = joined(Htg, None if lo is None else lo[1])
+        taus = learner_taus(int(seed_q), self._iqn_update_index(ctr, base), B, N).to(Hon.device)
+        if tau_out is not None:
+            tau_out.copy_(taus)
+        ar = torch.arange(B, device=Hon.device)
+        th_t, pre, cf = self._iqn_theta(Hon[:B], Pon, Eon, taus[:, 0], dt)
+        q_t = th_t.mean(-1)
+        a_star = self._iqn_theta(Hon[B:2 * B], Pon, Eon, taus[:, 1], dt)[0].mean(-1).argmax(1)
+        T = rew.to(dt)[:, None] + gam.to(dt)[:, None] * self._iqn_theta(Htg[:B], Ptg, Etg, taus[:, 2], dt)[0][ar, a_star]
+        th = th_t[ar, act.long()]
+        rho, c = quantile_huber_terms(th, T, kappa, taus[:, 0])
+        w = isw.to(dt) if isw is not None else torch.ones(B, dtype=dt, device=Hon.device)
+        td_abs.copy_((T.mean(-1) - th.mean(-1)).abs())
+        loss.copy_(w * rho.sum(-1))
+        g = -w[:, None] * grad_scale * c                           # d loss / d theta of (a_b, .)
+        onehot = torch.nn.functional.one_hot(act.long(), A).to(dt)
+        dadv = g[:, None, :] * (onehot - 1.0 / A)[:, :, None]      # [B, A, N]
+        dhead[:, :N] = g
+        dhead[:, N:] = dadv.reshape(B, A * N)
+        # back through the heads, the gate and the stream ReLUs
+        dxv = g[:, :, None] * Pon["wv"].to(dt).reshape(HS)          # [B, N, HS]
+        dxa = torch.einsum("bak,ac->bkc", dadv, Pon["wa"].to(dt))
+        dx = torch.cat([dxv, dxa], -1)
+        phi = torch.relu(pre)
+        h = Hon[:B]
+        dh = (phi * dx).sum(1) * (h > 0).to(dt)
+        split_into(dh, dH, None if lo is None else lo[2])
+        ws["dpre"].copy_((pre > 0).to(dt) * dx * h[:, None, :])
+        ws["cos"].copy_(cf)
+        ws["xg"].copy_((g[:, :, None] * (h[:, None, :] * phi)).sum(1))
+        ws["gsum"].copy_(g.sum(1))
+        if q_out is not None:
+            q_out.copy_(q_t)
+        if zero is not None:
+            zero.zero_()
+        self._is_norm_stats(isn, w.float())
+
+    def iqn_wgrad(self, act, ws, g: Dict[str, torch.Tensor], prio=None) -> None:
+        """The head and embedding weight gradients from what :meth:`iqn_head` left (the oracle of
+        csrc/iqn_wgrad.h ``iqn_wgrad_body``); written, not accumulated.  ``prio = (replay, idx, gen,
+        td_abs)``: also write the batch's priorities back (the HIP backend: one block of the same launch).
+        G[wv] = sum_b xg_b[:HS], G[wa][a] = sum_b ([a = a_b] - 1/A) xg_b[HS:], G[bv] = sum_b
+        gsum_b, G[ba][a] = sum_b ([a = a_b] - 1/A) gsum_b, G[btau] = sum_{b,k} dpre, G[wtau] =
+        sum_{b,k} dpre (x) cos."""
+        if prio is not None:
+            prio[0].update_priorities(prio[1], prio[3], prio[2])
+        dt = g["wa"].dtype
+        A, HS = g["wa"].shape
+        coef = torch.nn.functional.one_hot(act.long(), A).to(dt) - 1.0 / A
+        xg, gs = ws["xg"].to(dt), ws["gsum"].to(dt)
+        g["wv"].copy_(xg[:, :HS].sum(0).reshape(g["wv"].shape))
+        g["bv"].copy_(gs.sum().reshape(g["bv"].shape))
+        g["wa"].copy_(coef.t() @ xg[:, HS:])
+        g["ba"].copy_(coef.t() @ gs)
+        g["btau"].copy_(ws["dpre"].to(dt).sum((0, 1)))
+        g["wtau"].copy_(torch.einsum("bkc,bki->ci", ws["dpre"].to(dt), ws["cos"].to(dt)))
+
+    def iqn_actor_head(self, H, P, E, eps, ctr, seed, seed_q, tau_ctr, stream: int, num_samples: int,
+                       midpoint: bool, q_out, a_out, H_lo=None, tau_out=None):
+        """q = the mean of theta over K fractions per env row + epsilon-greedy (the oracle of
+        csrc/iqn_head.hip ``iqn_actor_head_kernel``): fractions of the counter word 64
+        tau_ctr + stream (learner/iqn.py ``stream_taus``), or the midpoints."""
+        from ..learner.iqn import midpoint_taus, stream_taus
+        K = int(num_samples)
+        dt = torch.float64 if P["wv"].dtype == torch.float64 else torch.float32
+        h = H.to(dt) if H_lo is None else H.to(dt) + H_lo.to(dt)
+        n_e, A = q_out.shape
+        if midpoint:
+            taus = midpoint_taus(K).to(h.device)[None, :].expand(n_e, K).contiguous()
+        else:
+            taus = stream_taus(int(seed_q), 64 * int(tau_ctr.reshape(-1)[0].item()) + int(stream), n_e, K).to(h.device)
+        if tau_out is not None:
+            tau_out.copy_(taus)
+        q = self._iqn_theta(h, P, E, taus, dt)[0].mean(-1)
+        q_out.copy_(q)
+        gen = torch.Generator(device="cpu").manual_seed(int(seed) * 1000003 + int(ctr.item()))
+        u = torch.rand(n_e, generator=gen).to(q.device)
+        r = torch.randint(0, A, (n_e,), generator=gen).to(q.device)
+        a_out.copy_(torch.where(u < eps.to(q.device), r, q.argmax(1)).to(a_out.dtype))
+
     def head_wgrad(self, Hon, dhead, g: Dict[str, torch.Tensor], prio=None, Hon_lo=None, pack=None):
         """``prio = (replay, idx, gen, td_abs)``: also write the batch's priorities back
         (the HIP backend runs it as one extra block of the same launch).  ``pack = (dst,
@@ -670,7 +805,8 @@ class HipBackend(TorchBackend):
         self.lib = _lib.require_kernels()
         self.native_conv = native_conv and hasattr(self.lib, "apex_conv_fwd")
         self.kernels = ["replay", "head", "head_wgrad", "optimizer", "actor_head", "c51_head", "c51_actor_head", "qr_head",
-                        "qr_actor_head", "noisy_compose", "noisy_sigma_grad", "mdqn_head"]
+                        "qr_actor_head", "noisy_compose", "noisy_sigma_grad", "mdqn_head", "iqn_head", "iqn_wgrad",
+                        "iqn_actor_head"]
         if self.native_conv:
             self.kernels += ["conv_fwd", "conv_dgrad", "conv_wgrad", "fc_fwd", "fc_bwd"]
         self.ws = C.Workspace()
@@ -962,6 +1098,100 @@ class HipBackend(TorchBackend):
         _lib.check(self.lib.apex_qr_actor_head(H.data_ptr(), self._hp(P), E, A, int(num_atoms), eps.data_ptr(),
                                                int(seed), ctr.data_ptr(), q_out.data_ptr(), a_out.data_ptr(),
                                                P["wv"].shape[-1], _lib.ptr(H_lo), _lib.stream_ptr()), "qr_actor_head")
+
+    @staticmethod
+    def _embed(E):
+        e = _lib.IqnEmbed()
+        assert E["wtau"].is_contiguous() and E["wtau"].shape[-1] == 64 and E["btau"].numel() == E["wtau"].shape[0]
+        e.w, e.b = E["wtau"].data_ptr(), E["btau"].data_ptr()
+        return e
+
+    def iqn_workspace(self, B: int, N: int, device, dtype=torch.float32) -> Dict[str, torch.Tensor]:
+        """The torch backend's buffers plus ``wpart``: the split partials of G[wtau | btau] that the weight
+        gradient leaves for its reduce launch (allocated here, never inside a capture)."""
+        ws = super().iqn_workspace(B, N, device, dtype)
+        ws["wpart"] = torch.zeros(self.lib.apex_iqn_wgrad_part_floats(), dtype=torch.float32, device=device)
+        return ws
+
+    def iqn_head(self, Hon, Htg, Pon, Ptg, Eon, Etg, act, rew, gam, isw, num_samples, kappa, grad_scale, seed_q, ctr,
+                 base, td_abs, loss, dH, dhead, ws, q_out=None, tau_out=None, zero=None, lo=None, isn=None,
+                 max_blocks=None):
+        """csrc/iqn_head.hip ``iqn_head_kernel`` (reads h: the fc epilogue is not deferred).  ``max_blocks``
+        caps the persistent grid (default: the CU count)."""
+        assert getattr(self, "_fc_part", None) is None, "the distributional head reads h: fc epilogue deferred"
+        N = int(num_samples)
+        a = _lib.IqnArgs()
+        a.Hon, a.Htg, a.Pon, a.Ptg = Hon.data_ptr(), Htg.data_ptr(), self._hp(Pon), self._hp(Ptg)
+        a.Eon, a.Etg = self._embed(Eon), self._embed(Etg)
+        a.act, a.rew, a.gam, a.isw = act.data_ptr(), rew.data_ptr(), gam.data_ptr(), _lib.ptr(isw)
+        a.B, a.A, a.N, a.hidden = act.shape[0], Pon["wa"].shape[0], N, Pon["wv"].shape[-1]
+        a.kappa, a.grad_scale, a.seed_q = float(kappa), float(grad_scale), int(seed_q)
+        assert ctr.dtype == torch.int64 and (base is None or base.dtype == torch.int64)
+        a.ctr, a.base = ctr.data_ptr(), _lib.ptr(base)
+        a.td_abs, a.loss, a.q_out, a.tau_out = td_abs.data_ptr(), loss.data_ptr(), _lib.ptr(q_out), _lib.ptr(tau_out)
+        a.dH, a.dhead = dH.data_ptr(), dhead.data_ptr()
+        a.dpre, a.cosT, a.xg, a.gsum = (ws["dpre"].data_ptr(), ws["cos"].data_ptr(), ws["xg"].data_ptr(),
+                                        ws["gsum"].data_ptr())
+        a.zero_ptr, a.zero_n = _lib.ptr(zero), 0 if zero is None else zero.numel()
+        a.lo = _lib.head_lo(*(lo if lo is not None else (None, None, None)))
+        if isn is not None:
+            a.isn.wscale, a.isn.out = _lib.ptr(isn[0]), _lib.ptr(isn[1])
+            a.isn.valid_count = _lib.ptr(isn[2]) if len(isn) > 2 else None
+        a.max_blocks = 0 if max_blocks is None else int(max_blocks)
+        assert Pon["wv"].numel() == a.hidden and Ptg["wv"].numel() == a.hidden and Eon["wtau"].shape[0] == 2 * a.hidden
+        assert Hon.shape[0] >= 2 * a.B and Htg.shape[0] >= a.B and Hon.is_contiguous() and Htg.is_contiguous()
+        assert dhead.shape == (a.B, (a.A + 1) * N) and dhead.is_contiguous() and dhead.dtype == torch.float32
+        assert dH.shape == (a.B, 2 * a.hidden) and dH.is_contiguous()
+        assert ws["dpre"].shape == (a.B, N, 2 * a.hidden) and ws["cos"].shape == (a.B, N, 64)
+        assert ws["xg"].shape == (a.B, 2 * a.hidden) and ws["gsum"].shape == (a.B,)
+        assert all(ws[k].dtype == torch.float32 and ws[k].is_contiguous() for k in ("dpre", "cos", "xg", "gsum"))
+        assert tau_out is None or (tau_out.shape == (a.B, 3, N) and tau_out.is_contiguous()
+                                   and tau_out.dtype == torch.float32)
+        assert q_out is None or (q_out.shape == (a.B, a.A) and q_out.is_contiguous())
+        _lib.check(self.lib.apex_iqn_head(a, _lib.stream_ptr()), "iqn_head")
+
+    def iqn_wgrad(self, act, ws, g, prio=None) -> None:
+        """csrc/sumtree.hip ``iqn_wgrad_prio_kernel`` + ``iqn_wgrad_reduce_kernel`` (csrc/iqn_wgrad.h): G[wv, bv, wa, ba, wtau, btau];
+        ``prio = (replay, idx, gen, td_abs)``: block 0 of the same launch writes the priorities back."""
+        h = _lib.IqnWgArgs()
+        B, N = ws["dpre"].shape[0], ws["dpre"].shape[1]
+        A, HS = g["wa"].shape
+        h.dpre, h.cosT, h.xg, h.gsum = (ws["dpre"].data_ptr(), ws["cos"].data_ptr(), ws["xg"].data_ptr(),
+                                        ws["gsum"].data_ptr())
+        h.act, h.B, h.A, h.N = act.data_ptr(), B, A, N
+        assert act.shape == (B,) and act.dtype == torch.int32 and HS == 512
+        assert g["wv"].numel() == HS and g["bv"].numel() == 1 and g["ba"].numel() == A
+        assert g["wtau"].shape == (2 * HS, 64) and g["btau"].numel() == 2 * HS
+        assert all(g[k].is_contiguous() and g[k].dtype == torch.float32 for k in ("wv", "bv", "wa", "ba", "wtau", "btau"))
+        h.gwv, h.gbv, h.gwa, h.gba = g["wv"].data_ptr(), g["bv"].data_ptr(), g["wa"].data_ptr(), g["ba"].data_ptr()
+        h.gwtau, h.gbtau = g["wtau"].data_ptr(), g["btau"].data_ptr()
+        assert ws["wpart"].numel() == self.lib.apex_iqn_wgrad_part_floats() and ws["wpart"].dtype == torch.float32
+        h.part = ws["wpart"].data_ptr()
+        if prio is not None and prio[0].use_hip and B <= 1024:
+            rp, idx, gen, td = prio
+            _lib.check(self.lib.apex_iqn_wgrad_prio(h, rp.tree_desc(), idx.data_ptr(), td.data_ptr(), _lib.ptr(gen),
+                                                    rp.gen.data_ptr(), rp.alpha, rp.eps, rp.ctr.data_ptr(),
+                                                    _lib.ptr(rp.local_stats), _lib.stream_ptr()), "iqn_wgrad_prio")
+            return
+        if prio is not None:
+            prio[0].update_priorities(prio[1], prio[3], prio[2])
+        _lib.check(self.lib.apex_iqn_wgrad(h, _lib.stream_ptr()), "iqn_wgrad")
+
+    def iqn_actor_head(self, H, P, E, eps, ctr, seed, seed_q, tau_ctr, stream, num_samples, midpoint, q_out, a_out,
+                       H_lo=None, tau_out=None):
+        """csrc/iqn_head.hip ``iqn_actor_head_kernel``."""
+        a = _lib.IqnActorArgs()
+        n_e, A = q_out.shape
+        a.H, a.H_lo, a.P, a.Em = H.data_ptr(), _lib.ptr(H_lo), self._hp(P), self._embed(E)
+        a.E, a.A, a.K, a.hidden, a.midpoint = n_e, A, int(num_samples), P["wv"].shape[-1], int(bool(midpoint))
+        a.eps, a.seed, a.ctr = eps.data_ptr(), int(seed), ctr.data_ptr()
+        a.seed_q, a.tau_ctr, a.stream = int(seed_q), _lib.ptr(tau_ctr), int(stream)
+        a.q_out, a.a_out, a.tau_out = q_out.data_ptr(), a_out.data_ptr(), _lib.ptr(tau_out)
+        assert H.shape[0] >= n_e and H.shape[1] == 2 * a.hidden and H.is_contiguous() and P["wa"].shape[0] == A
+        assert eps.numel() >= n_e and a_out.numel() >= n_e and q_out.is_contiguous()
+        assert tau_ctr is None or tau_ctr.dtype == torch.int64
+        assert tau_out is None or (tau_out.shape == (n_e, a.K) and tau_out.is_contiguous())
+        _lib.check(self.lib.apex_iqn_actor_head(a, _lib.stream_ptr()), "iqn_actor_head")
 
     def head_wgrad(self, Hon, dhead, g, prio=None, Hon_lo=None, pack=None, norm=None) -> int:
         """``norm = (partials, slot0)`` (the distributional head only): every block also leaves

@@ -29,6 +29,7 @@ import torch
 from ..actors.actor_group import ActorGroup, HostFrameStore
 from ..config import ApexConfig
 from ..envs.vector_envs import make_vec_env
+from ..learner.iqn import actor_tau_hook
 from ..learner.noisy import actor_noise_hook
 from ..learner.schedules import rt_lr
 from ..learner.torch_learner import TorchLearner
@@ -67,7 +68,8 @@ def train_inline(cfg: ApexConfig, learner_steps: int, device="cpu",
     learner = TorchLearner(cfg, device)
     actor_net = copy.deepcopy(learner.Q).eval()
     policy = _make_policy(actor_net, device)
-    group.noise_hook = actor_noise_hook(cfg, actor_net, 0)
+    # (noisy layers and the implicit head exclude each other: one hook at most)
+    group.noise_hook = actor_noise_hook(cfg, actor_net, 0) or actor_tau_hook(cfg, actor_net, 0)
     losses: List[float] = []
     t_actor = 0
     max_actor_steps = max_actor_steps or (10 ** 12)
@@ -113,7 +115,7 @@ def _actor_proc(rank_id: int, cfg_dict: Dict[str, Any], num_envs: int, offset: i
     if sd is not None:
         net.load_state_dict(sd)
     policy = _make_policy(net, "cpu")
-    group.noise_hook = actor_noise_hook(cfg, net, rank_id)
+    group.noise_hook = actor_noise_hook(cfg, net, rank_id) or actor_tau_hook(cfg, net, rank_id)
     flush = max(1, cfg.Actor.n_step_transition_batch_size)
     t = 0
     while not stop_evt.is_set() and t < max_steps:

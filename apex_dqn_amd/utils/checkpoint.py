@@ -126,6 +126,15 @@ def check_dist_head(ck: Dict[str, Any], runtime_conf) -> None:
     the same ``num_atoms`` the categorical and the quantile head have the same keys and
     shapes, but the numbers mean different things (logits / quantiles).  A checkpoint without
     a config (reference format) or with the scalar head is not judged here."""
+    qs = ck.get("Q_state") if isinstance(ck, dict) else None
+    if isinstance(qs, dict):
+        # the implicit quantile head is told by its keys (a reference-format state included)
+        has_tau = any(k.startswith("tau_embed.") for k in qs)
+        want = int(runtime_conf.num_atoms) >= 2 and str(runtime_conf.dist_head) == "implicit"
+        if has_tau != want:
+            raise ValueError("the checkpoint's Q_state has " + ("an" if has_tau else "no") + " implicit quantile "
+                             f"embedding (tau_embed.*), this learner runs Runtime.dist_head="
+                             f"{runtime_conf.dist_head!r} with Runtime.num_atoms={runtime_conf.num_atoms}")
     c = ck.get("config") if isinstance(ck, dict) else None
     if not isinstance(c, dict):
         return
