@@ -1,0 +1,461 @@
+"""The scalar double-DQN head on the GPU, kernel by kernel, against the fp64 oracles of
+tests/ddqn_fixtures.py (settled on the CPU by tests/test_ddqn_fixtures_cpu.py): ``ddqn_head_kernel`` and the
+narrow ``head_wgrad`` at both stream widths, both planes, both ``MAXA`` instantiations and small odd batches,
+the named edge cases, the zero and IsNorm side duties, the fc split-K epilogue folded into the head launch
+(``load_row_part``) at every boundary of its plane loop, and ``actor_head_kernel`` against the fp64 q and the
+host mirror of the counter RNG."""
+import numpy as np
+import pytest
+import torch
+
+import ddqn_fixtures as F
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda", 0)
+
+# Split-mode dH: the largest relative error of the joined planes (hi + lo) against the oracle over the elements
+# with |ref| > 1e-6 x the row's max, measured on an MI355X over every split problem of this file (main sweep,
+# named cases, fc problems), and the bound = 8 x that.  See ``_compare`` for what the figure is made of.
+SPLIT_DH_MEASURED = 2.475e-3
+SPLIT_DH_BOUND = 8 * SPLIT_DH_MEASURED
+
+
+def _dev(t):
+    return None if t is None else t.to(DEV)
+
+
+def _grad_views(flat, A, HS):
+    """Views of the flat head-gradient region in the parameter layout wv [HS] bv [1] wa [A, HS] ba [A]."""
+    g, o = {}, 0
+    for k, shape in (("wv", (HS,)), ("bv", (1,)), ("wa", (A, HS)), ("ba", (A,))):
+        n = int(np.prod(shape))
+        g[k] = flat[o:o + n].view(shape)
+        o += n
+    return g
+
+
+def _head_launch(be, Hon, Htg, Hon_lo, Htg_lo, c, B, A, HS, isn=None, q_out=True, zero_n=None, tail=0):
+    """One ``ops.head`` launch on device tensors with every output pre-filled by a sentinel (td, loss -1,
+    dhead 7, the head-gradient region 3, dH NaN-free garbage 9), then ``head_wgrad`` into that region."""
+    split = Hon_lo is not None
+    Pon, Ptg = {k: _dev(v) for k, v in c["Pon"].items()}, {k: _dev(v) for k, v in c["Ptg"].items()}
+    td, loss = torch.full((B,), -1.0, device=DEV), torch.full((B,), -1.0, device=DEV)
+    dH = torch.full((B, 2 * HS), 9.0, device=DEV, dtype=torch.bfloat16)
+    dH_lo = torch.full_like(dH, 9.0) if split else None
+    dhead = torch.full((B, A + 1), 7.0, device=DEV)
+    q = torch.full((B, A), 11.0, device=DEV)
+    n = HS + 1 + A * HS + A
+    flat = torch.full((n + tail,), 3.0, device=DEV)
+    zn = n if zero_n is None else zero_n
+    be.head(Hon, Htg, Pon, Ptg, _dev(c["act"]), _dev(c["rew"]), _dev(c["gam"]), _dev(c["isw"]), c["huber"], c["kappa"],
+            1.0 / B, td, loss, dH, dhead, q_out=q if q_out else None, zero=flat[:zn] if zn else None,
+            lo=(Hon_lo, Htg_lo, dH_lo) if split else None, isn=isn)
+    torch.cuda.synchronize()
+    zeroed = flat.clone()
+    gr = _grad_views(flat, A, HS)
+    be.head_wgrad(Hon, dhead, gr, Hon_lo=Hon_lo)
+    torch.cuda.synchronize()
+    dHj = dH.double() + (dH_lo.double() if split else 0.0)
+    return dict(td=td.cpu(), loss=loss.cpu(), dH=dHj.cpu(), dH_hi=dH.cpu(), dH_lo=None if dH_lo is None else dH_lo.cpu(),
+                dhead=dhead.cpu(), q=q.cpu(), g={k: v.cpu() for k, v in gr.items()}, zeroed=zeroed.cpu(), inputs=c)
+
+
+def _run_hip(B, A, HS=512, split=False, case="plain", **kw):
+    from apex_dqn_amd.ops.fused_ops import HipBackend
+    fx = F.fixture(B, A, HS, split)
+    c = F.case_inputs(fx, case)
+    return _head_launch(HipBackend(), _dev(fx["Hon"]), _dev(fx["Htg"]), _dev(fx["Hon_lo"]), _dev(fx["Htg_lo"]), c, B, A,
+                        HS, **kw)
+
+
+def _rel_err(got, ref):
+    """Largest relative error over the elements with |ref| > 1e-6 x the row's max (``kws - kcs / A``
+    cancels: the elements below carry no relative information)."""
+    m = ref.abs() > 1e-6 * ref.abs().max(1, keepdim=True).values
+    return float(((got - ref).abs() / ref.abs().clamp_min(1e-300))[m].max()) if bool(m.any()) else 0.0
+
+
+def _check_split_planes(h, r):
+    """The joined dH planes against the kernel's own dq (dhead[:, 0], an fp32 number) times the fp64 weight
+    factor, with bounds from the number formats alone.  bf16 keeps 8 significant bits: for 2^E <= |x| < 2^(E+1),
+    hi = bf16(x) (round to nearest) leaves |x - hi| <= 2^(E-8); a residual of exactly 2^(E-8) is a bf16 number,
+    a smaller one lies in a binade below and lo = bf16(x - hi) leaves at most 2^(E-17) <= 2^-17 |x| (measured
+    on an MI355X: 0.987 of the bound below at most).  x itself is an fp32 result: the value stream's x = dq wv is one product (2^-24 |x|), the
+    advantage stream's x = dq (wa[a] - sum_j wa[j] / A) an A-term fp32 sum, the product with the rounded 1 / A,
+    the difference and the product with dq, each rounding <= 2^-24 of the magnitudes summed, |wa[a]| + sum_j
+    |wa[j]| / A -- (A + 3) 2^-24 of that, with no division by the cancelled result.  The bound is (2^-17 +
+    2^-23) |x| + (A + 3) 2^-24 |dq| (|wa[a]| + sum_j |wa[j]| / A).  A lo plane that is missing, stale or of the
+    wrong element is off by up to 2^-8 |x| and by 2^-10 |x| on average; masked elements are exactly 0 in both
+    planes."""
+    c, HS = h["inputs"], r["dH"].shape[1] // 2
+    A = c["Pon"]["wa"].shape[0]
+    wv, wa = c["Pon"]["wv"].double(), c["Pon"]["wa"].double()
+    dq = h["dhead"][:, 0].double()[:, None]
+    sel = wa[c["act"].long()]
+    fac = torch.cat([wv[None, :].expand(dq.shape[0], HS), sel - wa.sum(0) / A], 1)
+    mag = torch.cat([torch.zeros(dq.shape[0], HS, dtype=torch.float64), sel.abs() + wa.abs().sum(0) / A], 1)
+    want = dq * fac * r["mask"]
+    bound = dq.abs() * ((2.0 ** -17 + 2.0 ** -23) * fac.abs() + (A + 3) * 2.0 ** -24 * mag) * r["mask"]
+    err = (h["dH"] - want).abs()
+    worst = float((err / bound.clamp_min(1e-300))[r["mask"]].max()) if bool(r["mask"].any()) else 0.0
+    assert bool((err <= bound).all()), worst
+    assert bool((h["dH_hi"][~r["mask"]] == 0).all()) and bool((h["dH_lo"][~r["mask"]] == 0).all())
+    return worst
+
+
+def _compare(h, r, split, what=""):
+    """The tolerances of ``_compare`` in tests/test_gpu_qr.py for td, loss, dH, dhead, q and the head
+    gradients; everything finite.
+
+    Split mode: the joined dH (hi + lo) is fp32-accurate, and the bf16 tolerance above (rtol 1e-2) would pass
+    a wrong lo plane.  Measured on an MI355X, the largest relative error of the joined dH against the oracle
+    over the elements with |ref| > 1e-6 x the row's max (``_rel_err``) is 2.475e-3, at the (33, 8) problem
+    of HS = 256; 1.7e-4 and below at every other problem.  ``SPLIT_DH_BOUND`` = 8 x that = 1.98e-2 is
+    asserted, but it is not far below the 2^-8 of a missing lo plane, so the figure was taken apart: it is
+    made of the cancellation in ``kws - kcs / A`` at elements just above the 1e-6 cut (an absolute error of
+    2^-24 of the operands is 6e-2 of a result 1e-6 of their size) and of dq's own relative error against the
+    oracle at a small |delta|; the value stream alone, which has neither cancellation nor a second plane of
+    operands, measures 3.6e-5 (fc problems, where dq's error dominates) and 9.3e-6 at most elsewhere.  The
+    lo plane is therefore pinned by ``_check_split_planes``, whose bounds come from the formats and which
+    measures at most the figure it prints ("planes", in units of its bound)."""
+    f = lambda t: t.float()                                              # noqa: E731
+    HS = r["dH"].shape[1] // 2
+    dh_rel, dv_rel = _rel_err(h["dH"], r["dH"]), _rel_err(h["dH"][:, :HS], r["dH"][:, :HS])
+    print(what, " ".join(f"{k} err {float((h[k].double() - r[k]).abs().max()):.2e}" for k in ("td", "loss", "dH", "dhead",
+                                                                                             "q")),
+          " ".join(f"g_{k} err {float((h['g'][k].double() - r['g'][k]).abs().max()):.2e}" for k in r["g"]),
+          f"dH rel {dh_rel:.3e} dv rel {dv_rel:.3e} split {split}")
+    for v in list(h.values()) + list(h["g"].values()):
+        if torch.is_tensor(v):
+            assert bool(torch.isfinite(v).all())
+    torch.testing.assert_close(h["td"], f(r["td"]), rtol=1e-4, atol=1e-4)
+    torch.testing.assert_close(h["loss"], f(r["loss"]), rtol=1e-4, atol=1e-5)
+    torch.testing.assert_close(f(h["dH"]), f(r["dH"]), rtol=1e-2, atol=1e-6)
+    torch.testing.assert_close(h["dhead"], f(r["dhead"]), rtol=1e-4, atol=1e-7)
+    torch.testing.assert_close(h["q"], f(r["q"]), rtol=1e-4, atol=1e-4)
+    for k in ("wv", "bv", "wa", "ba"):
+        torch.testing.assert_close(h["g"][k], f(r["g"][k]), rtol=1e-3, atol=1e-6)
+    if split:
+        assert dh_rel <= SPLIT_DH_BOUND, dh_rel
+        print(what, f"planes {_check_split_planes(h, r):.3f} of the bound")
+
+
+# ------------------------------------------------------------ 1. kernel vs oracle
+@pytest.mark.parametrize("HS", F.HIDDEN)
+@pytest.mark.parametrize("split", [False, True])
+@pytest.mark.parametrize("B,A", F.SWEEP)
+def test_ddqn_head_kernel_vs_fp64_oracle(B, A, split, HS):
+    """Both stream widths (NPL = 8: 16-byte, NPL = 4: 8-byte row loads and dH stores), bf16 and hi / lo
+    planes, A = 1, the MAXA = 8 / HEAD_MAXA switch at A = 8 / 9, A = HEAD_MAXA = 32, batches that are a
+    multiple of nothing.  No row is excluded (tests/test_ddqn_fixtures_cpu.py).  Split mode: the joined dH's
+    relative error measures 2.475e-3 at most (at (33, 8), HS = 256), the bound is 8 x that = 1.98e-2, and the lo
+    plane is held by the format-derived bounds of ``_check_split_planes`` (``_compare`` says why)."""
+    r = F.oracle(B, A, HS, split)
+    h = _run_hip(B, A, HS, split)
+    _compare(h, r, split, f"sweep ({B}, {A}, {HS})")
+    assert bool((h["zeroed"] == 0).all())
+
+
+@pytest.mark.parametrize("case,HS,split", [(c, 512, False) for c in F.CASES] + [(c, 256, True) for c in F.HARD_CASES])
+def test_ddqn_head_named_cases(case, HS, split):
+    B, A = F.CASE_BA
+    fx = F.fixture(B, A, HS, split)
+    c = F.case_inputs(fx, case)
+    r = F.oracle(B, A, HS, split, case)
+    h = _run_hip(B, A, HS, split, case)
+    _compare(h, r, split, f"case {case} ({HS})")
+    assert bool((h["zeroed"] == 0).all())
+    kappa = c["kappa"]
+    if case == "terminal":
+        qsa = r["q"][torch.arange(B), fx["act"].long()]
+        torch.testing.assert_close(r["td"], (fx["rew"].double() - qsa).abs(), rtol=0, atol=1e-12)
+    if case == "no_isw":
+        torch.testing.assert_close(h["dhead"][:, 0].abs(), (r["td"].clamp(max=kappa) / B).float(), rtol=1e-4, atol=1e-7)
+    if case == "zero_isw":
+        z = torch.arange(B) % 3 == 0
+        assert bool((h["loss"][z] == 0).all()) and bool((h["dhead"][z] == 0).all()) and bool((h["dH"][z] == 0).all())
+        assert bool((h["dhead"][~z, 0] != 0).all())
+    if case == "big_rewards":
+        assert float(r["td"].min()) > 4 * kappa
+        want = -torch.sign(r["delta"]) * fx["isw"].double() * kappa / B
+        torch.testing.assert_close(h["dhead"][:, 0].double(), want, rtol=1e-6, atol=0)
+    if case == "tie_all":
+        assert bool((r["astar"] == 0).all())                       # the oracle's target reads q_g[:, 0]
+        assert bool((h["q"] == h["q"][:, :1]).all())
+    if case == "tie_pair":
+        assert bool((r["astar"] == 1).all())
+    # the dueling split of the gradient: the advantage columns sum to zero over the actions
+    assert float(h["dhead"][:, 1:].sum(1).abs().max()) <= 4 * 2.0 ** -23 * float(h["dhead"][:, 0].abs().max())
+
+
+@pytest.mark.parametrize("HS,split", [(512, False), (256, True)])
+def test_q_out_is_optional(HS, split):
+    """q_out = None leaves td, loss, dhead and both dH planes bit-equal to the run with q_out."""
+    B, A = F.CASE_BA
+    h, h2 = _run_hip(B, A, HS, split), _run_hip(B, A, HS, split, q_out=False)
+    for k in ("td", "loss", "dhead", "dH_hi", "dH"):
+        assert torch.equal(h[k], h2[k]), k
+    assert bool((h2["q"] == 11.0).all())
+    for k in h["g"]:
+        assert torch.equal(h["g"][k], h2["g"][k]), k
+
+
+@pytest.mark.parametrize("B", [1, 33])
+def test_zero_duty_stops_at_its_length(B):
+    """zero = the first n = HS + 1 + A HS + A floats of a larger buffer (n = 2565 = 13 blocks of 192 + 69):
+    those are 0 after the launch, the rest keeps its sentinel."""
+    A, HS, tail = 4, 512, 1000
+    n = HS + 1 + A * HS + A
+    assert n % 192 != 0 and n % 64 != 0
+    h = _run_hip(B, A, HS, False, tail=tail)
+    assert h["zeroed"].numel() == n + tail
+    assert bool((h["zeroed"][:n] == 0).all()) and bool((h["zeroed"][n:] == 3.0).all())
+    # and a shorter length inside the region: zero_n is honoured, not the region's size
+    h = _run_hip(B, A, HS, False, zero_n=77)
+    assert bool((h["zeroed"][:77] == 0).all()) and bool((h["zeroed"][77:] == 3.0).all())
+
+
+# --------------------------------------------------------------------- IsNorm
+def _isn(wscale, with_out=True):
+    return (None if wscale is None else torch.full((1,), wscale, device=DEV),
+            torch.full((1,), -1.0, dtype=torch.float64, device=DEV) if with_out else None,
+            torch.full((1,), 5, dtype=torch.int64, device=DEV))
+
+
+@pytest.mark.parametrize("B", F.ISN_B)
+def test_is_norm_against_plain_arithmetic(B):
+    """out[0] = float64(max isw) / float64(wscale) exactly (both fp32 values), wscale null: 1, wscale 0: 0;
+    valid_count += the rows with isw > 0 (some are exactly 0); B = 130 runs the wave's strided loop."""
+    A = 4
+    fx = F.fixture(B, A)
+    isw = F.case_inputs(fx, "zero_isw")["isw"]
+    n_pos = int((isw > 0).sum())
+    assert 0 < n_pos < B
+    wmax = float(isw.max().double())
+    r = F.oracle(B, A, 512, False, "zero_isw")
+    for wscale, want in ((1.7, wmax / float(np.float64(np.float32(1.7)))), (None, wmax), (0.0, 0.0)):
+        isn = _isn(wscale)
+        h = _run_hip(B, A, 512, False, "zero_isw", isn=isn)
+        assert float(isn[1]) == want, (wscale, float(isn[1]), want)
+        assert int(isn[2]) == 5 + n_pos
+        torch.testing.assert_close(h["td"], r["td"].float(), rtol=1e-4, atol=1e-4)
+    # no `out`: only the count is written
+    isn = _isn(1.7, with_out=False)
+    h = _run_hip(B, A, 512, False, "zero_isw", isn=isn)
+    assert int(isn[2]) == 5 + n_pos and float(isn[0]) == float(np.float32(1.7))
+    torch.testing.assert_close(h["td"], r["td"].float(), rtol=1e-4, atol=1e-4)
+    # without a count
+    isn = _isn(1.7)[:2]
+    _run_hip(B, A, 512, False, "zero_isw", isn=isn)
+    assert float(isn[1]) == wmax / float(np.float64(np.float32(1.7)))
+
+
+def test_is_norm_without_weights_is_refused():
+    with pytest.raises(RuntimeError, match="ddqn_head"):
+        _run_hip(5, 4, 512, False, "no_isw", isn=_isn(1.7))
+    torch.cuda.synchronize()
+
+
+# ---------------------------------------------------------------- head_wgrad alone
+@pytest.mark.parametrize("HS", F.HIDDEN)
+@pytest.mark.parametrize("split", [False, True])
+@pytest.mark.parametrize("B,A", [(1, 1), (7, 4), (33, 18), (130, 6)])
+def test_head_wgrad_accumulates(B, A, split, HS):
+    """The narrow weight gradient on random dhead: B < 8 (idle waves store zeros into the LDS reduction), B
+    not a multiple of the 8 waves, HS = 256 (grid.y = 4), with and without the lo plane; g pre-filled with
+    random non-zero values: the result is pre-fill + gradient, and a second call adds the same again."""
+    from apex_dqn_amd.ops.fused_ops import HipBackend
+    g = torch.Generator().manual_seed(100 + B + A)
+    x = torch.relu(torch.randn(B, 2 * HS, generator=g))
+    Hon, Hon_lo = F.split_planes(x) if split else (x.to(torch.bfloat16), None)
+    dhead = torch.randn(B, A + 1, generator=g)
+    n = HS + 1 + A * HS + A
+    # (a small pre-fill: the relative tolerance below is then the increment's)
+    pre = (0.05 + 0.05 * torch.rand(n, generator=g)) * torch.sign(torch.randn(n, generator=g))
+    assert bool((pre != 0).all())
+    h64, d64 = F.join64(Hon, Hon_lo), dhead.double()
+    inc = torch.cat([d64[:, 0] @ h64[:, :HS], d64[:, 0].sum().view(1), (d64[:, 1:].t() @ h64[:, HS:]).reshape(-1),
+                     d64[:, 1:].sum(0)])
+    flat = pre.to(DEV)
+    gr = _grad_views(flat, A, HS)
+    be = HipBackend()
+    for k in (1, 2):
+        be.head_wgrad(_dev(Hon), _dev(dhead), gr, Hon_lo=_dev(Hon_lo))
+        torch.cuda.synchronize()
+        got = flat.cpu()
+        print(f"head_wgrad ({B}, {A}, {HS}, split {split}) call {k}: max err {float((got.double() - (pre.double() + k * inc)).abs().max()):.2e}")
+        assert bool(torch.isfinite(got).all())
+        torch.testing.assert_close(got, (pre.double() + k * inc).float(), rtol=1e-3, atol=1e-6)
+
+
+# ------------------------------------------- 2. the fc epilogue inside the head launch
+def _fc_run(B, HS, K, split, ksplit, defer, c2d=None, be=None):
+    """fc forward (+ head) of ``F.fc_fixture``: (h [3B, 2 HS] hi, lo, head outputs, nz the deferred launch
+    left, the backend)."""
+    from apex_dqn_amd.ops.fused_ops import HipBackend
+    be = HipBackend() if be is None else be
+    f = F.fc_fixture(B, HS, K, split)
+    A = f["A"]
+    x = _dev(f["x"]).reshape((3 * B, 7, 7, 64) if K == 3136 else (3 * B, K))
+    x_lo = None if not split else _dev(f["x_lo"]).reshape(x.shape)
+    h = torch.full((3 * B, 2 * HS), 5.0, device=DEV, dtype=torch.bfloat16)
+    h_lo = torch.full_like(h, 5.0) if split else None
+    lo = dict(x_lo=x_lo, w_lo=_dev(f["w_lo"]), w2_lo=_dev(f["w2_lo"]), out_lo=h_lo) if split else {}
+    be.fc_fwd(x, _dev(f["w"]), _dev(f["b"]), h, _dev(f["w2"]), _dev(f["b2"]), 2 * B, c2d=c2d, defer_head=defer,
+              ksplit=ksplit, **lo)
+    nz = None
+    if defer:
+        assert be._fc_part is not None, "fc_fwd did not defer its epilogue"
+        nz = be._fc_part["nz"]
+    else:
+        assert getattr(be, "_fc_part", None) is None
+    c = dict(Pon=f["Pon"], Ptg=f["Ptg"], act=f["act"], rew=f["rew"], gam=f["gam"], isw=f["isw"], huber=True,
+             kappa=F.KAPPA)
+    out = _head_launch(be, h[:2 * B], h[2 * B:], None if not split else h_lo[:2 * B], None if not split else h_lo[2 * B:],
+                       c, B, A, HS)
+    assert getattr(be, "_fc_part", None) is None
+    return h.cpu(), None if h_lo is None else h_lo.cpu(), out, nz, be
+
+
+def _check_fc_head(B, HS, K, split, ksplit, nz_want):
+    ha, ha_lo, oa, nz, _ = _fc_run(B, HS, K, split, ksplit, True)
+    hb, hb_lo, ob, _, _ = _fc_run(B, HS, K, split, ksplit, False)
+    assert nz == nz_want
+    # the kernel's contract: rows [0, B) of h as the separate epilogue launch leaves them, bit for bit
+    assert torch.equal(ha[:B], hb[:B])
+    assert bool((ha[B:] == 5.0).all())                      # (the deferred launch writes no other row)
+    if split:
+        assert torch.equal(ha_lo[:B], hb_lo[:B]) and bool((ha_lo[B:] == 5.0).all())
+    # (b)'s h against fp64, at the tolerances of tests/test_gpu_fc128.py test_fc128_matches_fp64
+    h64 = F.fc_h64(B, HS, K, split)
+    hbj = F.join64(hb, hb_lo)
+    err = float(((hbj - h64).abs() / (h64.abs() + 1e-1)).max())
+    print(f"fc ({B}, {HS}, K {K}, split {split}, ksplit {ksplit}): h err {err:.2e}")
+    assert err < (1e-4 if split else 8e-3), err
+    # both heads against the oracle fed with (b)'s h; (a)'s outputs are (b)'s bit for bit
+    r = F.fc_head_oracle(B, HS, K, split, hbj)
+    assert r["gap"] > F.MARGIN / 2 and r["kmargin"] > F.MARGIN / 2
+    _compare(oa, r, split, f"fc + head, deferred ({B}, {HS}, nz {nz})")
+    _compare(ob, r, split, f"fc + head, two launches ({B}, {HS})")
+    for k in ("td", "loss", "dhead", "q", "dH_hi", "dH"):
+        assert torch.equal(oa[k], ob[k]), k
+    for k in oa["g"]:
+        assert torch.equal(oa["g"][k], ob["g"][k]), k
+
+
+@pytest.mark.parametrize("B", [5, 43])
+@pytest.mark.parametrize("split", [False, True])
+@pytest.mark.parametrize("ksplit", [1, 2, 3, 5, 6, 10])
+def test_fc_epilogue_in_head(ksplit, split, B):
+    """K = 3136 (kt = 49): nz = ksplit partial planes -- 1 (the plane loop is not entered), 2 and 3 (one
+    partial group of ZU = 4), 5 (one full group), 6 (a full and a partial group), 10; M = 15 rows are one
+    partly clamped tile, M = 129 cross a 128-row tile with the weight switch at row 86."""
+    _check_fc_head(B, 512, 3136, split, ksplit, ksplit)
+
+
+@pytest.mark.parametrize("ksplit", [1, 3, 5])
+def test_fc_epilogue_in_head_hidden_256(ksplit):
+    """N = 512, K = 640 (kt = 10), split: the NPL = 4 instantiation of load_row_part (no learner reaches
+    it, the launcher accepts it)."""
+    _check_fc_head(5, 256, 640, True, ksplit, ksplit)
+
+
+@pytest.mark.parametrize("split", [False, True])
+def test_c2d_pack_rides_on_the_head_launch(split):
+    """B = 5: the 128 conv2 pack blocks behind the 5 head blocks leave the fragment buffer as the conv2
+    data gradient's own pack launch does, bit for bit (stale contents overwritten)."""
+    from apex_dqn_amd.ops import conv as C
+    from apex_dqn_amd.ops.fused_ops import HipBackend
+    g = torch.Generator().manual_seed(11)
+    c2h, c2l = (_dev(t) for t in F.split_planes(torch.randn(64, 4, 4, 64, generator=g) * 0.03))
+    dyh, dyl = (_dev(t) for t in F.split_planes(torch.randn(2, 9, 9, 64, generator=g)))
+    y1 = _dev(torch.relu(torch.randn(2, 20, 20, 64, generator=g)).to(torch.bfloat16))
+    be = HipBackend()
+    buf = C.c2d_wfrag_buffer(be.ws, DEV)
+    # the launcher's own pack (tests/test_gpu_fc128.py test_c2d_pack_in_fc_epilogue_matches_own_pack)
+    buf.fill_(3.0)
+    outs = [torch.zeros(2, 20, 20, 64, device=DEV, dtype=torch.bfloat16) for _ in range(4)]
+    lo = lambda o: dict(dy_lo=dyl, w_lo=c2l, out_lo=o) if split else {}          # noqa: E731
+    C.conv2_dgrad_img(be.lib, dyh, c2h, y1, outs[0], ws=be.ws, **lo(outs[1]))
+    torch.cuda.synchronize()
+    own = buf.clone()
+    assert not bool((own.view(torch.int16) == own.view(torch.int16)[0]).all())
+    buf.fill_(3.0)
+    _, _, out, nz, _ = _fc_run(5, 512, 3136, split, 2, True, c2d=(c2h, c2l if split else None), be=be)
+    assert nz == 2
+    torch.cuda.synchronize()
+    assert torch.equal(buf.view(torch.int16), own.view(torch.int16))
+    # the data gradient finds its weights packed: same bits as with its own pack
+    assert be._c2d_packed == (c2h.data_ptr(), c2l.data_ptr() if split else None)
+    C.conv2_dgrad_img(be.lib, dyh, c2h, y1, outs[2], ws=be.ws, packed=True, **lo(outs[3]))
+    torch.cuda.synchronize()
+    assert torch.equal(outs[0], outs[2]) and (not split or torch.equal(outs[1], outs[3]))
+    # and the head blocks in front of the pack blocks give what they give without them
+    out2 = _fc_run(5, 512, 3136, split, 2, True)[2]
+    for k in ("td", "loss", "dhead", "q", "dH_hi", "dH", "zeroed"):
+        assert torch.equal(out[k], out2[k]), k
+
+
+# ------------------------------------------------------------------ 3. actor head
+SEEDS = (5, (1 << 32) + 12345)
+CTRS = (0, 7, (1 << 40) + 3)
+
+
+@pytest.mark.parametrize("HS", F.HIDDEN)
+@pytest.mark.parametrize("split", [False, True])
+@pytest.mark.parametrize("E,A", F.ACTOR_EA)
+def test_actor_head_vs_fp64_q_and_rng_mirror(E, A, split, HS):
+    """q_out against the fp64 q; a_out exactly: where the mirror's u < eps the mirror's min(int(r A), A - 1),
+    elsewhere the argmax of the kernel's own q_out, which is the oracle's (top-2 gap > 2e-3 on every row).
+    Row 0 has eps 0, row 1 eps 1, a few rows eps = float32(u) itself (strict <: greedy).  Every (seed, ctr)
+    pair, a seed above 2^32 and a counter above 2^40 among them."""
+    from apex_dqn_amd.ops.fused_ops import HipBackend
+    f = F.actor_fixture(E, A, HS, split)
+    r = F.actor_oracle(E, A, HS, split)
+    assert r["gap"] > F.MARGIN
+    be = HipBackend()
+    H, H_lo, P = _dev(f["H"]), _dev(f["H_lo"]), {k: _dev(v) for k, v in f["P"].items()}
+    seen = set()
+    for seed in SEEDS:
+        for ctr in CTRS:
+            eps, u, rr, explore, a_rand = F.actor_draws(E, A, seed, ctr, f["eps"])
+            if (E, A) == (257, 18):
+                assert explore.any() and (~explore).any() and len(set(a_rand[explore].tolist())) >= 10
+            if E >= 3:
+                assert not explore[F.actor_forced_rows(E)].any() and not explore[0] and explore[1]
+            q = torch.full((E, A), 11.0, device=DEV)
+            a = torch.full((E,), -3, dtype=torch.int32, device=DEV)
+            be.actor_head(H, P, torch.from_numpy(eps).to(DEV), torch.tensor([ctr], dtype=torch.int64, device=DEV), seed, q,
+                          a, H_lo=H_lo)
+            torch.cuda.synchronize()
+            q, a = q.cpu(), a.cpu().long()
+            torch.testing.assert_close(q, r["q"].float(), rtol=1e-4, atol=1e-4)
+            assert torch.equal(F.first_argmax(q), r["greedy"])
+            want = torch.where(torch.from_numpy(explore), torch.from_numpy(a_rand), F.first_argmax(q))
+            bad = (a != want).nonzero().flatten().tolist()
+            assert not bad, (seed, ctr, bad[:8], a[bad[:8]].tolist(), want[bad[:8]].tolist())
+            seen.add(tuple(a.tolist()))
+    if E >= 70:
+        assert len(seen) == len(SEEDS) * len(CTRS)       # every (seed, ctr) drew another action vector
+
+
+def test_actor_head_consecutive_counters_differ():
+    """eps = 1 on every row: the action vector is the mirror's, and ctr, ctr + 1 give different ones."""
+    from apex_dqn_amd.ops.fused_ops import HipBackend
+    from apex_dqn_amd.replay.gpu_replay import apex_uniform
+    E, A = 257, 18
+    f = F.actor_fixture(E, A)
+    be = HipBackend()
+    H, P = _dev(f["H"]), {k: _dev(v) for k, v in f["P"].items()}
+    acts = []
+    for ctr in (7, 8):
+        e = np.arange(E, dtype=np.uint64)
+        want = np.minimum((apex_uniform(5, ctr, 2 * e + 1) * np.float32(A)).astype(np.int64), A - 1)
+        q, a = torch.zeros(E, A, device=DEV), torch.full((E,), -3, dtype=torch.int32, device=DEV)
+        be.actor_head(H, P, torch.ones(E, device=DEV), torch.tensor([ctr], dtype=torch.int64, device=DEV), 5, q, a)
+        torch.cuda.synchronize()
+        assert np.array_equal(a.cpu().numpy().astype(np.int64), want)
+        acts.append(want)
+    assert not np.array_equal(acts[0], acts[1])
+    assert len(set(acts[0].tolist())) == A               # 257 uniform draws reach all 18 actions
