@@ -315,19 +315,20 @@ class GpuActorGroup:
         distributional learner (``learner.N`` atoms) the expected q of its C51 head or the mean of
         its quantile head (``Runtime.dist_head``)."""
         n = int(getattr(self.learner, "N", 1))
+        ops, rt = self.ops, self.cfg.Runtime
+        # every actor head: (h, heads, [net], eps, ctr, seed, [own], q, act, H_lo)
+        net = ()
         if self.implicit:
             seed_q, stream, K = self._iqn
-            emb = {"wtau": self.P["wtau"], "btau": self.P["btau"]}
-            self.ops.iqn_actor_head(h, heads, emb, self.eps, self.ctr, self.seed, seed_q, self.ctr, stream, K, False,
-                                    self.q, self.act, H_lo=h_lo)
+            op, net = ops.iqn_actor_head, ({"wtau": self.P["wtau"], "btau": self.P["btau"]},)
+            own = (seed_q, self.ctr, stream, K, False)
         elif n >= 2 and self.cfg.quantile:
-            self.ops.qr_actor_head(h, heads, self.eps, self.ctr, self.seed, n, self.q, self.act, H_lo=h_lo)
+            op, own = ops.qr_actor_head, (n,)
         elif n >= 2:
-            rt = self.cfg.Runtime
-            self.ops.c51_actor_head(h, heads, self.eps, self.ctr, self.seed, n, rt.v_min, rt.v_max, self.q, self.act,
-                                    H_lo=h_lo)
+            op, own = ops.c51_actor_head, (n, rt.v_min, rt.v_max)
         else:
-            self.ops.actor_head(h, heads, self.eps, self.ctr, self.seed, self.q, self.act, H_lo=h_lo)
+            op, own = ops.actor_head, ()
+        op(h, heads, *net, self.eps, self.ctr, self.seed, *own, self.q, self.act, H_lo=h_lo)
 
     def step(self) -> int:
         """One env step for all E envs; returns the number of transitions inserted."""

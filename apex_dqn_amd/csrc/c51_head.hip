@@ -28,25 +28,11 @@
 #include "dist_head.h"
 
 struct C51Args {
-  const bf16_t* Hon;    // [2B][2 HS]
-  const bf16_t* Htg;    // [B][2 HS]
-  HeadParams Pon, Ptg;
-  const int32_t* act;
-  const float* rew;
-  const float* gam;
-  const float* isw;     // null: weights off
-  int B, A, N, hidden;
-  float vmin, vmax, grad_scale;
-  float* td_abs;
-  float* loss;
-  float* q_out;         // [B][A] expected q(S_t), or null
-  bf16_t* dH;           // [B][2 HS]
-  float* dhead;         // [B][(A + 1) N]
-  float* zero_ptr;      // head-gradient region zeroed for the head weight gradient
-  int zero_n;
-  HeadLo lo;
-  IsNorm isn;
+  HeadIO io;            // Hon [2B], Htg [B]; q_out the expected q(S_t); dhead [B][(A + 1) N]
+  int N;
+  float vmin, vmax;
 };
+static_assert(std::is_standard_layout_v<C51Args> && std::is_trivially_copyable_v<C51Args>);
 
 // softmax over the atoms of action a: this lane's probability and log-probability;
 // returns the expectation sum_i p_i z_i (wave-uniform)
@@ -61,11 +47,12 @@ __device__ __forceinline__ float c51_action(const DistRow& r, int a, int N, int 
   return wave_sum_dpp(p * z);
 }
 
-__global__ void __launch_bounds__(DIST_NT) c51_head_kernel(C51Args a) {
+__global__ void __launch_bounds__(DIST_NT) c51_head_kernel(C51Args ka) {
+  const HeadIO& a = ka.io;
   extern __shared__ __attribute__((aligned(16))) float c51_smem[];
   constexpr int HS = DIST_HS, ROW = 2 * HS, SPB = DIST_SPB, NR = 3 * SPB;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int B = a.B, A = a.A, N = a.N, AN = A * N, J = N + AN;
+  const int B = a.B, A = a.A, N = ka.N, AN = A * N, J = N + AN;
   const int Jp = (J + 3) & ~3;
   float* Hs = c51_smem;                  // [NR][ROW]: rows s (S_t), SPB + s (online S_t+n), 2 SPB + s (target)
   float* Ls = c51_smem + NR * ROW;       // [NR][Jp] logits (no biases); rows s later hold the dhead rows
@@ -75,7 +62,7 @@ __global__ void __launch_bounds__(DIST_NT) c51_head_kernel(C51Args a) {
   dist_head_side(a, tid, lane, wv);
   dist_head_stage(a, Hs, b0, tid, split);
   __syncthreads();
-  dist_head_logits(a, Hs, Ls, Jp, lane, wv);
+  dist_head_logits(a, N, Hs, Ls, Jp, lane, wv);
   __syncthreads();
 
   // ---- phase 2: wave s finishes sample s (lane = atom)
@@ -84,8 +71,8 @@ __global__ void __launch_bounds__(DIST_NT) c51_head_kernel(C51Args a) {
     const bool live = b0 + s < B;
     const int b = min(b0 + s, B - 1);
     const bool valid = lane < N;
-    const float delta = (a.vmax - a.vmin) / (float)(N - 1);
-    const float z = a.vmin + (float)lane * delta;
+    const float delta = (ka.vmax - ka.vmin) / (float)(N - 1);
+    const float z = ka.vmin + (float)lane * delta;
     const int a_b = a.act[b];
     const float rew_b = a.rew[b], gam_b = a.gam[b];
     const float w_b = a.isw != nullptr ? a.isw[b] : 1.f;
@@ -107,8 +94,8 @@ __global__ void __launch_bounds__(DIST_NT) c51_head_kernel(C51Args a) {
       const DistRow rg = dist_row(Ls + (2 * SPB + s) * Jp, a.Ptg, A, N, lane);
       c51_action(rg, astar, N, lane, z, p, lp);
       const float pj = valid ? p : 0.f;
-      const float tz = fminf(fmaxf(rew_b + gam_b * z, a.vmin), a.vmax);
-      const float bj = (tz - a.vmin) / delta;
+      const float tz = fminf(fmaxf(rew_b + gam_b * z, ka.vmin), ka.vmax);
+      const float bj = (tz - ka.vmin) / delta;
       const float fi = (float)lane;
       for (int j = 0; j < N; ++j) {      // increasing j: the oracle's order
         const float pp = __shfl(pj, j, 64), bb = __shfl(bj, j, 64);
@@ -138,13 +125,13 @@ __global__ void __launch_bounds__(DIST_NT) c51_head_kernel(C51Args a) {
   }
   __syncthreads();
 
-  dist_head_dh(a, Hs, Ls, Jp, b0, tid, split);
+  dist_head_dh(a, N, Hs, Ls, Jp, b0, tid, split);
 }
 
 APEX_EXPORT int apex_c51_head(C51Args a, hipStream_t st) {
   size_t lds = 0;
-  if (!dist_head_args_ok(a, &lds) || !(a.vmin < a.vmax)) return (int)hipErrorInvalidValue;
-  const int grid = (a.B + DIST_SPB - 1) / DIST_SPB;
+  if (!dist_head_args_ok(a.io, a.N, &lds) || !(a.vmin < a.vmax)) return (int)hipErrorInvalidValue;
+  const int grid = (a.io.B + DIST_SPB - 1) / DIST_SPB;
   c51_head_kernel<<<grid, DIST_NT, lds, st>>>(a);
   APEX_CHECK_LAUNCH();
 }

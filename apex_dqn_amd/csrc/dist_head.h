@@ -23,8 +23,8 @@
 //                      dhead . W (float4 weight loads, the coefficients broadcast from LDS);
 //                      the groups' partials are added through LDS in a fixed order.
 //
-// `Args` is the kernel's argument struct (C51Args / QRArgs: the fields used here have the
-// same names).  Nothing depends on the order blocks run in (no float atomics).
+// `a` is the kernel's shared argument block (head_common.h HeadIO), N its atom / quantile
+// count.  Nothing depends on the order blocks run in (no float atomics).
 // dist_actor_logits is phase 1 for the actor heads: one wave per env row, the row in
 // registers.
 #pragma once
@@ -115,8 +115,7 @@ static inline size_t dist_head_lds(int A, int N) {
   return (size_t)(3 * DIST_SPB) * (2 * DIST_HS + Jp) * sizeof(float);
 }
 
-template <class Args>
-__device__ __forceinline__ void dist_head_side(const Args& a, int tid, int lane, int wv) {
+__device__ __forceinline__ void dist_head_side(const HeadIO& a, int tid, int lane, int wv) {
   const int B = a.B;
   // zero the head-gradient region that the head weight gradient accumulates into
   if (a.zero_ptr != nullptr)
@@ -141,8 +140,7 @@ __device__ __forceinline__ void dist_head_side(const Args& a, int tid, int lane,
 
 // ---- phase 0: the block's activation rows -> LDS (fp32; a sample past the batch reads the last row)
 // Hs [3 SPB][ROW]: rows s (S_t), SPB + s (online S_t+n), 2 SPB + s (target)
-template <class Args>
-__device__ __forceinline__ void dist_head_stage(const Args& a, float* Hs, int b0, int tid, bool split) {
+__device__ __forceinline__ void dist_head_stage(const HeadIO& a, float* Hs, int b0, int tid, bool split) {
   constexpr int HS = DIST_HS, ROW = 2 * HS, SPB = DIST_SPB, NR = 3 * SPB;
   const int B = a.B;
   for (int r = 0; r < NR; ++r) {
@@ -163,10 +161,10 @@ __device__ __forceinline__ void dist_head_stage(const Args& a, float* Hs, int b0
 }
 
 // ---- phase 1: logits of every staged row -> Ls [3 SPB][Jp] (no biases)
-template <class Args>
-__device__ __forceinline__ void dist_head_logits(const Args& a, const float* Hs, float* Ls, int Jp, int lane, int wv) {
+__device__ __forceinline__ void dist_head_logits(const HeadIO& a, int N, const float* Hs, float* Ls, int Jp, int lane,
+                                                 int wv) {
   constexpr int HS = DIST_HS, ROW = 2 * HS, SPB = DIST_SPB;
-  const int N = a.N, AN = a.A * N;
+  const int AN = a.A * N;
   const int l16 = lane & 15;
   const int gv = (N + 3) >> 2, ga = (AN + 3) >> 2, G1 = gv + ga;
   constexpr int NW = DIST_NT / 64;
@@ -219,11 +217,10 @@ __device__ __forceinline__ void dist_head_store_dhead(float g, bool live, bool v
 }
 
 // ---- phase 3: dH[s][k] = relu'(h) sum_j dhead[s][j] W[j][k]  (contains block barriers)
-template <class Args>
-__device__ __forceinline__ void dist_head_dh(const Args& a, float* Hs, const float* Ls, int Jp, int b0, int tid,
+__device__ __forceinline__ void dist_head_dh(const HeadIO& a, int N, float* Hs, const float* Ls, int Jp, int b0, int tid,
                                              bool split) {
   constexpr int HS = DIST_HS, ROW = 2 * HS, SPB = DIST_SPB;
-  const int B = a.B, N = a.N, AN = a.A * N;
+  const int B = a.B, AN = a.A * N;
   const int q = tid >> 7, ct = tid & 127;       // row group, column quad
   float4 av[SPB], aa[SPB];
 #pragma unroll
@@ -300,17 +297,11 @@ __device__ __forceinline__ void dist_head_dh(const Args& a, float* Hs, const flo
   }
 }
 
-// The pointer / shape checks the head launchers share (C51Args / QRArgs); the LDS in `lds`.
-template <class Args>
-static inline bool dist_head_args_ok(const Args& a, size_t* lds) {
-  if (a.A < 1 || a.A > HEAD_MAXA || a.B < 1 || a.N < 2 || a.N > 64 || a.hidden != DIST_HS) return false;
-  if ((a.isn.out != nullptr || a.isn.valid_count != nullptr) && a.isw == nullptr) return false;
-  if (a.lo.Hon != nullptr && (a.lo.Htg == nullptr || a.lo.dH == nullptr)) return false;
-  if (((uintptr_t)a.Pon.wv | (uintptr_t)a.Pon.wa | (uintptr_t)a.Ptg.wv | (uintptr_t)a.Ptg.wa) & 15) return false;
-  if (((uintptr_t)a.Hon | (uintptr_t)a.Htg | (uintptr_t)a.dH | (uintptr_t)a.lo.Hon | (uintptr_t)a.lo.Htg |
-       (uintptr_t)a.lo.dH) & 7)
-    return false;
-  *lds = dist_head_lds(a.A, a.N);
+// head_io_ok plus what the C51 / QR launchers share of their own: the N range, the stream width
+// and the LDS bound; the LDS in `lds`.
+static inline bool dist_head_args_ok(const HeadIO& a, int N, size_t* lds) {
+  if (!head_io_ok(a) || N < 2 || N > 64 || a.hidden != DIST_HS) return false;
+  *lds = dist_head_lds(a.A, N);
   return *lds <= 65536;     // (A + 1) N <= 1706 logits per row
 }
 

@@ -4,6 +4,9 @@
 // weight gradient (head_wgrad_body, run by csrc/sumtree.hip head_wgrad_prio_kernel
 // and fc_wgrad_head_prio_kernel beside the priority write-back).
 #pragma once
+#include <initializer_list>
+#include <type_traits>
+
 #include "apex_common.h"
 
 #define HEAD_MAXA 32
@@ -33,6 +36,50 @@ struct IsNorm {
   double* out;           // null: off
   unsigned long long* valid_count;   // DP: += rows of this batch the rank drew (weight > 0); or null
 };
+
+// What every struct-argument loss head takes (C51Args, QRArgs, IqnArgs, MdqnArgs: their first
+// member `io`; ops/_lib.py HeadIO is the mirror).  Row plans: Hon [2B] = the online net at S_t,
+// S_t+n and Htg [B] = the target net at S_t+n; the Munchausen head Hon [B] = S_t and Htg [2B] =
+// S_t+n, S_t.
+struct HeadIO {
+  const bf16_t* Hon;    // [.][2 hidden]
+  const bf16_t* Htg;
+  HeadParams Pon, Ptg;
+  const int32_t* act;
+  const float* rew;
+  const float* gam;
+  const float* isw;     // IS weights, or null (1)
+  int B, A, hidden;
+  float grad_scale;
+  float* td_abs;
+  float* loss;
+  float* q_out;         // [B][A] q(S_t), or null
+  bf16_t* dH;           // [B][2 hidden]
+  float* dhead;
+  float* zero_ptr;      // head-gradient region zeroed for the head weight gradient (or null)
+  int zero_n;
+  HeadLo lo;
+  IsNorm isn;
+};
+static_assert(std::is_standard_layout_v<HeadIO> && std::is_trivially_copyable_v<HeadIO>);
+
+// The pointer / shape checks the head launchers share; each adds the conditions of its own.
+static inline bool head_io_ok(const HeadIO& a) {
+  if (a.A < 1 || a.A > HEAD_MAXA || a.B < 1) return false;
+  if (a.Hon == nullptr || a.Htg == nullptr || a.act == nullptr || a.rew == nullptr || a.gam == nullptr ||
+      a.td_abs == nullptr || a.loss == nullptr || a.dH == nullptr || a.dhead == nullptr)
+    return false;
+  for (const HeadParams& P : {a.Pon, a.Ptg})
+    if (P.wv == nullptr || P.bv == nullptr || P.wa == nullptr || P.ba == nullptr) return false;
+  if ((a.isn.out != nullptr || a.isn.valid_count != nullptr) && a.isw == nullptr) return false;
+  if (a.lo.Hon != nullptr && (a.lo.Htg == nullptr || a.lo.dH == nullptr)) return false;
+  // float4 weight loads; 8-byte row loads / stores of the activation and gradient planes
+  if (((uintptr_t)a.Pon.wv | (uintptr_t)a.Pon.wa | (uintptr_t)a.Ptg.wv | (uintptr_t)a.Ptg.wa) & 15) return false;
+  if (((uintptr_t)a.Hon | (uintptr_t)a.Htg | (uintptr_t)a.dH | (uintptr_t)a.lo.Hon | (uintptr_t)a.lo.Htg |
+       (uintptr_t)a.lo.dH) & 7)
+    return false;
+  return true;
+}
 
 // NPL consecutive fp32 weights (16-B aligned: NPL is 4 or 8) as float4 loads
 template <int NPL>

@@ -43,35 +43,21 @@ struct IqnEmbed {
 };
 
 struct IqnArgs {
-  const bf16_t* Hon;    // [2B][2 HS]
-  const bf16_t* Htg;    // [B][2 HS]
-  HeadParams Pon, Ptg;
-  IqnEmbed Eon, Etg;
-  const int32_t* act;
-  const float* rew;
-  const float* gam;
-  const float* isw;     // null: weights off
-  int B, A, N, hidden;
-  float kappa, grad_scale;
+  HeadIO io;            // Hon [2B], Htg [B]; dhead [B][(A + 1) N]
+  IqnEmbed Eon, Etg;    // (right behind io: with them after `base` iqn_head_kernel measured 0.5 % slower at A = 4)
+  int N;
+  float kappa;
   uint64_t seed_q;
   const int64_t* ctr;   // draw counter; u = ctr - base
   const int64_t* base;  // null: 0
-  float* td_abs;
-  float* loss;
-  float* q_out;         // [B][A] or null
   float* tau_out;       // [B][3][N] or null
-  bf16_t* dH;           // [B][2 HS]
-  float* dhead;         // [B][(A + 1) N]
   float* dpre;          // [B][N][2 HS]
   float* cosT;          // [B][N][64]
   float* xg;            // [B][2 HS]
   float* gsum;          // [B]
-  float* zero_ptr;
-  int zero_n;
-  HeadLo lo;
-  IsNorm isn;
   int max_blocks;       // <= 0: the CU count
 };
+static_assert(std::is_standard_layout_v<IqnArgs> && std::is_trivially_copyable_v<IqnArgs>);
 
 // cos(pi i tau): the fp32 product i tau rounds; its exact residual (one fma) enters to first order
 __device__ __forceinline__ float iqn_cos(int i, float tau) {
@@ -200,11 +186,12 @@ static inline size_t iqn_head_lds(int A, int N) {
   return (size_t)(3 * DIST_SPB * (2 * DIST_HS + Jp + 64) + (DIST_NT / 64) * Jp + DIST_SPB * N * IQN_E) * sizeof(float);
 }
 
-__global__ void __launch_bounds__(DIST_NT) iqn_head_kernel(IqnArgs a) {
+__global__ void __launch_bounds__(DIST_NT) iqn_head_kernel(IqnArgs ka) {
+  const HeadIO& a = ka.io;
   extern __shared__ __attribute__((aligned(16))) float iqn_smem[];
   constexpr int HS = DIST_HS, ROW = 2 * HS, SPB = DIST_SPB, NR = 3 * SPB, NW = DIST_NT / 64;
   const int tid0 = threadIdx.x;
-  const int B = a.B, A = a.A, N = a.N, J = (A + 1) * N;
+  const int B = a.B, A = a.A, N = ka.N, J = (A + 1) * N;
   const int Jp = (J + 3) & ~3;
   float* Hs = iqn_smem;                    // [NR][ROW]: rows s (S_t), SPB + s (online S_t+n), 2 SPB + s (target)
   float* Ls = Hs + NR * ROW;               // [NR][Jp] logits (no biases); rows s later hold the dhead rows
@@ -214,7 +201,7 @@ __global__ void __launch_bounds__(DIST_NT) iqn_head_kernel(IqnArgs a) {
   const bool split = a.lo.Hon != nullptr;
 
   dist_head_side(a, tid0, tid0 & 63, tid0 >> 6);
-  int64_t u = a.ctr[0] - (a.base != nullptr ? a.base[0] : 0);
+  int64_t u = ka.ctr[0] - (ka.base != nullptr ? ka.base[0] : 0);
   u = u < 0 ? 0 : u;
   const uint64_t cword = 64ull * (uint64_t)u;
   const float invA = 1.0f / (float)A;
@@ -235,8 +222,8 @@ __global__ void __launch_bounds__(DIST_NT) iqn_head_kernel(IqnArgs a) {
       const int b = min(b0 + s, B - 1);
       float tau = 0.f;
       if (k < N) {
-        tau = apex_uniform(a.seed_q, cword, (uint64_t)(3 * b + set) * 64ull + (uint64_t)k);
-        if (a.tau_out != nullptr && b0 + s < B) a.tau_out[((int64_t)b * 3 + set) * N + k] = tau;
+        tau = apex_uniform(ka.seed_q, cword, (uint64_t)(3 * b + set) * 64ull + (uint64_t)k);
+        if (ka.tau_out != nullptr && b0 + s < B) ka.tau_out[((int64_t)b * 3 + set) * N + k] = tau;
       }
       Ts[r * 64 + k] = tau;
     }
@@ -245,18 +232,18 @@ __global__ void __launch_bounds__(DIST_NT) iqn_head_kernel(IqnArgs a) {
     auto do_row = [&](int r, const HeadParams& P) {
       const int s = r % SPB;
       __syncthreads();                     // Ts staged; slot s and Pw free
-      const bool keep = r < SPB && b0 + s < B && a.cosT != nullptr;
-      iqn_fill_cos(Ts + r * 64, N, Cs + s * N * IQN_E, keep ? a.cosT + (int64_t)(b0 + s) * N * IQN_E : nullptr, tid);
+      const bool keep = r < SPB && b0 + s < B && ka.cosT != nullptr;
+      iqn_fill_cos(Ts + r * 64, N, Cs + s * N * IQN_E, keep ? ka.cosT + (int64_t)(b0 + s) * N * IQN_E : nullptr, tid);
       __syncthreads();
       // (the PRE form beside this kernel's other live values left 17 registers in scratch)
       iqn_row_logits<false>(wev, wea, bev, bea, P, Hs[r * ROW + tid], Hs[r * ROW + HS + tid], Cs + s * N * IQN_E, A, N,
                             Jp, Pw, Ls + r * Jp, tid, lane, wv);
     };
     __syncthreads();                       // (also keeps the 128 weight loads out of the staging code)
-    iqn_load_we(a.Etg, tid, wev, wea, bev, bea);
+    iqn_load_we(ka.Etg, tid, wev, wea, bev, bea);
 #pragma unroll 1
     for (int r = 2 * SPB; r < NR; ++r) do_row(r, a.Ptg);
-    iqn_load_we(a.Eon, tid, wev, wea, bev, bea);
+    iqn_load_we(ka.Eon, tid, wev, wea, bev, bea);
 #pragma unroll 1
     for (int ri = 0; ri < 2 * SPB; ++ri) do_row(ri < SPB ? SPB + ri : ri - SPB, a.Pon);
 
@@ -270,7 +257,7 @@ __global__ void __launch_bounds__(DIST_NT) iqn_head_kernel(IqnArgs a) {
       const int a_b = a.act[b];
       const float rew_b = a.rew[b], gam_b = a.gam[b];
       const float w_b = a.isw != nullptr ? a.isw[b] : 1.f;
-      const float kappa = a.kappa;
+      const float kappa = ka.kappa;
       int astar = 0;
       {
         const IqnRow rn = iqn_row(Ls + (SPB + s) * Jp, a.Pon, A, N, lane);
@@ -314,7 +301,7 @@ __global__ void __launch_bounds__(DIST_NT) iqn_head_kernel(IqnArgs a) {
       if (live && lane == 0) {
         a.td_abs[b] = fabsf(et - q_sa);
         a.loss[b] = w_b * ls;
-        if (a.gsum != nullptr) a.gsum[b] = gs;
+        if (ka.gsum != nullptr) ka.gsum[b] = gs;
       }
       dist_head_store_dhead(g, live, valid, a_b, A, N, lane, Ls + s * Jp, a.dhead + (int64_t)b * J);
     }
@@ -322,7 +309,7 @@ __global__ void __launch_bounds__(DIST_NT) iqn_head_kernel(IqnArgs a) {
 
     // ---- backward of set 0 (slot s holds the cosines of set 0).  The online We is loaded again: kept
     // live across wave s's finish above it cost 7 registers of scratch; the second read is an L2 hit
-    iqn_load_we(a.Eon, tid, wev, wea, bev, bea);
+    iqn_load_we(ka.Eon, tid, wev, wea, bev, bea);
 #pragma unroll 1
     for (int s = 0; s < SPB; ++s) {
       if (b0 + s >= B) break;
@@ -334,7 +321,7 @@ __global__ void __launch_bounds__(DIST_NT) iqn_head_kernel(IqnArgs a) {
       for (int j = 0; j < A; ++j) weff = fmaf((j == a_b ? 1.f : 0.f) - invA, a.Pon.wa[j * HS + tid], weff);
       const float hv = Hs[s * ROW + tid], ha = Hs[s * ROW + HS + tid];
       float dhv = 0.f, dha = 0.f, xgv = 0.f, xga = 0.f;
-      float* dp = a.dpre + (int64_t)b * N * ROW;
+      float* dp = ka.dpre + (int64_t)b * N * ROW;
 #pragma unroll 1
       for (int k = 0; k < N; ++k) {
         const float g = D[k];
@@ -349,8 +336,8 @@ __global__ void __launch_bounds__(DIST_NT) iqn_head_kernel(IqnArgs a) {
         xgv = fmaf(g, hv * fv, xgv);
         xga = fmaf(g, ha * fa, xga);
       }
-      a.xg[(int64_t)b * ROW + tid] = xgv;
-      a.xg[(int64_t)b * ROW + HS + tid] = xga;
+      ka.xg[(int64_t)b * ROW + tid] = xgv;
+      ka.xg[(int64_t)b * ROW + HS + tid] = xga;
       const float mv = hv > 0.f ? dhv : 0.f, ma = ha > 0.f ? dha : 0.f;
       const bf16_t hv16 = f32_to_bf16(mv), ha16 = f32_to_bf16(ma);
       a.dH[(int64_t)b * ROW + tid] = hv16;
@@ -363,9 +350,13 @@ __global__ void __launch_bounds__(DIST_NT) iqn_head_kernel(IqnArgs a) {
   }
 }
 
+static inline bool iqn_embed_ok(const IqnEmbed& E) {
+  return E.w != nullptr && E.b != nullptr && ((uintptr_t)E.w & 15) == 0;
+}
+
 static inline bool iqn_ptrs16(const HeadParams& P, const IqnEmbed& E) {
-  return (((uintptr_t)P.wv | (uintptr_t)P.wa | (uintptr_t)E.w) & 15) == 0 && P.bv != nullptr && P.ba != nullptr &&
-         E.b != nullptr && P.wv != nullptr && P.wa != nullptr && E.w != nullptr;
+  return (((uintptr_t)P.wv | (uintptr_t)P.wa) & 15) == 0 && P.bv != nullptr && P.ba != nullptr && P.wv != nullptr &&
+         P.wa != nullptr && iqn_embed_ok(E);
 }
 
 static int iqn_cu_count() {
@@ -381,18 +372,11 @@ static int iqn_cu_count() {
 }
 
 APEX_EXPORT int apex_iqn_head(IqnArgs a, hipStream_t st) {
-  if (a.A < 1 || a.A > HEAD_MAXA || a.B < 1 || a.N < 2 || a.N > 64 || a.hidden != DIST_HS || !(a.kappa > 0.f))
+  if (!head_io_ok(a.io) || a.N < 2 || a.N > 64 || a.io.hidden != DIST_HS || !(a.kappa > 0.f))
     return (int)hipErrorInvalidValue;
-  if ((a.isn.out != nullptr || a.isn.valid_count != nullptr) && a.isw == nullptr) return (int)hipErrorInvalidValue;
-  if (a.lo.Hon != nullptr && (a.lo.Htg == nullptr || a.lo.dH == nullptr)) return (int)hipErrorInvalidValue;
-  if (!iqn_ptrs16(a.Pon, a.Eon) || !iqn_ptrs16(a.Ptg, a.Etg)) return (int)hipErrorInvalidValue;
-  if (((uintptr_t)a.Hon | (uintptr_t)a.Htg | (uintptr_t)a.dH | (uintptr_t)a.lo.Hon | (uintptr_t)a.lo.Htg |
-       (uintptr_t)a.lo.dH) & 7)
-    return (int)hipErrorInvalidValue;
-  if (a.ctr == nullptr || a.dpre == nullptr || a.xg == nullptr || a.dhead == nullptr || a.dH == nullptr ||
-      a.td_abs == nullptr || a.loss == nullptr)
-    return (int)hipErrorInvalidValue;
-  const size_t lds = iqn_head_lds(a.A, a.N);
+  if (!iqn_embed_ok(a.Eon) || !iqn_embed_ok(a.Etg)) return (int)hipErrorInvalidValue;
+  if (a.ctr == nullptr || a.dpre == nullptr || a.xg == nullptr) return (int)hipErrorInvalidValue;
+  const size_t lds = iqn_head_lds(a.io.A, a.N);
   if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
   static size_t lds_set = 64 * 1024;      // raised once per size: not again inside a captured step
   if (lds > lds_set) {
@@ -401,7 +385,7 @@ APEX_EXPORT int apex_iqn_head(IqnArgs a, hipStream_t st) {
     if (e != hipSuccess) return (int)e;
     lds_set = lds;
   }
-  const int npairs = (a.B + DIST_SPB - 1) / DIST_SPB;
+  const int npairs = (a.io.B + DIST_SPB - 1) / DIST_SPB;
   const int cap = a.max_blocks > 0 ? a.max_blocks : iqn_cu_count();
   const int grid = npairs < cap ? npairs : cap;
   iqn_head_kernel<<<grid, DIST_NT, lds, st>>>(a);

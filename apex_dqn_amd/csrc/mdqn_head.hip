@@ -23,27 +23,13 @@
 #include "head_common.h"
 
 struct MdqnArgs {
-  const bf16_t* Hon;
-  const bf16_t* Htg;
-  HeadParams Pon, Ptg;
-  const int32_t* act;
-  const float* rew;
-  const float* gam;
-  const float* isw;      // IS weights, or null (1)
-  int B, A, huber, hidden;
-  float kappa, alpha, tau, clip, grad_scale;
-  float* td_abs;
-  float* loss;
-  float* q_out;          // or null
+  HeadIO io;             // Hon [B], Htg [2B]; dhead [B][1 + A]
+  int huber;
+  float kappa, alpha, tau, clip;
   float* aux;            // [B, 2] (bonus, vsoft), or null
-  bf16_t* dH;
-  float* dhead;
-  float* zero_ptr;       // head-gradient region to zero (or null)
-  int zero_n;
-  HeadLo lo;
-  IsNorm isn;
   HeadPart hp;           // must be all null: the deferred fc epilogue is not taken (see mdqn_head_kernel)
 };
+static_assert(std::is_standard_layout_v<MdqnArgs> && std::is_trivially_copyable_v<MdqnArgs>);
 
 // ddqn_head_body<HS, MAXA, true> (head_common.h) with the side job of ddqn_head_kernel's second wave.  The body
 // is instantiated with its HeadPart argument taken from the launch arguments, as ddqn_head_kernel does, although
@@ -51,12 +37,13 @@ struct MdqnArgs {
 // 0's head_q as it does in ddqn_head_kernel, and q_out is bit-equal to that kernel's (with the path folded away
 // two products of the value stream's dot product contract differently, one unit in the last place of q).
 template <int HS, int MAXA>
-__global__ void __launch_bounds__(192) mdqn_head_kernel(MdqnArgs a) {
+__global__ void __launch_bounds__(192) mdqn_head_kernel(MdqnArgs ka) {
+  const HeadIO& a = ka.io;
   float ad;
-  const MdqnTarget mt{a.alpha, a.tau, a.clip, a.aux};
-  const bool w0 = ddqn_head_body<HS, MAXA, true>(a.Hon, a.Htg, a.Pon, a.Ptg, a.act, a.rew, a.gam, a.isw, a.B, a.A, a.huber,
-                                                 a.kappa, a.grad_scale, a.td_abs, a.loss, a.q_out, a.dH, a.dhead, a.zero_ptr,
-                                                 a.zero_n, &ad, a.lo, a.hp, &mt);
+  const MdqnTarget mt{ka.alpha, ka.tau, ka.clip, ka.aux};
+  const bool w0 = ddqn_head_body<HS, MAXA, true>(a.Hon, a.Htg, a.Pon, a.Ptg, a.act, a.rew, a.gam, a.isw, a.B, a.A, ka.huber,
+                                                 ka.kappa, a.grad_scale, a.td_abs, a.loss, a.q_out, a.dH, a.dhead, a.zero_ptr,
+                                                 a.zero_n, &ad, a.lo, ka.hp, &mt);
   // batch-max IS normalisation: block 0's second wave (csrc/ddqn_head.hip, same semantics)
   if (!w0 && (a.isn.out != nullptr || a.isn.valid_count != nullptr) && blockIdx.x == 0 && (threadIdx.x >> 6) == 1) {
     float m = 0.f;
@@ -76,21 +63,17 @@ __global__ void __launch_bounds__(192) mdqn_head_kernel(MdqnArgs a) {
 }
 
 APEX_EXPORT int apex_mdqn_head(MdqnArgs a, hipStream_t st) {
-  if (a.A < 1 || a.A > HEAD_MAXA || a.B < 1 || a.hidden != 512) return (int)hipErrorInvalidValue;
+  const HeadIO& io = a.io;
+  if (!head_io_ok(io) || io.hidden != 512) return (int)hipErrorInvalidValue;
   if (!(a.tau > 0.f) || !(a.clip < 0.f) || !(a.alpha >= 0.f && a.alpha <= 1.f)) return (int)hipErrorInvalidValue;
-  if (a.Hon == nullptr || a.Htg == nullptr || a.act == nullptr || a.rew == nullptr || a.gam == nullptr ||
-      a.td_abs == nullptr || a.loss == nullptr || a.dH == nullptr || a.dhead == nullptr)
-    return (int)hipErrorInvalidValue;
-  if ((a.isn.out != nullptr || a.isn.valid_count != nullptr) && a.isw == nullptr) return (int)hipErrorInvalidValue;
-  if (a.lo.Hon != nullptr && (a.lo.Htg == nullptr || a.lo.dH == nullptr)) return (int)hipErrorInvalidValue;
-  if (a.zero_ptr != nullptr && a.zero_n < 0) return (int)hipErrorInvalidValue;
+  if (io.zero_ptr != nullptr && io.zero_n < 0) return (int)hipErrorInvalidValue;
   if (a.hp.part != nullptr || a.hp.hon != nullptr || a.hp.hon_lo != nullptr) return (int)hipErrorInvalidValue;
-  // 16-byte row loads / stores and float4 weight loads
-  if (((uintptr_t)a.Hon | (uintptr_t)a.Htg | (uintptr_t)a.dH | (uintptr_t)a.lo.Hon | (uintptr_t)a.lo.Htg |
-       (uintptr_t)a.lo.dH | (uintptr_t)a.Pon.wv | (uintptr_t)a.Pon.wa | (uintptr_t)a.Ptg.wv | (uintptr_t)a.Ptg.wa) & 15)
+  // 16-byte row loads / stores (head_io_ok asks for 8)
+  if (((uintptr_t)io.Hon | (uintptr_t)io.Htg | (uintptr_t)io.dH | (uintptr_t)io.lo.Hon | (uintptr_t)io.lo.Htg |
+       (uintptr_t)io.lo.dH) & 15)
     return (int)hipErrorInvalidValue;
   // the q arrays in registers: 8 actions keep the kernel free of scratch (as ddqn_head_kernel)
-  if (a.A <= 8) mdqn_head_kernel<512, 8><<<a.B, 192, 0, st>>>(a);
-  else mdqn_head_kernel<512, HEAD_MAXA><<<a.B, 192, 0, st>>>(a);
+  if (io.A <= 8) mdqn_head_kernel<512, 8><<<io.B, 192, 0, st>>>(a);
+  else mdqn_head_kernel<512, HEAD_MAXA><<<io.B, 192, 0, st>>>(a);
   APEX_CHECK_LAUNCH();
 }

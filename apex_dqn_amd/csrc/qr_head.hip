@@ -35,36 +35,23 @@
 #include "dist_head.h"
 
 struct QRArgs {
-  const bf16_t* Hon;    // [2B][2 HS]
-  const bf16_t* Htg;    // [B][2 HS]
-  HeadParams Pon, Ptg;
-  const int32_t* act;
-  const float* rew;
-  const float* gam;
-  const float* isw;     // null: weights off
-  int B, A, N, hidden;
-  float kappa, grad_scale;
-  float* td_abs;
-  float* loss;
-  float* q_out;         // [B][A] q(S_t) = mean of the quantiles, or null
-  bf16_t* dH;           // [B][2 HS]
-  float* dhead;         // [B][(A + 1) N]
-  float* zero_ptr;      // head-gradient region zeroed for the head weight gradient
-  int zero_n;
-  HeadLo lo;
-  IsNorm isn;
+  HeadIO io;            // Hon [2B], Htg [B]; q_out the q(S_t) = mean of the quantiles; dhead [B][(A + 1) N]
+  int N;
+  float kappa;
 };
+static_assert(std::is_standard_layout_v<QRArgs> && std::is_trivially_copyable_v<QRArgs>);
 
 // this lane's quantile of action a (0 in a lane past N)
 __device__ __forceinline__ float qr_theta(const DistRow& r, int a, int N, int lane) {
   return lane < N ? r.v + (r.L[N + a * N + lane] + r.ba[a * N + lane]) - r.mean : 0.f;
 }
 
-__global__ void __launch_bounds__(DIST_NT) qr_head_kernel(QRArgs a) {
+__global__ void __launch_bounds__(DIST_NT) qr_head_kernel(QRArgs ka) {
+  const HeadIO& a = ka.io;
   extern __shared__ __attribute__((aligned(16))) float qr_smem[];
   constexpr int HS = DIST_HS, ROW = 2 * HS, SPB = DIST_SPB, NR = 3 * SPB;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int B = a.B, A = a.A, N = a.N, AN = A * N, J = N + AN;
+  const int B = a.B, A = a.A, N = ka.N, AN = A * N, J = N + AN;
   const int Jp = (J + 3) & ~3;
   float* Hs = qr_smem;                   // [NR][ROW]: rows s (S_t), SPB + s (online S_t+n), 2 SPB + s (target)
   float* Ls = qr_smem + NR * ROW;        // [NR][Jp] logits (no biases); rows s later hold the dhead rows
@@ -74,7 +61,7 @@ __global__ void __launch_bounds__(DIST_NT) qr_head_kernel(QRArgs a) {
   dist_head_side(a, tid, lane, wv);
   dist_head_stage(a, Hs, b0, tid, split);
   __syncthreads();
-  dist_head_logits(a, Hs, Ls, Jp, lane, wv);
+  dist_head_logits(a, N, Hs, Ls, Jp, lane, wv);
   __syncthreads();
 
   // ---- phase 2: wave s finishes sample s (lane = quantile)
@@ -87,7 +74,7 @@ __global__ void __launch_bounds__(DIST_NT) qr_head_kernel(QRArgs a) {
     const int a_b = a.act[b];
     const float rew_b = a.rew[b], gam_b = a.gam[b];
     const float w_b = a.isw != nullptr ? a.isw[b] : 1.f;
-    const float kappa = a.kappa;
+    const float kappa = ka.kappa;
     // double DQN: a* from the online net at S_t+n (first maximum wins)
     int astar = 0;
     {
@@ -140,13 +127,13 @@ __global__ void __launch_bounds__(DIST_NT) qr_head_kernel(QRArgs a) {
   }
   __syncthreads();
 
-  dist_head_dh(a, Hs, Ls, Jp, b0, tid, split);
+  dist_head_dh(a, N, Hs, Ls, Jp, b0, tid, split);
 }
 
 APEX_EXPORT int apex_qr_head(QRArgs a, hipStream_t st) {
   size_t lds = 0;
-  if (!dist_head_args_ok(a, &lds) || !(a.kappa > 0.f)) return (int)hipErrorInvalidValue;
-  const int grid = (a.B + DIST_SPB - 1) / DIST_SPB;
+  if (!dist_head_args_ok(a.io, a.N, &lds) || !(a.kappa > 0.f)) return (int)hipErrorInvalidValue;
+  const int grid = (a.io.B + DIST_SPB - 1) / DIST_SPB;
   qr_head_kernel<<<grid, DIST_NT, lds, st>>>(a);
   APEX_CHECK_LAUNCH();
 }

@@ -557,6 +557,49 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
                           **self._lo(dh_lo=self.dH_lo, x_lo=sp and self.y3_lo[:B]))
         self._fc_slots = 0
 
+    def _head_fc_weight_grads(self, prio) -> None:
+        """The head and fc weight gradients with the priority write-back ``prio``: one launch on the HIP backend
+        (csrc/sumtree.hip fc_wgrad_head_prio_kernel), or the implicit head's own launches."""
+        if self.implicit:
+            return self._iqn_weight_grads(prio)
+        sp, B, G = self.split, self.B, self.G
+        self._fc_slots = self.ops.fc_head_wgrad(self.dH, self.y3[:B], G["wfc"], G["bfc"], self.h, self.dhead, G, prio,
+                                                norm=(self.norm_part, 0) if self._fuse_norm else None,
+                                                **self._lo(dh_lo=self.dH_lo, x_lo=sp and self.y3_lo[:B],
+                                                           Hon_lo=self.h_lo))
+
+    def _loss_head(self, isw) -> None:
+        """The step's loss head on ``h``: td_abs, loss_b, dH and dhead.  Every head takes the sampled act / rew /
+        gam, ``isw``, the 1 / (B world) gradient scale, the four outputs and ``zero`` / ``isn`` / ``lo``; an arm
+        adds the op and what is its own.  Rows of ``h``: [0, k) the first net's (``_rows_first``), the rest the
+        second's."""
+        B, rt, ops, S, sp, k = self.B, self.rt, self.ops, self.S, self.split, self._rows_first
+        h = (self.h[:k], self.h[k:], self._head_params(self.P), self._head_params(self.T))
+        data = (S["act"], S["rew"], S["gam"], isw)
+        out = (1.0 / (B * self.world), self.td_abs, self.loss_b, self.dH, self.dhead)
+        kw = dict(zero=self.g_head_region, isn=self._isn(),
+                  **self._lo(lo=sp and (self.h_lo[:k], self.h_lo[k:], self.dH_lo)))
+        if self.munchausen:
+            # Munchausen target: online S_t rows, target S_t+n and S_t rows (csrc/mdqn_head.hip)
+            mk = self.cfg.munchausen_kw()
+            ops.mdqn_head(*h, *data, rt.loss == "huber", rt.huber_delta, mk["alpha"], mk["tau"], mk["clip"], *out,
+                          aux=self.mdqn_aux, **kw)
+        elif self.implicit:
+            # implicit quantiles: the quantile Huber loss at fractions drawn for this update (the index read on
+            # the device: replay.ctr - upd_base, as the noisy layers' compose reads it)
+            ops.iqn_head(*h, self._embed(self.P), self._embed(self.T), *data, self.N, rt.huber_delta, out[0],
+                         self._seed_q, self.replay.ctr, self.upd_base, *out[1:], self.iqn_ws, tau_out=self.tau_out,
+                         **kw)
+        elif self.N >= 2 and self.quantile:
+            # quantile regression: the quantile Huber loss, kappa = huber_delta (Runtime.loss, v_min / v_max
+            # do not apply)
+            ops.qr_head(*h, *data, self.N, rt.huber_delta, *out, **kw)
+        elif self.N >= 2:
+            # categorical projection + cross-entropy (Runtime.loss / huber_delta do not apply)
+            ops.c51_head(*h, *data, self.N, rt.v_min, rt.v_max, *out, **kw)
+        else:
+            ops.head(*h, *data, rt.loss == "huber", rt.huber_delta, *out, **kw)
+
     def _head_params(self, V):
         if self.noisy and (V is self.P or V is self.T):     # the effective head parameters of that net
             V = self.EP if V is self.P else self.ET
@@ -574,8 +617,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
     def _seg1(self) -> None:
         """(sample), forward (online+target), loss, head + fc weight gradients with the
         priority write-back."""
-        B, rt, ops = self.B, self.rt, self.ops
-        ops.prepare(self.Pb)
+        self.ops.prepare(self.Pb)
         if not self._presample or self._sample_ver != self.replay.version:
             self._sample()
         S = self.S
@@ -584,57 +626,12 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         # conv1 reads the uint8 frame stacks straight from the replay ring by slot
         self.forward_all(defer_head=self._defer_fc_epilogue)
         self._mark("forward")
-        isw = S["weights"] if self._isw else None
-        sp = self.split
-        if self.munchausen:
-            # Munchausen target: online S_t rows, target S_t+n and S_t rows (csrc/mdqn_head.hip)
-            mk = self.cfg.munchausen_kw()
-            ops.mdqn_head(self.h[:B], self.h[B:], self._head_params(self.P), self._head_params(self.T), S["act"],
-                          S["rew"], S["gam"], isw, rt.loss == "huber", rt.huber_delta, mk["alpha"], mk["tau"],
-                          mk["clip"], 1.0 / (B * self.world), self.td_abs, self.loss_b, self.dH, self.dhead,
-                          aux=self.mdqn_aux, zero=self.g_head_region, isn=self._isn(),
-                          **self._lo(lo=sp and (self.h_lo[:B], self.h_lo[B:], self.dH_lo)))
-        elif self.implicit:
-            # implicit quantiles: the quantile Huber loss at fractions drawn for this update (the index read on
-            # the device: replay.ctr - upd_base, as the noisy layers' compose reads it)
-            ops.iqn_head(self.h[:2 * B], self.h[2 * B:], self._head_params(self.P), self._head_params(self.T),
-                         self._embed(self.P), self._embed(self.T), S["act"], S["rew"], S["gam"], isw, self.N,
-                         rt.huber_delta, 1.0 / (B * self.world), self._seed_q, self.replay.ctr, self.upd_base,
-                         self.td_abs, self.loss_b, self.dH, self.dhead, self.iqn_ws, tau_out=self.tau_out,
-                         zero=self.g_head_region, isn=self._isn(),
-                         **self._lo(lo=sp and (self.h_lo[:2 * B], self.h_lo[2 * B:], self.dH_lo)))
-        elif self.N >= 2 and self.quantile:
-            # quantile regression: the quantile Huber loss, kappa = huber_delta (Runtime.loss, v_min / v_max
-            # do not apply)
-            ops.qr_head(self.h[:2 * B], self.h[2 * B:], self._head_params(self.P), self._head_params(self.T),
-                        S["act"], S["rew"], S["gam"], isw, self.N, rt.huber_delta, 1.0 / (B * self.world),
-                        self.td_abs, self.loss_b, self.dH, self.dhead, zero=self.g_head_region, isn=self._isn(),
-                        **self._lo(lo=sp and (self.h_lo[:2 * B], self.h_lo[2 * B:], self.dH_lo)))
-        elif self.N >= 2:
-            # categorical projection + cross-entropy (Runtime.loss / huber_delta do not apply)
-            ops.c51_head(self.h[:2 * B], self.h[2 * B:], self._head_params(self.P), self._head_params(self.T),
-                         S["act"], S["rew"], S["gam"], isw, self.N, rt.v_min, rt.v_max, 1.0 / (B * self.world),
-                         self.td_abs, self.loss_b, self.dH, self.dhead, zero=self.g_head_region, isn=self._isn(),
-                         **self._lo(lo=sp and (self.h_lo[:2 * B], self.h_lo[2 * B:], self.dH_lo)))
-        else:
-            ops.head(self.h[:2 * B], self.h[2 * B:], self._head_params(self.P), self._head_params(self.T), S["act"],
-                     S["rew"], S["gam"], isw, rt.loss == "huber", rt.huber_delta, 1.0 / (B * self.world),
-                     self.td_abs, self.loss_b, self.dH, self.dhead, zero=self.g_head_region,
-                     isn=self._isn(), **self._lo(lo=sp and (self.h_lo[:2 * B], self.h_lo[2 * B:], self.dH_lo)))
+        self._loss_head(S["weights"] if self._isw else None)
         self._mark("head")
         prio = (self.replay, S["idx"], S["gen"], self.td_abs)
         if self._branched or self._dp:
             return           # the weight gradients: _seg2_branched / the DP step (dp_step.py)
-        # fc wgrad + head wgrad + priority write-back: one launch on the HIP backend
-        # (csrc/sumtree.hip fc_wgrad_head_prio_kernel)
-        nrm = (self.norm_part, 0) if self._fuse_norm else None
-        if self.implicit:
-            self._iqn_weight_grads(prio)
-        else:
-            self._fc_slots = ops.fc_head_wgrad(self.dH, self.y3[:B], self.G["wfc"], self.G["bfc"], self.h,
-                                               self.dhead, self.G, prio, norm=nrm,
-                                               **self._lo(dh_lo=self.dH_lo, x_lo=sp and self.y3_lo[:B],
-                                                          Hon_lo=self.h_lo))
+        self._head_fc_weight_grads(prio)
         self._noisy_sigma_grad()
         if self._comm_bf16:
             cut = self.layout.offsets["wfc"]
@@ -767,15 +764,6 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         main, side = torch.cuda.current_stream(self.device), self._wg_stream
         jobs = []
         prio = (self.replay, S["idx"], S["gen"], self.td_abs)
-        nrm = (self.norm_part, 0) if self._fuse_norm else None
-
-        def fc_wgrad():
-            if self.implicit:
-                return self._iqn_weight_grads(prio)
-            self._fc_slots = ops.fc_head_wgrad(self.dH, self.y3[:B], G["wfc"], G["bfc"], self.h, self.dhead, G,
-                                               prio, norm=nrm,
-                                               **self._lo(dh_lo=self.dH_lo, x_lo=sp and self.y3_lo[:B],
-                                                          Hon_lo=self.h_lo))
 
         # auto: fp32-class at >= 256 rows, 2,681 / 2,679 vs 2,654 / 2,665 steps/s; bf16 and
         # 74 rows lose (4,264 / 4,214 vs 4,367 / 4,403; 6,077 vs 6,415),
@@ -794,11 +782,11 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         if fc_main:
             # fc dgrad and the fc weight gradient back to back on the main stream, each on
             # the whole chip; the branch forks after them (its first wait, conv3's wgrad)
-            fc_wgrad()
+            self._head_fc_weight_grads(prio)
         else:
             side.wait_event(ev)
             with torch.cuda.stream(side):
-                fc_wgrad()
+                self._head_fc_weight_grads(prio)
                 # noisy layers: the sigma gradients right behind the fc / head weight gradients
                 # on the branch, which has slack beside the data-gradient chain
                 self._noisy_sigma_grad()

@@ -53,25 +53,27 @@ class HeadPart(ctypes.Structure):
 
 
 class IsNorm(ctypes.Structure):
-    """Batch-max IS normalisation output of the head kernel (``IsNorm``, csrc/ddqn_head.hip)."""
+    """Batch-max IS normalisation output of the head kernel (``IsNorm``, csrc/head_common.h)."""
     _fields_ = [("wscale", c_p), ("out", c_p), ("valid_count", c_p)]
+
+
+class HeadIO(ctypes.Structure):
+    """What every struct-argument loss head takes (``HeadIO``, csrc/head_common.h): the first member ``io`` of
+    ``C51Args``, ``QRArgs``, ``IqnArgs`` and ``MdqnArgs``."""
+    _fields_ = [("Hon", c_p), ("Htg", c_p), ("Pon", HeadParams), ("Ptg", HeadParams), ("act", c_p), ("rew", c_p),
+                ("gam", c_p), ("isw", c_p), ("B", c_i), ("A", c_i), ("hidden", c_i), ("grad_scale", c_f),
+                ("td_abs", c_p), ("loss", c_p), ("q_out", c_p), ("dH", c_p), ("dhead", c_p), ("zero_ptr", c_p),
+                ("zero_n", c_i), ("lo", HeadLo), ("isn", IsNorm)]
 
 
 class C51Args(ctypes.Structure):
     """Arguments of the distributional head kernel (``C51Args``, csrc/c51_head.hip)."""
-    _fields_ = [("Hon", c_p), ("Htg", c_p), ("Pon", HeadParams), ("Ptg", HeadParams), ("act", c_p), ("rew", c_p),
-                ("gam", c_p), ("isw", c_p), ("B", c_i), ("A", c_i), ("N", c_i), ("hidden", c_i), ("vmin", c_f),
-                ("vmax", c_f), ("grad_scale", c_f), ("td_abs", c_p), ("loss", c_p), ("q_out", c_p), ("dH", c_p),
-                ("dhead", c_p), ("zero_ptr", c_p), ("zero_n", c_i), ("lo", HeadLo), ("isn", IsNorm)]
+    _fields_ = [("io", HeadIO), ("N", c_i), ("vmin", c_f), ("vmax", c_f)]
 
 
 class QRArgs(ctypes.Structure):
-    """Arguments of the quantile-regression head kernel (``QRArgs``, csrc/qr_head.hip): ``C51Args`` with
-    ``kappa`` in the place of the support."""
-    _fields_ = [("Hon", c_p), ("Htg", c_p), ("Pon", HeadParams), ("Ptg", HeadParams), ("act", c_p), ("rew", c_p),
-                ("gam", c_p), ("isw", c_p), ("B", c_i), ("A", c_i), ("N", c_i), ("hidden", c_i), ("kappa", c_f),
-                ("grad_scale", c_f), ("td_abs", c_p), ("loss", c_p), ("q_out", c_p), ("dH", c_p),
-                ("dhead", c_p), ("zero_ptr", c_p), ("zero_n", c_i), ("lo", HeadLo), ("isn", IsNorm)]
+    """Arguments of the quantile-regression head kernel (``QRArgs``, csrc/qr_head.hip)."""
+    _fields_ = [("io", HeadIO), ("N", c_i), ("kappa", c_f)]
 
 
 class IqnEmbed(ctypes.Structure):
@@ -81,12 +83,9 @@ class IqnEmbed(ctypes.Structure):
 
 class IqnArgs(ctypes.Structure):
     """Arguments of the implicit quantile head kernel (``IqnArgs``, csrc/iqn_head.hip)."""
-    _fields_ = [("Hon", c_p), ("Htg", c_p), ("Pon", HeadParams), ("Ptg", HeadParams), ("Eon", IqnEmbed),
-                ("Etg", IqnEmbed), ("act", c_p), ("rew", c_p), ("gam", c_p), ("isw", c_p), ("B", c_i), ("A", c_i),
-                ("N", c_i), ("hidden", c_i), ("kappa", c_f), ("grad_scale", c_f), ("seed_q", c_u64), ("ctr", c_p),
-                ("base", c_p), ("td_abs", c_p), ("loss", c_p), ("q_out", c_p), ("tau_out", c_p), ("dH", c_p),
-                ("dhead", c_p), ("dpre", c_p), ("cosT", c_p), ("xg", c_p), ("gsum", c_p), ("zero_ptr", c_p),
-                ("zero_n", c_i), ("lo", HeadLo), ("isn", IsNorm), ("max_blocks", c_i)]
+    _fields_ = [("io", HeadIO), ("Eon", IqnEmbed), ("Etg", IqnEmbed), ("N", c_i), ("kappa", c_f), ("seed_q", c_u64),
+                ("ctr", c_p), ("base", c_p), ("tau_out", c_p), ("dpre", c_p), ("cosT", c_p), ("xg", c_p),
+                ("gsum", c_p), ("max_blocks", c_i)]
 
 
 class IqnWgArgs(ctypes.Structure):
@@ -105,11 +104,8 @@ class IqnActorArgs(ctypes.Structure):
 
 class MdqnArgs(ctypes.Structure):
     """Arguments of the Munchausen head kernel (``MdqnArgs``, csrc/mdqn_head.hip)."""
-    _fields_ = [("Hon", c_p), ("Htg", c_p), ("Pon", HeadParams), ("Ptg", HeadParams), ("act", c_p), ("rew", c_p),
-                ("gam", c_p), ("isw", c_p), ("B", c_i), ("A", c_i), ("huber", c_i), ("hidden", c_i), ("kappa", c_f),
-                ("alpha", c_f), ("tau", c_f), ("clip", c_f), ("grad_scale", c_f), ("td_abs", c_p), ("loss", c_p),
-                ("q_out", c_p), ("aux", c_p), ("dH", c_p), ("dhead", c_p), ("zero_ptr", c_p), ("zero_n", c_i),
-                ("lo", HeadLo), ("isn", IsNorm), ("hp", HeadPart)]
+    _fields_ = [("io", HeadIO), ("huber", c_i), ("kappa", c_f), ("alpha", c_f), ("tau", c_f), ("clip", c_f),
+                ("aux", c_p), ("hp", HeadPart)]
 
 
 class NoisyNet(ctypes.Structure):
@@ -359,6 +355,15 @@ def head_lo(Hon_lo=None, Htg_lo=None, dH_lo=None) -> HeadLo:
     lo = HeadLo()
     lo.Hon, lo.Htg, lo.dH = ptr(Hon_lo), ptr(Htg_lo), ptr(dH_lo)
     return lo
+
+
+def is_norm(isn=None) -> IsNorm:
+    """``isn = (wscale, out[, count])`` of the head ops as the kernels' ``IsNorm`` (all null for None)."""
+    s = IsNorm()
+    if isn is not None:
+        s.wscale, s.out = ptr(isn[0]), ptr(isn[1])
+        s.valid_count = ptr(isn[2]) if len(isn) > 2 else None
+    return s
 
 
 def check(rc: int, what: str) -> None:

@@ -30,9 +30,15 @@ from . import reference as R
 from .switches import SW
 
 
-def join(hi: torch.Tensor, lo: Optional[torch.Tensor]) -> torch.Tensor:
-    """hi (+ lo) as fp32."""
-    return hi.float() if lo is None else hi.float() + lo.float()
+def join(hi: torch.Tensor, lo: Optional[torch.Tensor], dtype=torch.float32) -> torch.Tensor:
+    """hi (+ lo) as fp32, or as ``dtype`` (the heads' fp64 reference)."""
+    return hi.to(dtype) if lo is None else hi.to(dtype) + lo.to(dtype)
+
+
+def _head_dtype(t: torch.Tensor):
+    """fp64 when ``t`` (a head weight, or the Munchausen head's activations) is fp64 -- the tests' reference --
+    else fp32."""
+    return torch.float64 if t.dtype == torch.float64 else torch.float32
 
 
 def split_into(v: torch.Tensor, hi: torch.Tensor, lo: Optional[torch.Tensor]) -> None:
@@ -140,85 +146,31 @@ class TorchBackend:
         gradient by it; csrc/ddqn_head.hip ``IsNorm``; ``out`` may be None), and ``count``
         (int64) += the rows with a non-zero weight (DP: the rows this rank drew)."""
         B = act.shape[0]
-        A = Pon["wa"].shape[0]
-        Hon = join(Hon, None if lo is None else lo[0])
-        Htg = join(Htg, None if lo is None else lo[1])
-
-        HS = Pon["wv"].numel()   # stream width (512 NatureCNN, 256 IMPALA)
-
-        def q_of(h, P):
-            v = h[:, :HS] @ P["wv"].float() + P["bv"].float()
-            a = h[:, HS:] @ P["wa"].float().t() + P["ba"].float()
-            return v[:, None] + a - a.mean(1, keepdim=True)
-
-        q_t = q_of(Hon[:B], Pon)
-        q_n = q_of(Hon[B:2 * B], Pon)
-        q_g = q_of(Htg[:B], Ptg)
+        dt = torch.float32
+        lo = lo if lo is not None else (None, None, None)
+        Hon, Htg = join(Hon, lo[0]), join(Htg, lo[1])
+        q_t = self._dueling_q(Hon[:B], Pon, dt)
+        q_n = self._dueling_q(Hon[B:2 * B], Pon, dt)
+        q_g = self._dueling_q(Htg[:B], Ptg, dt)
         a_star = q_n.argmax(1)
         G = rew.float() + gam.float() * q_g.gather(1, a_star[:, None]).squeeze(1)
-        q_sa = q_t.gather(1, act.long()[:, None]).squeeze(1)
-        delta = G - q_sa
-        ad = delta.abs()
-        if huber:
-            lval = torch.where(ad <= kappa, 0.5 * delta * delta, kappa * (ad - 0.5 * kappa))
-            dl = torch.where(ad <= kappa, delta, kappa * delta.sign())
-        else:
-            lval = 0.5 * delta * delta
-            dl = delta
-        w = isw.float() if isw is not None else torch.ones_like(delta)
-        dq = -w * dl * grad_scale
-        td_abs.copy_(ad)
-        loss.copy_(w * lval)
-        onehot = torch.nn.functional.one_hot(act.long(), A).float()
-        dadv = dq[:, None] * (onehot - 1.0 / A)
-        dhead[:, 0] = dq
-        dhead[:, 1:] = dadv
-        dv = dq[:, None] * Pon["wv"].float()[None, :]
-        da = dadv @ Pon["wa"].float()
-        dh = torch.cat([dv, da], 1) * (Hon[:B] > 0).float()
-        split_into(dh, dH, None if lo is None else lo[2])
-        if q_out is not None:
-            q_out.copy_(q_t)
-        if zero is not None:
-            zero.zero_()
-        self._is_norm_stats(isn, w)
+        self._td_loss_bwd(G, q_t, Hon[:B], Pon, act, isw, huber, kappa, grad_scale, td_abs, loss, dH, dhead, q_out,
+                          zero, lo[2], isn, dt)
 
-    def mdqn_head(self, Hon, Htg, Pon: Dict[str, torch.Tensor], Ptg: Dict[str, torch.Tensor], act, rew, gam, isw,
-                  huber: bool, kappa: float, alpha: float, tau: float, clip: float, grad_scale: float, td_abs, loss,
-                  dH, dhead, q_out=None, aux=None, zero: Optional[torch.Tensor] = None, lo=None, isn=None):
-        """The scalar head with the Munchausen-DQN target (csrc/mdqn_head.hip; learner/losses.py
-        munchausen_loss is the definition).  ``Hon`` [B, 2 HS]: the online net at S_t; ``Htg`` [2B, 2 HS]:
-        the target net, rows [0, B) at S_t+n (g1) and rows [B, 2B) at S_t (g0).  T = rew + alpha clamp(tau ln
-        pi(a | g0), clip, 0) + gam (max g1 + tau ln sum exp((g1 - max g1) / tau)), delta = T - q_on[a]; loss,
-        priority, ``dhead`` and ``dH`` as :meth:`head`.  ``aux`` [B, 2] fp32 (optional) receives (bonus, soft
-        value) per row; ``lo``, ``zero`` and ``isn`` as :meth:`head`."""
-        B = act.shape[0]
-        A = Pon["wa"].shape[0]
-        assert Hon.shape[0] == B and Htg.shape[0] == 2 * B
-        dt = Hon.dtype if Hon.dtype == torch.float64 else torch.float32     # (fp64 inputs: the tests' reference)
+    @staticmethod
+    def _dueling_q(h, P, dt):
+        """q [rows, A] of the scalar dueling head at stream activations ``h`` (stream width: 512 NatureCNN, 256
+        IMPALA)."""
+        HS = P["wv"].numel()
+        v = h[:, :HS] @ P["wv"].to(dt) + P["bv"].to(dt)
+        a = h[:, HS:] @ P["wa"].to(dt).t() + P["ba"].to(dt)
+        return v[:, None] + a - a.mean(1, keepdim=True)
 
-        def joined(hi, l):
-            return hi.to(dt) if l is None else hi.to(dt) + l.to(dt)
-
-        Hon = joined(Hon, None if lo is None else lo[0])
-        Htg = joined(Htg, None if lo is None else lo[1])
-        HS = Pon["wv"].numel()
-
-        def q_of(h, P):
-            v = h[:, :HS] @ P["wv"].to(dt) + P["bv"].to(dt)
-            a = h[:, HS:] @ P["wa"].to(dt).t() + P["ba"].to(dt)
-            return v[:, None] + a - a.mean(1, keepdim=True)
-
-        q_t = q_of(Hon, Pon)
-        g1 = q_of(Htg[:B], Ptg)
-        g0 = q_of(Htg[B:], Ptg)
-        tau, alpha, clip = float(tau), float(alpha), float(clip)
-        c0 = g0 - g0.max(1, keepdim=True).values
-        tl0 = c0.gather(1, act.long()[:, None]).squeeze(1) - tau * torch.log(torch.exp(c0 / tau).sum(1))
-        bonus = alpha * tl0.clamp(clip, 0.0)
-        m1 = g1.max(1).values
-        vsoft = m1 + tau * torch.log(torch.exp((g1 - m1[:, None]) / tau).sum(1))
-        G = rew.to(dt) + bonus + gam.to(dt) * vsoft
+    def _td_loss_bwd(self, G, q_t, h, Pon, act, isw, huber, kappa, grad_scale, td_abs, loss, dH, dhead, q_out, zero,
+                     dH_lo, isn, dt) -> None:
+        """What :meth:`head` and :meth:`mdqn_head` share once the target ``G`` [B] stands: delta = G - q(S_t)[a],
+        the Huber / squared loss, the priority, and the backward to ``dhead`` / ``dH`` (``h``: the online S_t
+        rows)."""
         q_sa = q_t.gather(1, act.long()[:, None]).squeeze(1)
         delta = G - q_sa
         ad = delta.abs()
@@ -232,22 +184,82 @@ class TorchBackend:
         dq = -w * dl * grad_scale
         td_abs.copy_(ad)
         loss.copy_(w * lval)
+        self._dueling_bwd(dq[:, None], act, Pon, h, dH, dhead, dH_lo, dt)
+        self._head_close(q_out, q_t, zero, isn, w)
+
+    @staticmethod
+    def _dhead(g, act, A: int, dhead, dt):
+        """``dhead [B, (A + 1) N]`` from ``g [B, N]``, the gradient at the taken action's N outputs (N = 1: the
+        scalar heads): the value rows get g, action a's rows g ([a = a_b] - 1/A).  Returns the advantage part
+        ``[B, A, N]``."""
+        B, N = g.shape
         onehot = torch.nn.functional.one_hot(act.long(), A).to(dt)
-        dadv = dq[:, None] * (onehot - 1.0 / A)
-        dhead[:, 0] = dq
-        dhead[:, 1:] = dadv
-        dv = dq[:, None] * Pon["wv"].to(dt)[None, :]
-        da = dadv @ Pon["wa"].to(dt)
-        dh = torch.cat([dv, da], 1) * (Hon > 0).to(dt)
-        split_into(dh, dH, None if lo is None else lo[2])
+        dadv = g[:, None, :] * (onehot - 1.0 / A)[:, :, None]
+        dhead[:, :N] = g
+        dhead[:, N:] = dadv.reshape(B, A * N)
+        return dadv
+
+    def _dueling_bwd(self, g, act, Pon, h, dH, dhead, dH_lo, dt) -> None:
+        """The dueling backward tail from ``g [B, N]`` (:meth:`_dhead`): ``dhead``, then through the head
+        weights ``wv (N, HS)`` / ``wa (A N, HS)`` and the stream ReLUs of ``h`` to ``dH`` (+ ``dH_lo``)."""
+        B, N = g.shape
+        HS = Pon["wv"].shape[-1]
+        A = Pon["wa"].shape[0] // N
+        dadv = self._dhead(g, act, A, dhead, dt)
+        wv = Pon["wv"].to(dt).reshape(N, HS)
+        dv = g @ wv if N > 1 else g * wv       # (one value row: the plain product, no GEMM)
+        da = dadv.reshape(B, A * N) @ Pon["wa"].to(dt)
+        dh = torch.cat([dv, da], 1) * (h > 0).to(dt)
+        split_into(dh, dH, dH_lo)
+
+    def _head_close(self, q_out, q_t, zero, isn, w) -> None:
+        """The heads' closing lines: ``q_out``, the zeroed head-gradient region, the IS statistic of ``w``."""
         if q_out is not None:
             q_out.copy_(q_t)
-        if aux is not None:
-            aux[:, 0] = bonus
-            aux[:, 1] = vsoft
         if zero is not None:
             zero.zero_()
         self._is_norm_stats(isn, w)
+
+    @staticmethod
+    def _eps_greedy(q, eps, ctr, seed, q_out, a_out) -> None:
+        """The actor heads' outputs: ``q_out`` and the epsilon-greedy action per row (host RNG seeded by
+        ``seed`` and the counter)."""
+        q_out.copy_(q)
+        E, A = q_out.shape
+        gen = torch.Generator(device="cpu").manual_seed(int(seed) * 1000003 + int(ctr.item()))
+        u = torch.rand(E, generator=gen).to(q.device)
+        r = torch.randint(0, A, (E,), generator=gen).to(q.device)
+        a_out.copy_(torch.where(u < eps.to(q.device), r, q.argmax(1)).to(a_out.dtype))
+
+    def mdqn_head(self, Hon, Htg, Pon: Dict[str, torch.Tensor], Ptg: Dict[str, torch.Tensor], act, rew, gam, isw,
+                  huber: bool, kappa: float, alpha: float, tau: float, clip: float, grad_scale: float, td_abs, loss,
+                  dH, dhead, q_out=None, aux=None, zero: Optional[torch.Tensor] = None, lo=None, isn=None):
+        """The scalar head with the Munchausen-DQN target (csrc/mdqn_head.hip; learner/losses.py
+        munchausen_loss is the definition).  ``Hon`` [B, 2 HS]: the online net at S_t; ``Htg`` [2B, 2 HS]:
+        the target net, rows [0, B) at S_t+n (g1) and rows [B, 2B) at S_t (g0).  T = rew + alpha clamp(tau ln
+        pi(a | g0), clip, 0) + gam (max g1 + tau ln sum exp((g1 - max g1) / tau)), delta = T - q_on[a]; loss,
+        priority, ``dhead`` and ``dH`` as :meth:`head`.  ``aux`` [B, 2] fp32 (optional) receives (bonus, soft
+        value) per row; ``lo``, ``zero`` and ``isn`` as :meth:`head`."""
+        B = act.shape[0]
+        assert Hon.shape[0] == B and Htg.shape[0] == 2 * B
+        dt = _head_dtype(Hon)
+        lo = lo if lo is not None else (None, None, None)
+        Hon, Htg = join(Hon, lo[0], dt), join(Htg, lo[1], dt)
+        q_t = self._dueling_q(Hon, Pon, dt)
+        g1 = self._dueling_q(Htg[:B], Ptg, dt)
+        g0 = self._dueling_q(Htg[B:], Ptg, dt)
+        tau, alpha, clip = float(tau), float(alpha), float(clip)
+        c0 = g0 - g0.max(1, keepdim=True).values
+        tl0 = c0.gather(1, act.long()[:, None]).squeeze(1) - tau * torch.log(torch.exp(c0 / tau).sum(1))
+        bonus = alpha * tl0.clamp(clip, 0.0)
+        m1 = g1.max(1).values
+        vsoft = m1 + tau * torch.log(torch.exp((g1 - m1[:, None]) / tau).sum(1))
+        G = rew.to(dt) + bonus + gam.to(dt) * vsoft
+        if aux is not None:
+            aux[:, 0] = bonus
+            aux[:, 1] = vsoft
+        self._td_loss_bwd(G, q_t, Hon, Pon, act, isw, huber, kappa, grad_scale, td_abs, loss, dH, dhead, q_out, zero,
+                          lo[2], isn, dt)
 
     @staticmethod
     def _is_norm_stats(isn, w) -> None:
@@ -285,14 +297,9 @@ class TorchBackend:
         from ..learner.losses import c51_project
         B, N = act.shape[0], int(num_atoms)
         A = Pon["wa"].shape[0] // N
-        dt = torch.float64 if Pon["wv"].dtype == torch.float64 else torch.float32
-        HS = Pon["wv"].shape[-1]
-
-        def joined(hi, l):
-            return hi.to(dt) if l is None else hi.to(dt) + l.to(dt)
-
-        Hon = joined(Hon, None if lo is None else lo[0])
-        Htg = joined(Htg, None if lo is None else lo[1])
+        dt = _head_dtype(Pon["wv"])
+        lo = lo if lo is not None else (None, None, None)
+        Hon, Htg = join(Hon, lo[0], dt), join(Htg, lo[1], dt)
         delta = (float(v_max) - float(v_min)) / (N - 1)
         z = float(v_min) + torch.arange(N, dtype=dt, device=Hon.device) * delta
         ar = torch.arange(B, device=Hon.device)
@@ -308,36 +315,20 @@ class TorchBackend:
         td_abs.copy_(((m * z).sum(-1) - (p * z).sum(-1)).abs())
         loss.copy_(-w * (m * lp).sum(-1))
         g = w[:, None] * (p - m) * grad_scale                      # d loss / d logits of (a_b, .)
-        onehot = torch.nn.functional.one_hot(act.long(), A).to(dt)
-        dadv = g[:, None, :] * (onehot - 1.0 / A)[:, :, None]      # [B, A, N]
-        dhead[:, :N] = g
-        dhead[:, N:] = dadv.reshape(B, A * N)
-        dv = g @ Pon["wv"].to(dt).reshape(N, HS)
-        da = dadv.reshape(B, A * N) @ Pon["wa"].to(dt)
-        dh = torch.cat([dv, da], 1) * (Hon[:B] > 0).to(dt)
-        split_into(dh, dH, None if lo is None else lo[2])
-        if q_out is not None:
-            q_out.copy_(q_t)
-        if zero is not None:
-            zero.zero_()
-        self._is_norm_stats(isn, w.float())
+        self._dueling_bwd(g, act, Pon, Hon[:B], dH, dhead, lo[2], dt)
+        self._head_close(q_out, q_t, zero, isn, w.float())
 
     def c51_actor_head(self, H, P, eps, ctr, seed, num_atoms: int, v_min: float, v_max: float, q_out, a_out,
                        H_lo=None):
         """Expected q of the distributional head + epsilon-greedy per row (the oracle of
         csrc/c51_head.hip ``c51_actor_head_kernel``)."""
         N = int(num_atoms)
-        dt = torch.float64 if P["wv"].dtype == torch.float64 else torch.float32
-        h = H.to(dt) if H_lo is None else H.to(dt) + H_lo.to(dt)
-        E, A = q_out.shape
+        dt = _head_dtype(P["wv"])
+        h = join(H, H_lo, dt)
         delta = (float(v_max) - float(v_min)) / (N - 1)
         z = float(v_min) + torch.arange(N, dtype=dt, device=h.device) * delta
-        q = (self._c51_logp(h, P, A, N, dt).exp() * z).sum(-1)
-        q_out.copy_(q)
-        gen = torch.Generator(device="cpu").manual_seed(int(seed) * 1000003 + int(ctr.item()))
-        u = torch.rand(E, generator=gen).to(q.device)
-        r = torch.randint(0, A, (E,), generator=gen).to(q.device)
-        a_out.copy_(torch.where(u < eps.to(q.device), r, q.argmax(1)).to(a_out.dtype))
+        q = (self._c51_logp(h, P, q_out.shape[1], N, dt).exp() * z).sum(-1)
+        self._eps_greedy(q, eps, ctr, seed, q_out, a_out)
 
     # ------------------------------------------- quantile-regression (QR-DQN) head
     @staticmethod
@@ -362,16 +353,11 @@ class TorchBackend:
         from ..learner.losses import quantile_huber_terms
         B, N = act.shape[0], int(num_atoms)
         A = Pon["wa"].shape[0] // N
-        dt = torch.float64 if Pon["wv"].dtype == torch.float64 else torch.float32
-        HS = Pon["wv"].shape[-1]
+        dt = _head_dtype(Pon["wv"])
         if not float(kappa) > 0.0:
             raise ValueError(f"qr_head: kappa must be > 0, got {kappa}")
-
-        def joined(hi, l):
-            return hi.to(dt) if l is None else hi.to(dt) + l.to(dt)
-
-        Hon = joined(Hon, None if lo is None else lo[0])
-        Htg = joined(Htg, None if lo is None else lo[1])
+        lo = lo if lo is not None else (None, None, None)
+        Hon, Htg = join(Hon, lo[0], dt), join(Htg, lo[1], dt)
         ar = torch.arange(B, device=Hon.device)
         th_t = self._qr_theta(Hon[:B], Pon, A, N, dt)
         q_t = th_t.mean(-1)
@@ -383,33 +369,16 @@ class TorchBackend:
         td_abs.copy_((T.mean(-1) - th.mean(-1)).abs())
         loss.copy_(w * rho.sum(-1))
         g = -w[:, None] * grad_scale * c                           # d loss / d theta of (a_b, .)
-        onehot = torch.nn.functional.one_hot(act.long(), A).to(dt)
-        dadv = g[:, None, :] * (onehot - 1.0 / A)[:, :, None]      # [B, A, N]
-        dhead[:, :N] = g
-        dhead[:, N:] = dadv.reshape(B, A * N)
-        dv = g @ Pon["wv"].to(dt).reshape(N, HS)
-        da = dadv.reshape(B, A * N) @ Pon["wa"].to(dt)
-        dh = torch.cat([dv, da], 1) * (Hon[:B] > 0).to(dt)
-        split_into(dh, dH, None if lo is None else lo[2])
-        if q_out is not None:
-            q_out.copy_(q_t)
-        if zero is not None:
-            zero.zero_()
-        self._is_norm_stats(isn, w.float())
+        self._dueling_bwd(g, act, Pon, Hon[:B], dH, dhead, lo[2], dt)
+        self._head_close(q_out, q_t, zero, isn, w.float())
 
     def qr_actor_head(self, H, P, eps, ctr, seed, num_atoms: int, q_out, a_out, H_lo=None):
         """q = mean of the quantiles + epsilon-greedy per row (the oracle of csrc/qr_head.hip
         ``qr_actor_head_kernel``)."""
         N = int(num_atoms)
-        dt = torch.float64 if P["wv"].dtype == torch.float64 else torch.float32
-        h = H.to(dt) if H_lo is None else H.to(dt) + H_lo.to(dt)
-        E, A = q_out.shape
-        q = self._qr_theta(h, P, A, N, dt).mean(-1)
-        q_out.copy_(q)
-        gen = torch.Generator(device="cpu").manual_seed(int(seed) * 1000003 + int(ctr.item()))
-        u = torch.rand(E, generator=gen).to(q.device)
-        r = torch.randint(0, A, (E,), generator=gen).to(q.device)
-        a_out.copy_(torch.where(u < eps.to(q.device), r, q.argmax(1)).to(a_out.dtype))
+        dt = _head_dtype(P["wv"])
+        q = self._qr_theta(join(H, H_lo, dt), P, q_out.shape[1], N, dt).mean(-1)
+        self._eps_greedy(q, eps, ctr, seed, q_out, a_out)
 
     # ------------------------------------------------- implicit quantile (IQN) head
     @staticmethod
@@ -457,16 +426,12 @@ class TorchBackend:
         from ..learner.losses import quantile_huber_terms
         B, N = act.shape[0], int(num_samples)
         A = Pon["wa"].shape[0]
-        dt = torch.float64 if Pon["wv"].dtype == torch.float64 else torch.float32
+        dt = _head_dtype(Pon["wv"])
         HS = Pon["wv"].shape[-1]
         if not float(kappa) > 0.0:
             raise ValueError(f"iqn_head: kappa must be > 0, got {kappa}")
-
-        def joined(hi, l):
-            return hi.to(dt) if l is None else hi.to(dt) + l.to(dt)
-
-        Hon = joined(Hon, None if lo is None else lo[0])
-        Htg = joined(Htg, None if lo is None else lo[1])
+        lo = lo if lo is not None else (None, None, None)
+        Hon, Htg = join(Hon, lo[0], dt), join(Htg, lo[1], dt)
         taus = learner_taus(int(seed_q), self._iqn_update_index(ctr, base), B, N).to(Hon.device)
         if tau_out is not None:
             tau_out.copy_(taus)
@@ -481,10 +446,7 @@ class TorchBackend:
         td_abs.copy_((T.mean(-1) - th.mean(-1)).abs())
         loss.copy_(w * rho.sum(-1))
         g = -w[:, None] * grad_scale * c                           # d loss / d theta of (a_b, .)
-        onehot = torch.nn.functional.one_hot(act.long(), A).to(dt)
-        dadv = g[:, None, :] * (onehot - 1.0 / A)[:, :, None]      # [B, A, N]
-        dhead[:, :N] = g
-        dhead[:, N:] = dadv.reshape(B, A * N)
+        dadv = self._dhead(g, act, A, dhead, dt)                    # [B, A, N]
         # back through the heads, the gate and the stream ReLUs
         dxv = g[:, :, None] * Pon["wv"].to(dt).reshape(HS)          # [B, N, HS]
         dxa = torch.einsum("bak,ac->bkc", dadv, Pon["wa"].to(dt))
@@ -492,16 +454,12 @@ class TorchBackend:
         phi = torch.relu(pre)
         h = Hon[:B]
         dh = (phi * dx).sum(1) * (h > 0).to(dt)
-        split_into(dh, dH, None if lo is None else lo[2])
+        split_into(dh, dH, lo[2])
         ws["dpre"].copy_((pre > 0).to(dt) * dx * h[:, None, :])
         ws["cos"].copy_(cf)
         ws["xg"].copy_((g[:, :, None] * (h[:, None, :] * phi)).sum(1))
         ws["gsum"].copy_(g.sum(1))
-        if q_out is not None:
-            q_out.copy_(q_t)
-        if zero is not None:
-            zero.zero_()
-        self._is_norm_stats(isn, w.float())
+        self._head_close(q_out, q_t, zero, isn, w.float())
 
     def iqn_wgrad(self, act, ws, g: Dict[str, torch.Tensor], prio=None) -> None:
         """The head and embedding weight gradients from what :meth:`iqn_head` left (the oracle of
@@ -530,9 +488,9 @@ class TorchBackend:
         tau_ctr + stream (learner/iqn.py ``stream_taus``), or the midpoints."""
         from ..learner.iqn import midpoint_taus, stream_taus
         K = int(num_samples)
-        dt = torch.float64 if P["wv"].dtype == torch.float64 else torch.float32
-        h = H.to(dt) if H_lo is None else H.to(dt) + H_lo.to(dt)
-        n_e, A = q_out.shape
+        dt = _head_dtype(P["wv"])
+        h = join(H, H_lo, dt)
+        n_e = q_out.shape[0]
         if midpoint:
             taus = midpoint_taus(K).to(h.device)[None, :].expand(n_e, K).contiguous()
         else:
@@ -540,11 +498,7 @@ class TorchBackend:
         if tau_out is not None:
             tau_out.copy_(taus)
         q = self._iqn_theta(h, P, E, taus, dt)[0].mean(-1)
-        q_out.copy_(q)
-        gen = torch.Generator(device="cpu").manual_seed(int(seed) * 1000003 + int(ctr.item()))
-        u = torch.rand(n_e, generator=gen).to(q.device)
-        r = torch.randint(0, A, (n_e,), generator=gen).to(q.device)
-        a_out.copy_(torch.where(u < eps.to(q.device), r, q.argmax(1)).to(a_out.dtype))
+        self._eps_greedy(q, eps, ctr, seed, q_out, a_out)
 
     def head_wgrad(self, Hon, dhead, g: Dict[str, torch.Tensor], prio=None, Hon_lo=None, pack=None):
         """``prio = (replay, idx, gen, td_abs)``: also write the batch's priorities back
@@ -577,17 +531,8 @@ class TorchBackend:
     def actor_head(self, H, P, eps, ctr, seed, q_out, a_out, H_lo=None):
         """Dueling q + epsilon-greedy per row (the oracle of csrc actor_head_kernel);
         ``H_lo``: split mode, the activations' lo plane."""
-        h = join(H, H_lo)
-        HS = P["wv"].numel()
-        v = h[:, :HS] @ P["wv"].float() + P["bv"].float()
-        a = h[:, HS:] @ P["wa"].float().t() + P["ba"].float()
-        q = v[:, None] + a - a.mean(1, keepdim=True)
-        q_out.copy_(q)
-        E, A = q.shape
-        gen = torch.Generator(device="cpu").manual_seed(int(seed) * 1000003 + int(ctr.item()))
-        u = torch.rand(E, generator=gen).to(q.device)
-        r = torch.randint(0, A, (E,), generator=gen).to(q.device)
-        a_out.copy_(torch.where(u < eps.to(q.device), r, q.argmax(1)).to(a_out.dtype))
+        q = self._dueling_q(join(H, H_lo), P, torch.float32)
+        self._eps_greedy(q, eps, ctr, seed, q_out, a_out)
 
     # ------------------------------------------------------------ backward
     def fc_bwd(self, dh, x, w, dx_out, dw_out, db_out):
@@ -1016,11 +961,19 @@ class HipBackend(TorchBackend):
                 pk.w, pk.w_lo = fp["c2d"][0].data_ptr(), _lib.ptr(fp["c2d"][1])
                 pk.out = C.c2d_wfrag_buffer(self.ws, Hon.device).data_ptr()
                 self._c2d_packed = (fp["c2d"][0].data_ptr(), _lib.ptr(fp["c2d"][1]))
-        isn_s = _lib.IsNorm()
-        if isn is not None:
-            isn_s.wscale, isn_s.out = _lib.ptr(isn[0]), _lib.ptr(isn[1])
-            isn_s.valid_count = _lib.ptr(isn[2]) if len(isn) > 2 else None
-        _lib.check(self.lib.apex_ddqn_head(*args, hl, hp, pk, isn_s, _lib.stream_ptr()), "ddqn_head")
+        _lib.check(self.lib.apex_ddqn_head(*args, hl, hp, pk, _lib.is_norm(isn), _lib.stream_ptr()), "ddqn_head")
+
+    def _head_io(self, io, Hon, Htg, Pon, Ptg, act, rew, gam, isw, A, hidden, grad_scale, td_abs, loss, dH, dhead,
+                 q_out, zero, lo, isn) -> None:
+        """Fill ``io``, the block every struct-argument head takes (``_lib.HeadIO``); ``B`` is ``act``'s."""
+        io.Hon, io.Htg, io.Pon, io.Ptg = Hon.data_ptr(), Htg.data_ptr(), self._hp(Pon), self._hp(Ptg)
+        io.act, io.rew, io.gam, io.isw = act.data_ptr(), rew.data_ptr(), gam.data_ptr(), _lib.ptr(isw)
+        io.B, io.A, io.hidden, io.grad_scale = act.shape[0], int(A), int(hidden), float(grad_scale)
+        io.td_abs, io.loss, io.q_out = td_abs.data_ptr(), loss.data_ptr(), _lib.ptr(q_out)
+        io.dH, io.dhead = dH.data_ptr(), dhead.data_ptr()
+        io.zero_ptr, io.zero_n = _lib.ptr(zero), 0 if zero is None else zero.numel()
+        io.lo = _lib.head_lo(*(lo if lo is not None else (None, None, None)))
+        io.isn = _lib.is_norm(isn)
 
     def mdqn_head(self, Hon, Htg, Pon, Ptg, act, rew, gam, isw, huber, kappa, alpha, tau, clip, grad_scale, td_abs,
                   loss, dH, dhead, q_out=None, aux=None, zero=None, lo=None, isn=None):
@@ -1028,22 +981,15 @@ class HipBackend(TorchBackend):
         forward never defers its epilogue)."""
         assert getattr(self, "_fc_part", None) is None, "the Munchausen head reads h: fc epilogue deferred"
         a = _lib.MdqnArgs()
-        a.Hon, a.Htg, a.Pon, a.Ptg = Hon.data_ptr(), Htg.data_ptr(), self._hp(Pon), self._hp(Ptg)
-        a.act, a.rew, a.gam, a.isw = act.data_ptr(), rew.data_ptr(), gam.data_ptr(), _lib.ptr(isw)
-        a.B, a.A, a.huber, a.hidden = act.shape[0], Pon["wa"].shape[0], int(huber), Pon["wv"].numel()
-        a.kappa, a.alpha, a.tau, a.clip, a.grad_scale = float(kappa), float(alpha), float(tau), float(clip), \
-            float(grad_scale)
-        a.td_abs, a.loss, a.q_out, a.aux = td_abs.data_ptr(), loss.data_ptr(), _lib.ptr(q_out), _lib.ptr(aux)
-        a.dH, a.dhead = dH.data_ptr(), dhead.data_ptr()
-        a.zero_ptr, a.zero_n = _lib.ptr(zero), 0 if zero is None else zero.numel()
-        a.lo = _lib.head_lo(*(lo if lo is not None else (None, None, None)))
-        if isn is not None:
-            a.isn.wscale, a.isn.out = _lib.ptr(isn[0]), _lib.ptr(isn[1])
-            a.isn.valid_count = _lib.ptr(isn[2]) if len(isn) > 2 else None
-        assert Hon.shape[0] == a.B and Htg.shape[0] == 2 * a.B and Hon.is_contiguous() and Htg.is_contiguous()
-        assert dhead.shape == (a.B, a.A + 1) and dhead.is_contiguous() and dH.is_contiguous()
-        assert aux is None or (aux.shape == (a.B, 2) and aux.dtype == torch.float32 and aux.is_contiguous())
-        assert q_out is None or (q_out.shape == (a.B, a.A) and q_out.is_contiguous())
+        B, A = act.shape[0], Pon["wa"].shape[0]
+        self._head_io(a.io, Hon, Htg, Pon, Ptg, act, rew, gam, isw, A, Pon["wv"].numel(), grad_scale, td_abs, loss, dH,
+                      dhead, q_out, zero, lo, isn)
+        a.huber, a.kappa, a.alpha, a.tau, a.clip = int(huber), float(kappa), float(alpha), float(tau), float(clip)
+        a.aux = _lib.ptr(aux)
+        assert Hon.shape[0] == B and Htg.shape[0] == 2 * B and Hon.is_contiguous() and Htg.is_contiguous()
+        assert dhead.shape == (B, A + 1) and dhead.is_contiguous() and dH.is_contiguous()
+        assert aux is None or (aux.shape == (B, 2) and aux.dtype == torch.float32 and aux.is_contiguous())
+        assert q_out is None or (q_out.shape == (B, A) and q_out.is_contiguous())
         _lib.check(self.lib.apex_mdqn_head(a, _lib.stream_ptr()), "mdqn_head")
 
     def c51_head(self, Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, v_min, v_max, grad_scale, td_abs, loss,
@@ -1052,18 +998,11 @@ class HipBackend(TorchBackend):
         assert getattr(self, "_fc_part", None) is None, "the distributional head reads h: fc epilogue deferred"
         N = int(num_atoms)
         a = _lib.C51Args()
-        a.Hon, a.Htg, a.Pon, a.Ptg = Hon.data_ptr(), Htg.data_ptr(), self._hp(Pon), self._hp(Ptg)
-        a.act, a.rew, a.gam, a.isw = act.data_ptr(), rew.data_ptr(), gam.data_ptr(), _lib.ptr(isw)
-        a.B, a.A, a.N, a.hidden = act.shape[0], Pon["wa"].shape[0] // N, N, Pon["wv"].shape[-1]
-        a.vmin, a.vmax, a.grad_scale = float(v_min), float(v_max), float(grad_scale)
-        a.td_abs, a.loss, a.q_out = td_abs.data_ptr(), loss.data_ptr(), _lib.ptr(q_out)
-        a.dH, a.dhead = dH.data_ptr(), dhead.data_ptr()
-        a.zero_ptr, a.zero_n = _lib.ptr(zero), 0 if zero is None else zero.numel()
-        a.lo = _lib.head_lo(*(lo if lo is not None else (None, None, None)))
-        if isn is not None:
-            a.isn.wscale, a.isn.out = _lib.ptr(isn[0]), _lib.ptr(isn[1])
-            a.isn.valid_count = _lib.ptr(isn[2]) if len(isn) > 2 else None
-        assert dhead.shape == (a.B, (a.A + 1) * N) and dhead.is_contiguous()
+        B, A = act.shape[0], Pon["wa"].shape[0] // N
+        self._head_io(a.io, Hon, Htg, Pon, Ptg, act, rew, gam, isw, A, Pon["wv"].shape[-1], grad_scale, td_abs, loss,
+                      dH, dhead, q_out, zero, lo, isn)
+        a.N, a.vmin, a.vmax = N, float(v_min), float(v_max)
+        assert dhead.shape == (B, (A + 1) * N) and dhead.is_contiguous()
         _lib.check(self.lib.apex_c51_head(a, _lib.stream_ptr()), "c51_head")
 
     def c51_actor_head(self, H, P, eps, ctr, seed, num_atoms, v_min, v_max, q_out, a_out, H_lo=None):
@@ -1079,18 +1018,11 @@ class HipBackend(TorchBackend):
         assert getattr(self, "_fc_part", None) is None, "the distributional head reads h: fc epilogue deferred"
         N = int(num_atoms)
         a = _lib.QRArgs()
-        a.Hon, a.Htg, a.Pon, a.Ptg = Hon.data_ptr(), Htg.data_ptr(), self._hp(Pon), self._hp(Ptg)
-        a.act, a.rew, a.gam, a.isw = act.data_ptr(), rew.data_ptr(), gam.data_ptr(), _lib.ptr(isw)
-        a.B, a.A, a.N, a.hidden = act.shape[0], Pon["wa"].shape[0] // N, N, Pon["wv"].shape[-1]
-        a.kappa, a.grad_scale = float(kappa), float(grad_scale)
-        a.td_abs, a.loss, a.q_out = td_abs.data_ptr(), loss.data_ptr(), _lib.ptr(q_out)
-        a.dH, a.dhead = dH.data_ptr(), dhead.data_ptr()
-        a.zero_ptr, a.zero_n = _lib.ptr(zero), 0 if zero is None else zero.numel()
-        a.lo = _lib.head_lo(*(lo if lo is not None else (None, None, None)))
-        if isn is not None:
-            a.isn.wscale, a.isn.out = _lib.ptr(isn[0]), _lib.ptr(isn[1])
-            a.isn.valid_count = _lib.ptr(isn[2]) if len(isn) > 2 else None
-        assert dhead.shape == (a.B, (a.A + 1) * N) and dhead.is_contiguous()
+        B, A = act.shape[0], Pon["wa"].shape[0] // N
+        self._head_io(a.io, Hon, Htg, Pon, Ptg, act, rew, gam, isw, A, Pon["wv"].shape[-1], grad_scale, td_abs, loss,
+                      dH, dhead, q_out, zero, lo, isn)
+        a.N, a.kappa = N, float(kappa)
+        assert dhead.shape == (B, (A + 1) * N) and dhead.is_contiguous()
         _lib.check(self.lib.apex_qr_head(a, _lib.stream_ptr()), "qr_head")
 
     def qr_actor_head(self, H, P, eps, ctr, seed, num_atoms, q_out, a_out, H_lo=None):
@@ -1121,33 +1053,26 @@ class HipBackend(TorchBackend):
         assert getattr(self, "_fc_part", None) is None, "the distributional head reads h: fc epilogue deferred"
         N = int(num_samples)
         a = _lib.IqnArgs()
-        a.Hon, a.Htg, a.Pon, a.Ptg = Hon.data_ptr(), Htg.data_ptr(), self._hp(Pon), self._hp(Ptg)
-        a.Eon, a.Etg = self._embed(Eon), self._embed(Etg)
-        a.act, a.rew, a.gam, a.isw = act.data_ptr(), rew.data_ptr(), gam.data_ptr(), _lib.ptr(isw)
-        a.B, a.A, a.N, a.hidden = act.shape[0], Pon["wa"].shape[0], N, Pon["wv"].shape[-1]
-        a.kappa, a.grad_scale, a.seed_q = float(kappa), float(grad_scale), int(seed_q)
+        B, A, hidden = act.shape[0], Pon["wa"].shape[0], Pon["wv"].shape[-1]
+        self._head_io(a.io, Hon, Htg, Pon, Ptg, act, rew, gam, isw, A, hidden, grad_scale, td_abs, loss, dH, dhead,
+                      q_out, zero, lo, isn)
+        a.N, a.kappa, a.seed_q = N, float(kappa), int(seed_q)
         assert ctr.dtype == torch.int64 and (base is None or base.dtype == torch.int64)
         a.ctr, a.base = ctr.data_ptr(), _lib.ptr(base)
-        a.td_abs, a.loss, a.q_out, a.tau_out = td_abs.data_ptr(), loss.data_ptr(), _lib.ptr(q_out), _lib.ptr(tau_out)
-        a.dH, a.dhead = dH.data_ptr(), dhead.data_ptr()
+        a.Eon, a.Etg, a.tau_out = self._embed(Eon), self._embed(Etg), _lib.ptr(tau_out)
         a.dpre, a.cosT, a.xg, a.gsum = (ws["dpre"].data_ptr(), ws["cos"].data_ptr(), ws["xg"].data_ptr(),
                                         ws["gsum"].data_ptr())
-        a.zero_ptr, a.zero_n = _lib.ptr(zero), 0 if zero is None else zero.numel()
-        a.lo = _lib.head_lo(*(lo if lo is not None else (None, None, None)))
-        if isn is not None:
-            a.isn.wscale, a.isn.out = _lib.ptr(isn[0]), _lib.ptr(isn[1])
-            a.isn.valid_count = _lib.ptr(isn[2]) if len(isn) > 2 else None
         a.max_blocks = 0 if max_blocks is None else int(max_blocks)
-        assert Pon["wv"].numel() == a.hidden and Ptg["wv"].numel() == a.hidden and Eon["wtau"].shape[0] == 2 * a.hidden
-        assert Hon.shape[0] >= 2 * a.B and Htg.shape[0] >= a.B and Hon.is_contiguous() and Htg.is_contiguous()
-        assert dhead.shape == (a.B, (a.A + 1) * N) and dhead.is_contiguous() and dhead.dtype == torch.float32
-        assert dH.shape == (a.B, 2 * a.hidden) and dH.is_contiguous()
-        assert ws["dpre"].shape == (a.B, N, 2 * a.hidden) and ws["cos"].shape == (a.B, N, 64)
-        assert ws["xg"].shape == (a.B, 2 * a.hidden) and ws["gsum"].shape == (a.B,)
+        assert Pon["wv"].numel() == hidden and Ptg["wv"].numel() == hidden and Eon["wtau"].shape[0] == 2 * hidden
+        assert Hon.shape[0] >= 2 * B and Htg.shape[0] >= B and Hon.is_contiguous() and Htg.is_contiguous()
+        assert dhead.shape == (B, (A + 1) * N) and dhead.is_contiguous() and dhead.dtype == torch.float32
+        assert dH.shape == (B, 2 * hidden) and dH.is_contiguous()
+        assert ws["dpre"].shape == (B, N, 2 * hidden) and ws["cos"].shape == (B, N, 64)
+        assert ws["xg"].shape == (B, 2 * hidden) and ws["gsum"].shape == (B,)
         assert all(ws[k].dtype == torch.float32 and ws[k].is_contiguous() for k in ("dpre", "cos", "xg", "gsum"))
-        assert tau_out is None or (tau_out.shape == (a.B, 3, N) and tau_out.is_contiguous()
+        assert tau_out is None or (tau_out.shape == (B, 3, N) and tau_out.is_contiguous()
                                    and tau_out.dtype == torch.float32)
-        assert q_out is None or (q_out.shape == (a.B, a.A) and q_out.is_contiguous())
+        assert q_out is None or (q_out.shape == (B, A) and q_out.is_contiguous())
         _lib.check(self.lib.apex_iqn_head(a, _lib.stream_ptr()), "iqn_head")
 
     def iqn_wgrad(self, act, ws, g, prio=None) -> None:

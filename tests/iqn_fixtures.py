@@ -8,6 +8,7 @@ KAPPA = 1.0
 SEED = 12345            # Runtime.seed of the head problems
 CTR, BASE = 9, 2        # draw counter and base word: update index u = 7
 SHAPES = [(64, 4, 8), (64, 18, 64), (64, 6, 21), (64, 2, 2), (5, 4, 8), (13, 4, 8)]
+WSCALE = 2.0            # the sampler's factor handed to the IS statistic (a power of two: the division is exact)
 KINK = 1e-5             # |pre| below this in the fp64 oracle: a ReLU-mask flip is a one-term difference
 
 
@@ -88,11 +89,13 @@ def run_torch(B, A, N, split=False, case="plain", kappa=KAPPA, dtype=torch.float
     taus = torch.zeros(B, 3, N)
     ws = be.iqn_workspace(B, N, "cpu", dtype)
     ctr, base = torch.tensor([CTR]), torch.tensor([BASE])
+    stat = (torch.full((1,), WSCALE), torch.full((1,), -1.0, dtype=torch.float64), torch.zeros((), dtype=torch.int64))
     be.iqn_head(Hon, Htg, Pon, Ptg, Eon, Etg, fx["act"], d(rew), d(gam), None if isw is None else d(isw), N, kappa,
-                1.0 / B, seed_q(), ctr, base, td, loss, dH, dhead, ws, q_out=q, tau_out=taus)
+                1.0 / B, seed_q(), ctr, base, td, loss, dH, dhead, ws, q_out=q, tau_out=taus,
+                isn=None if isw is None else stat)
     gr = {"wv": z(1, 512), "bv": z(1), "wa": z(A, 512), "ba": z(A), "wtau": z(1024, 64), "btau": z(1024)}
     be.iqn_wgrad(fx["act"], ws, gr)
-    out = dict(td=td, loss=loss, dH=dH, dhead=dhead, q=q, g=gr, taus=taus)
+    out = dict(td=td, loss=loss, dH=dH, dhead=dhead, q=q, g=gr, taus=taus, isn=float(stat[1]), count=int(stat[2]))
     if dtype == torch.float64:
         # diagnostics of the oracle alone: the top-2 gap of the online next-state q, the taken action's
         # quantiles and target samples, and the near-kink slack of the embedding's gradient rows

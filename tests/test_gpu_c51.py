@@ -51,9 +51,12 @@ def _fixture(B, A, N, split=False):
     return dict(Hon=Hon, Htg=Htg, Hon_lo=Hon_lo, Htg_lo=Htg_lo, Pon=Pon, Ptg=Ptg, act=act, rew=rew, gam=gam, isw=isw)
 
 
-def _oracle(fx, A, N, rew=None, gam=None, isw="fixture"):
+WSCALE = 2.0     # the sampler's factor of the IS-statistic case (a power of two: the division is exact)
+
+
+def _oracle(fx, A, N, rew=None, gam=None, isw="fixture", isn=False):
     """fp64 CPU oracle on the joined activations: (td, loss, dH, dhead, q, head gradients,
-    smallest top-2 gap of the online next-state q)."""
+    smallest top-2 gap of the online next-state q; with ``isn`` the IS statistic and row count)."""
     from apex_dqn_amd.ops.fused_ops import TorchBackend
     be = TorchBackend(torch.float64)
     B = fx["act"].shape[0]
@@ -68,18 +71,20 @@ def _oracle(fx, A, N, rew=None, gam=None, isw="fixture"):
     dH = torch.zeros(B, 1024, dtype=torch.float64)
     dhead = torch.zeros(B, (A + 1) * N, dtype=torch.float64)
     q = torch.zeros(B, A, dtype=torch.float64)
+    stat = (torch.full((1,), WSCALE), torch.full((1,), -1.0, dtype=torch.float64), torch.zeros((), dtype=torch.int64))
     be.c51_head(Hon, Htg, Pon, Ptg, fx["act"], d(rew), d(gam), None if isw is None else d(isw), N, VMIN, VMAX,
-                1.0 / B, td, loss, dH, dhead, q_out=q)
+                1.0 / B, td, loss, dH, dhead, q_out=q, isn=stat if isn else None)
     gr = {k: torch.zeros_like(v) for k, v in Pon.items()}
     be.head_wgrad(Hon, dhead, gr)
     z = VMIN + torch.arange(N, dtype=torch.float64) * ((VMAX - VMIN) / (N - 1))
     qn = (be._c51_logp(Hon[B:2 * B], Pon, A, N, torch.float64).exp() * z).sum(-1)
     top = qn.topk(2, dim=1).values
     lp_t = be._c51_logp(Hon[:B], Pon, A, N, torch.float64)[torch.arange(B), fx["act"].long()]
-    return dict(td=td, loss=loss, dH=dH, dhead=dhead, q=q, g=gr, gap=float((top[:, 0] - top[:, 1]).min()), lp=lp_t)
+    return dict(td=td, loss=loss, dH=dH, dhead=dhead, q=q, g=gr, gap=float((top[:, 0] - top[:, 1]).min()), lp=lp_t,
+                isn=float(stat[1]), count=int(stat[2]))
 
 
-def _run_hip(fx, A, N, rew=None, gam=None, isw="fixture"):
+def _run_hip(fx, A, N, rew=None, gam=None, isw="fixture", isn=False):
     from apex_dqn_amd.ops.fused_ops import HipBackend
     be = HipBackend()
     B = fx["act"].shape[0]
@@ -101,13 +106,18 @@ def _run_hip(fx, A, N, rew=None, gam=None, isw="fixture"):
     for k in ("wv", "bv", "wa", "ba"):
         gr[k] = flat[o:o + gr[k].numel()].view(gr[k].shape)
         o += gr[k].numel()
+    stat = (torch.full((1,), WSCALE, device=DEV), torch.full((1,), -1.0, dtype=torch.float64, device=DEV),
+            torch.zeros((), dtype=torch.int64, device=DEV))
     be.c51_head(Hon, Htg, Pon, Ptg, dev(fx["act"]), dev(rew), dev(gam), dev(isw), N, VMIN, VMAX, 1.0 / B, td, loss,
-                dH, dhead, q_out=q, zero=flat, lo=(Hon_lo, Htg_lo, dH_lo) if split else None)
+                dH, dhead, q_out=q, zero=flat, lo=(Hon_lo, Htg_lo, dH_lo) if split else None,
+                isn=stat if isn else None)
+    torch.cuda.synchronize()
+    zeroed = bool((flat == 0).all())
     be.head_wgrad(Hon, dhead, gr, Hon_lo=Hon_lo)
     torch.cuda.synchronize()
     dHj = dH.double() + (dH_lo.double() if split else 0.0)
     return dict(td=td.cpu(), loss=loss.cpu(), dH=dHj.cpu(), dhead=dhead.cpu(), q=q.cpu(),
-                g={k: v.cpu() for k, v in gr.items()})
+                g={k: v.cpu() for k, v in gr.items()}, zeroed=zeroed, isn=float(stat[1].cpu()), count=int(stat[2].cpu()))
 
 
 def _compare(h, r):
@@ -138,6 +148,23 @@ def test_c51_head_kernel_vs_fp64_oracle(B, A, N, split):
           f"td err {float((h['td'] - r['td']).abs().max()):.2e}, loss err {float((h['loss'] - r['loss']).abs().max()):.2e}, "
           f"dhead err {float((h['dhead'] - r['dhead']).abs().max()):.2e}")
     _compare(h, r)
+
+
+def test_c51_head_every_optional_argument_at_once():
+    """q_out, the zeroed region, the three lo planes, the IS weights and the IS statistic with its output and
+    its row count, all given: every member of the argument block the launch passes is read or written through,
+    so a member at the wrong offset shows as a wrong number.  Two blocks, the second with one live row; the
+    smallest head (N = 2).  The statistic is max(isw) / 2 formed in fp64 from the same fp32 weights, and the
+    count an integer: both equal the oracle's exactly."""
+    B, A, N = 3, 3, 2          # B = DIST_SPB + 1 (csrc/dist_head.h)
+    fx = _fixture(B, A, N, True)
+    r = _oracle(fx, A, N, isn=True)
+    assert r["gap"] >= 1e-3, r["gap"]
+    h = _run_hip(fx, A, N, isn=True)
+    _compare(h, r)
+    assert h["zeroed"]
+    assert r["count"] == B and h["count"] == r["count"]
+    assert r["isn"] == float(fx["isw"].max().double() / WSCALE) and h["isn"] == r["isn"]
 
 
 # ------------------------------------------------------------ 2. edge cases

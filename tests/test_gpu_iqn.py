@@ -43,7 +43,8 @@ def _run_hip(B, A, N, split=False, case="plain", kappa=F.KAPPA, max_blocks=None,
         m = int(torch.tensor(s).prod())
         gr[k] = flat[o:o + m].view(s)
         o += m
-    isn_out = (torch.full((1,), 2.0, device=DEV), torch.full((1,), -1.0, dtype=torch.float64, device=DEV)) if isn else None
+    isn_out = (torch.full((1,), F.WSCALE, device=DEV), torch.full((1,), -1.0, dtype=torch.float64, device=DEV),
+               torch.zeros((), dtype=torch.int64, device=DEV)) if isn else None
     be.iqn_head(Hon, Htg, Pon, Ptg, Eon, Etg, _dev(fx["act"]), _dev(rew), _dev(gam), _dev(isw), N, kappa, 1.0 / B,
                 F.seed_q(), torch.tensor([ctr], device=DEV), torch.tensor([F.BASE], device=DEV), td, loss, dH, dhead,
                 ws, q_out=q, tau_out=taus, zero=flat, lo=(Hon_lo, Htg_lo, dH_lo) if split else None, isn=isn_out,
@@ -55,7 +56,8 @@ def _run_hip(B, A, N, split=False, case="plain", kappa=F.KAPPA, max_blocks=None,
     dHj = dH.double() + (dH_lo.double() if split else 0.0)
     return dict(td=td.cpu(), loss=loss.cpu(), dH=dHj.cpu(), dhead=dhead.cpu(), q=q.cpu(), taus=taus.cpu(),
                 g={k: v.cpu().clone() for k, v in gr.items()}, zeroed=zeroed,
-                isn=None if isn_out is None else float(isn_out[1].cpu()))
+                isn=None if isn_out is None else float(isn_out[1].cpu()),
+                count=None if isn_out is None else int(isn_out[2].cpu()))
 
 
 # --------------------------------------------------------- 1. kernels vs oracle
@@ -81,6 +83,23 @@ def test_iqn_head_and_wgrad_kernels_vs_fp64_oracle(B, A, N, max_blocks, split):
     assert torch.equal(h["taus"], r["taus"])                  # bit-equal to the mirror
     assert h["zeroed"]
     F.compare(h, r)
+
+
+def test_iqn_head_every_optional_argument_at_once():
+    """q_out, tau_out, the zeroed region, the three lo planes, the IS weights and the IS statistic with its
+    output and its row count, all given: every member of the argument block the launch passes is read or
+    written through, so a member at the wrong offset shows as a wrong number.  Two sample pairs, the second
+    with one live row; the smallest head (N = 2).  The statistic is max(isw) / 2 formed in fp64 from the same
+    fp32 weights, and the count an integer: both equal the oracle's exactly."""
+    B, A, N = 3, 3, 2           # B = DIST_SPB + 1 (csrc/dist_head.h)
+    r = F.oracle(B, A, N, True)
+    assert r["gap"] >= 1e-3, r["gap"]
+    h = _run_hip(B, A, N, True, isn=True)
+    assert torch.equal(h["taus"], r["taus"])
+    assert h["zeroed"]
+    F.compare(h, r)
+    assert r["count"] == B and h["count"] == r["count"]
+    assert r["isn"] == float(F.fixture(B, A, True)["isw"].max().double() / F.WSCALE) and h["isn"] == r["isn"]
 
 
 def test_iqn_head_grid_size_does_not_change_a_bit():

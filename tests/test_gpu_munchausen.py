@@ -45,6 +45,7 @@ def _fixture(B, A, split=False):
     return dict(Hon=Hon, Htg=Htg, Hon_lo=Hon_lo, Htg_lo=Htg_lo, Pon=Pon, Ptg=Ptg, act=act, rew=rew, gam=gam, isw=isw)
 
 
+WSCALE = 2.0     # the sampler's factor handed to the oracle's IS statistic (a power of two: the division is exact)
 CASES = ("plain", "terminal", "no_isw", "equal_q", "huge_gaps", "alpha0", "mse", "tau1")
 
 
@@ -90,8 +91,9 @@ def _oracle(B, A, split=False, case="plain"):
     dhead = torch.zeros(B, A + 1, dtype=torch.float64)
     q = torch.zeros(B, A, dtype=torch.float64)
     aux = torch.zeros(B, 2, dtype=torch.float64)
+    stat = (torch.full((1,), WSCALE), torch.full((1,), -1.0, dtype=torch.float64), torch.zeros((), dtype=torch.int64))
     be.mdqn_head(Hon, Htg, Pon, Ptg, fx["act"], d(rew), d(gam), None if isw is None else d(isw), huber, KAPPA, alpha,
-                 tau, CLIP, 1.0 / B, td, loss, dH, dhead, q_out=q, aux=aux)
+                 tau, CLIP, 1.0 / B, td, loss, dH, dhead, q_out=q, aux=aux, isn=None if isw is None else stat)
     # the head gradients of TorchBackend.head_wgrad, in fp64
     gr = {"wv": dhead[:, 0] @ Hon[:, :512], "bv": dhead[:, 0].sum().view(1), "wa": dhead[:, 1:].t() @ Hon[:, 512:],
           "ba": dhead[:, 1:].sum(0)}
@@ -101,7 +103,8 @@ def _oracle(B, A, split=False, case="plain"):
         return (h[:, :512] @ P["wv"] + P["bv"])[:, None] + a - a.mean(1, keepdim=True)
     g1, g0 = q_of(Htg[:B], Ptg), q_of(Htg[B:], Ptg)
     tl = tau_log_policy(g0, tau).gather(1, fx["act"].long()[:, None]).squeeze(1)
-    return dict(td=td, loss=loss, dH=dH, dhead=dhead, q=q, aux=aux, g=gr, tl=tl, g0=g0, g1=g1)
+    return dict(td=td, loss=loss, dH=dH, dhead=dhead, q=q, aux=aux, g=gr, tl=tl, g0=g0, g1=g1, isn=float(stat[1]),
+                count=int(stat[2]))
 
 
 def _run_hip(B, A, split=False, case="plain", isn=None, q_out=True):
@@ -165,6 +168,24 @@ def test_mdqn_head_kernel_vs_fp64_oracle(B, A, split):
     _compare(h, r)
     assert bool((h["zeroed"] == 0).all())
     assert bool((h["aux"][:, 0] <= 0).all()) and bool((h["aux"][:, 0] >= ALPHA * CLIP).all())
+
+
+def test_mdqn_head_every_optional_argument_at_once():
+    """q_out, aux, the zeroed region, the three lo planes, the IS weights and the IS statistic with its output
+    and its row count, all given: every member of the argument block the launch passes is read or written
+    through, so a member at the wrong offset shows as a wrong number.  Two blocks (one per sample).  The
+    statistic is max(isw) / 2 formed in fp64 from the same fp32 weights, and the count an integer: both equal
+    the oracle's exactly."""
+    B, A = 2, 3
+    fx = _fixture(B, A, True)
+    r = _oracle(B, A, True)
+    isn = (torch.full((1,), WSCALE, device=DEV), torch.full((1,), -1.0, dtype=torch.float64, device=DEV),
+           torch.zeros((), dtype=torch.int64, device=DEV))
+    h = _run_hip(B, A, True, isn=isn)
+    _compare(h, r)
+    assert bool((h["zeroed"] == 0).all())
+    assert r["count"] == B and int(isn[2]) == r["count"]
+    assert r["isn"] == float(fx["isw"].max().double() / WSCALE) and float(isn[1]) == r["isn"]
 
 
 # ------------------------------------------------------------ 2. edge cases
