@@ -130,6 +130,12 @@ class RuntimeConf:
     munchausen_alpha: float = 0.9
     munchausen_tau: float = 0.03
     munchausen_clip: float = -1.0
+    # soft (Polyak) target network: after every update t <- (1 - rho) t + rho p over the whole flat parameter
+    # vector, inside the optimizer launch (csrc/rmsprop_common.h EMA, learner/schedules.py target_ema the mirror).
+    # 0 = the hard copy every Learner.q_target_sync_freq updates; > 0 turns that copy off (the key is ignored).
+    # Single-rank NatureCNN with any head kind and the torch learners (mlp); not IMPALA, the DP step or the
+    # graph learner
+    target_ema_rate: float = 0.0
     priority_eps: float = 1e-6      # priority floor: leaves hold (|delta| + priority_eps)^alpha
     use_is_weights: bool = True
     is_normalise: str = "batch_max"  # IS weights (N P(i))^-beta divided by their max over the sampled batch
@@ -373,6 +379,16 @@ class ApexConfig:
             if int(rt.world_size) > 1 or rt.force_dp:
                 raise ValueError("Runtime.munchausen runs on a single rank: the data-parallel step (world_size > 1, "
                                  "force_dp) has no Munchausen target")
+        rho = rt.target_ema_rate
+        if isinstance(rho, bool) or not isinstance(rho, (int, float)) or not 0.0 <= float(rho) <= 1.0:
+            raise ValueError(f"Runtime.target_ema_rate (the soft target's rate) must be a number in [0, 1], got "
+                             f"{rho!r}")
+        if float(rho) > 0.0:
+            if net not in ("nature64", "nature32", "mlp"):
+                raise ValueError(f"Runtime.target_ema_rate needs network nature64, nature32 or mlp, got {net!r}")
+            if int(rt.world_size) > 1 or rt.force_dp:
+                raise ValueError("Runtime.target_ema_rate runs on a single rank: the data-parallel step "
+                                 "(world_size > 1, force_dp) keeps the hard target sync")
         if net in ("nature64", "nature32", "impala") and len(ss) != 3:
             raise ValueError(f"network {net} needs an image state_shape [C,H,W], got {ss}")
         if net in ("nature64", "nature32") and tuple(ss[1:]) != (84, 84):

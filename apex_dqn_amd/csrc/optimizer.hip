@@ -40,6 +40,12 @@ __global__ void __launch_bounds__(256) opt_sched_kernel(RmspropArgs a) {
   rmsprop_body<MODE>(a, blockIdx.x, gridDim.x);
 }
 
+// the same three updates with the soft target averaged in the launch (rmsprop_common.h EMA)
+template <int MODE>
+__global__ void __launch_bounds__(256) opt_ema_kernel(RmspropArgs a) {
+  rmsprop_body<MODE, true>(a, blockIdx.x, gridDim.x);
+}
+
 static int launch_opt(const RmspropArgs& a, hipStream_t st) {
   if (((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.v | (uintptr_t)a.m) & 15) return (int)hipErrorInvalidValue;
   if (((uintptr_t)a.pb | (uintptr_t)a.pb_lo) & 7) return (int)hipErrorInvalidValue;
@@ -47,6 +53,14 @@ static int launch_opt(const RmspropArgs& a, hipStream_t st) {
   if (mode != OPT_RMSPROP && (a.os.ctr == nullptr || a.os.base == nullptr)) return (int)hipErrorInvalidValue;
   int nb = (int)((a.n / 4 + 255) / 256);
   nb = nb < 1 ? 1 : (nb > 2048 ? 2048 : nb);
+  // (these launch forms store no fragments: a.fo is empty, so a target fragment block is refused)
+  if (opt_target_check(a.tg, a.pb_lo, a.fo, a.n, (int64_t)nb * 256 * 4)) return (int)hipErrorInvalidValue;
+  if (a.tg.t != nullptr) {
+    if (mode == OPT_ADAM) opt_ema_kernel<OPT_ADAM><<<nb, 256, 0, st>>>(a);
+    else if (mode == OPT_RMSPROP_SCHED) opt_ema_kernel<OPT_RMSPROP_SCHED><<<nb, 256, 0, st>>>(a);
+    else opt_ema_kernel<OPT_RMSPROP><<<nb, 256, 0, st>>>(a);
+    APEX_CHECK_LAUNCH();
+  }
   if (mode == OPT_ADAM) opt_sched_kernel<OPT_ADAM><<<nb, 256, 0, st>>>(a);
   else if (mode == OPT_RMSPROP_SCHED) opt_sched_kernel<OPT_RMSPROP_SCHED><<<nb, 256, 0, st>>>(a);
   else rmsprop_kernel<<<nb, 256, 0, st>>>(a);
@@ -71,9 +85,9 @@ APEX_EXPORT int apex_grad_sqnorm_partials(const float* g, int64_t n, double* par
 APEX_EXPORT int apex_rmsprop_step(float* p, const float* g, float* v, float* m, bf16_t* pb, int64_t n,
                                   const double* partials, float lr, float alpha, float eps, float clip,
                                   int centered, float* norm_out, bf16_t* pb_lo, const double* wnorm, int wn,
-                                  int wstride, OptSched os, hipStream_t st) {
+                                  int wstride, OptSched os, OptTarget tg, hipStream_t st) {
   return launch_opt(RmspropArgs{p, g, v, m, pb, n, partials, NPART, lr, alpha, eps, clip, centered, norm_out, pb_lo,
-                                wnorm, wn, wstride, CfFragOut{}, nullptr, 0, os},
+                                wnorm, wn, wstride, CfFragOut{}, nullptr, 0, os, tg},
                     st);
 }
 
@@ -82,9 +96,9 @@ APEX_EXPORT int apex_rmsprop_step(float* p, const float* g, float* v, float* m, 
 APEX_EXPORT int apex_rmsprop_step_np(float* p, const float* g, float* v, float* m, bf16_t* pb, int64_t n,
                                      const double* partials, int npart, float lr, float alpha, float eps, float clip,
                                      int centered, float* norm_out, bf16_t* pb_lo, const double* wnorm, int wn,
-                                     int wstride, OptSched os, hipStream_t st) {
+                                     int wstride, OptSched os, OptTarget tg, hipStream_t st) {
   return launch_opt(RmspropArgs{p, g, v, m, pb, n, partials, npart, lr, alpha, eps, clip, centered, norm_out, pb_lo,
-                                wnorm, wn, wstride, CfFragOut{}, nullptr, 0, os},
+                                wnorm, wn, wstride, CfFragOut{}, nullptr, 0, os, tg},
                     st);
 }
 

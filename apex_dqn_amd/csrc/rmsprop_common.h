@@ -117,6 +117,20 @@ __host__ __device__ inline int opt_mode(const OptSched& s) {
   return s.adam ? OPT_ADAM : (s.ctr != nullptr ? OPT_RMSPROP_SCHED : OPT_RMSPROP);
 }
 
+// Soft (Polyak) target network, Runtime.target_ema_rate = rho: the launch that has just
+// formed the updated weight p' also writes
+//   t' = fl(fl(a t) + fl(rho p')),  a = fl(1 - rho)   (fp32, no contraction: rho = 1 gives p' exactly)
+// in every format the forward reads the target net in: the fp32 master copy, the bf16 hi
+// (/ lo) planes and, in the peeled first chunk, the target halves of the fused forward's
+// fragment buffers.  learner/schedules.py target_ema is the host mirror, bit for bit.
+struct OptTarget {
+  float* t;             // fp32 target parameters (null: off)
+  bf16_t* tb;           // their bf16 copy
+  bf16_t* tb_lo;        // its lo plane (split mode: set exactly when RmspropArgs.pb_lo is)
+  float rho;
+  CfFragOut tfo;        // the fused forward's TARGET operands in fragment order (w1frag null: off)
+};
+
 struct RmspropArgs {
   float* p;
   const float* g;
@@ -136,10 +150,13 @@ struct RmspropArgs {
   const float* gpre;    // clip norm: a gradient range summed in every block (clip_coef_from_partials), or null
   int64_t npre;
   OptSched os;          // update index + schedules + Adam constants (all-zero: OPT_RMSPROP)
+  OptTarget tg;         // soft target net averaged in the same launch (t null: off, the EMA = false code)
 };
 
 // one block `bid` of `nblk` (grid-stride over float4 chunks)
-template <int MODE = OPT_RMSPROP>
+// EMA: the launch also averages the target net (OptTarget); every difference is an
+// `if constexpr`, so the EMA = false instantiations are the code of before
+template <int MODE = OPT_RMSPROP, bool EMA = false>
 __device__ __forceinline__ void rmsprop_body(const RmspropArgs& A_, int bid, int nblk) {
   // no FMA contraction: every inlined copy of the update (steady loop, peeled chunk, the
   // other launches) rounds identically
@@ -164,15 +181,31 @@ __device__ __forceinline__ void rmsprop_body(const RmspropArgs& A_, int bid, int
   float4* m4 = reinterpret_cast<float4*>(m);
   uint2* pb4 = reinterpret_cast<uint2*>(pb);
   uint2* pbl4 = reinterpret_cast<uint2*>(pbl);
+  float* __restrict__ t = nullptr;
+  bf16_t* __restrict__ tb = nullptr;
+  bf16_t* __restrict__ tbl = nullptr;
+  float4* t4 = nullptr;
+  uint2* tb4 = nullptr;
+  uint2* tbl4 = nullptr;
+  float rho = 0.f, arho = 0.f;
+  if constexpr (EMA) {
+    t = A_.tg.t; tb = A_.tg.tb; tbl = A_.tg.tb_lo;
+    t4 = reinterpret_cast<float4*>(t);
+    tb4 = reinterpret_cast<uint2*>(tb);
+    tbl4 = reinterpret_cast<uint2*>(tbl);
+    rho = A_.tg.rho;
+    arho = 1.0f - rho;
+  }
   const int64_t stride = (int64_t)nblk * blockDim.x;
   int64_t i = (int64_t)bid * blockDim.x + threadIdx.x;
   // the first chunk's loads are in flight while the block sums the clip-norm
   // partials, and every iteration prefetches the next chunk (one-deep pipeline)
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 gg = z4, pp = z4, vv = z4, mm = z4;
+  float4 gg = z4, pp = z4, vv = z4, mm = z4, tt = z4;
   if (i < n4) {
     gg = g4[i]; pp = p4[i]; vv = v4[i];
     if (centered) mm = m4[i];
+    if constexpr (EMA) tt = t4[i];
   }
   if constexpr (MODE != OPT_RMSPROP) {
     if (threadIdx.x == 0) {
@@ -198,7 +231,8 @@ __device__ __forceinline__ void rmsprop_body(const RmspropArgs& A_, int bid, int
     d1 = 1.0f - b1;
   }
   const float a1 = 1.0f - alpha;
-  auto update = [&](int64_t i, const float4 gg, const float4 pp, const float4 vv, const float4 mm, const bool frag) {
+  auto update = [&](int64_t i, const float4 gg, const float4 pp, const float4 vv, const float4 mm, const float4 tt,
+                    const bool frag) {
     float gx[4] = {gg.x * coef, gg.y * coef, gg.z * coef, gg.w * coef};
     float px[4] = {pp.x, pp.y, pp.z, pp.w};
     float vx[4] = {vv.x, vv.y, vv.z, vv.w};
@@ -235,6 +269,29 @@ __device__ __forceinline__ void rmsprop_body(const RmspropArgs& A_, int bid, int
       pb4[i] = hb;
       if (frag) cf_frag_store(A_.fo, 4 * i, px, hb, make_uint2(0u, 0u));
     }
+    if constexpr (EMA) {
+      // the target net from the weights just written: two products and a sum, each rounded
+      float tx[4] = {tt.x, tt.y, tt.z, tt.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float ta = arho * tx[j], pr = rho * px[j];
+        tx[j] = ta + pr;
+      }
+      t4[i] = make_float4(tx[0], tx[1], tx[2], tx[3]);
+      const bool tfrag = frag && A_.tg.tfo.w1frag != nullptr;
+      if (tbl != nullptr) {
+        uint32_t h01, l01, h23, l23;
+        split_pk_bf16_h(tx[0], tx[1], h01, l01);
+        split_pk_bf16_h(tx[2], tx[3], h23, l23);
+        tb4[i] = make_uint2(h01, h23);
+        tbl4[i] = make_uint2(l01, l23);
+        if (tfrag) cf_frag_store(A_.tg.tfo, 4 * i, tx, make_uint2(h01, h23), make_uint2(l01, l23));
+      } else {
+        const uint2 hb = make_uint2(pack_bf16x2(tx[0], tx[1]), pack_bf16x2(tx[2], tx[3]));
+        tb4[i] = hb;
+        if (tfrag) cf_frag_store(A_.tg.tfo, 4 * i, tx, hb, make_uint2(0u, 0u));
+      }
+    }
   };
   // The first chunk is peeled: the fused forward's operand stores (A_.fo, the launcher
   // checks that w1 / w2 lie within every thread's first chunk) run before the next
@@ -244,22 +301,25 @@ __device__ __forceinline__ void rmsprop_body(const RmspropArgs& A_, int bid, int
   // per element hold 86 / 87 VGPRs, 5 waves per SIMD -- the fused launch's 256 blocks of 8
   // waves are one per CU either way
   if (i < n4) {
-    update(i, gg, pp, vv, mm, A_.fo.w1frag != nullptr);
+    update(i, gg, pp, vv, mm, tt, A_.fo.w1frag != nullptr);     // (the launcher: tg.tfo only beside fo)
     i += stride;
     if (i < n4) {
       gg = g4[i]; pp = p4[i]; vv = v4[i];
       if (centered) mm = m4[i];
+      if constexpr (EMA) tt = t4[i];
     }
   }
   for (; i < n4; i += stride) {
     const int64_t inx = i + stride;
-    float4 gn = z4, pn = z4, vn = z4, mn = z4;
+    float4 gn = z4, pn = z4, vn = z4, mn = z4, tn = z4;
     if (inx < n4) {
       gn = g4[inx]; pn = p4[inx]; vn = v4[inx];
       if (centered) mn = m4[inx];
+      if constexpr (EMA) tn = t4[inx];
     }
-    update(i, gg, pp, vv, mm, false);
+    update(i, gg, pp, vv, mm, tt, false);
     gg = gn; pp = pn; vv = vn; mm = mn;
+    if constexpr (EMA) tt = tn;
   }
   for (int64_t i = n4 * 4 + (int64_t)bid * blockDim.x + threadIdx.x; i < n; i += (int64_t)nblk * blockDim.x) {
     float gg = g[i] * coef;
@@ -281,5 +341,35 @@ __device__ __forceinline__ void rmsprop_body(const RmspropArgs& A_, int bid, int
     p[i] = pp;
     pb[i] = f32_to_bf16(pp);
     if (pbl != nullptr) pbl[i] = f32_to_bf16(pp - bf16_to_f32(pb[i]));
+    if constexpr (EMA) {
+      const float ta = arho * t[i], pr = rho * pp;
+      const float tn = ta + pr;
+      t[i] = tn;
+      tb[i] = f32_to_bf16(tn);
+      if (tbl != nullptr) tbl[i] = f32_to_bf16(tn - bf16_to_f32(tb[i]));
+    }
   }
+}
+
+// Launcher-side checks of an optimizer launch's target block against its online arguments
+// (`first`: the elements every thread's first chunk covers, the range cf_frag_store runs in;
+// `n0`: the elements of the range that holds the fragment sources).  0 = fine.
+inline int opt_target_check(const OptTarget& g, const bf16_t* pb_lo, const CfFragOut& fo, int64_t n0, int64_t first) {
+  if (g.t == nullptr) return (g.tb != nullptr || g.tb_lo != nullptr || g.tfo.w1frag != nullptr) ? 1 : 0;
+  if (g.tb == nullptr || (g.tb_lo != nullptr) != (pb_lo != nullptr) || !(g.rho >= 0.f && g.rho <= 1.f)) return 1;
+  if (((uintptr_t)g.t & 15) || (((uintptr_t)g.tb | (uintptr_t)g.tb_lo) & 7)) return 1;
+  const CfFragOut& f = g.tfo;
+  if (f.w1frag == nullptr) return 0;
+  // the target fragments go where the online ones do: same offsets, same first-chunk rule
+  if (fo.w1frag == nullptr || f.c2f == nullptr || f.C != fo.C || f.w1_off != fo.w1_off || f.w2_off != fo.w2_off ||
+      (f.c3f != nullptr) != (fo.c3f != nullptr) || (f.c3f != nullptr && f.w3_off != fo.w3_off) ||
+      f.in_scale != fo.in_scale)
+    return 1;
+  if ((f.C != 1 && f.C != 2 && f.C != 4) || (f.w1_off & 3) || (f.w2_off & 7) || f.w1_off + 4096LL * f.C > n0 ||
+      f.w2_off + 65536 > n0 || f.w1_off + 4096LL * f.C > first || f.w2_off + 65536 > first ||
+      (((uintptr_t)f.w1frag | (uintptr_t)f.c2f) & 15))
+    return 1;
+  if (f.c3f != nullptr && ((f.w3_off & 3) || f.w3_off + 36864 > n0 || f.w3_off + 36864 > first || ((uintptr_t)f.c3f & 15)))
+    return 1;
+  return 0;
 }

@@ -661,15 +661,17 @@ struct RmsSegs {
   int64_t len[3];
 };
 
-template <int NT, bool SEG, int MODE = OPT_RMSPROP>
+// EMA: the whole-range form also averages the soft target (rmsprop_common.h OptTarget)
+template <int NT, bool SEG, int MODE = OPT_RMSPROP, bool EMA = false>
 __global__ void __launch_bounds__(NT) rmsprop_sample_kernel(RmspropArgs a, SampleArgs s, int nsb, RmsSegs sg) {
+  static_assert(!(SEG && EMA), "the sharded update is never launched with a target");
   if ((int)blockIdx.x < nsb) {
     tree_sample_body(s, blockIdx.x);
     return;
   }
   const int b = blockIdx.x - nsb;
   if constexpr (!SEG) {
-    rmsprop_body<MODE>(a, b, gridDim.x - nsb);
+    rmsprop_body<MODE, EMA>(a, b, gridDim.x - nsb);
   } else {
     int k = 0;
     while (k + 1 < sg.nseg && b >= sg.blk0[k + 1]) ++k;
@@ -781,7 +783,7 @@ APEX_EXPORT int apex_fill16(void* p, int64_t n, int nt, hipStream_t st) {
   APEX_CHECK_LAUNCH();
 }
 
-APEX_EXPORT int apex_abi_version() { return 13; }
+APEX_EXPORT int apex_abi_version() { return 14; }
 
 // 1 if this library was built with -DAPEX_DEBUG_BOUNDS
 APEX_EXPORT int apex_debug_bounds_enabled() {
@@ -830,7 +832,7 @@ APEX_EXPORT int apex_rmsprop_sample(float* p, const float* g, float* v, float* m
                                     int shard_world, uint64_t shard_seed, float* out_wscale, int64_t mcap,
                                     BetaSched bs, bf16_t* pb_lo, const double* wnorm, int wn, int wstride, CfFragOut fo,
                                     const RmsSegs* seg, const float* gpre, int64_t npre, OptSched os,
-                                    hipStream_t st) {
+                                    OptTarget tg, hipStream_t st) {
   const int mode = opt_mode(os);
   if (mode != OPT_RMSPROP && (os.ctr == nullptr || os.base == nullptr)) return (int)hipErrorInvalidValue;
   if (mcap <= 0) mcap = (int64_t)shard_world * B;
@@ -886,8 +888,11 @@ APEX_EXPORT int apex_rmsprop_sample(float* p, const float* g, float* v, float* m
       ((fo.w3_off & 3) || fo.w3_off + 36864 > n0 || (fo.w3_off + 36864) / 4 > (int64_t)nb * nt || ((uintptr_t)fo.c3f & 15)))
     return (int)hipErrorInvalidValue;
   if (((uintptr_t)gpre & 15) || npre < 0 || (npre > 0 && gpre == nullptr)) return (int)hipErrorInvalidValue;
+  // the soft target: the whole-range form only; its fragment stores obey the online ones' rules
+  if (tg.t != nullptr && seg != nullptr) return (int)hipErrorInvalidValue;
+  if (opt_target_check(tg, pb_lo, fo, n0, (int64_t)nb * nt * 4)) return (int)hipErrorInvalidValue;
   const RmspropArgs ra{p, g, v, m, pb, n, partials, npart, lr, alpha, eps_opt, clip, centered, norm_out, pb_lo,
-                      wnorm, wn, wstride, fo, npre > 0 ? gpre : nullptr, npre, os};
+                      wnorm, wn, wstride, fo, npre > 0 ? gpre : nullptr, npre, os, tg};
   const SampleArgs sa{t, r, B, seed, ctr, beta, out_idx, out_w, out_gen, out_obs, out_nxt,
                       out_act, out_rew, out_gam, out_nxt2, out_obs2, shard_stats, shard_rank, shard_world,
                       shard_seed, out_wscale, mcap, bs};
@@ -897,9 +902,15 @@ APEX_EXPORT int apex_rmsprop_sample(float* p, const float* g, float* v, float* m
     if (seg != nullptr) rmsprop_sample_kernel<nt, true, MODE><<<grid, nt, 0, st>>>(ra, sa, nsb, sg);    \
     else rmsprop_sample_kernel<nt, false, MODE><<<grid, nt, 0, st>>>(ra, sa, nsb, sg);                  \
   } while (0)
-  if (mode == OPT_ADAM) APEX_OPT_LAUNCH(OPT_ADAM);
+#define APEX_EMA_LAUNCH(MODE) rmsprop_sample_kernel<nt, false, MODE, true><<<grid, nt, 0, st>>>(ra, sa, nsb, sg)
+  if (tg.t != nullptr) {
+    if (mode == OPT_ADAM) APEX_EMA_LAUNCH(OPT_ADAM);
+    else if (mode == OPT_RMSPROP_SCHED) APEX_EMA_LAUNCH(OPT_RMSPROP_SCHED);
+    else APEX_EMA_LAUNCH(OPT_RMSPROP);
+  } else if (mode == OPT_ADAM) APEX_OPT_LAUNCH(OPT_ADAM);
   else if (mode == OPT_RMSPROP_SCHED) APEX_OPT_LAUNCH(OPT_RMSPROP_SCHED);
   else APEX_OPT_LAUNCH(OPT_RMSPROP);
+#undef APEX_EMA_LAUNCH
 #undef APEX_OPT_LAUNCH
   APEX_CHECK_LAUNCH();
 }

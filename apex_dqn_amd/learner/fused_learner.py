@@ -38,7 +38,8 @@ Precision (``Runtime.dtype``):
   * ``bf16``: bf16 operands, fp32 accumulation and master weights (the round-1 path).
 
 Periodic host work between steps: target sync (D2D copy, every
-``q_target_sync_freq``), FIFO eviction + exact tree rebuild (every
+``q_target_sync_freq``; none with ``Runtime.target_ema_rate`` > 0, where the optimizer launch
+averages the target after every update), FIFO eviction + exact tree rebuild (every
 ``remove_old_xp_freq``), checkpoint (rank 0).
 
 Reference parity: ``Learner.learn`` / ``compute_loss_and_priorities`` /
@@ -61,7 +62,7 @@ from ..utils.checkpoint import (adopt_obs_scale, check_dist_head, check_noisy, l
                                 pack_flat_state, save_checkpoint, unpack_flat_state, checkpoint_network)
 from .dp_step import DataParallelStep, Streams
 from .is_norm import IsNormMixin
-from .schedules import StepIndexMixin
+from .schedules import StepIndexMixin, target_ema_on
 
 
 def _enable_sharding(replay, comm, rt, mcap: int = 0) -> None:
@@ -132,6 +133,12 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         if self.munchausen and self._dp:
             raise ValueError("Runtime.munchausen: the Munchausen target runs on a single rank, not in the "
                              "data-parallel step (world > 1, Runtime.force_dp, the emulated world)")
+        # soft (Polyak) target: t <- (1 - rho) t + rho p after every update, inside the optimizer launch
+        # (csrc/rmsprop_common.h EMA); it replaces the hard sync every Learner.q_target_sync_freq updates
+        self.ema = float(self.rt.target_ema_rate) if target_ema_on(self.rt) else 0.0
+        if self.ema and self._dp:
+            raise ValueError("Runtime.target_ema_rate: the soft target is averaged on a single rank, not in the "
+                             "data-parallel step (world > 1, Runtime.force_dp, the emulated world)")
         if self.rt.dtype not in ("fp32", "bf16"):
             raise ValueError("Runtime.dtype must be fp32 or bf16")
         self.precision = self.rt.dtype
@@ -172,6 +179,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         self.rms_m = torch.zeros(n, dtype=torch.float32, device=d)
         self.t32 = torch.zeros(n, dtype=torch.float32, device=d)
         self._frag_out = None    # the optimizer stores the fused forward's online operands
+        self._frag_out_t = None  # ... and, with the soft target, the target set's
         self.P = self.layout.views(self.p32)
         self.Pb = self.layout.views(self.pbf)
         self.G = self.layout.views(self.g32)
@@ -318,7 +326,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         (csrc/cf_pack.h cf_frag_store; elementwise, no hand-off between workgroups), so the
         step runs no pack launch for the online set (forward_all pack_sets).  Host-side
         weight changes repack eagerly (_online_changed).  SW.opt_frags = False: pack launch."""
-        self._frag_out = None
+        self._frag_out = self._frag_out_t = None
         ops = self.ops
         if not SW.opt_frags:
             return
@@ -329,6 +337,11 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         off = self.layout.offsets
         self._frag_out = C.conv12_frag_out(ops.ws, self.P["w1"], off["w1"], off["w2"], self.rt.obs_scale,
                                            w3_off=off["w3"])
+        if self.ema:
+            # the soft target: the same launch stores the target set's halves (else the forward
+            # repacks them every update, forward_all pack_sets)
+            self._frag_out_t = C.conv12_frag_out(ops.ws, self.P["w1"], off["w1"], off["w2"], self.rt.obs_scale,
+                                                 w3_off=off["w3"], target=True)
         self._online_changed()
 
     def _online_changed(self) -> None:
@@ -502,7 +515,8 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             c3 = self._conv3_weights() if self._conv123 else None
             ops.conv12_fwd(self.replay.frames, self.slots, self.frames, rt.obs_scale, self.y1, self.y1_lo, self.y2,
                            self.y2_lo, c1, c2, rows_first=r1, copy_n=B,
-                           pack_sets=online | (0 if self._tgt_packed else 2), c3=c3, y3=self.y3, y3_lo=self.y3_lo)
+                           pack_sets=online | (0 if self._tgt_current() else 2), c3=c3, y3=self.y3,
+                           y3_lo=self.y3_lo)
         else:
             c2f = (Pb["w2"], None, Tb["w2"], None)
             ops.conv1_fwd_ring(self.replay.frames, self.slots, self.frames, Pb["w1"], P["b1"], rt.obs_scale, self.y1,
@@ -531,6 +545,11 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         P, T, Pb, Tb, Pl, Tl = self.P, self.T, self.Pb, self.Tb, self.Pl, self.Tl
         sp = self.split
         return (Pb["w3"], Pl["w3"] if sp else None, P["b3"], Tb["w3"], Tl["w3"] if sp else None, T["b3"])
+
+    def _tgt_current(self) -> bool:
+        """The fused forward's target fragments are current at the head of an update: packed at the
+        last target change and, with the soft target, kept by the optimizer launch's stores."""
+        return self._tgt_packed and (not self.ema or self._frag_out_t is not None)
 
     def _target_changed(self) -> None:
         """The target weights (t32 / tbf) changed: repack the fused forward's target
@@ -745,11 +764,20 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
                       ((self.norm_part, norm_slots) if norm_slots else None), sample=nxt,
                       wnorm=self._wnorm(), **self._lo(pb_lo=self.pbf_lo),
                       **({"frag_out": self._frag_out} if (self._frag_out is not None and nxt is not None) else {}),
+                      **self._target_kw(nxt is not None),
                       **({"segs": segs} if segs is not None else {}),
                       **({"norm_prefix": norm_prefix} if norm_prefix is not None else {}), **self._opt_kw())
         if self._presample:
             self._sample_ver = self.replay.version
         self._mark("optimizer")
+
+    def _target_kw(self, frags: bool) -> Dict[str, Any]:
+        """``target=`` of ``ops.optimizer`` with the soft target (empty for the default: the launches of
+        before); ``frags``: the launch stores the online fragments, so the target's ride with them."""
+        if not self.ema:
+            return {}
+        tfo = self._frag_out_t if (frags and self._frag_out is not None) else None
+        return {"target": (self.t32, self.tbf, self.tbf_lo, self.ema, tfo)}
 
     def _seg2_branched(self) -> None:
         """Backward with the weight gradients on a second stream (SW.bwd_branches): the
@@ -897,14 +925,15 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             self._body()
         self.num_q_updates += 1
         L = self.cfg.Learner
-        if self.num_q_updates % L.q_target_sync_freq == 0:
+        if not self.ema and self.num_q_updates % L.q_target_sync_freq == 0:
             self.sync_target()
 
     def steps(self, n: int) -> None:
         """``n`` learner updates.  With HIP graphs, chunks of ``Runtime.graph_steps``
         updates replay ONE graph holding that many steps (each graph launch costs
         ~9 us of idle GPU at its boundary); chunks never straddle a target-network
-        sync.  Same updates as ``n`` calls of :meth:`step`."""
+        sync (the soft target has none: it is averaged inside every update).  Same updates
+        as ``n`` calls of :meth:`step`."""
         k = int(self.rt.graph_steps)
         if k <= 1 or not self._graphs_enabled():
             for _ in range(n):
@@ -912,7 +941,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             return
         f = self.cfg.Learner.q_target_sync_freq
         while n > 0:
-            to_sync = f - self.num_q_updates % f
+            to_sync = k if self.ema else f - self.num_q_updates % f
             if n < k or to_sync < k:
                 self.step()
                 n -= 1
@@ -927,7 +956,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             self._multi.replay()
             self.num_q_updates += k
             n -= k
-            if self.num_q_updates % f == 0:
+            if not self.ema and self.num_q_updates % f == 0:
                 self.sync_target()
 
     def prepare_graphs(self, multi: bool = True) -> int:
@@ -1128,7 +1157,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         self._wait_params()
         torch.cuda.synchronize(self.device)
         snap = self._snapshot()
-        state = (self.p32, self._pbf_all, self.rms_v, self.rms_m)
+        state = (self.p32, self._pbf_all, self.rms_v, self.rms_m) + ((self.t32, self._tbf_all) if self.ema else ())
         if self._presample and self._sample_ver != self.replay.version:
             self._sample()
         self._graphs.replay()
@@ -1151,16 +1180,22 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
 
     def _snapshot(self):
         rp = self.replay
+        # (the soft target moves with every update: the target net is part of the state)
         return [t.clone() for t in (self.p32, self._pbf_all, self.rms_v, self.rms_m, rp.leaf, rp.nodes,
-                                    rp.min_bits, rp.ctr)] + ([rp.shard_stats.clone()] if rp.sharded else [])
+                                    rp.min_bits, rp.ctr)] + ([rp.shard_stats.clone()] if rp.sharded else []) + \
+            ([self.t32.clone(), self._tbf_all.clone()] if self.ema else [])
 
     def _restore(self, snap) -> None:
         rp = self.replay
         dst = [self.p32, self._pbf_all, self.rms_v, self.rms_m, rp.leaf, rp.nodes, rp.min_bits, rp.ctr]
         if rp.sharded:
             dst.append(rp.shard_stats)
+        if self.ema:
+            dst += [self.t32, self._tbf_all]
         for t, src in zip(dst, snap):
             t.copy_(src)
+        if self.ema:
+            self._target_changed()      # (repacks the target fragments; composes the noisy layers, as below)
         self._online_changed()
 
     def _refresh_bf16(self) -> None:
@@ -1178,6 +1213,8 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         m = self._is_metrics()
         if self.noisy:     # mean |sigma| of the fc weight sigma (the metrics above synced already)
             m["noisy_sigma_mean"] = float(self.P["swfc"].abs().mean())
+        if self.ema:       # mean |online - target| of the fc weights (syncs, as the noisy metric)
+            m["target_gap"] = float((self.P["wfc"] - self.T["wfc"]).abs().mean())
         if self.munchausen:     # the last update's mean bonus (<= 0) and mean soft value of S_t+n
             mean = self.mdqn_aux.double().mean(0)
             m["munchausen_bonus_mean"], m["soft_value_mean"] = float(mean[0]), float(mean[1])

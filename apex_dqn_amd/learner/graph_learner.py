@@ -68,6 +68,9 @@ class GraphLearner(StepIndexMixin):
         if self.rt.noisy:
             raise ValueError("Runtime.noisy: the graph learner (Runtime.use_hip_kernels = false on the GPU) has no "
                              "noisy layers; run the HIP kernels or noisy = false")
+        if float(self.rt.target_ema_rate) > 0.0:
+            raise ValueError("Runtime.target_ema_rate: the graph learner (Runtime.use_hip_kernels = false on the GPU) "
+                             "keeps the hard target sync; run the HIP kernels or target_ema_rate = 0")
         self.device = torch.device(device)
         self.replay = replay
         self.comm = comm

@@ -78,6 +78,9 @@ class FusedImpalaLearner(IsNormMixin, StepIndexMixin):
         self.device = torch.device(device)
         self.replay = replay
         self.comm = comm
+        if float(self.rt.target_ema_rate) > 0.0:
+            raise ValueError("Runtime.target_ema_rate: the IMPALA step keeps the hard target sync (the soft target "
+                             "is the NatureCNN learner's)")
         self.world, _, self.B, self.mcap = dp_layout(cfg, comm, batch_size, allow_force=False)
         self.C = cfg.frame_stack
         if self.C != 4 or tuple(cfg.env_conf.state_shape[1:]) != (84, 84):

@@ -62,6 +62,26 @@ def adam_corrections(u: int, beta1: float, beta2: float):
     return np.float32(np.float64(1.0) - pow_int(beta1, t)), np.float32(np.float64(1.0) - pow_int(beta2, t))
 
 
+def target_ema(t, p, rho: float) -> np.ndarray:
+    """The soft (Polyak) target after an update, ``Runtime.target_ema_rate`` = ``rho``: on fp32 arrays
+    ``t`` (the target) and ``p`` (the weights the optimizer has just written),
+    ``t' = fl(fl(a t) + fl(r p))`` with ``r = fp32(rho)`` and ``a = fl(1 - r)`` formed once -- two
+    products and a sum, each rounded to fp32 (csrc/rmsprop_common.h EMA: no contraction).  ``rho = 1``
+    gives ``p`` exactly.  Returns a new fp32 array."""
+    t, p = np.asarray(t), np.asarray(p)
+    if t.dtype != np.float32 or p.dtype != np.float32:
+        raise TypeError("target_ema mirrors fp32 arithmetic: pass float32 arrays")
+    r = np.float32(rho)
+    a = np.float32(np.float32(1.0) - r)
+    ta = (a * t).astype(np.float32)
+    pr = (r * p).astype(np.float32)
+    return (ta + pr).astype(np.float32)
+
+
+def target_ema_on(rt) -> bool:
+    return float(getattr(rt, "target_ema_rate", 0.0)) > 0.0
+
+
 def rt_lr(rt, u: int) -> float:
     """lr(u) of a ``Runtime`` section."""
     return float(lr_at(u, rt.lr, rt.lr_warmup_steps, rt.lr_decay_steps, rt.lr_end))

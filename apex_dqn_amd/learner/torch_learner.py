@@ -21,7 +21,7 @@ from ..config import ApexConfig
 from ..models.dueling import build_network
 from ..utils.checkpoint import adopt_obs_scale, check_dist_head, check_noisy, load_checkpoint, save_checkpoint
 from .losses import c51_loss, ddqn_loss, munchausen_loss, munchausen_targets, quantile_huber_loss
-from .schedules import lr_scheduled, rt_lr
+from .schedules import lr_scheduled, rt_lr, target_ema_on
 
 
 def make_optimizer(params, rt) -> torch.optim.Optimizer:
@@ -128,9 +128,23 @@ class TorchLearner:
                 gr["lr"] = rt_lr(self.rt, self.num_q_updates)
         self.optimizer.step()
         self.num_q_updates += 1
-        if self.num_q_updates % self.cfg.Learner.q_target_sync_freq == 0:
+        if target_ema_on(self.rt):
+            self.ema_target()
+        elif self.num_q_updates % self.cfg.Learner.q_target_sync_freq == 0:
             self.sync_target()
         return gnorm
+
+    def ema_target(self) -> None:
+        """The soft target (Runtime.target_ema_rate): every parameter of the target module averaged with the
+        online one just written -- learner/schedules.py ``target_ema`` in tensor operations (two fp32
+        products and a sum, no addcmul / lerp).  It replaces the hard sync."""
+        r = torch.tensor(float(self.rt.target_ema_rate), dtype=torch.float32, device=self.device)
+        a = torch.ones_like(r) - r
+        with torch.no_grad():
+            for t, p in zip(self.Q_target.parameters(), self.Q.parameters()):
+                ta = t * a
+                pr = p.detach() * r
+                torch.add(ta, pr, out=t)
 
     def sync_target(self) -> None:
         self.Q_target.load_state_dict(self.Q.state_dict())

@@ -133,6 +133,12 @@ class CfFragOut(ctypes.Structure):
                 ("in_scale", c_f), ("c3f", c_p), ("w3_off", c_i64)]
 
 
+class OptTarget(ctypes.Structure):
+    """The soft target an optimizer launch averages (``OptTarget``, csrc/rmsprop_common.h);
+    all-zero = off."""
+    _fields_ = [("t", c_p), ("tb", c_p), ("tb_lo", c_p), ("rho", c_f), ("tfo", CfFragOut)]
+
+
 class RmsSegs(ctypes.Structure):
     """Ranges of the flat parameters one optimizer launch updates (``RmsSegs``,
     csrc/sumtree.hip; the sharded data-parallel update)."""
@@ -225,11 +231,11 @@ _SIGS = {
     "apex_debug_errors": ([c_p, c_p, c_i], c_i),
     "apex_grad_sqnorm_partials": ([c_p, c_i64, c_p, c_p], c_i),
     "apex_rmsprop_step": ([c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_f, c_f, c_f, c_f, c_i, c_p, c_p, c_p, c_i, c_i,
-                           OptSched, c_p], c_i),
+                           OptSched, OptTarget, c_p], c_i),
     "apex_cast_bf16": ([c_p, c_p, c_i64, c_p, c_p], c_i),
     "apex_spin_hold": ([c_i, c_i, c_i, c_p, c_p], c_i),
     "apex_rmsprop_step_np": ([c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i, c_f, c_f, c_f, c_f, c_i, c_p, c_p, c_p,
-                              c_i, c_i, OptSched, c_p], c_i),
+                              c_i, c_i, OptSched, OptTarget, c_p], c_i),
     "apex_grad_finalize": ([FinalizeDesc, c_p], c_i),
     "apex_norm_total": ([c_p, c_i, c_p, c_p], c_i),
     "apex_ddqn_head": ([c_p, c_p, HeadParams, HeadParams, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p,
@@ -237,7 +243,7 @@ _SIGS = {
     "apex_rmsprop_sample": ([c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i, c_f, c_f, c_f, c_f, c_i, c_p,
                              TreeDesc, RecordDesc, c_i, c_u64, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                              c_p, c_p, c_p, c_i, c_i, c_u64, c_p, c_i64, BetaSched, c_p, c_p, c_i, c_i, CfFragOut, c_p,
-                             c_p, c_i64, OptSched, c_p], c_i),
+                             c_p, c_i64, OptSched, OptTarget, c_p], c_i),
     "apex_head_wgrad_prio": ([c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, TreeDesc, c_p, c_p, c_p, c_p, c_f, c_f,
                               c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_i64, c_i, c_p, c_p], c_i),
     "apex_fc_wgrad_head_prio": ([WgradDesc, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, TreeDesc, c_p, c_p, c_p,
@@ -285,7 +291,7 @@ def _declare(lib: ctypes.CDLL) -> None:
     conv_sigs.declare(lib)
 
 
-ABI_VERSION = 13    # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
+ABI_VERSION = 14    # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
 
 
 def load(build_if_missing: bool = True) -> Optional[ctypes.CDLL]:

@@ -282,18 +282,22 @@ def conv12_pack(lib, ws: "Workspace", w1, b1, w2, w2_lo, b2, scale: float, w1b=N
 
 
 def conv12_frag_out(ws: "Workspace", w1: torch.Tensor, w1_off: int, w2_off: int, scale: float,
-                    w3_off: Optional[int] = None):
+                    w3_off: Optional[int] = None, target: bool = False):
     """``CfFragOut`` for the optimizer launch: the fused forward's online conv1 / conv2
     operand buffers of ``ws`` and the flat offsets of w1 / w2 in the parameter vector the
-    optimizer updates (csrc/cf_pack.h cf_frag_store)."""
+    optimizer updates (csrc/cf_pack.h cf_frag_store).  ``target``: the target set's halves of
+    the same buffers (the soft target, averaged from the weights at the same flat offsets):
+    conv1 fragments of set 1 (csrc/cf_pack.h cf_pack_w1_block: 1024 C uint4 per set), planes 2 /
+    3 of the C2F and C3F fragments (csrc/conv2_wfrag.h)."""
     C = int(w1.shape[1])
     dev = w1.device
     fo = _lib.CfFragOut()
-    fo.w1frag = ws.get(("cf_w1frag",), CF_W1FRAG_BYTES, dev, torch.uint8).data_ptr()
-    fo.c2f = ws.get(("cf_c2f_wfrag",), 4 * 8192 * 16, dev, torch.uint8).data_ptr()
+    s = 1 if target else 0
+    fo.w1frag = ws.get(("cf_w1frag",), CF_W1FRAG_BYTES, dev, torch.uint8).data_ptr() + s * 1024 * C * 16
+    fo.c2f = ws.get(("cf_c2f_wfrag",), 4 * 8192 * 16, dev, torch.uint8).data_ptr() + s * 2 * 8192 * 16
     fo.w1_off, fo.w2_off, fo.C, fo.in_scale = int(w1_off), int(w2_off), C, float(scale)
     if w3_off is not None:      # the fused conv3's C3F fragments (csrc/cf_pack.h)
-        fo.c3f = ws.get(("cf_c3f",), C3F_BYTES, dev, torch.uint8).data_ptr()
+        fo.c3f = ws.get(("cf_c3f",), C3F_BYTES, dev, torch.uint8).data_ptr() + s * 2 * 4608 * 16
         fo.w3_off = int(w3_off)
     return fo
 

@@ -615,7 +615,8 @@ class TorchBackend:
 
     # ----------------------------------------------------------- optimizer
     def optimizer(self, p32, g32, v, m, pbf, lr, alpha, eps, clip, centered, partials, norm_out, norm_total=None,
-                  sample=None, pb_lo=None, wnorm=None, frag_out=None, segs=None, norm_prefix=None, opt=None):
+                  sample=None, pb_lo=None, wnorm=None, frag_out=None, segs=None, norm_prefix=None, opt=None,
+                  target=None):
         """``sample = (replay, B, out, nxt2[, obs2])``: also draw the next
         batch after the update (the HIP backend fuses it into the optimizer launch; ``obs2``: the
         sampler's second copy of the S_t slots, the Munchausen row plan).
@@ -629,9 +630,16 @@ class TorchBackend:
         gradient range whose squares join the partials' sum (summed inside the launch).
         ``opt`` (learner/schedules.py ``OptSpec``): Adam instead of RMSprop (``v`` / ``m`` hold
         the second / first moment; ``alpha``, ``eps`` and ``centered`` are unused) and / or
-        the step-indexed learning rate, both from the update index on the device."""
+        the step-indexed learning rate, both from the update index on the device.
+        ``target = (t32, tbf, tbf_lo, rho, frag_out_target)``: the soft target net averaged with the
+        weights just written, t <- (1 - rho) t + rho p (learner/schedules.py ``target_ema``), and its
+        bf16 planes; ``frag_out_target``: the fused forward's target fragments too (HIP backend)."""
         self._optimizer(p32, g32, v, m, pbf, lr, alpha, eps, clip, centered, norm_out, pb_lo, wnorm, norm_total,
                         segs, norm_prefix, opt)
+        if target is not None:
+            if segs is not None:
+                raise ValueError("the soft target is averaged over the whole parameter vector, not in a sharded update")
+            self._target_ema(p32, *target[:4])
         if sample is not None:
             rp, B, out, nxt2, obs2 = _sample5(sample)
             rp.sample(B, out=out, nxt2=nxt2, **({} if obs2 is None else {"obs2": obs2}))
@@ -679,6 +687,16 @@ class TorchBackend:
             pr.sub_(lr * g / (var.clamp_min(0).sqrt() + eps))
             split_into(pr, pbf[r], None if pb_lo is None else pb_lo[r])
         norm_out.copy_(norm.view(1))
+
+    @staticmethod
+    def _target_ema(p32, t32, tbf, tbf_lo, rho) -> None:
+        """The mirror's three roundings as separate fp32 tensor operations (no addcmul / lerp)."""
+        r = torch.tensor(float(rho), dtype=torch.float32, device=p32.device)
+        a = torch.ones_like(r) - r
+        ta = t32 * a
+        pr = p32 * r
+        torch.add(ta, pr, out=t32)
+        split_into(t32, tbf, tbf_lo)
 
     def gather_frames(self, replay, slots, out):
         replay.gather_frames(slots, out)
@@ -1166,13 +1184,27 @@ class HipBackend(TorchBackend):
         return os_
 
     def optimizer(self, p32, g32, v, m, pbf, lr, alpha, eps, clip, centered, partials, norm_out, norm_total=None,
-                  sample=None, pb_lo=None, wnorm=None, frag_out=None, segs=None, norm_prefix=None, opt=None) -> bool:
+                  sample=None, pb_lo=None, wnorm=None, frag_out=None, segs=None, norm_prefix=None, opt=None,
+                  target=None) -> bool:
         """``frag_out`` (ops/conv.py conv12_frag_out): the launch also stores the updated
         w1 / w2 in the fused forward's fragment order.  Returns whether it did (the fused
         optimizer + sample launch only).  ``segs``: the ranges to update (the sharded DP
-        update: one launch, csrc/sumtree.hip ``RmsSegs``)."""
+        update: one launch, csrc/sumtree.hip ``RmsSegs``).  ``target``: the soft target net, averaged in the
+        same launch (csrc/rmsprop_common.h ``OptTarget``)."""
         n = p32.numel()
         osd = self._opt_sched(opt)
+        tg = _lib.OptTarget()
+        if target is not None:
+            t32, tbf, tbf_lo, rho, tfo = target
+            if segs is not None:
+                raise ValueError("the soft target is averaged over the whole parameter vector, not in a sharded update")
+            if tfo is not None and frag_out is None:
+                raise ValueError("the target's fragment stores ride beside the online ones (frag_out)")
+            assert t32.dtype == torch.float32 and t32.numel() == n and tbf.numel() == n and tbf.dtype == pbf.dtype \
+                and (tbf_lo is None) == (pb_lo is None) and (tbf_lo is None or tbf_lo.numel() == n)
+            tg.t, tg.tb, tg.tb_lo, tg.rho = t32.data_ptr(), tbf.data_ptr(), _lib.ptr(tbf_lo), float(rho)
+            if tfo is not None:
+                tg.tfo = tfo
         if opt is not None and opt.adam:
             eps = opt.adam_eps        # (RmspropArgs.eps carries Adam's epsilon)
         if segs is not None:
@@ -1208,14 +1240,14 @@ class HipBackend(TorchBackend):
                 float(lr), float(alpha), float(eps), float(clip), int(centered), norm_out.data_ptr(),
                 *rp.sample_launch_args(B, out, nxt2, obs2), lo, *wn,
                 frag_out if frag_out is not None else _lib.CfFragOut(),
-                segp, _lib.ptr(norm_prefix), 0 if norm_prefix is None else norm_prefix.numel(), osd, st),
+                segp, _lib.ptr(norm_prefix), 0 if norm_prefix is None else norm_prefix.numel(), osd, tg, st),
                 "rmsprop_sample")
             return frag_out is not None
         if norm_prefix is not None:
             raise ValueError("norm_prefix runs in the fused optimizer + sample launch")
         if sample is not None:
             self.optimizer(p32, g32, v, m, pbf, lr, alpha, eps, clip, centered, partials, norm_out, norm_total,
-                           pb_lo=pb_lo, wnorm=wnorm, opt=opt)
+                           pb_lo=pb_lo, wnorm=wnorm, opt=opt, target=target)
             rp, B, out, nxt2, obs2 = _sample5(sample)
             rp.sample(B, out=out, nxt2=nxt2, **({} if obs2 is None else {"obs2": obs2}))
             return
@@ -1224,13 +1256,13 @@ class HipBackend(TorchBackend):
             _lib.check(self.lib.apex_rmsprop_step_np(p32.data_ptr(), g32.data_ptr(), v.data_ptr(), m.data_ptr(),
                                                      pbf.data_ptr(), n, part.data_ptr(), npart, float(lr),
                                                      float(alpha), float(eps), float(clip), int(centered),
-                                                     norm_out.data_ptr(), lo, *wn, osd, st), "rmsprop_np")
+                                                     norm_out.data_ptr(), lo, *wn, osd, tg, st), "rmsprop_np")
             return
         _lib.check(self.lib.apex_grad_sqnorm_partials(g32.data_ptr(), n, partials.data_ptr(), st), "sqnorm")
         _lib.check(self.lib.apex_rmsprop_step(p32.data_ptr(), g32.data_ptr(), v.data_ptr(), m.data_ptr(),
                                               pbf.data_ptr(), n, partials.data_ptr(), float(lr), float(alpha),
                                               float(eps), float(clip), int(centered), norm_out.data_ptr(), lo, *wn,
-                                              osd, st),
+                                              osd, tg, st),
                    "rmsprop")
 
     def _pack_args(self, dst: torch.Tensor, segs):
