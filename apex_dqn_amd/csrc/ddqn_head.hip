@@ -96,15 +96,10 @@ APEX_EXPORT int apex_ddqn_head(const bf16_t* Hon, const bf16_t* Htg, HeadParams 
   APEX_CHECK_LAUNCH();
 }
 
-// nv >= 2: nv value rows and A advantage rows (the distributional head: dhead [B, nv + A])
-APEX_EXPORT int apex_head_wgrad(const bf16_t* Hon, const float* dhead, int B, int A, float* gwv, float* gbv,
-                                float* gwa, float* gba, int hidden, const bf16_t* Hon_lo, int nv, double* norm_part,
-                                hipStream_t st) {
-  if ((hidden != 512 && hidden != 256) || nv < 1 || A < 1 || B < 1) return (int)hipErrorInvalidValue;
-  if (norm_part != nullptr && nv < 2) return (int)hipErrorInvalidValue;    // (the wide head's partials only)
-  dim3 grid(nv >= 2 ? head_wgrad_wide_tiles(nv, A) : A + 1, hidden / 64);
-  head_wgrad_kernel<<<grid, 512, 0, st>>>(HeadWgArgs{Hon, dhead, B, A, gwv, gbv, gwa, gba, hidden, Hon_lo, nv,
-                                                     norm_part});
+// h.NV >= 2: NV value rows and A advantage rows (the distributional head: dhead [B, NV + A])
+APEX_EXPORT int apex_head_wgrad(HeadWgArgs h, hipStream_t st) {
+  if (!head_wg_args_ok(h)) return (int)hipErrorInvalidValue;
+  head_wgrad_kernel<<<dim3(head_wg_rows(h), h.HS / 64), 512, 0, st>>>(h);
   APEX_CHECK_LAUNCH();
 }
 

@@ -609,6 +609,13 @@ __host__ __device__ __forceinline__ int head_wgrad_wide_tiles(int NV, int A) {
   return (NV + HWG_JT - 1) / HWG_JT + (A + HWG_JT - 1) / HWG_JT;
 }
 
+// what every head weight-gradient launcher checks (norm_part: the wide head's partials only), and the rows of
+// blocks it launches
+inline bool head_wg_args_ok(const HeadWgArgs& h) {
+  return (h.HS == 512 || h.HS == 256) && h.NV >= 1 && h.A >= 1 && h.B >= 1 && (h.norm_part == nullptr || h.NV >= 2);
+}
+inline int head_wg_rows(const HeadWgArgs& h) { return h.NV >= 2 ? head_wgrad_wide_tiles(h.NV, h.A) : h.A + 1; }
+
 // (`slot`: the block's index among the wide blocks, its place in h.norm_part)
 __device__ __forceinline__ void head_wgrad_wide_body(const HeadWgArgs& h, int tile, int chunk, int slot) {
   const bf16_t* __restrict__ Hon = h.Hon;

@@ -12,8 +12,6 @@
 #include "rmsprop_common.h"
 #include "pack_rows.h"
 
-#define NPART 1024
-
 __global__ void __launch_bounds__(256) sqnorm_partial_kernel(const float* __restrict__ g, int64_t n,
                                                              double* __restrict__ partials) {
   __shared__ double red[4];
@@ -46,24 +44,20 @@ __global__ void __launch_bounds__(256) opt_ema_kernel(RmspropArgs a) {
   rmsprop_body<MODE, true>(a, blockIdx.x, gridDim.x);
 }
 
-static int launch_opt(const RmspropArgs& a, hipStream_t st) {
-  if (((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.v | (uintptr_t)a.m) & 15) return (int)hipErrorInvalidValue;
-  if (((uintptr_t)a.pb | (uintptr_t)a.pb_lo) & 7) return (int)hipErrorInvalidValue;
-  const int mode = opt_mode(a.os);
-  if (mode != OPT_RMSPROP && (a.os.ctr == nullptr || a.os.base == nullptr)) return (int)hipErrorInvalidValue;
+// `a.partials` holds `a.npart` squared-norm partials: SQNORM_NPART of apex_grad_sqnorm_partials, or what the
+// gradient producers wrote (fc wgrad epilogue + grad_finalize blocks: no separate squared-norm pass).
+// This form stores no fragments and sums no gradient prefix (apex_opt_sample does).
+APEX_EXPORT int apex_opt_step(RmspropArgs a, hipStream_t st) {
   int nb = (int)((a.n / 4 + 255) / 256);
   nb = nb < 1 ? 1 : (nb > 2048 ? 2048 : nb);
-  // (these launch forms store no fragments: a.fo is empty, so a target fragment block is refused)
-  if (opt_target_check(a.tg, a.pb_lo, a.fo, a.n, (int64_t)nb * 256 * 4)) return (int)hipErrorInvalidValue;
-  if (a.tg.t != nullptr) {
-    if (mode == OPT_ADAM) opt_ema_kernel<OPT_ADAM><<<nb, 256, 0, st>>>(a);
-    else if (mode == OPT_RMSPROP_SCHED) opt_ema_kernel<OPT_RMSPROP_SCHED><<<nb, 256, 0, st>>>(a);
-    else opt_ema_kernel<OPT_RMSPROP><<<nb, 256, 0, st>>>(a);
-    APEX_CHECK_LAUNCH();
-  }
-  if (mode == OPT_ADAM) opt_sched_kernel<OPT_ADAM><<<nb, 256, 0, st>>>(a);
-  else if (mode == OPT_RMSPROP_SCHED) opt_sched_kernel<OPT_RMSPROP_SCHED><<<nb, 256, 0, st>>>(a);
-  else rmsprop_kernel<<<nb, 256, 0, st>>>(a);
+  if (a.fo.w1frag != nullptr || a.gpre != nullptr || a.npre != 0 || !opt_args_ok(a, a.n, (int64_t)nb * 256 * 4))
+    return (int)hipErrorInvalidValue;
+  opt_dispatch(a, [&](auto mode, auto ema) {
+    constexpr int MODE = decltype(mode)::value;
+    if constexpr (decltype(ema)::value) opt_ema_kernel<MODE><<<nb, 256, 0, st>>>(a);
+    else if constexpr (MODE == OPT_RMSPROP) rmsprop_kernel<<<nb, 256, 0, st>>>(a);
+    else opt_sched_kernel<MODE><<<nb, 256, 0, st>>>(a);
+  });
   APEX_CHECK_LAUNCH();
 }
 
@@ -78,28 +72,8 @@ __global__ void cast_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict
 }
 
 APEX_EXPORT int apex_grad_sqnorm_partials(const float* g, int64_t n, double* partials, hipStream_t st) {
-  sqnorm_partial_kernel<<<NPART, 256, 0, st>>>(g, n, partials);
+  sqnorm_partial_kernel<<<SQNORM_NPART, 256, 0, st>>>(g, n, partials);
   APEX_CHECK_LAUNCH();
-}
-
-APEX_EXPORT int apex_rmsprop_step(float* p, const float* g, float* v, float* m, bf16_t* pb, int64_t n,
-                                  const double* partials, float lr, float alpha, float eps, float clip,
-                                  int centered, float* norm_out, bf16_t* pb_lo, const double* wnorm, int wn,
-                                  int wstride, OptSched os, OptTarget tg, hipStream_t st) {
-  return launch_opt(RmspropArgs{p, g, v, m, pb, n, partials, NPART, lr, alpha, eps, clip, centered, norm_out, pb_lo,
-                                wnorm, wn, wstride, CfFragOut{}, nullptr, 0, os, tg},
-                    st);
-}
-
-// the same step with the clip norm taken from ``npart`` producer-written partials
-// (fc wgrad epilogue + grad_finalize blocks): no separate squared-norm pass
-APEX_EXPORT int apex_rmsprop_step_np(float* p, const float* g, float* v, float* m, bf16_t* pb, int64_t n,
-                                     const double* partials, int npart, float lr, float alpha, float eps, float clip,
-                                     int centered, float* norm_out, bf16_t* pb_lo, const double* wnorm, int wn,
-                                     int wstride, OptSched os, OptTarget tg, hipStream_t st) {
-  return launch_opt(RmspropArgs{p, g, v, m, pb, n, partials, npart, lr, alpha, eps, clip, centered, norm_out, pb_lo,
-                                wnorm, wn, wstride, CfFragOut{}, nullptr, 0, os, tg},
-                    st);
 }
 
 APEX_EXPORT int apex_cast_bf16(const float* x, bf16_t* y, int64_t n, bf16_t* lo, hipStream_t st) {

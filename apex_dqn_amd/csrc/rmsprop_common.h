@@ -8,8 +8,11 @@
 // with a step-indexed learning rate, and Adam.  The last two read the update index
 // from device memory (OptSched), so a replayed graph needs no host round trip.
 #pragma once
+#include <type_traits>
 #include "apex_common.h"
 #include "cf_pack.h"
+
+#define SQNORM_NPART 1024    // partials apex_grad_sqnorm_partials writes (ops/_lib.py SQNORM_PARTIALS)
 
 // Batch-max IS-weight normalisation (Runtime.is_normalise = "batch_max"): the head
 // kernel leaves m = max_j (p_j / p_min)^-beta over the batch (DP: one per rank, in the
@@ -372,4 +375,26 @@ inline int opt_target_check(const OptTarget& g, const bf16_t* pb_lo, const CfFra
   if (f.c3f != nullptr && ((f.w3_off & 3) || f.w3_off + 36864 > n0 || f.w3_off + 36864 > first || ((uintptr_t)f.c3f & 15)))
     return 1;
   return 0;
+}
+
+// The checks every optimizer launch form makes (`n0`, `first`: as opt_target_check): the float4 / packed-bf16
+// alignment of the flat arrays, a step-indexed mode's counter and base, and the target block.
+inline bool opt_args_ok(const RmspropArgs& a, int64_t n0, int64_t first) {
+  if (((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.v | (uintptr_t)a.m) & 15) return false;
+  if (((uintptr_t)a.pb | (uintptr_t)a.pb_lo) & 7) return false;
+  if (opt_mode(a.os) != OPT_RMSPROP && (a.os.ctr == nullptr || a.os.base == nullptr)) return false;
+  return opt_target_check(a.tg, a.pb_lo, a.fo, n0, first) == 0;
+}
+
+// f(mode, ema) with the block's MODE and EMA as integral constants: the one MODE x EMA ladder of the launchers
+template <class F>
+inline void opt_dispatch(const RmspropArgs& a, F&& f) {
+  auto with_ema = [&](auto ema) {
+    const int mode = opt_mode(a.os);
+    if (mode == OPT_ADAM) f(std::integral_constant<int, OPT_ADAM>{}, ema);
+    else if (mode == OPT_RMSPROP_SCHED) f(std::integral_constant<int, OPT_RMSPROP_SCHED>{}, ema);
+    else f(std::integral_constant<int, OPT_RMSPROP>{}, ema);
+  };
+  if (a.tg.t != nullptr) with_ema(std::true_type{});
+  else with_ema(std::false_type{});
 }

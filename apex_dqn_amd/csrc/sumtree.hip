@@ -723,21 +723,18 @@ APEX_EXPORT int apex_replay_insert(TreeDesc t, RecordDesc r, int64_t start, int 
   APEX_CHECK_LAUNCH();
 }
 
-APEX_EXPORT int apex_tree_sample(TreeDesc t, RecordDesc r, int B, uint64_t seed, const uint64_t* ctr,
-                                 float beta, int64_t* out_idx, float* out_w,
-                                 int32_t* out_gen, int32_t* out_obs, int32_t* out_nxt, int32_t* out_act,
-                                 float* out_rew, float* out_gam, int32_t* out_nxt2, int32_t* out_obs2,
-                                 const double* shard_stats, int shard_rank, int shard_world, uint64_t shard_seed,
-                                 float* out_wscale, int64_t mcap, BetaSched bs, hipStream_t st) {
-  if (B <= 0) return 0;
-  if (mcap <= 0) mcap = (int64_t)shard_world * B;
-  if (shard_stats != nullptr && (B < 3 || shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world))
-    return (int)hipErrorInvalidValue;
+// what both sampling entry points check: the `mcap` default (W B) and the sharded draw's arguments
+static bool sample_args_ok(SampleArgs& s) {
+  if (s.mcap <= 0) s.mcap = (int64_t)s.shard_world * s.B;
+  return s.shard_stats == nullptr ||
+         (s.B >= 3 && s.shard_world >= 1 && s.shard_rank >= 0 && s.shard_rank < s.shard_world);
+}
+
+APEX_EXPORT int apex_tree_sample(SampleArgs s, hipStream_t st) {
+  if (s.B <= 0) return 0;
+  if (!sample_args_ok(s)) return (int)hipErrorInvalidValue;
   const int waves_per_block = 4;
-  tree_sample_kernel<<<blocks_for(B, waves_per_block), 64 * waves_per_block, 0, st>>>(
-      SampleArgs{t, r, B, seed, ctr, beta, out_idx, out_w, out_gen, out_obs, out_nxt, out_act,
-                 out_rew, out_gam, out_nxt2, out_obs2, shard_stats, shard_rank, shard_world, shard_seed,
-                 out_wscale, mcap, bs});
+  tree_sample_kernel<<<blocks_for(s.B, waves_per_block), 64 * waves_per_block, 0, st>>>(s);
   APEX_CHECK_LAUNCH();
 }
 
@@ -783,7 +780,17 @@ APEX_EXPORT int apex_fill16(void* p, int64_t n, int nt, hipStream_t st) {
   APEX_CHECK_LAUNCH();
 }
 
-APEX_EXPORT int apex_abi_version() { return 14; }
+APEX_EXPORT int apex_abi_version() { return 15; }
+
+// sizeof of every block that crosses the ABI by value in the launchers below, in the order of ops/_lib.py
+// ABI_STRUCTS (host only): a mirror that drifts by a field would otherwise only shift kernarg contents
+APEX_EXPORT int apex_abi_struct_sizes(int* out, int cap) {
+  const int sz[] = {(int)sizeof(RmspropArgs), (int)sizeof(SampleArgs), (int)sizeof(RmsSegs), (int)sizeof(TreeUpdArgs),
+                    (int)sizeof(HeadWgArgs), (int)sizeof(IqnWgArgs), (int)sizeof(WgradDesc)};
+  const int n = (int)(sizeof(sz) / sizeof(sz[0]));
+  for (int i = 0; i < n && i < cap; ++i) out[i] = sz[i];
+  return n;
+}
 
 // 1 if this library was built with -DAPEX_DEBUG_BOUNDS
 APEX_EXPORT int apex_debug_bounds_enabled() {
@@ -819,27 +826,13 @@ APEX_EXPORT int apex_debug_errors(int* counts, long long* first, int reset) {
 #endif
 }
 
-// rmsprop (clip norm from `npart` partials, as apex_rmsprop_step_np) + tree_sample of B.
+// The optimizer (clip norm from `a.npart` partials, as apex_opt_step) + tree_sample of s.B.
 // `seg` (nullable): update only those ranges (offsets relative to p / g / v / m / pb);
 // blk0 is filled in here.
-APEX_EXPORT int apex_rmsprop_sample(float* p, const float* g, float* v, float* m, bf16_t* pb, int64_t n,
-                                    const double* partials, int npart, float lr, float alpha, float eps_opt,
-                                    float clip, int centered, float* norm_out, TreeDesc t, RecordDesc r, int B,
-                                    uint64_t seed, const uint64_t* ctr, float beta,
-                                    int64_t* out_idx, float* out_w, int32_t* out_gen, int32_t* out_obs,
-                                    int32_t* out_nxt, int32_t* out_act, float* out_rew, float* out_gam,
-                                    int32_t* out_nxt2, int32_t* out_obs2, const double* shard_stats, int shard_rank,
-                                    int shard_world, uint64_t shard_seed, float* out_wscale, int64_t mcap,
-                                    BetaSched bs, bf16_t* pb_lo, const double* wnorm, int wn, int wstride, CfFragOut fo,
-                                    const RmsSegs* seg, const float* gpre, int64_t npre, OptSched os,
-                                    OptTarget tg, hipStream_t st) {
-  const int mode = opt_mode(os);
-  if (mode != OPT_RMSPROP && (os.ctr == nullptr || os.base == nullptr)) return (int)hipErrorInvalidValue;
-  if (mcap <= 0) mcap = (int64_t)shard_world * B;
-  if (shard_stats != nullptr && (B < 3 || shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world))
-    return (int)hipErrorInvalidValue;
-  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)v | (uintptr_t)m) & 15) return (int)hipErrorInvalidValue;
-  if ((((uintptr_t)pb | (uintptr_t)pb_lo) & 7) || B < 0) return (int)hipErrorInvalidValue;
+APEX_EXPORT int apex_opt_sample(RmspropArgs a, SampleArgs s, const RmsSegs* seg, hipStream_t st) {
+  if (!sample_args_ok(s) || s.B < 0) return (int)hipErrorInvalidValue;
+  const CfFragOut& fo = a.fo;
+  const int64_t n = a.n;
   // 512-thread blocks, grid capped at 256: every block first sums the ~2.6 K clip-norm
   // partials, so fewer, fatter blocks cut those L2 reads (256 x 512 measured 2,540 / 4,175
   // fp32 / bf16 steps/s vs 2,528 / 4,107 at 512 x 512 and 3497-3520 vs 3543-3576 at
@@ -875,7 +868,7 @@ APEX_EXPORT int apex_rmsprop_sample(float* p, const float* g, float* v, float* m
     sg.blk0[sg.nseg] = b0;
     nb = sg.blk0[1];              // segment 0's blocks: the fragment-store check below
   }
-  const int nsb = B > 0 ? blocks_for(B, nt / 64) : 0;
+  const int nsb = s.B > 0 ? blocks_for(s.B, nt / 64) : 0;
   const int64_t n0 = seg != nullptr ? sg.len[0] : n;
   if (fo.w1frag != nullptr && (seg != nullptr && sg.off[0] != 0)) return (int)hipErrorInvalidValue;
   if (fo.w1frag != nullptr && (fo.c2f == nullptr || (fo.C != 1 && fo.C != 2 && fo.C != 4) ||
@@ -887,48 +880,37 @@ APEX_EXPORT int apex_rmsprop_sample(float* p, const float* g, float* v, float* m
   if (fo.w1frag != nullptr && fo.c3f != nullptr &&
       ((fo.w3_off & 3) || fo.w3_off + 36864 > n0 || (fo.w3_off + 36864) / 4 > (int64_t)nb * nt || ((uintptr_t)fo.c3f & 15)))
     return (int)hipErrorInvalidValue;
-  if (((uintptr_t)gpre & 15) || npre < 0 || (npre > 0 && gpre == nullptr)) return (int)hipErrorInvalidValue;
+  if (((uintptr_t)a.gpre & 15) || a.npre < 0 || (a.npre > 0 && a.gpre == nullptr)) return (int)hipErrorInvalidValue;
+  if (a.npre == 0) a.gpre = nullptr;
   // the soft target: the whole-range form only; its fragment stores obey the online ones' rules
-  if (tg.t != nullptr && seg != nullptr) return (int)hipErrorInvalidValue;
-  if (opt_target_check(tg, pb_lo, fo, n0, (int64_t)nb * nt * 4)) return (int)hipErrorInvalidValue;
-  const RmspropArgs ra{p, g, v, m, pb, n, partials, npart, lr, alpha, eps_opt, clip, centered, norm_out, pb_lo,
-                      wnorm, wn, wstride, fo, npre > 0 ? gpre : nullptr, npre, os, tg};
-  const SampleArgs sa{t, r, B, seed, ctr, beta, out_idx, out_w, out_gen, out_obs, out_nxt,
-                      out_act, out_rew, out_gam, out_nxt2, out_obs2, shard_stats, shard_rank, shard_world,
-                      shard_seed, out_wscale, mcap, bs};
+  if (a.tg.t != nullptr && seg != nullptr) return (int)hipErrorInvalidValue;
+  if (!opt_args_ok(a, n0, (int64_t)nb * nt * 4)) return (int)hipErrorInvalidValue;
   const int grid = (seg != nullptr ? sg.blk0[sg.nseg] : nb) + nsb;
-#define APEX_OPT_LAUNCH(MODE)                                                                          \
-  do {                                                                                                 \
-    if (seg != nullptr) rmsprop_sample_kernel<nt, true, MODE><<<grid, nt, 0, st>>>(ra, sa, nsb, sg);    \
-    else rmsprop_sample_kernel<nt, false, MODE><<<grid, nt, 0, st>>>(ra, sa, nsb, sg);                  \
-  } while (0)
-#define APEX_EMA_LAUNCH(MODE) rmsprop_sample_kernel<nt, false, MODE, true><<<grid, nt, 0, st>>>(ra, sa, nsb, sg)
-  if (tg.t != nullptr) {
-    if (mode == OPT_ADAM) APEX_EMA_LAUNCH(OPT_ADAM);
-    else if (mode == OPT_RMSPROP_SCHED) APEX_EMA_LAUNCH(OPT_RMSPROP_SCHED);
-    else APEX_EMA_LAUNCH(OPT_RMSPROP);
-  } else if (mode == OPT_ADAM) APEX_OPT_LAUNCH(OPT_ADAM);
-  else if (mode == OPT_RMSPROP_SCHED) APEX_OPT_LAUNCH(OPT_RMSPROP_SCHED);
-  else APEX_OPT_LAUNCH(OPT_RMSPROP);
-#undef APEX_EMA_LAUNCH
-#undef APEX_OPT_LAUNCH
+  opt_dispatch(a, [&](auto mode, auto ema) {
+    constexpr int MODE = decltype(mode)::value;
+    if constexpr (decltype(ema)::value) rmsprop_sample_kernel<nt, false, MODE, true><<<grid, nt, 0, st>>>(a, s, nsb, sg);
+    else if (seg != nullptr) rmsprop_sample_kernel<nt, true, MODE><<<grid, nt, 0, st>>>(a, s, nsb, sg);
+    else rmsprop_sample_kernel<nt, false, MODE><<<grid, nt, 0, st>>>(a, s, nsb, sg);
+  });
   APEX_CHECK_LAUNCH();
 }
 
-APEX_EXPORT int apex_head_wgrad_prio(const bf16_t* Hon, const float* dhead, int B, int A, float* gwv, float* gbv,
-                                     float* gwa, float* gba, int hidden, TreeDesc t, const int64_t* idx,
-                                     const float* td, const int32_t* gen_expect, const int32_t* gen,
-                                     float alpha, float eps, uint64_t* ctr_to_bump, const bf16_t* Hon_lo,
-                                     double* stats_out, const uint16_t* const* psrc, const int64_t* pld,
+// The single-block tree update of `n` items inside a launch of `threads`-thread blocks (TU_MAXR items per
+// thread): checks the caller's part of the block and fills in `n` and `kfirst`.
+static bool tree_upd_fill(TreeUpdArgs& tu, int n, int threads) {
+  if (n < 1 || n > 1024 || n > TU_MAXR * threads || tu.idx == nullptr || tu.td == nullptr) return false;
+  tu.n = n;
+  tu.kfirst = tree_kfirst(tu.t);
+  return true;
+}
+
+// (hw.NV >= 2: the distributional head's NV value rows + A advantage rows, head_wgrad_wide_body)
+// optional row pack in the same launch (pnseg > 0): up to 256 tail blocks
+APEX_EXPORT int apex_head_wgrad_prio(HeadWgArgs hw, TreeUpdArgs tu, const uint16_t* const* psrc, const int64_t* pld,
                                      const int* pcols, int pnseg, int prows, uint16_t* pdst, int64_t pdld,
-                                     int nv, double* norm_part, hipStream_t st) {
-  if (norm_part != nullptr && nv < 2) return (int)hipErrorInvalidValue;    // (the wide head's partials only)
-  // the single-block tree update holds TU_MAXR items per thread
-  if ((hidden != 512 && hidden != 256) || B < 1 || B > 1024 || B > TU_MAXR * 512 || idx == nullptr || nv < 1 || A < 1)
-    return (int)hipErrorInvalidValue;
-  // (nv >= 2: the distributional head's nv value rows + A advantage rows, head_wgrad_wide_body)
-  const int nhw = (nv >= 2 ? head_wgrad_wide_tiles(nv, A) : A + 1) * (hidden / 64);
-  // optional row pack in the same launch (pnseg > 0): up to 256 tail blocks
+                                     hipStream_t st) {
+  if (!head_wg_args_ok(hw) || !tree_upd_fill(tu, hw.B, 512)) return (int)hipErrorInvalidValue;
+  const int nhw = head_wg_rows(hw) * (hw.HS / 64);
   PackRows pk{};
   int npk = 0;
   if (pnseg > 0) {
@@ -938,62 +920,50 @@ APEX_EXPORT int apex_head_wgrad_prio(const bf16_t* Hon, const float* dhead, int 
     npk = (int)((nchunks + 511) / 512);
     npk = npk > 256 ? 256 : npk;
   }
-  head_wgrad_prio_kernel<<<1 + nhw + npk, 512, 0, st>>>(
-      HeadWgArgs{Hon, dhead, B, A, gwv, gbv, gwa, gba, hidden, Hon_lo, nv, norm_part},
-      TreeUpdArgs{t, idx, td, gen_expect, gen, ctr_to_bump, alpha, eps, B, tree_kfirst(t), stats_out}, pk, nhw, npk);
+  head_wgrad_prio_kernel<<<1 + nhw + npk, 512, 0, st>>>(hw, tu, pk, nhw, npk);
   APEX_CHECK_LAUNCH();
 }
 
 APEX_EXPORT int apex_iqn_wgrad_part_floats() { return IQN_WG_S * (2 * DIST_HS * IQN_E + 2 * DIST_HS); }
 
-// without the priority write-back (tests, benchmarks)
+// `tu` (nullable): block 0 of the launch writes the priorities back; without it (tests, benchmarks) the blocks
+// start at 0
+static int launch_iqn_wgrad(const IqnWgArgs& h, const TreeUpdArgs* tu, hipStream_t st) {
+  const int prio = tu != nullptr ? 1 : 0;
+  iqn_wgrad_prio_kernel<<<prio + iqn_wgrad_blocks(h.A), 512, 0, st>>>(h, prio ? *tu : TreeUpdArgs{}, prio);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  iqn_wgrad_reduce_kernel<<<(2 * DIST_HS * IQN_E + 2 * DIST_HS + 255) / 256, 256, 0, st>>>(h);
+  APEX_CHECK_LAUNCH();
+}
+
 APEX_EXPORT int apex_iqn_wgrad(IqnWgArgs h, hipStream_t st) {
   if (!iqn_wgrad_args_ok(h)) return (int)hipErrorInvalidValue;
-  iqn_wgrad_prio_kernel<<<iqn_wgrad_blocks(h.A), 512, 0, st>>>(h, TreeUpdArgs{}, 0);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
-  iqn_wgrad_reduce_kernel<<<(2 * DIST_HS * IQN_E + 2 * DIST_HS + 255) / 256, 256, 0, st>>>(h);
-  APEX_CHECK_LAUNCH();
+  return launch_iqn_wgrad(h, nullptr, st);
 }
 
-APEX_EXPORT int apex_iqn_wgrad_prio(IqnWgArgs h, TreeDesc t, const int64_t* idx, const float* td,
-                                    const int32_t* gen_expect, const int32_t* gen, float alpha, float eps,
-                                    uint64_t* ctr_to_bump, double* stats_out, hipStream_t st) {
-  // the single-block tree update holds TU_MAXR items per thread
-  if (!iqn_wgrad_args_ok(h) || h.B > 1024 || h.B > TU_MAXR * 512 || idx == nullptr || td == nullptr)
-    return (int)hipErrorInvalidValue;
-  iqn_wgrad_prio_kernel<<<1 + iqn_wgrad_blocks(h.A), 512, 0, st>>>(
-      h, TreeUpdArgs{t, idx, td, gen_expect, gen, ctr_to_bump, alpha, eps, h.B, tree_kfirst(t), stats_out}, 1);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
-  iqn_wgrad_reduce_kernel<<<(2 * DIST_HS * IQN_E + 2 * DIST_HS + 255) / 256, 256, 0, st>>>(h);
-  APEX_CHECK_LAUNCH();
+APEX_EXPORT int apex_iqn_wgrad_prio(IqnWgArgs h, TreeUpdArgs tu, hipStream_t st) {
+  if (!iqn_wgrad_args_ok(h) || !tree_upd_fill(tu, h.B, 512)) return (int)hipErrorInvalidValue;
+  return launch_iqn_wgrad(h, &tu, st);
 }
 
-// the fused launch above; returns hipErrorInvalidValue when the fc problem is not
+// the fused launch above (the scalar head only); returns hipErrorInvalidValue when the fc problem is not
 // the (CT=4, NT=1, single split, dense) shape it is compiled for -- the caller then
 // issues the three launches separately
-APEX_EXPORT int apex_fc_wgrad_head_prio(WgradDesc d, const bf16_t* Hon, const float* dhead, int B, int A,
-                                        float* gwv, float* gbv, float* gwa, float* gba, int hidden, TreeDesc t,
-                                        const int64_t* idx, const float* td, const int32_t* gen_expect,
-                                        const int32_t* gen, float alpha, float eps, uint64_t* ctr_to_bump,
-                                        const bf16_t* Hon_lo, double* stats_out, hipStream_t st) {
-  // 256-thread blocks: the single-block tree update holds TU_MAXR items per thread
-  if ((hidden != 512 && hidden != 256) || B < 1 || B > 1024 || B > TU_MAXR * 256 || idx == nullptr)
-    return (int)hipErrorInvalidValue;
+APEX_EXPORT int apex_fc_wgrad_head_prio(WgradDesc d, HeadWgArgs hw, TreeUpdArgs tu, hipStream_t st) {
+  // 256-thread blocks
+  if (!head_wg_args_ok(hw) || hw.NV != 1 || !tree_upd_fill(tu, hw.B, 256)) return (int)hipErrorInvalidValue;
   if (d.mode != 0 || (d.Kc & 63) || (d.Co & 63) || d.rows_per_split < d.Mred) return (int)hipErrorInvalidValue;
   if ((int64_t)d.Mred * d.ldd * 2 >= 0x7ffffff0LL || (int64_t)d.Mred * d.ldx * 2 >= 0x7ffffff0LL)
     return (int)hipErrorInvalidValue;
   const bool split = d.dy_lo != nullptr;
-  if (split && (d.x_lo == nullptr || Hon_lo == nullptr)) return (int)hipErrorInvalidValue;
+  if (split && (d.x_lo == nullptr || hw.Hon_lo == nullptr)) return (int)hipErrorInvalidValue;
   const int kt = d.Kc / 64, ct = d.Co / 64;
   // the compiled shape: {CT,NT} = {4,1} (index 2) in bf16, {2,1} (index 6) in split mode
   if (wgrad_shape(kt, ct, d.Kc, d.Co, split ? 1 : 0) != (split ? 6 : 2)) return (int)hipErrorInvalidValue;
   const int gx = kt, gy = ct / (split ? 2 : 4);
-  const int nhw = (A + 1) * (hidden / 64);
+  const int nhw = (hw.A + 1) * (hw.HS / 64);
   const int blk0 = (1 + nhw + 7) & ~7;
-  const HeadWgArgs hw{Hon, dhead, B, A, gwv, gbv, gwa, gba, hidden, Hon_lo};
-  const TreeUpdArgs tu{t, idx, td, gen_expect, gen, ctr_to_bump, alpha, eps, B, tree_kfirst(t), stats_out};
   if (split) fc_wgrad_head_prio_kernel<1><<<blk0 + gx * gy, 256, 0, st>>>(d, gx, gy, hw, tu, nhw, blk0);
   else fc_wgrad_head_prio_kernel<0><<<blk0 + gx * gy, 256, 0, st>>>(d, gx, gy, hw, tu, nhw, blk0);
   APEX_CHECK_LAUNCH();

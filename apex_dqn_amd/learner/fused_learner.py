@@ -764,9 +764,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
                       ((self.norm_part, norm_slots) if norm_slots else None), sample=nxt,
                       wnorm=self._wnorm(), **self._lo(pb_lo=self.pbf_lo),
                       **({"frag_out": self._frag_out} if (self._frag_out is not None and nxt is not None) else {}),
-                      **self._target_kw(nxt is not None),
-                      **({"segs": segs} if segs is not None else {}),
-                      **({"norm_prefix": norm_prefix} if norm_prefix is not None else {}), **self._opt_kw())
+                      **self._target_kw(nxt is not None), segs=segs, norm_prefix=norm_prefix, **self._opt_kw())
         if self._presample:
             self._sample_ver = self.replay.version
         self._mark("optimizer")

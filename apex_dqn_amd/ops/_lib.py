@@ -158,6 +158,36 @@ class BetaSched(ctypes.Structure):
     _fields_ = [("ubase", c_p), ("beta0", ctypes.c_double), ("beta_end", ctypes.c_double), ("steps", c_i64)]
 
 
+class RmspropArgs(ctypes.Structure):
+    """Everything an optimizer launch takes (``RmspropArgs``, csrc/rmsprop_common.h)."""
+    _fields_ = [("p", c_p), ("g", c_p), ("v", c_p), ("m", c_p), ("pb", c_p), ("n", c_i64), ("partials", c_p),
+                ("npart", c_i), ("lr", c_f), ("alpha", c_f), ("eps", c_f), ("clip", c_f), ("centered", c_i),
+                ("norm_out", c_p), ("pb_lo", c_p), ("wnorm", c_p), ("wn", c_i), ("wstride", c_i), ("fo", CfFragOut),
+                ("gpre", c_p), ("npre", c_i64), ("os", OptSched), ("tg", OptTarget)]
+
+
+class SampleArgs(ctypes.Structure):
+    """One stratified draw and where its rows go (``SampleArgs``, csrc/sumtree.hip)."""
+    _fields_ = [("t", TreeDesc), ("r", RecordDesc), ("B", c_i), ("seed", c_u64), ("ctr", c_p), ("beta", c_f),
+                ("out_idx", c_p), ("out_w", c_p), ("out_gen", c_p), ("out_obs", c_p), ("out_nxt", c_p),
+                ("out_act", c_p), ("out_rew", c_p), ("out_gam", c_p), ("out_nxt2", c_p), ("out_obs2", c_p),
+                ("shard_stats", c_p), ("shard_rank", c_i), ("shard_world", c_i), ("shard_seed", c_u64),
+                ("out_wscale", c_p), ("mcap", c_i64), ("bs", BetaSched)]
+
+
+class TreeUpdArgs(ctypes.Structure):
+    """A priority write-back riding in a weight-gradient launch (``TreeUpdArgs``, csrc/sumtree.hip); the
+    launcher fills ``n`` and ``kfirst``."""
+    _fields_ = [("t", TreeDesc), ("idx", c_p), ("td", c_p), ("gen_expect", c_p), ("gen", c_p), ("ctr_to_bump", c_p),
+                ("alpha", c_f), ("eps", c_f), ("n", c_i), ("kfirst", c_i), ("stats_out", c_p)]
+
+
+class HeadWgArgs(ctypes.Structure):
+    """The head weight gradient's operands (``HeadWgArgs``, csrc/head_common.h)."""
+    _fields_ = [("Hon", c_p), ("dhead", c_p), ("B", c_i), ("A", c_i), ("gwv", c_p), ("gbv", c_p), ("gwa", c_p),
+                ("gba", c_p), ("HS", c_i), ("Hon_lo", c_p), ("NV", c_i), ("norm_part", c_p)]
+
+
 class C2dPack(ctypes.Structure):
     """conv2 weight-fragment pack job riding on another launch (``C2dPackJob``, csrc/conv2_wfrag.h)."""
     _fields_ = [("w", c_p), ("w_lo", c_p), ("out", c_p)]
@@ -223,32 +253,24 @@ _SIGS = {
     "apex_tree_zero_range": ([TreeDesc, c_i64, c_i64, c_p], c_i),
     "apex_replay_insert": ([TreeDesc, RecordDesc, c_i64, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_p],
                            c_i),
-    "apex_tree_sample": ([TreeDesc, RecordDesc, c_i, c_u64, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                          c_p, c_p, c_p, c_p, c_i, c_i, c_u64, c_p, c_i64, BetaSched, c_p], c_i),
+    "apex_abi_struct_sizes": ([c_p, c_i], c_i),
+    "apex_tree_sample": ([SampleArgs, c_p], c_i),
     "apex_tree_rebuild": ([TreeDesc, c_p], c_i),
     "apex_gather_frames": ([c_p, c_p, c_i, c_i64, c_i64, c_p, c_p], c_i),
     "apex_debug_bounds_enabled": ([], c_i),
     "apex_debug_errors": ([c_p, c_p, c_i], c_i),
     "apex_grad_sqnorm_partials": ([c_p, c_i64, c_p, c_p], c_i),
-    "apex_rmsprop_step": ([c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_f, c_f, c_f, c_f, c_i, c_p, c_p, c_p, c_i, c_i,
-                           OptSched, OptTarget, c_p], c_i),
+    "apex_opt_step": ([RmspropArgs, c_p], c_i),
     "apex_cast_bf16": ([c_p, c_p, c_i64, c_p, c_p], c_i),
     "apex_spin_hold": ([c_i, c_i, c_i, c_p, c_p], c_i),
-    "apex_rmsprop_step_np": ([c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i, c_f, c_f, c_f, c_f, c_i, c_p, c_p, c_p,
-                              c_i, c_i, OptSched, OptTarget, c_p], c_i),
     "apex_grad_finalize": ([FinalizeDesc, c_p], c_i),
     "apex_norm_total": ([c_p, c_i, c_p, c_p], c_i),
     "apex_ddqn_head": ([c_p, c_p, HeadParams, HeadParams, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p,
                         c_p, c_p, c_p, c_p, c_p, c_i, c_i, HeadLo, HeadPart, C2dPack, IsNorm, c_p], c_i),
-    "apex_rmsprop_sample": ([c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i, c_f, c_f, c_f, c_f, c_i, c_p,
-                             TreeDesc, RecordDesc, c_i, c_u64, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                             c_p, c_p, c_p, c_i, c_i, c_u64, c_p, c_i64, BetaSched, c_p, c_p, c_i, c_i, CfFragOut, c_p,
-                             c_p, c_i64, OptSched, OptTarget, c_p], c_i),
-    "apex_head_wgrad_prio": ([c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, TreeDesc, c_p, c_p, c_p, c_p, c_f, c_f,
-                              c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_i64, c_i, c_p, c_p], c_i),
-    "apex_fc_wgrad_head_prio": ([WgradDesc, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, TreeDesc, c_p, c_p, c_p,
-                                 c_p, c_f, c_f, c_p, c_p, c_p, c_p], c_i),
-    "apex_head_wgrad": ([c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p], c_i),
+    "apex_opt_sample": ([RmspropArgs, SampleArgs, c_p, c_p], c_i),
+    "apex_head_wgrad_prio": ([HeadWgArgs, TreeUpdArgs, c_p, c_p, c_p, c_i, c_i, c_p, c_i64, c_p], c_i),
+    "apex_fc_wgrad_head_prio": ([WgradDesc, HeadWgArgs, TreeUpdArgs, c_p], c_i),
+    "apex_head_wgrad": ([HeadWgArgs, c_p], c_i),
     "apex_c51_head": ([C51Args, c_p], c_i),
     "apex_c51_actor_head": ([c_p, HeadParams, c_i, c_i, c_i, c_f, c_f, c_p, c_u64, c_p, c_p, c_p, c_i, c_p, c_p], c_i),
     "apex_qr_head": ([QRArgs, c_p], c_i),
@@ -256,7 +278,7 @@ _SIGS = {
     "apex_iqn_head": ([IqnArgs, c_p], c_i),
     "apex_iqn_wgrad": ([IqnWgArgs, c_p], c_i),
     "apex_iqn_wgrad_part_floats": ([], c_i),
-    "apex_iqn_wgrad_prio": ([IqnWgArgs, TreeDesc, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p], c_i),
+    "apex_iqn_wgrad_prio": ([IqnWgArgs, TreeUpdArgs, c_p], c_i),
     "apex_iqn_actor_head": ([IqnActorArgs, c_p], c_i),
     "apex_qr_actor_head": ([c_p, HeadParams, c_i, c_i, c_i, c_p, c_u64, c_p, c_p, c_p, c_i, c_p, c_p], c_i),
     "apex_actor_head": ([c_p, HeadParams, c_i, c_i, c_p, c_u64, c_p, c_p, c_p, c_i, c_p, c_p], c_i),
@@ -291,7 +313,19 @@ def _declare(lib: ctypes.CDLL) -> None:
     conv_sigs.declare(lib)
 
 
-ABI_VERSION = 14    # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
+ABI_VERSION = 15    # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
+SQNORM_PARTIALS = 1024   # what apex_grad_sqnorm_partials writes (csrc/rmsprop_common.h SQNORM_NPART)
+# the blocks that cross the ABI by value, in the order of csrc/sumtree.hip apex_abi_struct_sizes()
+ABI_STRUCTS = (RmspropArgs, SampleArgs, RmsSegs, TreeUpdArgs, HeadWgArgs, IqnWgArgs, WgradDesc)
+
+
+def check_struct_sizes(sizes, where: str = "libapex_kernels") -> None:
+    """Raise, naming the struct, when the library's ``sizeof`` list differs from the mirrors'."""
+    if len(sizes) != len(ABI_STRUCTS):
+        raise RuntimeError(f"{where}: {len(sizes)} argument blocks != {len(ABI_STRUCTS)}")
+    for cls, size in zip(ABI_STRUCTS, sizes):
+        if int(size) != ctypes.sizeof(cls):
+            raise RuntimeError(f"{where}: sizeof({cls.__name__}) = {int(size)}, its mirror has {ctypes.sizeof(cls)}")
 
 
 def load(build_if_missing: bool = True) -> Optional[ctypes.CDLL]:
@@ -308,6 +342,8 @@ def load(build_if_missing: bool = True) -> Optional[ctypes.CDLL]:
         _declare(lib)
         if lib.apex_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{path}: ABI {lib.apex_abi_version()} != {ABI_VERSION}")
+        sizes = (c_i * 16)()
+        check_struct_sizes(sizes[:lib.apex_abi_struct_sizes(sizes, 16)], path)
         _LIB = lib
     except Exception as e:  # pragma: no cover - depends on toolchain
         _LOAD_ERROR = repr(e)

@@ -802,19 +802,14 @@ def dense_wgrad(lib, dy: torch.Tensor, x: torch.Tensor, dw_out: torch.Tensor, db
     return 4 * wgrad_blocks(dy.shape[1], x.shape[1], 1 if dy_lo is not None else 0)
 
 
-def dense_wgrad_head_prio(lib, dy, x, dw_out, db_out, norm, Hon, dhead, g, replay, idx, gen, td, dy_lo=None,
-                          x_lo=None, Hon_lo=None) -> Optional[int]:
-    """The fc weight gradient (as ``dense_wgrad``), the head weight gradient and the
-    priority write-back in one launch (csrc/sumtree.hip fc_wgrad_head_prio_kernel).
+def dense_wgrad_head_prio(lib, dy, x, dw_out, db_out, norm, hw, tu, dy_lo=None, x_lo=None) -> Optional[int]:
+    """The fc weight gradient (as ``dense_wgrad``), the head weight gradient (``hw``: its
+    ``HeadWgArgs``) and the priority write-back (``tu``: its ``TreeUpdArgs``) in one launch
+    (csrc/sumtree.hip fc_wgrad_head_prio_kernel).
     Returns the norm slots used, or None when the shape is not the fused kernel's
     (nothing launched: the caller runs the three ops separately)."""
     d = _dense_wgrad_desc(dy, x, dw_out, db_out, norm, dy_lo, x_lo)
-    B, A1 = dhead.shape
-    rc = lib.apex_fc_wgrad_head_prio(d, Hon.data_ptr(), dhead.data_ptr(), B, A1 - 1, g["wv"].data_ptr(),
-                                     g["bv"].data_ptr(), g["wa"].data_ptr(), g["ba"].data_ptr(), g["wv"].numel(),
-                                     replay.tree_desc(), idx.data_ptr(), td.data_ptr(), _lib.ptr(gen),
-                                     replay.gen.data_ptr(), replay.alpha, replay.eps, replay.ctr.data_ptr(),
-                                     _lib.ptr(Hon_lo), _lib.ptr(replay.local_stats), _lib.stream_ptr())
+    rc = lib.apex_fc_wgrad_head_prio(d, hw, tu, _lib.stream_ptr())
     if rc == 1:          # hipErrorInvalidValue: not the compiled shape
         return None
     _lib.check(rc, "fc_wgrad_head_prio")

@@ -888,9 +888,9 @@ class HipBackend(TorchBackend):
         # head weight gradient + priority write-back launch, then the fc weight gradient)
         if self.native_conv and prio is not None and prio[0].use_hip and g_head["bv"].numel() == 1:
             rp, idx, gen, td = prio
-            r = C.dense_wgrad_head_prio(self.lib, dh, x.reshape(x.shape[0], -1), dw_out, db_out, norm, Hon, dhead,
-                                        g_head, rp, idx, gen, td, dy_lo=dh_lo,
-                                        x_lo=None if x_lo is None else x_lo.reshape(x.shape[0], -1), Hon_lo=Hon_lo)
+            r = C.dense_wgrad_head_prio(self.lib, dh, x.reshape(x.shape[0], -1), dw_out, db_out, norm,
+                                        self._head_wg(Hon, dhead, g_head, Hon_lo)[0], rp.tree_upd_args(idx, td, gen),
+                                        dy_lo=dh_lo, x_lo=None if x_lo is None else x_lo.reshape(x.shape[0], -1))
             if r is not None:
                 return r
         if self.native_conv and norm is not None and g_head["bv"].numel() > 1:
@@ -1112,9 +1112,8 @@ class HipBackend(TorchBackend):
         h.part = ws["wpart"].data_ptr()
         if prio is not None and prio[0].use_hip and B <= 1024:
             rp, idx, gen, td = prio
-            _lib.check(self.lib.apex_iqn_wgrad_prio(h, rp.tree_desc(), idx.data_ptr(), td.data_ptr(), _lib.ptr(gen),
-                                                    rp.gen.data_ptr(), rp.alpha, rp.eps, rp.ctr.data_ptr(),
-                                                    _lib.ptr(rp.local_stats), _lib.stream_ptr()), "iqn_wgrad_prio")
+            _lib.check(self.lib.apex_iqn_wgrad_prio(h, rp.tree_upd_args(idx, td, gen), _lib.stream_ptr()),
+                       "iqn_wgrad_prio")
             return
         if prio is not None:
             prio[0].update_priorities(prio[1], prio[3], prio[2])
@@ -1136,34 +1135,38 @@ class HipBackend(TorchBackend):
         assert tau_out is None or (tau_out.shape == (n_e, a.K) and tau_out.is_contiguous())
         _lib.check(self.lib.apex_iqn_actor_head(a, _lib.stream_ptr()), "iqn_actor_head")
 
+    @staticmethod
+    def _head_wg(Hon, dhead, g, Hon_lo=None, norm=None):
+        """``HeadWgArgs`` of a head weight gradient and the norm slots its blocks write (``norm =
+        (partials, slot0)``, the distributional head only)."""
+        B, J = dhead.shape
+        nv = g["bv"].numel()          # value rows: 1, or the distributional head's atoms
+        h = _lib.HeadWgArgs(Hon=Hon.data_ptr(), Hon_lo=_lib.ptr(Hon_lo), dhead=dhead.data_ptr(), B=B, A=J - nv, NV=nv,
+                            HS=g["wv"].shape[-1], gwv=g["wv"].data_ptr(), gbv=g["bv"].data_ptr(),
+                            gwa=g["wa"].data_ptr(), gba=g["ba"].data_ptr())
+        nslots = 0
+        if norm is not None:
+            assert nv >= 2
+            nslots = (-(-nv // 8) + -(-(J - nv) // 8)) * (h.HS // 64)       # csrc/head_common.h HWG_JT
+            h.norm_part = norm[0].data_ptr() + 8 * int(norm[1])
+            assert int(norm[1]) + nslots <= norm[0].numel() and norm[0].dtype == torch.float64
+        return h, nslots
+
     def head_wgrad(self, Hon, dhead, g, prio=None, Hon_lo=None, pack=None, norm=None) -> int:
         """``norm = (partials, slot0)`` (the distributional head only): every block also leaves
         the squared norm of what it stores; returns the slots written."""
-        B, J = dhead.shape
-        nv = g["bv"].numel()          # value rows: 1, or the distributional head's atoms
-        hidden = g["wv"].shape[-1]
-        npart, nslots = None, 0
-        if norm is not None:
-            assert nv >= 2
-            nslots = (-(-nv // 8) + -(-(J - nv) // 8)) * (hidden // 64)       # csrc/head_common.h HWG_JT
-            npart = norm[0].data_ptr() + 8 * int(norm[1])
-            assert int(norm[1]) + nslots <= norm[0].numel() and norm[0].dtype == torch.float64
-        if prio is not None and prio[0].use_hip and B <= 1024:
+        h, nslots = self._head_wg(Hon, dhead, g, Hon_lo, norm)
+        if prio is not None and prio[0].use_hip and h.B <= 1024:
             rp, idx, gen, td = prio
             pk = self._pack_args(*pack) if pack is not None else (None, None, None, 0, 0, None, 0)
-            _lib.check(self.lib.apex_head_wgrad_prio(
-                Hon.data_ptr(), dhead.data_ptr(), B, J - nv, g["wv"].data_ptr(), g["bv"].data_ptr(),
-                g["wa"].data_ptr(), g["ba"].data_ptr(), hidden, rp.tree_desc(), idx.data_ptr(),
-                td.data_ptr(), _lib.ptr(gen), rp.gen.data_ptr(), rp.alpha, rp.eps, rp.ctr.data_ptr(),
-                _lib.ptr(Hon_lo), _lib.ptr(rp.local_stats), *pk, nv, npart, _lib.stream_ptr()), "head_wgrad_prio")
+            _lib.check(self.lib.apex_head_wgrad_prio(h, rp.tree_upd_args(idx, td, gen), *pk, _lib.stream_ptr()),
+                       "head_wgrad_prio")
             return nslots
         if pack is not None:
             self.pack_rows(*pack)
         if prio is not None:
             prio[0].update_priorities(prio[1], prio[3], prio[2])
-        _lib.check(self.lib.apex_head_wgrad(Hon.data_ptr(), dhead.data_ptr(), B, J - nv, g["wv"].data_ptr(),
-                                            g["bv"].data_ptr(), g["wa"].data_ptr(), g["ba"].data_ptr(),
-                                            hidden, _lib.ptr(Hon_lo), nv, npart, _lib.stream_ptr()), "head_wgrad")
+        _lib.check(self.lib.apex_head_wgrad(h, _lib.stream_ptr()), "head_wgrad")
         return nslots
 
     def actor_head(self, H, P, eps, ctr, seed, q_out, a_out, H_lo=None):
@@ -1177,11 +1180,34 @@ class HipBackend(TorchBackend):
         """``OptSched`` of an ``OptSpec`` (all-zero for None: RMSprop, lr by value)."""
         os_ = _lib.OptSched()
         if opt is not None:
-            os_.ctr, os_.base, os_.adam = opt.ctr.data_ptr(), opt.base.data_ptr(), int(opt.adam)
+            os_.ctr, os_.base, os_.adam = _lib.ptr(opt.ctr), _lib.ptr(opt.base), int(opt.adam)
             os_.warmup, os_.decay = int(opt.warmup), int(opt.decay)
             os_.lr0, os_.lr_end = float(opt.lr), float(opt.lr if opt.lr_end is None else opt.lr_end)
             os_.beta1, os_.beta2 = float(opt.beta1), float(opt.beta2)
         return os_
+
+    def _opt_args(self, p32, g32, v, m, pbf, lr, alpha, eps, clip, centered, norm_out, pb_lo, wnorm, frag_out,
+                  norm_prefix, opt, target) -> "_lib.RmspropArgs":
+        """``RmspropArgs`` of an optimizer launch, but for the clip norm's partials (``partials``, ``npart``)."""
+        n = p32.numel()
+        if opt is not None and opt.adam:
+            eps = opt.adam_eps        # (RmspropArgs.eps carries Adam's epsilon)
+        a = _lib.RmspropArgs(p=p32.data_ptr(), g=g32.data_ptr(), v=v.data_ptr(), m=m.data_ptr(), pb=pbf.data_ptr(),
+                             pb_lo=_lib.ptr(pb_lo), n=n, lr=float(lr), alpha=float(alpha), eps=float(eps),
+                             clip=float(clip), centered=int(centered), norm_out=norm_out.data_ptr(),
+                             os=self._opt_sched(opt), gpre=_lib.ptr(norm_prefix),
+                             npre=0 if norm_prefix is None else norm_prefix.numel())
+        if wnorm is not None:
+            a.wnorm, a.wn, a.wstride = wnorm[0].data_ptr(), int(wnorm[1]), int(wnorm[2])
+        if frag_out is not None:
+            a.fo = frag_out
+        if target is not None:
+            t32, tbf, tbf_lo, rho, tfo = target
+            assert t32.dtype == torch.float32 and t32.numel() == n and tbf.numel() == n and tbf.dtype == pbf.dtype \
+                and (tbf_lo is None) == (pb_lo is None) and (tbf_lo is None or tbf_lo.numel() == n)
+            a.tg = _lib.OptTarget(t32.data_ptr(), tbf.data_ptr(), _lib.ptr(tbf_lo), float(rho),
+                                  _lib.CfFragOut() if tfo is None else tfo)
+        return a
 
     def optimizer(self, p32, g32, v, m, pbf, lr, alpha, eps, clip, centered, partials, norm_out, norm_total=None,
                   sample=None, pb_lo=None, wnorm=None, frag_out=None, segs=None, norm_prefix=None, opt=None,
@@ -1191,79 +1217,40 @@ class HipBackend(TorchBackend):
         optimizer + sample launch only).  ``segs``: the ranges to update (the sharded DP
         update: one launch, csrc/sumtree.hip ``RmsSegs``).  ``target``: the soft target net, averaged in the
         same launch (csrc/rmsprop_common.h ``OptTarget``)."""
-        n = p32.numel()
-        osd = self._opt_sched(opt)
-        tg = _lib.OptTarget()
-        if target is not None:
-            t32, tbf, tbf_lo, rho, tfo = target
-            if segs is not None:
-                raise ValueError("the soft target is averaged over the whole parameter vector, not in a sharded update")
-            if tfo is not None and frag_out is None:
-                raise ValueError("the target's fragment stores ride beside the online ones (frag_out)")
-            assert t32.dtype == torch.float32 and t32.numel() == n and tbf.numel() == n and tbf.dtype == pbf.dtype \
-                and (tbf_lo is None) == (pb_lo is None) and (tbf_lo is None or tbf_lo.numel() == n)
-            tg.t, tg.tb, tg.tb_lo, tg.rho = t32.data_ptr(), tbf.data_ptr(), _lib.ptr(tbf_lo), float(rho)
-            if tfo is not None:
-                tg.tfo = tfo
-        if opt is not None and opt.adam:
-            eps = opt.adam_eps        # (RmspropArgs.eps carries Adam's epsilon)
-        if segs is not None:
-            if norm_total is None:
-                raise ValueError("a sharded update needs the clip norm's partials (norm_total)")
-            if sample is None or not sample[0].use_hip:
-                raise ValueError("the sharded update runs in the fused optimizer + sample launch")
-            sg = _lib.RmsSegs()
-            sg.nseg = len(segs)
-            assert 1 <= sg.nseg <= 3
-            for k, (o, ln) in enumerate(segs):
-                sg.off[k], sg.len[k] = int(o), int(ln)
-            segp = ctypes.byref(sg)
-        else:
-            segp = None
-        st = _lib.stream_ptr()
-        lo = _lib.ptr(pb_lo)
-        wn = (wnorm[0].data_ptr(), int(wnorm[1]), int(wnorm[2])) if wnorm is not None else (None, 0, 0)
-        if frag_out is not None and not (sample is not None and sample[0].use_hip):
-            raise ValueError("frag_out needs the fused optimizer + sample launch (a HIP replay)")
-        if sample is not None and sample[0].use_hip:
-            # the next batch's draw rides in the optimizer launch (csrc/sumtree.hip: rmsprop_sample_kernel)
-            rp, B, out, nxt2, obs2 = _sample5(sample)
-            if norm_total is None:
-                _lib.check(self.lib.apex_grad_sqnorm_partials(g32.data_ptr(), n, partials.data_ptr(), st), "sqnorm")
-                part, npart = partials, partials.numel()
-            elif isinstance(norm_total, tuple):   # (producer partials, count): summed in the launch
-                part, npart = norm_total
-            else:
-                part, npart = norm_total, 1
-            _lib.check(self.lib.apex_rmsprop_sample(
-                p32.data_ptr(), g32.data_ptr(), v.data_ptr(), m.data_ptr(), pbf.data_ptr(), n, part.data_ptr(), npart,
-                float(lr), float(alpha), float(eps), float(clip), int(centered), norm_out.data_ptr(),
-                *rp.sample_launch_args(B, out, nxt2, obs2), lo, *wn,
-                frag_out if frag_out is not None else _lib.CfFragOut(),
-                segp, _lib.ptr(norm_prefix), 0 if norm_prefix is None else norm_prefix.numel(), osd, tg, st),
-                "rmsprop_sample")
-            return frag_out is not None
-        if norm_prefix is not None:
-            raise ValueError("norm_prefix runs in the fused optimizer + sample launch")
-        if sample is not None:
+        # the next batch's draw rides in the optimizer launch (csrc/sumtree.hip: rmsprop_sample_kernel)
+        fused = sample is not None and sample[0].use_hip
+        if target is not None and segs is not None:
+            raise ValueError("the soft target is averaged over the whole parameter vector, not in a sharded update")
+        if target is not None and target[4] is not None and frag_out is None:
+            raise ValueError("the target's fragment stores ride beside the online ones (frag_out)")
+        if segs is not None and norm_total is None:
+            raise ValueError("a sharded update needs the clip norm's partials (norm_total)")
+        for name, arg in (("segs", segs), ("frag_out", frag_out), ("norm_prefix", norm_prefix)):
+            if arg is not None and not fused:
+                raise ValueError(f"{name} needs the fused optimizer + sample launch (a HIP replay)")
+        if sample is not None and not fused:
             self.optimizer(p32, g32, v, m, pbf, lr, alpha, eps, clip, centered, partials, norm_out, norm_total,
                            pb_lo=pb_lo, wnorm=wnorm, opt=opt, target=target)
             rp, B, out, nxt2, obs2 = _sample5(sample)
             rp.sample(B, out=out, nxt2=nxt2, **({} if obs2 is None else {"obs2": obs2}))
             return
-        if norm_total is not None:   # squared norm already summed by the gradient producers
-            part, npart = norm_total if isinstance(norm_total, tuple) else (norm_total, 1)
-            _lib.check(self.lib.apex_rmsprop_step_np(p32.data_ptr(), g32.data_ptr(), v.data_ptr(), m.data_ptr(),
-                                                     pbf.data_ptr(), n, part.data_ptr(), npart, float(lr),
-                                                     float(alpha), float(eps), float(clip), int(centered),
-                                                     norm_out.data_ptr(), lo, *wn, osd, tg, st), "rmsprop_np")
+        a = self._opt_args(p32, g32, v, m, pbf, lr, alpha, eps, clip, centered, norm_out, pb_lo, wnorm, frag_out,
+                           norm_prefix, opt, target)
+        if norm_total is None:                # the optimizer's own squared-norm pass
+            norm_total = (partials, self.grad_sqnorm_partials(g32, partials))
+        # (producer partials, count), summed in the launch; or the total
+        part, a.npart = norm_total if isinstance(norm_total, tuple) else (norm_total, 1)
+        a.partials = part.data_ptr()
+        if not fused:
+            _lib.check(self.lib.apex_opt_step(a, _lib.stream_ptr()), "opt_step")
             return
-        _lib.check(self.lib.apex_grad_sqnorm_partials(g32.data_ptr(), n, partials.data_ptr(), st), "sqnorm")
-        _lib.check(self.lib.apex_rmsprop_step(p32.data_ptr(), g32.data_ptr(), v.data_ptr(), m.data_ptr(),
-                                              pbf.data_ptr(), n, partials.data_ptr(), float(lr), float(alpha),
-                                              float(eps), float(clip), int(centered), norm_out.data_ptr(), lo, *wn,
-                                              osd, tg, st),
-                   "rmsprop")
+        rp, B, out, nxt2, obs2 = _sample5(sample)
+        sg = None if segs is None else _lib.RmsSegs(nseg=len(segs))
+        for k, (o, ln) in enumerate(segs or ()):      # (at most three: the launcher checks nseg)
+            sg.off[k], sg.len[k] = int(o), int(ln)
+        _lib.check(self.lib.apex_opt_sample(a, rp.sample_launch_args(B, out, nxt2, obs2),
+                                            None if sg is None else ctypes.byref(sg), _lib.stream_ptr()), "opt_sample")
+        return frag_out is not None
 
     def _pack_args(self, dst: torch.Tensor, segs):
         """(src*, ld*, cols*, nseg, rows, dst, dst ld) of a row pack (csrc/pack_rows.h); the
@@ -1287,9 +1274,10 @@ class HipBackend(TorchBackend):
     def grad_sqnorm_partials(self, g32, partials) -> int:
         """Squared-norm partials of the whole gradient (the optimizer's own pass);
         returns the partial count."""
+        assert partials.numel() >= _lib.SQNORM_PARTIALS
         _lib.check(self.lib.apex_grad_sqnorm_partials(g32.data_ptr(), g32.numel(), partials.data_ptr(),
                                                       _lib.stream_ptr()), "sqnorm")
-        return partials.numel()
+        return _lib.SQNORM_PARTIALS
 
     def sqnorm_ranges(self, ranges, partials: torch.Tensor, nblk: int) -> int:
         (a, b) = (list(ranges) + [None])[:2]

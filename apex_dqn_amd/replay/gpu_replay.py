@@ -493,7 +493,7 @@ class GpuReplayShard:
         if self.sharded and B < 3:
             raise ValueError("sharded sampling needs B >= 3")
         if self.use_hip:
-            _lib.check(self.lib.apex_tree_sample(*self.sample_launch_args(B, out, nxt2, obs2), self._stream()),
+            _lib.check(self.lib.apex_tree_sample(self.sample_launch_args(B, out, nxt2, obs2), self._stream()),
                        "tree_sample")
             return out
         leaf = self.leaf.double().cpu()
@@ -545,14 +545,22 @@ class GpuReplayShard:
         return out
 
     def sample_launch_args(self, B: int, out: Dict[str, torch.Tensor], nxt2: Optional[torch.Tensor] = None,
-                           obs2: Optional[torch.Tensor] = None) -> tuple:
-        """The tree_sample arguments (TreeDesc .. shard_seed) of :meth:`sample`, for
-        kernels that draw the batch inside another launch (``apex_rmsprop_sample``)."""
-        return (self.tree_desc(), self.record_desc(), B, self.seed, self.ctr.data_ptr(), self.beta,
-                out["idx"].data_ptr(), out["weights"].data_ptr(), out["gen"].data_ptr(), out["obs"].data_ptr(),
-                out["nxt"].data_ptr(), out["act"].data_ptr(), out["rew"].data_ptr(), out["gam"].data_ptr(),
-                _lib.ptr(nxt2), _lib.ptr(obs2), _lib.ptr(self.shard_stats), self.shard_rank, self.shard_world,
-                self.shard_seed, _lib.ptr(out.get("wscale")), int(self.shard_mcap), self._beta_sched_arg())
+                           obs2: Optional[torch.Tensor] = None) -> "_lib.SampleArgs":
+        """The ``SampleArgs`` of :meth:`sample`, also for kernels that draw the batch inside another launch
+        (``apex_opt_sample``)."""
+        return _lib.SampleArgs(
+            self.tree_desc(), self.record_desc(), B, self.seed, self.ctr.data_ptr(), self.beta,
+            out["idx"].data_ptr(), out["weights"].data_ptr(), out["gen"].data_ptr(), out["obs"].data_ptr(),
+            out["nxt"].data_ptr(), out["act"].data_ptr(), out["rew"].data_ptr(), out["gam"].data_ptr(),
+            _lib.ptr(nxt2), _lib.ptr(obs2), _lib.ptr(self.shard_stats), self.shard_rank, self.shard_world,
+            self.shard_seed, _lib.ptr(out.get("wscale")), int(self.shard_mcap), self._beta_sched_arg())
+
+    def tree_upd_args(self, idx: torch.Tensor, td_abs: torch.Tensor, gen: Optional[torch.Tensor]) -> "_lib.TreeUpdArgs":
+        """The ``TreeUpdArgs`` of a batch's priority write-back riding in a weight-gradient launch (what
+        :meth:`update_priorities` does, counter bump included; the launcher fills ``n`` and ``kfirst``)."""
+        return _lib.TreeUpdArgs(t=self.tree_desc(), idx=idx.data_ptr(), td=td_abs.data_ptr(), gen_expect=_lib.ptr(gen),
+                                gen=self.gen.data_ptr(), ctr_to_bump=self.ctr.data_ptr(), alpha=self.alpha,
+                                eps=self.eps, stats_out=_lib.ptr(self.local_stats))
 
     def alloc_sample_buffers(self, B: int) -> Dict[str, torch.Tensor]:
         d = self.device

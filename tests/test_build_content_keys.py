@@ -89,3 +89,21 @@ def test_keys_do_not_depend_on_the_checkout_path(monkeypatch):
         monkeypatch.setattr(build, "HIP_FLAGS", [csrc if f.endswith("/csrc") else f for f in build.HIP_FLAGS])
         monkeypatch.setattr(build, "CXX_FLAGS", [csrc if f.endswith("/csrc") else f for f in build.CXX_FLAGS])
         assert (build.kernel_plan().build_id, build.runtime_plan().build_id) == ids
+
+
+def test_struct_size_mismatch_names_the_struct():
+    """The loader's comparison of the library's ``sizeof`` list (``apex_abi_struct_sizes``) with the ctypes
+    mirrors: equal lists pass; a block that drifted by one field, or a list of another length, is refused
+    with the struct named."""
+    from apex_dqn_amd.ops import _lib
+    good = [ctypes.sizeof(c) for c in _lib.ABI_STRUCTS]
+    assert [c.__name__ for c in _lib.ABI_STRUCTS] == ["RmspropArgs", "SampleArgs", "RmsSegs", "TreeUpdArgs",
+                                                      "HeadWgArgs", "IqnWgArgs", "WgradDesc"]
+    _lib.check_struct_sizes(good)
+    for k, cls in enumerate(_lib.ABI_STRUCTS):
+        bad = list(good)
+        bad[k] += 8
+        with pytest.raises(RuntimeError, match=rf"sizeof\({cls.__name__}\) = {bad[k]}, its mirror has {good[k]}"):
+            _lib.check_struct_sizes(bad)
+    with pytest.raises(RuntimeError, match="argument blocks"):
+        _lib.check_struct_sizes(good[:-1])

@@ -1,6 +1,8 @@
 """Adam and the step-indexed lr / IS-exponent schedules on the GPU: the optimizer kernels'
 Adam variant (csrc/rmsprop_common.h OPT_ADAM) in every launch form, and the learner's
 device-resident update index inside replayed graphs, the DP step and a resume."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -331,3 +333,111 @@ def test_gpu_adam_resume_matches_uninterrupted_run(tmp_path):
     for a, b in ((L.p32, L2.p32), (L.rms_v, L2.rms_v), (L.rms_m, L2.rms_m), (L.t32, L2.t32), (rp.leaf, rp2.leaf),
                  (rp.ctr, rp2.ctr), (L.S["weights"], L2.S["weights"])):
         assert torch.equal(a, b)
+
+
+# --------------------------------------------------------------- 6. refusals
+class _Small:
+    """n = 4096 parameters, B = 8, a replay of capacity 64; every buffer holds a value an update, a target
+    average or a draw would change."""
+    n, B = 4096, 8
+
+    def __init__(self):
+        from apex_dqn_amd.ops.fused_ops import HipBackend
+        from apex_dqn_amd.replay.gpu_replay import GpuReplayShard
+        n, B = self.n, self.B
+        self.be = HipBackend()
+        self.rp = GpuReplayShard(64, 64, 64, 4, device=DEV, seed=7)
+        _fill(self.rp, K=48)
+        f = lambda x, dt=torch.float32, k=n: torch.full((k,), x, dtype=dt, device=DEV)
+        self.p, self.g, self.v, self.m, self.t = f(1.0), f(0.5), f(1e-6), f(1e-4), f(2.0)
+        self.hi, self.th = f(0.0, torch.bfloat16), f(0.0, torch.bfloat16)
+        self.part, self.gn = f(1.0, torch.float64, 1024), f(-1.0, k=1)
+        self.S = self.rp.alloc_sample_buffers(B)
+        self.S["idx"].fill_(-1)
+        self.nxt2 = torch.zeros(B, 4, dtype=torch.int32, device=DEV)
+        torch.cuda.synchronize()
+
+    def args(self, p=None):
+        return (self.p if p is None else p, self.g, self.v, self.m, self.hi, 1e-4, 0.95, 1.5e-7, 40.0, True,
+                self.part, self.gn)
+
+    def form_kw(self, form):
+        """The producer-partials launch (``apex_opt_step``) or the fused optimizer + sample launch
+        (``apex_opt_sample``); with the partials given, a refused call launches nothing at all."""
+        kw = dict(norm_total=(self.part, 1))
+        if form == "sample":
+            kw["sample"] = (self.rp, self.B, self.S, self.nxt2)
+        return kw
+
+    def untouched(self):
+        torch.cuda.synchronize()
+        return (bool((self.p == 1.0).all()) and bool((self.v == 1e-6).all()) and bool((self.t == 2.0).all())
+                and not self.hi.any() and not self.th.any() and float(self.gn) == -1.0
+                and bool((self.S["idx"] == -1).all()) and int(self.rp.ctr.item()) == 0)
+
+
+@pytest.mark.parametrize("form", ["step", "sample"])
+@pytest.mark.parametrize("bad", ["p_misaligned", "adam_no_counter", "rho", "target_misaligned"])
+def test_shared_optimizer_refusals_hold_in_both_launch_forms(form, bad):
+    """What the launchers' common check (csrc/rmsprop_common.h ``opt_args_ok``) refuses, it refuses in the
+    plain and in the fused optimizer + sample form; nothing is launched."""
+    s = _Small()
+    args, kw = s.args(), s.form_kw(form)
+    if bad == "p_misaligned":                  # 4 bytes off the float4 path
+        args = s.args(torch.ones(s.n + 1, device=DEV)[1:])
+    elif bad == "adam_no_counter":
+        kw["opt"] = adam_spec(DEV)
+        kw["opt"].ctr = None
+    elif bad == "rho":                         # a rate outside [0, 1]
+        kw["target"] = (s.t, s.th, None, 1.5, None)
+    else:
+        kw["target"] = (torch.full((s.n + 1,), 2.0, device=DEV)[1:], s.th, None, 0.25, None)
+    with pytest.raises(RuntimeError, match="opt_step" if form == "step" else "opt_sample"):
+        s.be.optimizer(*args, **kw)
+    assert s.untouched()
+
+
+def test_each_optimizer_form_keeps_its_own_refusals():
+    """``segs`` with a target (the sample form), ``frag_out`` and ``norm_prefix`` outside the fused launch
+    (the plain form): refused by the backend, and by the launchers when handed such a block directly."""
+    from apex_dqn_amd.ops import _lib
+    s = _Small()
+    be, n = s.be, s.n
+    target = (s.t, s.th, None, 0.25, None)
+    fo = _lib.CfFragOut()
+    fo.w1frag, fo.c2f, fo.C = s.hi.data_ptr(), s.th.data_ptr(), 1
+    with pytest.raises(ValueError, match="sharded"):
+        be.optimizer(*s.args(), **s.form_kw("sample"), segs=[(0, n)], target=target)
+    with pytest.raises(ValueError, match="frag_out"):
+        be.optimizer(*s.args(), **s.form_kw("step"), frag_out=fo)
+    with pytest.raises(ValueError, match="norm_prefix"):
+        be.optimizer(*s.args(), **s.form_kw("step"), norm_prefix=s.g[:64])
+    st = _lib.stream_ptr()
+
+    def block(**kw):
+        a = be._opt_args(*s.args()[:10], s.gn, None, None, kw.get("frag_out"), kw.get("norm_prefix"), None,
+                         kw.get("target"))
+        a.partials, a.npart = s.part.data_ptr(), 1
+        return a
+    assert be.lib.apex_opt_step(block(frag_out=fo), st) == 1
+    assert be.lib.apex_opt_step(block(norm_prefix=s.g[:64]), st) == 1
+    sg = _lib.RmsSegs()
+    sg.nseg, sg.off[0], sg.len[0] = 1, 0, n
+    sa = s.rp.sample_launch_args(s.B, s.S, s.nxt2)
+    assert be.lib.apex_opt_sample(block(target=target), sa, ctypes.byref(sg), st) == 1
+    assert s.untouched()
+    # the same blocks without the offending member run
+    assert be.lib.apex_opt_sample(block(), sa, ctypes.byref(sg), st) == 0
+    torch.cuda.synchronize()
+    assert not s.untouched() and bool((s.S["idx"] >= 0).all())
+
+
+def test_sharded_draw_of_two_rows_is_refused_by_the_optimizer_form():
+    """``shard_stats`` set and B = 2 (a sharded draw needs B >= 3): the fused form's launcher refuses."""
+    s = _Small()
+    s.rp.enable_sharding(0, 1, 3)
+    S2, nxt2 = s.rp.alloc_sample_buffers(2), torch.zeros(2, 4, dtype=torch.int32, device=DEV)
+    S2["idx"].fill_(-1)
+    with pytest.raises(RuntimeError, match="opt_sample"):
+        s.be.optimizer(*s.args(), norm_total=(s.part, 1), sample=(s.rp, 2, S2, nxt2))
+    assert s.untouched() and bool((S2["idx"] == -1).all())

@@ -462,3 +462,19 @@ def test_sharded_draw_partitions_the_strata(ranks, B, mcap):
         j_next += nv
         c0 = c1
     assert j_next == M
+
+
+def test_sharded_draw_of_two_rows_is_refused():
+    """``shard_stats`` set and B = 2 (an interval catches up to floor(T M / sum) + 2 strata, so a sharded
+    draw needs B >= 3): ``sample`` refuses, and so does the launcher when handed the block; nothing is drawn."""
+    rp, _, _ = _filled(64)
+    rp.enable_sharding(0, 1, 3)
+    out = rp.alloc_sample_buffers(2)
+    out["idx"].fill_(-1)
+    with pytest.raises(ValueError, match="B >= 3"):
+        rp.sample(2, out=out)
+    assert rp.lib.apex_tree_sample(rp.sample_launch_args(2, out), rp._stream()) == 1
+    torch.cuda.synchronize()
+    assert bool((out["idx"] == -1).all())
+    assert rp.lib.apex_tree_sample(rp.sample_launch_args(3, rp.alloc_sample_buffers(3)), rp._stream()) == 0
+    torch.cuda.synchronize()
