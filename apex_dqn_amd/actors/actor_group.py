@@ -54,7 +54,7 @@ class ActorGroup:
                  eps_base: float = 0.4, eps_alpha: float = 7.0, global_actor_offset: int = 0,
                  total_actors: Optional[int] = None, seed: int = 0,
                  frame_store=None, materialize: bool = True,
-                 obs_builder: Optional[Callable] = None):
+                 obs_builder: Optional[Callable] = None, value_rescale_eps: float = 0.0):
         self.env = env
         self.E = int(num_envs)
         self.C = int(frame_stack)
@@ -76,7 +76,7 @@ class ActorGroup:
             obs_shape, obs_dtype = tuple(env.obs_shape), np.float32
         self.obs_builder = obs_builder
         self.builder = make_nstep_builder(self.E, n, gamma, obs_shape, obs_dtype,
-                                    env_id_offset=global_actor_offset)
+                                    env_id_offset=global_actor_offset, value_rescale_eps=value_rescale_eps)
         self.t = 0
         # noisy layers (learner/noisy.py actor_noise_hook): called with the inference-call index
         # before every batched policy call; one draw serves all envs of the call

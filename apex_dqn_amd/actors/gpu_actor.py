@@ -132,7 +132,9 @@ class GpuActorGroup:
             self._nz = NoisyPlan(A=self.A, N=int(learner.N), offsets=dict(learner.layout.offsets),
                                  seed=noise_seed(cfg.Runtime.seed), ctr=self.ctr, base=None,
                                  every=int(cfg.Runtime.noisy_actor_resample), stream0=actor_stream(group))
-        self.builder = make_nstep_builder(self.E, a.num_steps, a.gamma, (self.C,), np.int64, env_id_offset=global_offset)
+        # (Runtime.value_rescale: the initial priorities on the rescaled target's scale, as the learner writes back)
+        self.builder = make_nstep_builder(self.E, a.num_steps, a.gamma, (self.C,), np.int64, env_id_offset=global_offset,
+                                          value_rescale_eps=cfg.rescale_eps or 0.0)
         self.global_offset = global_offset
         self.payload: Optional[np.ndarray] = None
         self.t = 0
@@ -206,7 +208,8 @@ class GpuActorGroup:
         """Drop the partial n-step windows and start fresh episodes (actor restart)."""
         a = self.cfg.Actor
         self.builder = make_nstep_builder(self.E, a.num_steps, a.gamma, (self.C,), np.int64,
-                                          env_id_offset=self.global_offset)
+                                          env_id_offset=self.global_offset,
+                                          value_rescale_eps=self.cfg.rescale_eps or 0.0)
         self.payload = None
 
     # --------------------------------------------------------------- acting
@@ -560,14 +563,15 @@ def make_gpu_actor_group(cfg, learner, replay, num_envs: int, rank: int = 0, wor
         groups = []
         for k in range(K):
             env = make_vec_env(cfg.env_backend, cfg.env_conf.name, h, cfg.env_conf.action_dim,
-                               seed=seed + 1000 * rank + 100003 * k, preprocess=pre)
+                               seed=seed + 1000 * rank + 100003 * k, preprocess=pre,
+                               clip_rewards=cfg.Runtime.clip_rewards)
             g = GpuActorGroup(cfg, learner, replay, env, h, global_offset=rank * num_envs + k * h,
                               total_actors=total, seed=seed + rank, rank=rank, world=world, group=k)
             g.eps = torch.tensor(eps_all[k * h:(k + 1) * h], dtype=torch.float32, device=learner.device)
             groups.append(g)
         return PipelinedActorGroups(groups)
     env = make_vec_env(cfg.env_backend, cfg.env_conf.name, num_envs, cfg.env_conf.action_dim,
-                       seed=seed + 1000 * rank, preprocess=pre)
+                       seed=seed + 1000 * rank, preprocess=pre, clip_rewards=cfg.Runtime.clip_rewards)
     kind = getattr(learner, "kind", "")
     cls = {"graph": GraphActorGroup, "impala": ImpalaActorGroup}.get(kind, GpuActorGroup)
     return cls(cfg, learner, replay, env, num_envs, global_offset=rank * num_envs,

@@ -16,7 +16,10 @@ intended Ape-X semantics:
 The actor's initial priority ``|R + Gamma*max_a q(S_{t+n}) - q(S_t, A_t)|``
 (``actor.py:127-143``, A1 fixed: one priority per transition) needs
 ``q(S_{t+n})``, which the actor only computes on its next step, so a full
-window transition waits one step in a per-env "pending" slot.
+window transition waits one step in a per-env "pending" slot.  With
+``value_rescale_eps`` > 0 (``Runtime.value_rescale``) the priorities are on the
+rescaled target's scale, ``|h(R + Gamma h^-1(max_a q(S_{t+n}))) - q|`` and
+``|h(R) - q|`` on the terminal flush (learner/rescale.py); the stored ``R`` stays raw.
 
 Everything is vectorised over E environments (one actor group); the
 observation payload per step is an arbitrary fixed-shape array (the frame
@@ -29,11 +32,16 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
+from ..learner.rescale import h as rescale_h, rescale_target
+
 
 class NStepBuilder:
     def __init__(self, num_envs: int, n: int, gamma: float, obs_shape, obs_dtype,
-                 env_id_offset: int = 0):
+                 env_id_offset: int = 0, value_rescale_eps: float = 0.0):
         self.E = int(num_envs)
+        self.value_rescale_eps = float(value_rescale_eps)      # 0 = off: the code and bits of before
+        if not 0.0 <= self.value_rescale_eps <= 1.0:
+            raise ValueError(f"value_rescale_eps must be in (0, 1] (or 0: off), got {value_rescale_eps}")
         self.n = int(n)
         self.gamma = float(gamma)
         self.obs_shape = tuple(obs_shape)
@@ -92,7 +100,10 @@ class NStepBuilder:
         pv = np.nonzero(self.p_valid)[0]
         if len(pv):
             gn = self.gamma ** self.n
-            target = self.p_R[pv] + gn * qmax[pv]
+            if self.value_rescale_eps > 0.0:
+                target = rescale_target(self.p_R[pv], gn, qmax[pv], self.value_rescale_eps)
+            else:
+                target = self.p_R[pv] + gn * qmax[pv]
             prio = np.abs(target - self.p_qsa[pv])
             self._emit(self.p_obs[pv].copy(), self.p_next[pv].copy(), self.p_act[pv],
                        self.p_R[pv], np.full(len(pv), gn), prio, self.p_key[pv], self.env_ids[pv])
@@ -113,7 +124,8 @@ class NStepBuilder:
                 rw = self.w_rew[e, :m]
                 # R_j = sum_{k>=j} gamma^(k-j) r_k over the remaining window
                 R = np.array([np.dot(self.disc[:m - j], rw[j:]) for j in range(m)])
-                prio = np.abs(R - self.w_qsa[e, :m])
+                tgt = rescale_h(R, self.value_rescale_eps) if self.value_rescale_eps > 0.0 else R
+                prio = np.abs(tgt - self.w_qsa[e, :m])
                 keys = np.array([self._keys(np.array([e]))[0] for _ in range(m)], np.int64)
                 self._emit(self.w_obs[e, :m].copy(), np.repeat(obs[e:e + 1], m, axis=0),
                            self.w_act[e, :m].copy(), R, np.zeros(m), prio, keys,
@@ -155,15 +167,17 @@ class NStepBuilder:
         return out
 
 
-def make_nstep_builder(num_envs: int, n: int, gamma: float, obs_shape, obs_dtype, env_id_offset: int = 0):
+def make_nstep_builder(num_envs: int, n: int, gamma: float, obs_shape, obs_dtype, env_id_offset: int = 0,
+                       value_rescale_eps: float = 0.0):
     """The native builder (csrc/runtime/nstep.cpp) when the host runtime library is
     available, else this numpy one (its test oracle).  APEX_NUMPY_NSTEP=1 forces numpy."""
     import os
     if os.environ.get("APEX_NUMPY_NSTEP", "0") != "1":
         from ..runtime import native
         if native.available():
-            return native.NativeNStepBuilder(num_envs, n, gamma, obs_shape, obs_dtype, env_id_offset)
-    return NStepBuilder(num_envs, n, gamma, obs_shape, obs_dtype, env_id_offset)
+            return native.NativeNStepBuilder(num_envs, n, gamma, obs_shape, obs_dtype, env_id_offset,
+                                             value_rescale_eps)
+    return NStepBuilder(num_envs, n, gamma, obs_shape, obs_dtype, env_id_offset, value_rescale_eps)
 
 
 def nstep_returns_reference(rewards, dones, gamma: float, n: int):

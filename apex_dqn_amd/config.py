@@ -136,6 +136,18 @@ class RuntimeConf:
     # Single-rank NatureCNN with any head kind and the torch learners (mlp); not IMPALA, the DP step or the
     # graph learner
     target_ema_rate: float = 0.0
+    # invertible value rescaling of the n-step target (Pohlen et al. 2018; learner/rescale.py, csrc/value_rescale.h):
+    # the network learns h(Q), h(x) = sign(x) (sqrt(|x| + 1) - 1) + eps x, against T = h(R + Gamma h^-1(Q_target)),
+    # so returns of any magnitude are learnable without clipping the rewards.  All four loss heads (per target
+    # sample on the quantile heads, the support in transformed space on the categorical one) and the actors'
+    # initial priorities; q_values and the actor heads return transformed q.  Single-rank NatureCNN and the torch
+    # learners (mlp), with noisy layers, Adam, the schedules and the soft target; not Runtime.munchausen, IMPALA,
+    # the DP step or the graph learner
+    value_rescale: bool = False
+    value_rescale_eps: float = 1e-3
+    # Atari wrappers clip rewards to {-1, 0, +1} (envs/vector_envs.py AtariWrapperVec); false keeps the raw rewards
+    # (with value_rescale; the two keys are independent)
+    clip_rewards: bool = True
     priority_eps: float = 1e-6      # priority floor: leaves hold (|delta| + priority_eps)^alpha
     use_is_weights: bool = True
     is_normalise: str = "batch_max"  # IS weights (N P(i))^-beta divided by their max over the sampled batch
@@ -389,6 +401,21 @@ class ApexConfig:
             if int(rt.world_size) > 1 or rt.force_dp:
                 raise ValueError("Runtime.target_ema_rate runs on a single rank: the data-parallel step "
                                  "(world_size > 1, force_dp) keeps the hard target sync")
+        for key in ("value_rescale", "clip_rewards"):
+            if not isinstance(getattr(rt, key), bool):
+                raise ValueError(f"Runtime.{key} must be true or false, got {getattr(rt, key)!r}")
+        eps = rt.value_rescale_eps
+        if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 < float(eps) <= 1.0:
+            raise ValueError(f"Runtime.value_rescale_eps (the linear term of h) must be a number in (0, 1], got {eps!r}")
+        if rt.value_rescale:
+            if rt.munchausen:
+                raise ValueError("Runtime.value_rescale with Runtime.munchausen is not built: the Munchausen target "
+                                 "is not rescaled")
+            if net not in ("nature64", "nature32", "mlp"):
+                raise ValueError(f"Runtime.value_rescale needs network nature64, nature32 or mlp, got {net!r}")
+            if int(rt.world_size) > 1 or rt.force_dp:
+                raise ValueError("Runtime.value_rescale runs on a single rank: the data-parallel step (world_size > 1, "
+                                 "force_dp) has no rescaled target")
         if net in ("nature64", "nature32", "impala") and len(ss) != 3:
             raise ValueError(f"network {net} needs an image state_shape [C,H,W], got {ss}")
         if net in ("nature64", "nature32") and tuple(ss[1:]) != (84, 84):
@@ -414,6 +441,12 @@ class ApexConfig:
         if rt.noisy:       # (only then: the non-noisy call is the one of before)
             kw.update(noisy=True, noisy_sigma0=float(rt.noisy_sigma0))
         return kw
+
+    @property
+    def rescale_eps(self) -> Optional[float]:
+        """eps of the rescaled target (learner/rescale.py), or None with ``Runtime.value_rescale`` off: the
+        ``rescale_eps`` of the loss oracles and the head ops."""
+        return float(self.Runtime.value_rescale_eps) if self.Runtime.value_rescale else None
 
     def munchausen_kw(self) -> Dict[str, float]:
         """(alpha, tau, clip) of the Munchausen target (learner/losses.py munchausen_loss)."""

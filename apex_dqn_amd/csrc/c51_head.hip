@@ -13,6 +13,9 @@
 //   g_i      = w_b (p(S_t)[a_b,i] - m_i) grad_scale;  d v[i] = g_i,
 //              d adv[a,i] = g_i ([a = a_b] - 1/A)  -> dhead [B][(A + 1) N]
 //   dH       = dhead . W, masked by the stream ReLUs (bf16, or hi / lo planes)
+// Runtime.value_rescale (c51_head_kernel<true>, HeadIO.rescale_eps > 0): the support and v_min / v_max live in
+// transformed space, b_j = (clamp(h(R + G h^-1(z_j))) - v_min) / delta (csrc/value_rescale.h); the projection and
+// td_abs are as above.
 //
 // c51_head_kernel: one block of DIST_NT threads per DIST_SPB samples.  Staging the
 // activation rows, the logits and dH (phases 0, 1 and 3) are csrc/dist_head.h's, shared
@@ -47,6 +50,7 @@ __device__ __forceinline__ float c51_action(const DistRow& r, int a, int N, int 
   return wave_sum_dpp(p * z);
 }
 
+template <bool RESCALE>
 __global__ void __launch_bounds__(DIST_NT) c51_head_kernel(C51Args ka) {
   const HeadIO& a = ka.io;
   extern __shared__ __attribute__((aligned(16))) float c51_smem[];
@@ -94,7 +98,10 @@ __global__ void __launch_bounds__(DIST_NT) c51_head_kernel(C51Args ka) {
       const DistRow rg = dist_row(Ls + (2 * SPB + s) * Jp, a.Ptg, A, N, lane);
       c51_action(rg, astar, N, lane, z, p, lp);
       const float pj = valid ? p : 0.f;
-      const float tz = fminf(fmaxf(rew_b + gam_b * z, ka.vmin), ka.vmax);
+      float tz0;
+      if constexpr (RESCALE) tz0 = value_rescale_target(rew_b, gam_b, z, a.rescale_eps);
+      else tz0 = rew_b + gam_b * z;
+      const float tz = fminf(fmaxf(tz0, ka.vmin), ka.vmax);
       const float bj = (tz - ka.vmin) / delta;
       const float fi = (float)lane;
       for (int j = 0; j < N; ++j) {      // increasing j: the oracle's order
@@ -132,7 +139,8 @@ APEX_EXPORT int apex_c51_head(C51Args a, hipStream_t st) {
   size_t lds = 0;
   if (!dist_head_args_ok(a.io, a.N, &lds) || !(a.vmin < a.vmax)) return (int)hipErrorInvalidValue;
   const int grid = (a.io.B + DIST_SPB - 1) / DIST_SPB;
-  c51_head_kernel<<<grid, DIST_NT, lds, st>>>(a);
+  if (a.io.rescale_eps > 0.f) c51_head_kernel<true><<<grid, DIST_NT, lds, st>>>(a);
+  else c51_head_kernel<false><<<grid, DIST_NT, lds, st>>>(a);
   APEX_CHECK_LAUNCH();
 }
 

@@ -25,22 +25,27 @@
 // hp.part != null: the fc forward's split-K epilogue runs inside (head_common.h
 // load_row_part); blocks >= B run the conv2 weight-fragment pack job (pk.out != null)
 // that otherwise rides on that epilogue's launch.
-template <int HS, int MAXA>
+// Eps = <float>: the rescaled target (csrc/value_rescale.h) with that trailing eps argument; everything else, the
+// deferred fc epilogue, the pack blocks and IsNorm included, is the code of the plain instantiation, whose
+// argument list (Eps empty) is the one of before.
+template <int HS, int MAXA, typename... Eps>
 __global__ void __launch_bounds__(192) ddqn_head_kernel(
     const bf16_t* __restrict__ Hon, const bf16_t* __restrict__ Htg, HeadParams Pon, HeadParams Ptg,
     const int32_t* __restrict__ act, const float* __restrict__ rew, const float* __restrict__ gam,
     const float* __restrict__ isw, int B, int A, int huber, float kappa, float grad_scale,
     float* __restrict__ td_abs, float* __restrict__ loss, float* __restrict__ q_out,
     bf16_t* __restrict__ dH, float* __restrict__ dhead, float* __restrict__ zero_ptr, int zero_n, HeadLo lo,
-    HeadPart hp, C2dPackJob pk, IsNorm isn) {
+    HeadPart hp, C2dPackJob pk, IsNorm isn, Eps... rescale_eps) {
+  static_assert(sizeof...(Eps) <= 1);
   if ((int)blockIdx.x >= B) {
     for (int i = ((int)blockIdx.x - B) * 192 + (int)threadIdx.x; i < C2D_PACK_THREADS; i += ((int)gridDim.x - B) * 192)
       pack_c2d_wfrag_word(i, pk.w, pk.w_lo, pk.out);
     return;
   }
   float ad;
-  const bool w0 = ddqn_head_body<HS, MAXA>(Hon, Htg, Pon, Ptg, act, rew, gam, isw, B, A, huber, kappa, grad_scale, td_abs,
-                                     loss, q_out, dH, dhead, zero_ptr, zero_n, &ad, lo, hp);
+  const bool w0 = ddqn_head_body<HS, MAXA, false, sizeof...(Eps) == 1>(Hon, Htg, Pon, Ptg, act, rew, gam, isw, B, A, huber, kappa,
+                                                           grad_scale, td_abs, loss, q_out, dH, dhead, zero_ptr, zero_n,
+                                                           &ad, lo, hp, nullptr, rescale_eps...);
   if (!w0 && (isn.out != nullptr || isn.valid_count != nullptr) && blockIdx.x == 0 && (threadIdx.x >> 6) == 1) {
     float m = 0.f;
     int nv = 0;
@@ -69,7 +74,10 @@ APEX_EXPORT int apex_ddqn_head(const bf16_t* Hon, const bf16_t* Htg, HeadParams 
                                int B, int A, int huber, float kappa, float grad_scale, float* td_abs,
                                float* loss, float* q_out, bf16_t* dH, float* dhead, float* zero_ptr,
                                int zero_n, int hidden, HeadLo lo, HeadPart hp, C2dPackJob pk, IsNorm isn,
-                               hipStream_t st) {
+                               float rescale_eps, hipStream_t st) {
+  // rescale_eps: 0 = the plain double-DQN target; else Runtime.value_rescale_eps in (0, 1]
+  if (!(rescale_eps >= 0.f && rescale_eps <= 1.f)) return (int)hipErrorInvalidValue;
+  const bool rs = rescale_eps > 0.f;
   if (A < 1 || A > HEAD_MAXA || B < 1) return (int)hipErrorInvalidValue;
   if ((isn.out != nullptr || isn.valid_count != nullptr) && isw == nullptr) return (int)hipErrorInvalidValue;
   if (lo.Hon != nullptr && (lo.Htg == nullptr || lo.dH == nullptr)) return (int)hipErrorInvalidValue;
@@ -80,19 +88,43 @@ APEX_EXPORT int apex_ddqn_head(const bf16_t* Hon, const bf16_t* Htg, HeadParams 
   }
   if (pk.out != nullptr && (pk.w == nullptr || ((uintptr_t)pk.out & 15))) return (int)hipErrorInvalidValue;
   const int grid = B + (pk.out != nullptr ? 128 : 0);
-#define APEX_HEAD_LAUNCH(HS_, MA_)                                                                              \
-  ddqn_head_kernel<HS_, MA_><<<grid, 192, 0, st>>>(Hon, Htg, Pon, Ptg, act, rew, gam, isw, B, A, huber, kappa,     \
-                                                   grad_scale, td_abs, loss, q_out, dH, dhead, zero_ptr, zero_n, lo, \
-                                                   hp, pk, isn)
+#define APEX_HEAD_ARGS                                                                                              \
+  Hon, Htg, Pon, Ptg, act, rew, gam, isw, B, A, huber, kappa, grad_scale, td_abs, loss, q_out, dH, dhead, zero_ptr, \
+      zero_n, lo, hp, pk, isn
+#define APEX_HEAD_LAUNCH(HS_, MA_) ddqn_head_kernel<HS_, MA_><<<grid, 192, 0, st>>>(APEX_HEAD_ARGS)
+#define APEX_HEAD_LAUNCH_RS(HS_, MA_) ddqn_head_kernel<HS_, MA_, float><<<grid, 192, 0, st>>>(APEX_HEAD_ARGS, rescale_eps)
   // the q arrays in registers: 8 actions (every ALE minimal action set but the full
   // 18) keep the kernel free of scratch
-  if (hidden == 512 && A <= 8) APEX_HEAD_LAUNCH(512, 8);
+  // (the rescaled target is the NatureCNN learner's: no 256-wide instantiation, whose MAXA = 32 form would spill)
+  if (rs && hidden != 512) return (int)hipErrorInvalidValue;
+  if (rs && A <= 8) APEX_HEAD_LAUNCH_RS(512, 8);
+  else if (rs) APEX_HEAD_LAUNCH_RS(512, HEAD_MAXA);
+  else if (hidden == 512 && A <= 8) APEX_HEAD_LAUNCH(512, 8);
   else if (hidden == 512) APEX_HEAD_LAUNCH(512, HEAD_MAXA);
   else if (hidden == 256 && A <= 8) APEX_HEAD_LAUNCH(256, 8);
   else if (hidden == 256) APEX_HEAD_LAUNCH(256, HEAD_MAXA);
   else
     return (int)hipErrorInvalidValue;
 #undef APEX_HEAD_LAUNCH
+#undef APEX_HEAD_LAUNCH_RS
+#undef APEX_HEAD_ARGS
+  APEX_CHECK_LAUNCH();
+}
+
+// Element-wise probe of csrc/value_rescale.h for the unit test: out[i] = T(R[i], Gamma[i], y[i], eps).
+__global__ void __launch_bounds__(256) value_rescale_probe_kernel(const float* __restrict__ y, const float* __restrict__ R,
+                                                                  const float* __restrict__ G, float eps,
+                                                                  float* __restrict__ out, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = value_rescale_target(R[i], G[i], y[i], eps);
+}
+
+APEX_EXPORT int apex_value_rescale_probe(const float* y, const float* R, const float* Gamma, float eps, float* out,
+                                         int64_t n, hipStream_t st) {
+  if (y == nullptr || R == nullptr || Gamma == nullptr || out == nullptr || n < 1 || n > (int64_t)1 << 30 ||
+      !(eps > 0.f && eps <= 1.f))
+    return (int)hipErrorInvalidValue;
+  value_rescale_probe_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(y, R, Gamma, eps, out, n);
   APEX_CHECK_LAUNCH();
 }
 

@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "apex_common.h"
+#include "value_rescale.h"
 
 #define HEAD_MAXA 32
 
@@ -58,6 +59,8 @@ struct HeadIO {
   float* dhead;
   float* zero_ptr;      // head-gradient region zeroed for the head weight gradient (or null)
   int zero_n;
+  float rescale_eps;    // Runtime.value_rescale: eps in (0, 1] of csrc/value_rescale.h, 0 = the plain target (the four
+                        // bytes before `lo` that were padding: no block that starts with a HeadIO changes size)
   HeadLo lo;
   IsNorm isn;
 };
@@ -66,6 +69,7 @@ static_assert(std::is_standard_layout_v<HeadIO> && std::is_trivially_copyable_v<
 // The pointer / shape checks the head launchers share; each adds the conditions of its own.
 static inline bool head_io_ok(const HeadIO& a) {
   if (a.A < 1 || a.A > HEAD_MAXA || a.B < 1) return false;
+  if (!(a.rescale_eps >= 0.f && a.rescale_eps <= 1.f)) return false;
   if (a.Hon == nullptr || a.Htg == nullptr || a.act == nullptr || a.rew == nullptr || a.gam == nullptr ||
       a.td_abs == nullptr || a.loss == nullptr || a.dH == nullptr || a.dhead == nullptr)
     return false;
@@ -344,14 +348,18 @@ struct MdqnTarget {
 // difference is an `if constexpr`: the default instantiation compiles to the code of before (its ISA is
 // compared with the parent's, docs/PERF_NOTES.md).  The deferred fc epilogue (hp.part) is not laid out for the
 // MDQN row plan: apex_mdqn_head refuses it.
-template <int HS, int MAXA = HEAD_MAXA, bool MDQN = false>
+// RESCALE (Runtime.value_rescale; ddqn_head_kernel only): the double-DQN target becomes T = h(rew + gam h^-1(
+// q_target[a*])) of csrc/value_rescale.h with eps = `rescale_eps`, one fp64 evaluation per sample; loss, dhead and
+// dH are as before.  Again an `if constexpr`: the off instantiations are the code of before.
+template <int HS, int MAXA = HEAD_MAXA, bool MDQN = false, bool RESCALE = false>
 __device__ __forceinline__ bool ddqn_head_body(
     const bf16_t* __restrict__ Hon, const bf16_t* __restrict__ Htg, HeadParams Pon, HeadParams Ptg,
     const int32_t* __restrict__ act, const float* __restrict__ rew, const float* __restrict__ gam,
     const float* __restrict__ isw, int B, int A, int huber, float kappa, float grad_scale,
     float* __restrict__ td_abs, float* __restrict__ loss, float* __restrict__ q_out,
     bf16_t* __restrict__ dH, float* __restrict__ dhead, float* __restrict__ zero_ptr, int zero_n,
-    float* ad_out, HeadLo lo, const HeadPart& hp, const MdqnTarget* mt = nullptr) {
+    float* ad_out, HeadLo lo, const HeadPart& hp, const MdqnTarget* mt = nullptr, float rescale_eps = 0.f) {
+  static_assert(!(MDQN && RESCALE), "the Munchausen target is not rescaled");
   __shared__ float qs[2][MAXA];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int b = blockIdx.x;
@@ -427,6 +435,7 @@ __device__ __forceinline__ bool ddqn_head_body(
   }
   (void)astar;
   float G = rew_b + gam_b * qg_star;
+  if constexpr (RESCALE) G = value_rescale_target(rew_b, gam_b, qg_star, rescale_eps);
   if constexpr (MDQN) {
     // q_n = g1 (target net, S_t+n), q_g = g0 (target net, S_t): wave-uniform values, no shuffles; every exponent
     // is max-subtracted (no overflow, underflow to 0 is the correct limit); accurate expf / logf

@@ -186,6 +186,9 @@ static inline size_t iqn_head_lds(int A, int N) {
   return (size_t)(3 * DIST_SPB * (2 * DIST_HS + Jp + 64) + (DIST_NT / 64) * Jp + DIST_SPB * N * IQN_E) * sizeof(float);
 }
 
+// RESCALE (Runtime.value_rescale): T_j = h(R + G h^-1(theta_target[a*, j])) per target sample (csrc/value_rescale.h)
+// and td_abs from the mean of the transformed T_j summed in increasing j, as qr_head_kernel<true>.
+template <bool RESCALE>
 __global__ void __launch_bounds__(DIST_NT) iqn_head_kernel(IqnArgs ka) {
   const HeadIO& a = ka.io;
   extern __shared__ __attribute__((aligned(16))) float iqn_smem[];
@@ -271,7 +274,10 @@ __global__ void __launch_bounds__(DIST_NT) iqn_head_kernel(IqnArgs ka) {
       float T;
       {
         const IqnRow rg = iqn_row(Ls + (2 * SPB + s) * Jp, a.Ptg, A, N, lane);
-        T = valid ? rew_b + gam_b * iqn_theta(rg, astar, N, lane) : 0.f;
+        if constexpr (RESCALE)
+          T = valid ? value_rescale_target(rew_b, gam_b, iqn_theta(rg, astar, N, lane), a.rescale_eps) : 0.f;
+        else
+          T = valid ? rew_b + gam_b * iqn_theta(rg, astar, N, lane) : 0.f;
       }
       float th_sa = 0.f, q_sa = 0.f;
       {
@@ -285,8 +291,10 @@ __global__ void __launch_bounds__(DIST_NT) iqn_head_kernel(IqnArgs ka) {
       }
       const float tau = Ts[s * 64 + lane];
       float rho = 0.f, c = 0.f;
+      float tsum = 0.f;                    // RESCALE: sum_j T_j in increasing j (the oracle's order)
       for (int j = 0; j < N; ++j) {
         const float Tj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(T), j));
+        if constexpr (RESCALE) tsum += Tj;
         const float uu = Tj - th_sa;
         const float au = fabsf(uu);
         const float wgt = fabsf(tau - (uu < 0.f ? 1.f : 0.f));
@@ -295,7 +303,9 @@ __global__ void __launch_bounds__(DIST_NT) iqn_head_kernel(IqnArgs ka) {
       }
       const float sc = invN / kappa;
       const float ls = wave_sum_dpp(valid ? rho * sc : 0.f);
-      const float et = wave_sum_dpp(T) * invN;
+      float et;
+      if constexpr (RESCALE) et = tsum * invN;
+      else et = wave_sum_dpp(T) * invN;
       const float g = valid ? -w_b * a.grad_scale * (c * sc) : 0.f;
       const float gs = wave_sum_dpp(g);
       if (live && lane == 0) {
@@ -376,19 +386,22 @@ APEX_EXPORT int apex_iqn_head(IqnArgs a, hipStream_t st) {
     return (int)hipErrorInvalidValue;
   if (!iqn_embed_ok(a.Eon) || !iqn_embed_ok(a.Etg)) return (int)hipErrorInvalidValue;
   if (a.ctr == nullptr || a.dpre == nullptr || a.xg == nullptr) return (int)hipErrorInvalidValue;
+  const bool rs = a.io.rescale_eps > 0.f;
   const size_t lds = iqn_head_lds(a.io.A, a.N);
   if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
-  static size_t lds_set = 64 * 1024;      // raised once per size: not again inside a captured step
-  if (lds > lds_set) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(iqn_head_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  static size_t lds_set[2] = {64 * 1024, 64 * 1024};   // raised once per size and variant: not again inside a captured step
+  if (lds > lds_set[rs]) {
+    const void* fn = rs ? reinterpret_cast<const void*>(iqn_head_kernel<true>)
+                        : reinterpret_cast<const void*>(iqn_head_kernel<false>);
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
-    lds_set = lds;
+    lds_set[rs] = lds;
   }
   const int npairs = (a.io.B + DIST_SPB - 1) / DIST_SPB;
   const int cap = a.max_blocks > 0 ? a.max_blocks : iqn_cu_count();
   const int grid = npairs < cap ? npairs : cap;
-  iqn_head_kernel<<<grid, DIST_NT, lds, st>>>(a);
+  if (rs) iqn_head_kernel<true><<<grid, DIST_NT, lds, st>>>(a);
+  else iqn_head_kernel<false><<<grid, DIST_NT, lds, st>>>(a);
   APEX_CHECK_LAUNCH();
 }
 

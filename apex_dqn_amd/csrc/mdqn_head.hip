@@ -68,6 +68,7 @@ APEX_EXPORT int apex_mdqn_head(MdqnArgs a, hipStream_t st) {
   if (!(a.tau > 0.f) || !(a.clip < 0.f) || !(a.alpha >= 0.f && a.alpha <= 1.f)) return (int)hipErrorInvalidValue;
   if (io.zero_ptr != nullptr && io.zero_n < 0) return (int)hipErrorInvalidValue;
   if (a.hp.part != nullptr || a.hp.hon != nullptr || a.hp.hon_lo != nullptr) return (int)hipErrorInvalidValue;
+  if (io.rescale_eps != 0.f) return (int)hipErrorInvalidValue;      // the Munchausen target is not rescaled
   // 16-byte row loads / stores (head_io_ok asks for 8)
   if (((uintptr_t)io.Hon | (uintptr_t)io.Htg | (uintptr_t)io.dH | (uintptr_t)io.lo.Hon | (uintptr_t)io.lo.Htg |
        (uintptr_t)io.lo.dH) & 15)

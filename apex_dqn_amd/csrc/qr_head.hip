@@ -16,6 +16,9 @@
 //                (the j-sums in increasing j; the i-sum a wave sum)
 //   d v[i] = g_i,  d adv[a,i] = g_i ([a = a_b] - 1/A)  -> dhead [B][(A + 1) N]
 //   td_abs_b   = |(1/N) sum_j T_j - q(S_t)[a_b]| = |R + G q_target[a*] - q[a_b]|
+// Runtime.value_rescale (qr_head_kernel<true>, HeadIO.rescale_eps > 0): T_j = h(R + G h^-1(theta_target[a*,j])) per
+// target sample (csrc/value_rescale.h; exact for quantiles, h being increasing) and td_abs_b takes the mean of the
+// transformed T_j, summed in increasing j -- the shortcut through q_target no longer equals it.
 //   dH         = dhead . W, masked by the stream ReLUs (bf16, or hi / lo planes)
 //
 // qr_head_kernel: one block of DIST_NT threads per DIST_SPB samples.  Staging the
@@ -46,6 +49,7 @@ __device__ __forceinline__ float qr_theta(const DistRow& r, int a, int N, int la
   return lane < N ? r.v + (r.L[N + a * N + lane] + r.ba[a * N + lane]) - r.mean : 0.f;
 }
 
+template <bool RESCALE>
 __global__ void __launch_bounds__(DIST_NT) qr_head_kernel(QRArgs ka) {
   const HeadIO& a = ka.io;
   extern __shared__ __attribute__((aligned(16))) float qr_smem[];
@@ -90,7 +94,10 @@ __global__ void __launch_bounds__(DIST_NT) qr_head_kernel(QRArgs ka) {
     float T;
     {
       const DistRow rg = dist_row(Ls + (2 * SPB + s) * Jp, a.Ptg, A, N, lane);
-      T = valid ? rew_b + gam_b * qr_theta(rg, astar, N, lane) : 0.f;
+      if constexpr (RESCALE)
+        T = valid ? value_rescale_target(rew_b, gam_b, qr_theta(rg, astar, N, lane), a.rescale_eps) : 0.f;
+      else
+        T = valid ? rew_b + gam_b * qr_theta(rg, astar, N, lane) : 0.f;
     }
     // S_t: q of every action, the taken action's quantiles
     float th_sa = 0.f, q_sa = 0.f;
@@ -106,8 +113,10 @@ __global__ void __launch_bounds__(DIST_NT) qr_head_kernel(QRArgs ka) {
     // this lane's quantile against every target sample, in increasing j
     const float tau = (2.f * (float)lane + 1.f) / (2.f * (float)N);
     float rho = 0.f, c = 0.f;
+    float tsum = 0.f;                    // RESCALE: sum_j T_j in increasing j (the oracle's order)
     for (int j = 0; j < N; ++j) {
       const float Tj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(T), j));
+      if constexpr (RESCALE) tsum += Tj;
       const float u = Tj - th_sa;
       const float au = fabsf(u);
       const float wgt = fabsf(tau - (u < 0.f ? 1.f : 0.f));
@@ -116,7 +125,9 @@ __global__ void __launch_bounds__(DIST_NT) qr_head_kernel(QRArgs ka) {
     }
     const float sc = invN / kappa;
     const float ls = wave_sum_dpp(valid ? rho * sc : 0.f);
-    const float et = wave_sum_dpp(T) * invN;
+    float et;
+    if constexpr (RESCALE) et = tsum * invN;
+    else et = wave_sum_dpp(T) * invN;
     const float g = valid ? -w_b * a.grad_scale * (c * sc) : 0.f;
     if (live && lane == 0) {
       a.td_abs[b] = fabsf(et - q_sa);
@@ -134,7 +145,8 @@ APEX_EXPORT int apex_qr_head(QRArgs a, hipStream_t st) {
   size_t lds = 0;
   if (!dist_head_args_ok(a.io, a.N, &lds) || !(a.kappa > 0.f)) return (int)hipErrorInvalidValue;
   const int grid = (a.io.B + DIST_SPB - 1) / DIST_SPB;
-  qr_head_kernel<<<grid, DIST_NT, lds, st>>>(a);
+  if (a.io.rescale_eps > 0.f) qr_head_kernel<true><<<grid, DIST_NT, lds, st>>>(a);
+  else qr_head_kernel<false><<<grid, DIST_NT, lds, st>>>(a);
   APEX_CHECK_LAUNCH();
 }
 

@@ -40,6 +40,7 @@ APEX_RT_API int64_t apex_rt_seqlock_read(const uint64_t* seq, void* dst, const v
 // ---- sliding-window n-step transition builder (csrc/runtime/nstep.cpp)
 APEX_RT_API void* apex_rt_ns_create(int E, int n, double gamma, int obs_bytes, int64_t env_id_offset);
 APEX_RT_API void apex_rt_ns_destroy(void* h);
+APEX_RT_API int apex_rt_ns_set_rescale(void* h, double eps);
 APEX_RT_API int apex_rt_ns_step(void* h, const void* obs, const float* q, int A, const int64_t* actions,
                                 const float* rewards, const uint8_t* dones, const void* next_obs);
 APEX_RT_API int64_t apex_rt_ns_size(void* h);

@@ -11,6 +11,9 @@
 // opaque fixed-size byte payloads (frame sequence numbers for Atari, the state
 // vector for CartPole).  The numpy version spends ~0.3 ms per step on 256 envs
 // in Python-level indexing; this one is a few microseconds.
+// Runtime.value_rescale (apex_rt_ns_set_rescale, eps > 0): the priorities are on the rescaled target's scale,
+// |h(R + Gamma h^-1(max_a q(S_{t+n}))) - q| and |h(R) - q| on the terminal flush, h / h^-1 written operation by
+// operation as learner/rescale.py writes them (fp64); the stored R stays raw.  eps = 0 is the code of before.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -23,6 +26,20 @@ namespace {
 struct NStep {
   int E, n, ob;  // envs, window, observation bytes
   double gamma, gamma_n;
+  double rescale_eps = 0.0;          // > 0: Runtime.value_rescale_eps
+  static double rs_h(double x, double eps) { return x / (std::sqrt(std::fabs(x) + 1.0) + 1.0) + eps * x; }
+  static double rs_h_inv(double y, double eps) {
+    const double ay = std::fabs(y);
+    const double t = 2.0 * ay / (std::sqrt(1.0 + 4.0 * eps * (ay + 1.0 + eps)) + 1.0 + 2.0 * eps);
+    const double sgn = (double)((y > 0.0) - (y < 0.0));
+    return sgn * (t * (t + 2.0));
+  }
+  // the target of a transition's initial priority from the raw return and the bootstrap value
+  double target(double R, double G, double qmax) const {
+    if (rescale_eps > 0.0) return rs_h(R + G * rs_h_inv(qmax, rescale_eps), rescale_eps);
+    return R + G * qmax;
+  }
+  double target_terminal(double R) const { return rescale_eps > 0.0 ? rs_h(R, rescale_eps) : R; }
   std::vector<uint8_t> w_obs;        // [E][n][ob]
   std::vector<int64_t> w_act;        // [E][n]
   std::vector<double> w_rew, w_qsa;  // [E][n]
@@ -88,6 +105,13 @@ APEX_RT_API void* apex_rt_ns_create(int E, int n, double gamma, int obs_bytes, i
 
 APEX_RT_API void apex_rt_ns_destroy(void* h) { delete static_cast<NStep*>(h); }
 
+// eps of the rescaled target the priorities are measured against (0 = off); 1 when out of (0, 1]
+APEX_RT_API int apex_rt_ns_set_rescale(void* h, double eps) {
+  if (h == nullptr || !(eps >= 0.0 && eps <= 1.0)) return 1;
+  static_cast<NStep*>(h)->rescale_eps = eps;
+  return 0;
+}
+
 // One vectorised env step: obs / next_obs [E][obs_bytes], q [E][A] fp32,
 // actions [E] int64, rewards [E] fp32, dones [E] uint8.
 APEX_RT_API int apex_rt_ns_step(void* h, const void* obs_v, const float* q, int A, const int64_t* actions,
@@ -103,7 +127,7 @@ APEX_RT_API int apex_rt_ns_step(void* h, const void* obs_v, const float* q, int 
     if (!s.p_valid[e]) continue;
     double qmax = (double)q[(size_t)e * A];
     for (int a = 1; a < A; ++a) qmax = std::fmax(qmax, (double)q[(size_t)e * A + a]);
-    const double target = s.p_R[e] + s.gamma_n * qmax;
+    const double target = s.target(s.p_R[e], s.gamma_n, qmax);
     s.emit(&s.p_obs[(size_t)e * ob], &s.p_next[(size_t)e * ob], s.p_act[e], s.p_R[e], s.gamma_n,
            std::fabs(target - s.p_qsa[e]), s.p_key[e], s.env_ids[e]);
     s.p_valid[e] = 0;
@@ -127,7 +151,7 @@ APEX_RT_API int apex_rt_ns_step(void* h, const void* obs_v, const float* q, int 
       double R = 0.0;
       for (int k = 0; k < m - j; ++k) R += s.disc[k] * s.w_rew[w0 + j + k];
       s.emit(&s.w_obs[(w0 + j) * ob], obs + (size_t)e * ob, s.w_act[w0 + j], R, 0.0,
-             std::fabs(R - s.w_qsa[w0 + j]), s.key(e), s.env_ids[e]);
+             std::fabs(s.target_terminal(R) - s.w_qsa[w0 + j]), s.key(e), s.env_ids[e]);
     }
     s.cnt[e] = 0;
   }

@@ -423,9 +423,11 @@ class ALEVec(AtariWrapperVec):  # pragma: no cover - ale_py is not available in 
 
 
 def make_vec_env(backend: str, name: str, num_envs: int, action_dim: int,
-                 seed: int = 0, frame_hw: Optional[Tuple[int, int]] = None, preprocess: str = "host"):
+                 seed: int = 0, frame_hw: Optional[Tuple[int, int]] = None, preprocess: str = "host",
+                 clip_rewards: bool = True):
     """Factory replacing ``make_local_env`` (``env.py:3-4``).  ``preprocess`` "device": the
-    emulator-backed envs hand over raw frame pairs (``AtariWrapperVec``)."""
+    emulator-backed envs hand over raw frame pairs (``AtariWrapperVec``).  ``clip_rewards``
+    (``Runtime.clip_rewards``): the Atari wrappers' reward clip to {-1, 0, +1}; the other backends never clip."""
     if preprocess not in ("host", "device"):
         raise ValueError(f"preprocess must be 'host' or 'device', got {preprocess!r}")
     if preprocess == "device" and backend in ("cartpole", "synthetic"):
@@ -438,7 +440,8 @@ def make_vec_env(backend: str, name: str, num_envs: int, action_dim: int,
                                  frame_hw=frame_hw or (84, 84))
     if backend in ("fake_ale", "fake_ale_target"):
         return AtariWrapperVec([FakeALE(seed=seed + i, n_actions=action_dim, target=backend == "fake_ale_target")
-                                for i in range(num_envs)], seed=seed, preprocess=preprocess)
+                                for i in range(num_envs)], seed=seed, preprocess=preprocess,
+                               clip_rewards=clip_rewards)
     if backend == "ale":  # pragma: no cover
-        return ALEVec(name, num_envs, seed=seed, preprocess=preprocess)
+        return ALEVec(name, num_envs, seed=seed, preprocess=preprocess, clip_rewards=clip_rewards)
     raise ValueError(f"unknown env backend {backend!r}")

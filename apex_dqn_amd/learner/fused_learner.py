@@ -11,7 +11,10 @@ Per step (B = local batch), entirely on device, one stream, no host sync:
                                                  csrc/c51_head.hip, projected cross-entropy,
                                                  or csrc/qr_head.hip, quantile Huber loss,
                                                  then head wgrad + write-back and fc wgrad as
-                                                 two launches on the backward's branch)
+                                                 two launches on the backward's branch;
+                                                 Runtime.value_rescale: the same launches
+                                                 with the target T = h(R + Gamma h^-1(.)),
+                                                 csrc/value_rescale.h)
   fc wgrad + head wgrad + priority write-back    ONE launch (csrc/sumtree.hip
   (generation-checked, last writer wins)         fc_wgrad_head_prio_kernel)
   backward: fc, conv3, conv2 dgrad+wgrad, conv1  csrc/conv_mfma.hip, conv2_img.hip,
@@ -132,6 +135,14 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             raise ValueError(f"Runtime.munchausen is a target of the scalar head, not of Runtime.num_atoms={self.N}")
         if self.munchausen and self._dp:
             raise ValueError("Runtime.munchausen: the Munchausen target runs on a single rank, not in the "
+                             "data-parallel step (world > 1, Runtime.force_dp, the emulated world)")
+        # rescaled n-step target T = h(R + Gamma h^-1(.)) (csrc/value_rescale.h): a variant of every head but the
+        # Munchausen one, eps riding in the head's argument block; None = the launches and the bits of before
+        self.rescale_eps = cfg.rescale_eps
+        if self.rescale_eps is not None and self.munchausen:
+            raise ValueError("Runtime.value_rescale: the Munchausen target (Runtime.munchausen) is not rescaled")
+        if self.rescale_eps is not None and self._dp:
+            raise ValueError("Runtime.value_rescale: the rescaled target runs on a single rank, not in the "
                              "data-parallel step (world > 1, Runtime.force_dp, the emulated world)")
         # soft (Polyak) target: t <- (1 - rho) t + rho p after every update, inside the optimizer launch
         # (csrc/rmsprop_common.h EMA); it replaces the hard sync every Learner.q_target_sync_freq updates
@@ -598,6 +609,8 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         out = (1.0 / (B * self.world), self.td_abs, self.loss_b, self.dH, self.dhead)
         kw = dict(zero=self.g_head_region, isn=self._isn(),
                   **self._lo(lo=sp and (self.h_lo[:k], self.h_lo[k:], self.dH_lo)))
+        if self.rescale_eps is not None:     # (only then: the other calls are the ones of before)
+            kw["rescale_eps"] = self.rescale_eps
         if self.munchausen:
             # Munchausen target: online S_t rows, target S_t+n and S_t rows (csrc/mdqn_head.hip)
             mk = self.cfg.munchausen_kw()

@@ -71,6 +71,9 @@ class GraphLearner(StepIndexMixin):
         if float(self.rt.target_ema_rate) > 0.0:
             raise ValueError("Runtime.target_ema_rate: the graph learner (Runtime.use_hip_kernels = false on the GPU) "
                              "keeps the hard target sync; run the HIP kernels or target_ema_rate = 0")
+        if self.rt.value_rescale:
+            raise ValueError("Runtime.value_rescale: the graph learner (Runtime.use_hip_kernels = false on the GPU) "
+                             "has no rescaled target; run the HIP kernels or value_rescale = false")
         self.device = torch.device(device)
         self.replay = replay
         self.comm = comm

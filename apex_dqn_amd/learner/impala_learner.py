@@ -81,6 +81,9 @@ class FusedImpalaLearner(IsNormMixin, StepIndexMixin):
         if float(self.rt.target_ema_rate) > 0.0:
             raise ValueError("Runtime.target_ema_rate: the IMPALA step keeps the hard target sync (the soft target "
                              "is the NatureCNN learner's)")
+        if self.rt.value_rescale:
+            raise ValueError("Runtime.value_rescale: the IMPALA step has no rescaled target (it is the NatureCNN "
+                             "learner's and the torch learners')")
         self.world, _, self.B, self.mcap = dp_layout(cfg, comm, batch_size, allow_force=False)
         self.C = cfg.frame_stack
         if self.C != 4 or tuple(cfg.env_conf.state_shape[1:]) != (84, 84):

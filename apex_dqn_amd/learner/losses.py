@@ -14,6 +14,8 @@ from typing import Tuple
 
 import torch
 
+from .rescale import rescale_target
+
 
 def huber(delta: torch.Tensor, kappa: float = 1.0) -> torch.Tensor:
     a = delta.abs()
@@ -21,25 +23,34 @@ def huber(delta: torch.Tensor, kappa: float = 1.0) -> torch.Tensor:
 
 
 def ddqn_targets(q_online_next: torch.Tensor, q_target_next: torch.Tensor,
-                 R: torch.Tensor, Gamma: torch.Tensor) -> torch.Tensor:
+                 R: torch.Tensor, Gamma: torch.Tensor, rescale_eps: float = None) -> torch.Tensor:
+    """``rescale_eps`` (``Runtime.value_rescale``): T = h(R + Gamma h^-1(q_target[a*])), learner/rescale.py."""
     a_star = q_online_next.argmax(dim=1, keepdim=True)
+    if rescale_eps is not None:
+        return rescale_target(R, Gamma, q_target_next.gather(1, a_star).squeeze(1), float(rescale_eps))
     return R + Gamma * q_target_next.gather(1, a_star).squeeze(1)
 
 
 def c51_project(p_next: torch.Tensor, R: torch.Tensor, Gamma: torch.Tensor, v_min: float,
-                v_max: float) -> torch.Tensor:
+                v_max: float, rescale_eps: float = None) -> torch.Tensor:
     """Categorical projection of the n-step target ``R + Gamma z`` onto the support
     z_i = v_min + i delta (N atoms): ``m_i = sum_j p'_j max(0, 1 - |b_j - i|)`` with
     ``b_j = (clamp(R + Gamma z_j, v_min, v_max) - v_min) / delta`` -- the usual floor / ceil
     split written as a gather (deterministic, continuous in b, no scatter), summed in
     increasing j.  Gamma = 0 (terminal) needs no special case; sum_i m_i = 1.  Computes in
-    ``p_next``'s dtype (fp64 inputs: the tests' reference).  p_next [B, N] -> m [B, N]."""
+    ``p_next``'s dtype (fp64 inputs: the tests' reference).  p_next [B, N] -> m [B, N].
+    ``rescale_eps`` (``Runtime.value_rescale``): the support lives in transformed space and the atoms move
+    to ``clamp(h(R + Gamma h^-1(z_j)), v_min, v_max)`` (learner/rescale.py)."""
     N = p_next.shape[-1]
     dt = p_next.dtype
     delta = (float(v_max) - float(v_min)) / (N - 1)
     idx = torch.arange(N, dtype=dt, device=p_next.device)
     z = float(v_min) + idx * delta
-    tz = (R.to(dt)[:, None] + Gamma.to(dt)[:, None] * z[None, :]).clamp(float(v_min), float(v_max))
+    if rescale_eps is not None:
+        tz = rescale_target(R.to(dt)[:, None], Gamma.to(dt)[:, None], z[None, :], float(rescale_eps))
+    else:
+        tz = R.to(dt)[:, None] + Gamma.to(dt)[:, None] * z[None, :]
+    tz = tz.clamp(float(v_min), float(v_max))
     b = (tz - float(v_min)) / delta
     m = torch.zeros_like(p_next)
     for j in range(N):        # fixed order: the kernels' sum
@@ -49,7 +60,7 @@ def c51_project(p_next: torch.Tensor, R: torch.Tensor, Gamma: torch.Tensor, v_mi
 
 def c51_loss(logp_t: torch.Tensor, q_online_next: torch.Tensor, p_target_next: torch.Tensor,
              A: torch.Tensor, R: torch.Tensor, Gamma: torch.Tensor, v_min: float, v_max: float,
-             weights: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
+             weights: torch.Tensor = None, rescale_eps: float = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Distributional double-DQN loss.  ``logp_t`` [B, A, N]: log p(S_t) of the online net;
     ``q_online_next`` [B, A]: its expected q at S_{t+n} (picks a*, first maximum);
     ``p_target_next`` [B, A, N]: the target net's probabilities at S_{t+n}.  Returns (mean
@@ -61,7 +72,7 @@ def c51_loss(logp_t: torch.Tensor, q_online_next: torch.Tensor, p_target_next: t
     ar = torch.arange(B, device=logp_t.device)
     with torch.no_grad():
         a_star = q_online_next.argmax(dim=1)
-        m = c51_project(p_target_next[ar, a_star].to(dt), R, Gamma, v_min, v_max)
+        m = c51_project(p_target_next[ar, a_star].to(dt), R, Gamma, v_min, v_max, rescale_eps)
         delta = (float(v_max) - float(v_min)) / (N - 1)
         z = float(v_min) + torch.arange(N, dtype=dt, device=logp_t.device) * delta
     lp = logp_t[ar, A.long().view(-1)]
@@ -102,9 +113,19 @@ def quantile_huber_terms(theta: torch.Tensor, T: torch.Tensor, kappa: float,
     return rho / (N * kappa), c / (N * kappa)
 
 
+def quantile_targets(R: torch.Tensor, Gamma: torch.Tensor, theta: torch.Tensor,
+                     rescale_eps: float = None) -> torch.Tensor:
+    """The target samples T_j [B, N] of the two quantile heads from the target net's ``theta`` [B, N] of a*:
+    R + Gamma theta_j, or with ``rescale_eps`` (``Runtime.value_rescale``) h(R + Gamma h^-1(theta_j)) per
+    sample -- exact, the quantiles of a monotone image being the images of the quantiles."""
+    if rescale_eps is not None:
+        return rescale_target(R[:, None], Gamma[:, None], theta, float(rescale_eps))
+    return R[:, None] + Gamma[:, None] * theta
+
+
 def quantile_huber_loss(theta_t: torch.Tensor, q_online_next: torch.Tensor, theta_target_next: torch.Tensor,
                         A: torch.Tensor, R: torch.Tensor, Gamma: torch.Tensor, kappa: float,
-                        weights: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                        weights: torch.Tensor = None, rescale_eps: float = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Quantile-regression (QR-DQN) double-DQN loss.  ``theta_t`` [B, A, N]: the online
     net's quantiles at S_t; ``q_online_next`` [B, A]: its q (mean of the quantiles) at
     S_{t+n}, which picks a* (first maximum); ``theta_target_next`` [B, A, N]: the target
@@ -112,13 +133,14 @@ def quantile_huber_loss(theta_t: torch.Tensor, q_online_next: torch.Tensor, thet
     needs no special case).  Returns (mean over the batch of w sum_i rho_i, see
     :func:`quantile_huber_terms`; |mean_j T_j - q(S_t)[a]| per sample): the priority is the
     absolute TD error of the expectations, on the scale of the actors' initial priorities.
-    Computes in ``theta_t``'s dtype."""
+    Computes in ``theta_t``'s dtype.  With ``rescale_eps`` the priority takes the mean of the transformed T_j
+    (no longer |R + Gamma q_target[a*] - q|)."""
     B = theta_t.shape[0]
     dt = theta_t.dtype
     ar = torch.arange(B, device=theta_t.device)
     with torch.no_grad():
         a_star = q_online_next.argmax(dim=1)
-        T = R.to(dt)[:, None] + Gamma.to(dt)[:, None] * theta_target_next[ar, a_star].to(dt)
+        T = quantile_targets(R.to(dt), Gamma.to(dt), theta_target_next[ar, a_star].to(dt), rescale_eps)
     th = theta_t[ar, A.long().view(-1)]
     per = quantile_huber_terms(th, T, kappa)[0].sum(-1)
     if weights is not None:
@@ -130,7 +152,7 @@ def quantile_huber_loss(theta_t: torch.Tensor, q_online_next: torch.Tensor, thet
 
 def iqn_loss(theta_t: torch.Tensor, tau_t: torch.Tensor, q_online_next: torch.Tensor,
              theta_target_next: torch.Tensor, A: torch.Tensor, R: torch.Tensor, Gamma: torch.Tensor, kappa: float,
-             weights: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
+             weights: torch.Tensor = None, rescale_eps: float = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Implicit quantile (IQN) double-DQN loss: :func:`quantile_huber_loss` with sampled
     fractions.  ``theta_t`` [B, A, N]: the online net at S_t evaluated at ``tau_t`` [B, N];
     ``q_online_next`` [B, A]: its q at S_{t+n} (the mean over its own tau set), which picks a*
@@ -142,7 +164,7 @@ def iqn_loss(theta_t: torch.Tensor, tau_t: torch.Tensor, q_online_next: torch.Te
     ar = torch.arange(B, device=theta_t.device)
     with torch.no_grad():
         a_star = q_online_next.argmax(dim=1)
-        T = R.to(dt)[:, None] + Gamma.to(dt)[:, None] * theta_target_next[ar, a_star].to(dt)
+        T = quantile_targets(R.to(dt), Gamma.to(dt), theta_target_next[ar, a_star].to(dt), rescale_eps)
     th = theta_t[ar, A.long().view(-1)]
     per = quantile_huber_terms(th, T, kappa, tau_t)[0].sum(-1)
     if weights is not None:
@@ -203,10 +225,15 @@ def munchausen_loss(q_t: torch.Tensor, q_target_t: torch.Tensor, q_target_next: 
 def ddqn_loss(q_online_t: torch.Tensor, q_online_next: torch.Tensor,
               q_target_next: torch.Tensor, A: torch.Tensor, R: torch.Tensor,
               Gamma: torch.Tensor, weights: torch.Tensor = None, loss: str = "huber",
-              kappa: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Return (scalar loss, |delta| per sample)."""
+              kappa: float = 1.0, rescale_eps: float = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Return (scalar loss, |delta| per sample).  ``rescale_eps``: the rescaled target of :func:`ddqn_targets`
+    (fp64 on the fp32 inputs, rounded to fp32 once: the kernel's evaluation)."""
     with torch.no_grad():
-        G = ddqn_targets(q_online_next.float(), q_target_next.float(), R.float(), Gamma.float())
+        if rescale_eps is not None:
+            G = ddqn_targets(q_online_next.float().double(), q_target_next.float().double(), R.float().double(),
+                             Gamma.float().double(), rescale_eps).float()
+        else:
+            G = ddqn_targets(q_online_next.float(), q_target_next.float(), R.float(), Gamma.float())
     q_sa = q_online_t.float().gather(1, A.long().view(-1, 1)).squeeze(1)
     delta = G - q_sa
     per = huber(delta, kappa) if loss == "huber" else 0.5 * delta * delta

@@ -71,6 +71,7 @@ class TorchLearner:
         G = self._to(batch["Gamma"], torch.float32)
         w = self._to(batch["weights"], torch.float32) if (
             self.rt.use_is_weights and "weights" in batch) else None
+        rs = self.cfg.rescale_eps        # Runtime.value_rescale: the rescaled target (learner/rescale.py), or None
         if self.cfg.implicit:
             # IQN: the quantile Huber loss at sampled fractions, three sets per row drawn by the fused learner's
             # convention (learner/iqn.py: update index = num_q_updates), so both see the same fractions
@@ -83,21 +84,21 @@ class TorchLearner:
                 q_next_online = self.Q.quantiles_at(S_tpn, taus[:, 1]).mean(-1)
                 th_next_target = self.Q_target.quantiles_at(S_tpn, taus[:, 2])
             return iqn_loss(self.Q.quantiles_at(S_t, taus[:, 0]), taus[:, 0], q_next_online, th_next_target, A, R, G,
-                            self.rt.huber_delta, w)
+                            self.rt.huber_delta, w, rescale_eps=rs)
         if self.cfg.quantile:
             # QR-DQN: quantile Huber loss against the target net's quantiles (learner/losses.py)
             with torch.no_grad():
                 q_next_online = self.Q(S_tpn)[2]
                 th_next_target = self.Q_target.quantiles(S_tpn)
             return quantile_huber_loss(self.Q.quantiles(S_t), q_next_online, th_next_target, A, R, G,
-                                       self.rt.huber_delta, w)
+                                       self.rt.huber_delta, w, rescale_eps=rs)
         if self.cfg.distributional:
             # C51: cross-entropy against the projected target distribution (learner/losses.py)
             with torch.no_grad():
                 q_next_online = self.Q(S_tpn)[2]
                 p_next_target = self.Q_target.log_probs(S_tpn).exp()
             return c51_loss(self.Q.log_probs(S_t), q_next_online, p_next_target, A, R, G,
-                            self.rt.v_min, self.rt.v_max, w)
+                            self.rt.v_min, self.rt.v_max, w, rescale_eps=rs)
         if self.rt.munchausen:
             # Munchausen-DQN: the target net at S_t and S_t+n, no online argmax (learner/losses.py)
             with torch.no_grad():
@@ -113,7 +114,7 @@ class TorchLearner:
             q_next_target = self.Q_target(S_tpn)[2]
         q_t = self.Q(S_t)[2]
         return ddqn_loss(q_t, q_next_online, q_next_target, A, R, G, w,
-                         loss=self.rt.loss, kappa=self.rt.huber_delta)
+                         loss=self.rt.loss, kappa=self.rt.huber_delta, rescale_eps=rs)
 
     def update_Q(self, loss: torch.Tensor) -> float:
         self.optimizer.zero_grad(set_to_none=False)

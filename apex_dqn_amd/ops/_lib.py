@@ -63,7 +63,7 @@ class HeadIO(ctypes.Structure):
     _fields_ = [("Hon", c_p), ("Htg", c_p), ("Pon", HeadParams), ("Ptg", HeadParams), ("act", c_p), ("rew", c_p),
                 ("gam", c_p), ("isw", c_p), ("B", c_i), ("A", c_i), ("hidden", c_i), ("grad_scale", c_f),
                 ("td_abs", c_p), ("loss", c_p), ("q_out", c_p), ("dH", c_p), ("dhead", c_p), ("zero_ptr", c_p),
-                ("zero_n", c_i), ("lo", HeadLo), ("isn", IsNorm)]
+                ("zero_n", c_i), ("rescale_eps", c_f), ("lo", HeadLo), ("isn", IsNorm)]
 
 
 class C51Args(ctypes.Structure):
@@ -266,7 +266,8 @@ _SIGS = {
     "apex_grad_finalize": ([FinalizeDesc, c_p], c_i),
     "apex_norm_total": ([c_p, c_i, c_p, c_p], c_i),
     "apex_ddqn_head": ([c_p, c_p, HeadParams, HeadParams, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p,
-                        c_p, c_p, c_p, c_p, c_p, c_i, c_i, HeadLo, HeadPart, C2dPack, IsNorm, c_p], c_i),
+                        c_p, c_p, c_p, c_p, c_p, c_i, c_i, HeadLo, HeadPart, C2dPack, IsNorm, c_f, c_p], c_i),
+    "apex_value_rescale_probe": ([c_p, c_p, c_p, c_f, c_p, c_i64, c_p], c_i),
     "apex_opt_sample": ([RmspropArgs, SampleArgs, c_p, c_p], c_i),
     "apex_head_wgrad_prio": ([HeadWgArgs, TreeUpdArgs, c_p, c_p, c_p, c_i, c_i, c_p, c_i64, c_p], c_i),
     "apex_fc_wgrad_head_prio": ([WgradDesc, HeadWgArgs, TreeUpdArgs, c_p], c_i),
@@ -313,7 +314,7 @@ def _declare(lib: ctypes.CDLL) -> None:
     conv_sigs.declare(lib)
 
 
-ABI_VERSION = 15    # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
+ABI_VERSION = 16    # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
 SQNORM_PARTIALS = 1024   # what apex_grad_sqnorm_partials writes (csrc/rmsprop_common.h SQNORM_NPART)
 # the blocks that cross the ABI by value, in the order of csrc/sumtree.hip apex_abi_struct_sizes()
 ABI_STRUCTS = (RmspropArgs, SampleArgs, RmsSegs, TreeUpdArgs, HeadWgArgs, IqnWgArgs, WgradDesc)
@@ -406,6 +407,14 @@ def is_norm(isn=None) -> IsNorm:
         s.wscale, s.out = ptr(isn[0]), ptr(isn[1])
         s.valid_count = ptr(isn[2]) if len(isn) > 2 else None
     return s
+
+
+def rescale_eps_arg(rescale_eps) -> float:
+    """``rescale_eps`` of the head ops as the launchers' float: 0 = off (None), else eps in (0, 1]."""
+    if rescale_eps is None:
+        return 0.0
+    from ..learner.rescale import check_eps
+    return check_eps(rescale_eps)
 
 
 def check(rc: int, what: str) -> None:

@@ -27,6 +27,7 @@ import torch
 from . import _lib
 from . import conv as C
 from . import reference as R
+from ..learner.rescale import rescale_target
 from .switches import SW
 
 
@@ -140,8 +141,10 @@ class TorchBackend:
     # ---------------------------------------------------------------- head
     def head(self, Hon, Htg, Pon: Dict[str, torch.Tensor], Ptg: Dict[str, torch.Tensor], act, rew, gam, isw,
              huber: bool, kappa: float, grad_scale: float, td_abs, loss, dH, dhead, q_out=None,
-             zero: Optional[torch.Tensor] = None, lo=None, isn=None):
-        """``lo = (Hon_lo, Htg_lo, dH_lo)`` in split mode.  ``isn = (wscale, out[, count])``:
+             zero: Optional[torch.Tensor] = None, lo=None, isn=None, rescale_eps=None):
+        """``rescale_eps`` (``Runtime.value_rescale``): the target is T = h(R + Gamma h^-1(q_target[a*])) of
+        learner/rescale.py, fp64 on the fp32 values and rounded once (csrc/value_rescale.h).
+        ``lo = (Hon_lo, Htg_lo, dH_lo)`` in split mode.  ``isn = (wscale, out[, count])``:
         batch-max IS normalisation, ``out[0] = max(isw) / wscale`` (the optimizer divides the
         gradient by it; csrc/ddqn_head.hip ``IsNorm``; ``out`` may be None), and ``count``
         (int64) += the rows with a non-zero weight (DP: the rows this rank drew)."""
@@ -153,7 +156,11 @@ class TorchBackend:
         q_n = self._dueling_q(Hon[B:2 * B], Pon, dt)
         q_g = self._dueling_q(Htg[:B], Ptg, dt)
         a_star = q_n.argmax(1)
-        G = rew.float() + gam.float() * q_g.gather(1, a_star[:, None]).squeeze(1)
+        if rescale_eps is not None:
+            G = rescale_target(rew.float().double(), gam.float().double(), q_g.gather(1, a_star[:, None]).squeeze(1).double(),
+                               _lib.rescale_eps_arg(rescale_eps)).to(dt)
+        else:
+            G = rew.float() + gam.float() * q_g.gather(1, a_star[:, None]).squeeze(1)
         self._td_loss_bwd(G, q_t, Hon[:B], Pon, act, isw, huber, kappa, grad_scale, td_abs, loss, dH, dhead, q_out,
                           zero, lo[2], isn, dt)
 
@@ -286,7 +293,7 @@ class TorchBackend:
 
     def c51_head(self, Hon, Htg, Pon: Dict[str, torch.Tensor], Ptg: Dict[str, torch.Tensor], act, rew, gam, isw,
                  num_atoms: int, v_min: float, v_max: float, grad_scale: float, td_abs, loss, dH, dhead,
-                 q_out=None, zero: Optional[torch.Tensor] = None, lo=None, isn=None):
+                 q_out=None, zero: Optional[torch.Tensor] = None, lo=None, isn=None, rescale_eps=None):
         """The distributional counterpart of :meth:`head` (the oracle of csrc/c51_head.hip
         ``c51_head_kernel``): head weights ``wv (N, HS)``, ``bv (N,)``, ``wa (A N, HS)``, ``ba
         (A N,)``; loss = -w sum_i m_i log p(S_t)[a, i] with m the projected target
@@ -294,7 +301,6 @@ class TorchBackend:
         |sum_i m_i z_i - q(S_t)[a]|, ``dhead [B, (A + 1) N]`` (value atoms, then action a's
         atoms at N + a N), ``q_out`` the expected q(S_t).  Computes in the head weights'
         dtype when that is fp64 (the tests' reference), else fp32."""
-        from ..learner.losses import c51_project
         B, N = act.shape[0], int(num_atoms)
         A = Pon["wa"].shape[0] // N
         dt = _head_dtype(Pon["wv"])
@@ -308,7 +314,7 @@ class TorchBackend:
         q_n = (self._c51_logp(Hon[B:2 * B], Pon, A, N, dt).exp() * z).sum(-1)
         a_star = q_n.argmax(1)
         p_g = self._c51_logp(Htg[:B], Ptg, A, N, dt)[ar, a_star].exp()
-        m = c51_project(p_g, rew, gam, v_min, v_max)
+        m = self._c51_m(p_g, rew, gam, v_min, v_max, rescale_eps)
         lp = lp_t[ar, act.long()]
         p = lp.exp()
         w = isw.to(dt) if isw is not None else torch.ones(B, dtype=dt, device=Hon.device)
@@ -317,6 +323,27 @@ class TorchBackend:
         g = w[:, None] * (p - m) * grad_scale                      # d loss / d logits of (a_b, .)
         self._dueling_bwd(g, act, Pon, Hon[:B], dH, dhead, lo[2], dt)
         self._head_close(q_out, q_t, zero, isn, w.float())
+
+    @staticmethod
+    def _c51_m(p_g, rew, gam, v_min, v_max, rescale_eps):
+        """The projected target distribution (learner/losses.py ``c51_project``).  With ``rescale_eps`` the moved
+        atoms are formed as the kernel forms them: fp64 on the fp32 inputs, rounded to the head's dtype once."""
+        from ..learner.losses import c51_project
+        if rescale_eps is None:
+            return c51_project(p_g, rew, gam, v_min, v_max)
+        eps = _lib.rescale_eps_arg(rescale_eps)
+        if p_g.dtype == torch.float64:
+            return c51_project(p_g, rew, gam, v_min, v_max, eps)
+        N, dt = p_g.shape[-1], p_g.dtype
+        delta = (float(v_max) - float(v_min)) / (N - 1)
+        idx = torch.arange(N, dtype=dt, device=p_g.device)
+        z = float(v_min) + idx * delta
+        tz = rescale_target(rew.to(dt).double()[:, None], gam.to(dt).double()[:, None], z.double()[None, :], eps).to(dt)
+        b = (tz.clamp(float(v_min), float(v_max)) - float(v_min)) / delta
+        m = torch.zeros_like(p_g)
+        for j in range(N):
+            m = m + p_g[:, j:j + 1] * (1.0 - (b[:, j:j + 1] - idx[None, :]).abs()).clamp_min(0.0)
+        return m
 
     def c51_actor_head(self, H, P, eps, ctr, seed, num_atoms: int, v_min: float, v_max: float, q_out, a_out,
                        H_lo=None):
@@ -342,7 +369,7 @@ class TorchBackend:
 
     def qr_head(self, Hon, Htg, Pon: Dict[str, torch.Tensor], Ptg: Dict[str, torch.Tensor], act, rew, gam, isw,
                 num_atoms: int, kappa: float, grad_scale: float, td_abs, loss, dH, dhead,
-                q_out=None, zero: Optional[torch.Tensor] = None, lo=None, isn=None):
+                q_out=None, zero: Optional[torch.Tensor] = None, lo=None, isn=None, rescale_eps=None):
         """The quantile-regression counterpart of :meth:`c51_head` (the oracle of
         csrc/qr_head.hip ``qr_head_kernel``), the same head weights read as N quantiles per
         action: T_j = R + Gamma theta_target(S_t+n)[a*, j] with a* the online net's double-DQN
@@ -362,7 +389,7 @@ class TorchBackend:
         th_t = self._qr_theta(Hon[:B], Pon, A, N, dt)
         q_t = th_t.mean(-1)
         a_star = self._qr_theta(Hon[B:2 * B], Pon, A, N, dt).mean(-1).argmax(1)
-        T = rew.to(dt)[:, None] + gam.to(dt)[:, None] * self._qr_theta(Htg[:B], Ptg, A, N, dt)[ar, a_star]
+        T = self._quantile_T(rew.to(dt), gam.to(dt), self._qr_theta(Htg[:B], Ptg, A, N, dt)[ar, a_star], rescale_eps)
         th = th_t[ar, act.long()]
         rho, c = quantile_huber_terms(th, T, kappa)
         w = isw.to(dt) if isw is not None else torch.ones(B, dtype=dt, device=Hon.device)
@@ -371,6 +398,15 @@ class TorchBackend:
         g = -w[:, None] * grad_scale * c                           # d loss / d theta of (a_b, .)
         self._dueling_bwd(g, act, Pon, Hon[:B], dH, dhead, lo[2], dt)
         self._head_close(q_out, q_t, zero, isn, w.float())
+
+    @staticmethod
+    def _quantile_T(rew, gam, theta, rescale_eps):
+        """The target samples of the quantile heads (learner/losses.py ``quantile_targets``); with ``rescale_eps``
+        in fp64 on the values of the head's dtype, rounded once (csrc/value_rescale.h)."""
+        from ..learner.losses import quantile_targets
+        if rescale_eps is None:
+            return quantile_targets(rew, gam, theta)
+        return quantile_targets(rew.double(), gam.double(), theta.double(), _lib.rescale_eps_arg(rescale_eps)).to(theta.dtype)
 
     def qr_actor_head(self, H, P, eps, ctr, seed, num_atoms: int, q_out, a_out, H_lo=None):
         """q = mean of the quantiles + epsilon-greedy per row (the oracle of csrc/qr_head.hip
@@ -413,7 +449,8 @@ class TorchBackend:
     def iqn_head(self, Hon, Htg, Pon: Dict[str, torch.Tensor], Ptg: Dict[str, torch.Tensor],
                  Eon: Dict[str, torch.Tensor], Etg: Dict[str, torch.Tensor], act, rew, gam, isw, num_samples: int,
                  kappa: float, grad_scale: float, seed_q: int, ctr, base, td_abs, loss, dH, dhead, ws, q_out=None,
-                 tau_out=None, zero: Optional[torch.Tensor] = None, lo=None, isn=None, max_blocks=None):
+                 tau_out=None, zero: Optional[torch.Tensor] = None, lo=None, isn=None, max_blocks=None,
+                 rescale_eps=None):
         """The implicit quantile counterpart of :meth:`qr_head` (the oracle of csrc/iqn_head.hip
         ``iqn_head_kernel``): the scalar head's weights ``P`` gated by the cosine embedding
         ``E`` (:meth:`_iqn_theta`) at three tau sets of N fractions per sample, drawn by the
@@ -439,7 +476,8 @@ class TorchBackend:
         th_t, pre, cf = self._iqn_theta(Hon[:B], Pon, Eon, taus[:, 0], dt)
         q_t = th_t.mean(-1)
         a_star = self._iqn_theta(Hon[B:2 * B], Pon, Eon, taus[:, 1], dt)[0].mean(-1).argmax(1)
-        T = rew.to(dt)[:, None] + gam.to(dt)[:, None] * self._iqn_theta(Htg[:B], Ptg, Etg, taus[:, 2], dt)[0][ar, a_star]
+        T = self._quantile_T(rew.to(dt), gam.to(dt), self._iqn_theta(Htg[:B], Ptg, Etg, taus[:, 2], dt)[0][ar, a_star],
+                             rescale_eps)
         th = th_t[ar, act.long()]
         rho, c = quantile_huber_terms(th, T, kappa, taus[:, 0])
         w = isw.to(dt) if isw is not None else torch.ones(B, dtype=dt, device=Hon.device)
@@ -958,7 +996,7 @@ class HipBackend(TorchBackend):
         return h
 
     def head(self, Hon, Htg, Pon, Ptg, act, rew, gam, isw, huber, kappa, grad_scale, td_abs, loss, dH,
-             dhead, q_out=None, zero=None, lo=None, isn=None):
+             dhead, q_out=None, zero=None, lo=None, isn=None, rescale_eps=None):
         B = act.shape[0]
         A = Pon["wa"].shape[0]
         args = (Hon.data_ptr(), Htg.data_ptr(), self._hp(Pon), self._hp(Ptg), act.data_ptr(), rew.data_ptr(),
@@ -979,10 +1017,20 @@ class HipBackend(TorchBackend):
                 pk.w, pk.w_lo = fp["c2d"][0].data_ptr(), _lib.ptr(fp["c2d"][1])
                 pk.out = C.c2d_wfrag_buffer(self.ws, Hon.device).data_ptr()
                 self._c2d_packed = (fp["c2d"][0].data_ptr(), _lib.ptr(fp["c2d"][1]))
-        _lib.check(self.lib.apex_ddqn_head(*args, hl, hp, pk, _lib.is_norm(isn), _lib.stream_ptr()), "ddqn_head")
+        _lib.check(self.lib.apex_ddqn_head(*args, hl, hp, pk, _lib.is_norm(isn), _lib.rescale_eps_arg(rescale_eps),
+                                           _lib.stream_ptr()), "ddqn_head")
+
+    def value_rescale_probe(self, y, R, Gamma, eps, out) -> None:
+        """csrc/ddqn_head.hip ``value_rescale_probe_kernel``: ``out[i] = T(R[i], Gamma[i], y[i], eps)`` of
+        csrc/value_rescale.h, element-wise on fp32 vectors (the unit test of the device function)."""
+        n = out.numel()
+        assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n for t in (y, R, Gamma, out))
+        _lib.check(self.lib.apex_value_rescale_probe(y.data_ptr(), R.data_ptr(), Gamma.data_ptr(),
+                                                     _lib.rescale_eps_arg(eps), out.data_ptr(), n, _lib.stream_ptr()),
+                   "value_rescale_probe")
 
     def _head_io(self, io, Hon, Htg, Pon, Ptg, act, rew, gam, isw, A, hidden, grad_scale, td_abs, loss, dH, dhead,
-                 q_out, zero, lo, isn) -> None:
+                 q_out, zero, lo, isn, rescale_eps=None) -> None:
         """Fill ``io``, the block every struct-argument head takes (``_lib.HeadIO``); ``B`` is ``act``'s."""
         io.Hon, io.Htg, io.Pon, io.Ptg = Hon.data_ptr(), Htg.data_ptr(), self._hp(Pon), self._hp(Ptg)
         io.act, io.rew, io.gam, io.isw = act.data_ptr(), rew.data_ptr(), gam.data_ptr(), _lib.ptr(isw)
@@ -992,6 +1040,7 @@ class HipBackend(TorchBackend):
         io.zero_ptr, io.zero_n = _lib.ptr(zero), 0 if zero is None else zero.numel()
         io.lo = _lib.head_lo(*(lo if lo is not None else (None, None, None)))
         io.isn = _lib.is_norm(isn)
+        io.rescale_eps = _lib.rescale_eps_arg(rescale_eps)
 
     def mdqn_head(self, Hon, Htg, Pon, Ptg, act, rew, gam, isw, huber, kappa, alpha, tau, clip, grad_scale, td_abs,
                   loss, dH, dhead, q_out=None, aux=None, zero=None, lo=None, isn=None):
@@ -1011,14 +1060,14 @@ class HipBackend(TorchBackend):
         _lib.check(self.lib.apex_mdqn_head(a, _lib.stream_ptr()), "mdqn_head")
 
     def c51_head(self, Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, v_min, v_max, grad_scale, td_abs, loss,
-                 dH, dhead, q_out=None, zero=None, lo=None, isn=None):
+                 dH, dhead, q_out=None, zero=None, lo=None, isn=None, rescale_eps=None):
         """csrc/c51_head.hip ``c51_head_kernel`` (reads h: the fc epilogue is not deferred)."""
         assert getattr(self, "_fc_part", None) is None, "the distributional head reads h: fc epilogue deferred"
         N = int(num_atoms)
         a = _lib.C51Args()
         B, A = act.shape[0], Pon["wa"].shape[0] // N
         self._head_io(a.io, Hon, Htg, Pon, Ptg, act, rew, gam, isw, A, Pon["wv"].shape[-1], grad_scale, td_abs, loss,
-                      dH, dhead, q_out, zero, lo, isn)
+                      dH, dhead, q_out, zero, lo, isn, rescale_eps)
         a.N, a.vmin, a.vmax = N, float(v_min), float(v_max)
         assert dhead.shape == (B, (A + 1) * N) and dhead.is_contiguous()
         _lib.check(self.lib.apex_c51_head(a, _lib.stream_ptr()), "c51_head")
@@ -1031,14 +1080,14 @@ class HipBackend(TorchBackend):
                                                 _lib.ptr(H_lo), _lib.stream_ptr()), "c51_actor_head")
 
     def qr_head(self, Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, kappa, grad_scale, td_abs, loss,
-                dH, dhead, q_out=None, zero=None, lo=None, isn=None):
+                dH, dhead, q_out=None, zero=None, lo=None, isn=None, rescale_eps=None):
         """csrc/qr_head.hip ``qr_head_kernel`` (reads h: the fc epilogue is not deferred)."""
         assert getattr(self, "_fc_part", None) is None, "the distributional head reads h: fc epilogue deferred"
         N = int(num_atoms)
         a = _lib.QRArgs()
         B, A = act.shape[0], Pon["wa"].shape[0] // N
         self._head_io(a.io, Hon, Htg, Pon, Ptg, act, rew, gam, isw, A, Pon["wv"].shape[-1], grad_scale, td_abs, loss,
-                      dH, dhead, q_out, zero, lo, isn)
+                      dH, dhead, q_out, zero, lo, isn, rescale_eps)
         a.N, a.kappa = N, float(kappa)
         assert dhead.shape == (B, (A + 1) * N) and dhead.is_contiguous()
         _lib.check(self.lib.apex_qr_head(a, _lib.stream_ptr()), "qr_head")
@@ -1065,7 +1114,7 @@ class HipBackend(TorchBackend):
 
     def iqn_head(self, Hon, Htg, Pon, Ptg, Eon, Etg, act, rew, gam, isw, num_samples, kappa, grad_scale, seed_q, ctr,
                  base, td_abs, loss, dH, dhead, ws, q_out=None, tau_out=None, zero=None, lo=None, isn=None,
-                 max_blocks=None):
+                 max_blocks=None, rescale_eps=None):
         """csrc/iqn_head.hip ``iqn_head_kernel`` (reads h: the fc epilogue is not deferred).  ``max_blocks``
         caps the persistent grid (default: the CU count)."""
         assert getattr(self, "_fc_part", None) is None, "the distributional head reads h: fc epilogue deferred"
@@ -1073,7 +1122,7 @@ class HipBackend(TorchBackend):
         a = _lib.IqnArgs()
         B, A, hidden = act.shape[0], Pon["wa"].shape[0], Pon["wv"].shape[-1]
         self._head_io(a.io, Hon, Htg, Pon, Ptg, act, rew, gam, isw, A, hidden, grad_scale, td_abs, loss, dH, dhead,
-                      q_out, zero, lo, isn)
+                      q_out, zero, lo, isn, rescale_eps)
         a.N, a.kappa, a.seed_q = N, float(kappa), int(seed_q)
         assert ctr.dtype == torch.int64 and (base is None or base.dtype == torch.int64)
         a.ctr, a.base = ctr.data_ptr(), _lib.ptr(base)

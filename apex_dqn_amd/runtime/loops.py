@@ -41,10 +41,11 @@ from .shared_params import SharedParams
 
 def _make_group(cfg: ApexConfig, num_envs: int, offset: int, total: int, seed: int) -> ActorGroup:
     env = make_vec_env(cfg.env_backend, cfg.env_conf.name, num_envs, cfg.env_conf.action_dim,
-                       seed=seed + offset)
+                       seed=seed + offset, clip_rewards=cfg.Runtime.clip_rewards)
     a = cfg.Actor
     return ActorGroup(env, num_envs, a.num_steps, a.gamma, cfg.frame_stack, a.epsilon, a.alpha,
-                      global_actor_offset=offset, total_actors=total, seed=seed, materialize=True)
+                      global_actor_offset=offset, total_actors=total, seed=seed, materialize=True,
+                      value_rescale_eps=cfg.rescale_eps or 0.0)
 
 
 def _make_policy(net: torch.nn.Module, device):

@@ -32,6 +32,7 @@ _SIGS = {
     "apex_rt_seqlock_read": ([c_p, c_p, c_p, c_i64, c_i64, c_i], c_i64),
     "apex_rt_ns_create": ([c_i, c_i, c_d, c_i, c_i64], c_p),
     "apex_rt_ns_destroy": ([c_p], None),
+    "apex_rt_ns_set_rescale": ([c_p, c_d], c_i),
     "apex_rt_ns_step": ([c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p], c_i),
     "apex_rt_ns_size": ([c_p], c_i64),
     "apex_rt_ns_take": ([c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p], c_i64),
@@ -136,8 +137,10 @@ class NativeNStepBuilder:
     semantics, emission order and ``get`` batches; observations are opaque
     fixed-shape payloads of ``obs_dtype``."""
 
-    def __init__(self, num_envs: int, n: int, gamma: float, obs_shape, obs_dtype, env_id_offset: int = 0):
+    def __init__(self, num_envs: int, n: int, gamma: float, obs_shape, obs_dtype, env_id_offset: int = 0,
+                 value_rescale_eps: float = 0.0):
         self.E, self.n, self.gamma = int(num_envs), int(n), float(gamma)
+        self.value_rescale_eps = float(value_rescale_eps)
         self.obs_shape = tuple(obs_shape)
         self.obs_dtype = np.dtype(obs_dtype)
         self._ob = int(np.prod(self.obs_shape)) * self.obs_dtype.itemsize
@@ -146,6 +149,8 @@ class NativeNStepBuilder:
         self._h = self._lib.apex_rt_ns_create(self.E, self.n, self.gamma, self._ob, int(env_id_offset))
         if not self._h:
             raise ValueError("invalid n-step builder shape")
+        if self.value_rescale_eps != 0.0 and self._lib.apex_rt_ns_set_rescale(self._h, self.value_rescale_eps):
+            raise ValueError(f"value_rescale_eps must be in (0, 1] (or 0: off), got {value_rescale_eps}")
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
