@@ -19,48 +19,26 @@
 //   act int32, rew/gam/isw fp32
 // Outputs: td_abs[B], loss[B], q_t[B,A] (optional), dH[B,1024] bf16 (gradient
 // at the pre-ReLU stream outputs), dhead[B,1+A] fp32 (d value, d advantage).
-#include "head_common.h"
-#include "conv2_wfrag.h"
+#include "ddqn_args.h"
 
 // hp.part != null: the fc forward's split-K epilogue runs inside (head_common.h
 // load_row_part); blocks >= B run the conv2 weight-fragment pack job (pk.out != null)
 // that otherwise rides on that epilogue's launch.
-// Eps = <float>: the rescaled target (csrc/value_rescale.h) with that trailing eps argument; everything else, the
-// deferred fc epilogue, the pack blocks and IsNorm included, is the code of the plain instantiation, whose
-// argument list (Eps empty) is the one of before.
-template <int HS, int MAXA, typename... Eps>
-__global__ void __launch_bounds__(192) ddqn_head_kernel(
-    const bf16_t* __restrict__ Hon, const bf16_t* __restrict__ Htg, HeadParams Pon, HeadParams Ptg,
-    const int32_t* __restrict__ act, const float* __restrict__ rew, const float* __restrict__ gam,
-    const float* __restrict__ isw, int B, int A, int huber, float kappa, float grad_scale,
-    float* __restrict__ td_abs, float* __restrict__ loss, float* __restrict__ q_out,
-    bf16_t* __restrict__ dH, float* __restrict__ dhead, float* __restrict__ zero_ptr, int zero_n, HeadLo lo,
-    HeadPart hp, C2dPackJob pk, IsNorm isn, Eps... rescale_eps) {
-  static_assert(sizeof...(Eps) <= 1);
+// RESCALE: the rescaled target (csrc/value_rescale.h, eps = io.rescale_eps); everything else is the plain code.
+template <int HS, int MAXA, bool RESCALE>
+__global__ void __launch_bounds__(192) ddqn_head_kernel(DdqnArgs ka) {
+  const HeadIO& a = ka.io;
+  const int B = a.B;
   if ((int)blockIdx.x >= B) {
     for (int i = ((int)blockIdx.x - B) * 192 + (int)threadIdx.x; i < C2D_PACK_THREADS; i += ((int)gridDim.x - B) * 192)
-      pack_c2d_wfrag_word(i, pk.w, pk.w_lo, pk.out);
+      pack_c2d_wfrag_word(i, ka.pk.w, ka.pk.w_lo, ka.pk.out);
     return;
   }
   float ad;
-  const bool w0 = ddqn_head_body<HS, MAXA, false, sizeof...(Eps) == 1>(Hon, Htg, Pon, Ptg, act, rew, gam, isw, B, A, huber, kappa,
-                                                           grad_scale, td_abs, loss, q_out, dH, dhead, zero_ptr, zero_n,
-                                                           &ad, lo, hp, nullptr, rescale_eps...);
-  if (!w0 && (isn.out != nullptr || isn.valid_count != nullptr) && blockIdx.x == 0 && (threadIdx.x >> 6) == 1) {
-    float m = 0.f;
-    int nv = 0;
-    for (int i = threadIdx.x & 63; i < B; i += 64) {
-      m = fmaxf(m, isw[i]);
-      nv += isw[i] > 0.f ? 1 : 0;
-    }
-    m = wave_max(m);
-    nv = wave_sum(nv);
-    if ((threadIdx.x & 63) == 0) {
-      const float ws = isn.wscale != nullptr ? isn.wscale[0] : 1.f;
-      if (isn.out != nullptr) isn.out[0] = ws > 0.f ? (double)m / (double)ws : 0.0;
-      if (isn.valid_count != nullptr) atomicAdd(isn.valid_count, (unsigned long long)nv);
-    }
-  }
+  const bool w0 = ddqn_head_body<HS, MAXA, false, RESCALE>(a, ka.huber, ka.kappa, &ad, ka.hp);
+  // batch-max IS normalisation: block 0's second wave
+  if (!w0 && (a.isn.out != nullptr || a.isn.valid_count != nullptr) && blockIdx.x == 0 && (threadIdx.x >> 6) == 1)
+    head_is_norm(a, threadIdx.x & 63);
 }
 
 // (h.NV >= 2: the wide head of csrc/c51_head.hip, blockIdx.x = row tile)
@@ -69,45 +47,35 @@ __global__ void __launch_bounds__(512) head_wgrad_kernel(HeadWgArgs h) {
   else head_wgrad_body(h, blockIdx.x, blockIdx.y);
 }
 
-APEX_EXPORT int apex_ddqn_head(const bf16_t* Hon, const bf16_t* Htg, HeadParams Pon, HeadParams Ptg,
-                               const int32_t* act, const float* rew, const float* gam, const float* isw,
-                               int B, int A, int huber, float kappa, float grad_scale, float* td_abs,
-                               float* loss, float* q_out, bf16_t* dH, float* dhead, float* zero_ptr,
-                               int zero_n, int hidden, HeadLo lo, HeadPart hp, C2dPackJob pk, IsNorm isn,
-                               float rescale_eps, hipStream_t st) {
-  // rescale_eps: 0 = the plain double-DQN target; else Runtime.value_rescale_eps in (0, 1]
-  if (!(rescale_eps >= 0.f && rescale_eps <= 1.f)) return (int)hipErrorInvalidValue;
-  const bool rs = rescale_eps > 0.f;
-  if (A < 1 || A > HEAD_MAXA || B < 1) return (int)hipErrorInvalidValue;
-  if ((isn.out != nullptr || isn.valid_count != nullptr) && isw == nullptr) return (int)hipErrorInvalidValue;
-  if (lo.Hon != nullptr && (lo.Htg == nullptr || lo.dH == nullptr)) return (int)hipErrorInvalidValue;
-  if (hp.part != nullptr) {   // split-K partials [nz][3B][2 hidden]; rows [0, B) of h written to hp.hon
-    if (hp.nz < 1 || hp.hon == nullptr || hp.bias_on == nullptr || hp.bias_tg == nullptr || hp.two_b != 2 * B ||
-        (lo.Hon != nullptr) != (hp.hon_lo != nullptr) || (((uintptr_t)hp.part | (uintptr_t)hp.hon) & 15))
+APEX_EXPORT int apex_ddqn_head(DdqnArgs a, hipStream_t st) {
+  const HeadIO& io = a.io;
+  if (!head_io_ok(io) || (io.zero_ptr != nullptr && io.zero_n < 0)) return (int)hipErrorInvalidValue;
+  // 16-byte row loads / stores of the 512-wide streams (head_io_ok asks for 8)
+  if (io.hidden == 512 && (((uintptr_t)io.Hon | (uintptr_t)io.Htg | (uintptr_t)io.dH | (uintptr_t)io.lo.Hon |
+                            (uintptr_t)io.lo.Htg | (uintptr_t)io.lo.dH) & 15))
+    return (int)hipErrorInvalidValue;
+  if (const HeadPart& hp = a.hp; hp.part != nullptr) {   // partials [nz][3B][2 hidden]; rows [0, B) of h go to hp.hon
+    if (hp.nz < 1 || hp.hon == nullptr || hp.bias_on == nullptr || hp.bias_tg == nullptr || hp.two_b != 2 * io.B ||
+        (io.lo.Hon != nullptr) != (hp.hon_lo != nullptr) || (((uintptr_t)hp.part | (uintptr_t)hp.hon) & 15))
       return (int)hipErrorInvalidValue;
   }
-  if (pk.out != nullptr && (pk.w == nullptr || ((uintptr_t)pk.out & 15))) return (int)hipErrorInvalidValue;
-  const int grid = B + (pk.out != nullptr ? 128 : 0);
-#define APEX_HEAD_ARGS                                                                                              \
-  Hon, Htg, Pon, Ptg, act, rew, gam, isw, B, A, huber, kappa, grad_scale, td_abs, loss, q_out, dH, dhead, zero_ptr, \
-      zero_n, lo, hp, pk, isn
-#define APEX_HEAD_LAUNCH(HS_, MA_) ddqn_head_kernel<HS_, MA_><<<grid, 192, 0, st>>>(APEX_HEAD_ARGS)
-#define APEX_HEAD_LAUNCH_RS(HS_, MA_) ddqn_head_kernel<HS_, MA_, float><<<grid, 192, 0, st>>>(APEX_HEAD_ARGS, rescale_eps)
+  if (a.pk.out != nullptr && (a.pk.w == nullptr || ((uintptr_t)a.pk.out & 15))) return (int)hipErrorInvalidValue;
+  const int grid = io.B + (a.pk.out != nullptr ? 128 : 0);
+  const bool rs = io.rescale_eps > 0.f;       // 0 = the plain double-DQN target
+#define APEX_HEAD_LAUNCH(HS_, MA_, RS_) ddqn_head_kernel<HS_, MA_, RS_><<<grid, 192, 0, st>>>(a)
   // the q arrays in registers: 8 actions (every ALE minimal action set but the full
   // 18) keep the kernel free of scratch
   // (the rescaled target is the NatureCNN learner's: no 256-wide instantiation, whose MAXA = 32 form would spill)
-  if (rs && hidden != 512) return (int)hipErrorInvalidValue;
-  if (rs && A <= 8) APEX_HEAD_LAUNCH_RS(512, 8);
-  else if (rs) APEX_HEAD_LAUNCH_RS(512, HEAD_MAXA);
-  else if (hidden == 512 && A <= 8) APEX_HEAD_LAUNCH(512, 8);
-  else if (hidden == 512) APEX_HEAD_LAUNCH(512, HEAD_MAXA);
-  else if (hidden == 256 && A <= 8) APEX_HEAD_LAUNCH(256, 8);
-  else if (hidden == 256) APEX_HEAD_LAUNCH(256, HEAD_MAXA);
+  if (rs && io.hidden != 512) return (int)hipErrorInvalidValue;
+  if (rs && io.A <= 8) APEX_HEAD_LAUNCH(512, 8, true);
+  else if (rs) APEX_HEAD_LAUNCH(512, HEAD_MAXA, true);
+  else if (io.hidden == 512 && io.A <= 8) APEX_HEAD_LAUNCH(512, 8, false);
+  else if (io.hidden == 512) APEX_HEAD_LAUNCH(512, HEAD_MAXA, false);
+  else if (io.hidden == 256 && io.A <= 8) APEX_HEAD_LAUNCH(256, 8, false);
+  else if (io.hidden == 256) APEX_HEAD_LAUNCH(256, HEAD_MAXA, false);
   else
     return (int)hipErrorInvalidValue;
 #undef APEX_HEAD_LAUNCH
-#undef APEX_HEAD_LAUNCH_RS
-#undef APEX_HEAD_ARGS
   APEX_CHECK_LAUNCH();
 }
 
@@ -140,17 +108,14 @@ APEX_EXPORT int apex_head_wgrad(HeadWgArgs h, hipStream_t st) {
 // H_lo (fp32 learner, split mode): the lo plane of the stream activations, so the
 // actor's q-values (and the initial priorities built from them) are fp32-accurate.
 template <int HS, int MAXA>
-__global__ void __launch_bounds__(256) actor_head_kernel(const bf16_t* __restrict__ H, HeadParams P, int E,
-                                                         int A, const float* __restrict__ eps, uint64_t seed,
-                                                         const uint64_t* __restrict__ ctr,
-                                                         float* __restrict__ q_out, int32_t* __restrict__ a_out,
-                                                         const bf16_t* __restrict__ H_lo) {
+__global__ void __launch_bounds__(256) actor_head_kernel(ActorIO a) {
+  const int A = a.A;
   const int lane = threadIdx.x & 63;
   const int e = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (e >= E) return;
+  if (e >= a.E) return;
   float q[MAXA], hv[HS / 64], ha[HS / 64];
-  head_row<HS, MAXA>(H + (int64_t)e * 2 * HS, H_lo != nullptr ? H_lo + (int64_t)e * 2 * HS : nullptr, P, A, lane, q,
-                     hv, ha);
+  head_row<HS, MAXA>(a.H + (int64_t)e * 2 * HS, a.H_lo != nullptr ? a.H_lo + (int64_t)e * 2 * HS : nullptr, a.P, A, lane,
+                     q, hv, ha);
   int best = 0;
   float bq = -3.4e38f;
 #pragma unroll
@@ -161,28 +126,20 @@ __global__ void __launch_bounds__(256) actor_head_kernel(const bf16_t* __restric
 #pragma unroll
     for (int j = 0; j < MAXA; ++j)
       if (j == lane) qv = q[j];
-    q_out[(int64_t)e * A + lane] = qv;
+    a.q_out[(int64_t)e * A + lane] = qv;
   }
-  if (lane == 0) {
-    const uint64_t c = ctr ? ctr[0] : 0;
-    float u = apex_uniform(seed, c, 2 * (uint64_t)e);
-    float r = apex_uniform(seed, c, 2 * (uint64_t)e + 1);
-    int a = best;
-    if (u < eps[e]) a = min((int)(r * (float)A), A - 1);
-    a_out[e] = a;
-  }
+  if (lane == 0) dist_actor_draw(best, e, A, a.eps, a.seed, a.ctr, a.a_out);
 }
 
-APEX_EXPORT int apex_actor_head(const bf16_t* H, HeadParams P, int E, int A, const float* eps, uint64_t seed,
-                                const uint64_t* ctr, float* q_out, int32_t* a_out, int hidden, const bf16_t* H_lo,
-                                hipStream_t st) {
-  if (A < 1 || A > HEAD_MAXA || E < 1) return (int)hipErrorInvalidValue;
-#define APEX_ACTOR_HEAD(HS_, MA_) \
-  actor_head_kernel<HS_, MA_><<<(E + 3) / 4, 256, 0, st>>>(H, P, E, A, eps, seed, ctr, q_out, a_out, H_lo)
-  if (hidden == 512 && A <= 8) APEX_ACTOR_HEAD(512, 8);
-  else if (hidden == 512) APEX_ACTOR_HEAD(512, HEAD_MAXA);
-  else if (hidden == 256 && A <= 8) APEX_ACTOR_HEAD(256, 8);
-  else if (hidden == 256) APEX_ACTOR_HEAD(256, HEAD_MAXA);
+APEX_EXPORT int apex_actor_head(ActorIO a, hipStream_t st) {
+  if (!actor_io_ok(a)) return (int)hipErrorInvalidValue;
+  // 16-byte row loads of the 512-wide streams (actor_io_ok asks for 8)
+  if (a.hidden == 512 && (((uintptr_t)a.H | (uintptr_t)a.H_lo) & 15)) return (int)hipErrorInvalidValue;
+#define APEX_ACTOR_HEAD(HS_, MA_) actor_head_kernel<HS_, MA_><<<(a.E + 3) / 4, 256, 0, st>>>(a)
+  if (a.hidden == 512 && a.A <= 8) APEX_ACTOR_HEAD(512, 8);
+  else if (a.hidden == 512) APEX_ACTOR_HEAD(512, HEAD_MAXA);
+  else if (a.hidden == 256 && a.A <= 8) APEX_ACTOR_HEAD(256, 8);
+  else if (a.hidden == 256) APEX_ACTOR_HEAD(256, HEAD_MAXA);
   else return (int)hipErrorInvalidValue;
 #undef APEX_ACTOR_HEAD
   APEX_CHECK_LAUNCH();

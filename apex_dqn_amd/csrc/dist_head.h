@@ -116,26 +116,12 @@ static inline size_t dist_head_lds(int A, int N) {
 }
 
 __device__ __forceinline__ void dist_head_side(const HeadIO& a, int tid, int lane, int wv) {
-  const int B = a.B;
   // zero the head-gradient region that the head weight gradient accumulates into
   if (a.zero_ptr != nullptr)
     for (int i = blockIdx.x * DIST_NT + tid; i < a.zero_n; i += gridDim.x * DIST_NT) a.zero_ptr[i] = 0.f;
   // batch-max IS statistic (ddqn_head_kernel's): block 0's last wave
-  if ((a.isn.out != nullptr || a.isn.valid_count != nullptr) && blockIdx.x == 0 && wv == DIST_NT / 64 - 1) {
-    float m = 0.f;
-    int nv = 0;
-    for (int i = lane; i < B; i += 64) {
-      m = fmaxf(m, a.isw[i]);
-      nv += a.isw[i] > 0.f ? 1 : 0;
-    }
-    m = wave_max(m);
-    nv = wave_sum(nv);
-    if (lane == 0) {
-      const float ws = a.isn.wscale != nullptr ? a.isn.wscale[0] : 1.f;
-      if (a.isn.out != nullptr) a.isn.out[0] = ws > 0.f ? (double)m / (double)ws : 0.0;
-      if (a.isn.valid_count != nullptr) atomicAdd(a.isn.valid_count, (unsigned long long)nv);
-    }
-  }
+  if ((a.isn.out != nullptr || a.isn.valid_count != nullptr) && blockIdx.x == 0 && wv == DIST_NT / 64 - 1)
+    head_is_norm(a, lane);
 }
 
 // ---- phase 0: the block's activation rows -> LDS (fp32; a sample past the batch reads the last row)
@@ -351,14 +337,35 @@ __device__ __forceinline__ void dist_actor_logits(const bf16_t* __restrict__ H, 
   }
 }
 
-// The actor heads' epsilon-greedy draw of actor_head_kernel (same counter-RNG words): lane 0
-// of a live row.
-__device__ __forceinline__ void dist_actor_draw(int best, int e, int A, const float* __restrict__ eps, uint64_t seed,
-                                                const uint64_t* __restrict__ ctr, int32_t* __restrict__ a_out) {
-  const uint64_t c = ctr ? ctr[0] : 0;
-  const float u = apex_uniform(seed, c, 2 * (uint64_t)e);
-  const float rr = apex_uniform(seed, c, 2 * (uint64_t)e + 1);
-  int act = best;
-  if (u < eps[e]) act = min((int)(rr * (float)A), A - 1);
-  a_out[e] = act;
+// Arguments of the C51 / QR actor heads (csrc/c51_head.hip, csrc/qr_head.hip; ops/_lib.py holds the mirrors)
+struct C51ActorArgs {
+  ActorIO io;
+  int N;
+  float vmin, vmax;
+};
+struct QRActorArgs {
+  ActorIO io;
+  int N;
+};
+static_assert(std::is_trivially_copyable_v<C51ActorArgs> && std::is_trivially_copyable_v<QRActorArgs> &&
+              std::is_standard_layout_v<C51ActorArgs> && std::is_standard_layout_v<QRActorArgs>);
+
+// actor_io_ok plus what the C51 / QR actor launchers share of their own; the LDS of a block in `lds`
+static inline bool dist_actor_args_ok(const ActorIO& a, int N, size_t* lds) {
+  *lds = (size_t)4 * (((a.A + 1) * N + 3) & ~3) * sizeof(float);
+  return actor_io_ok(a) && N >= 2 && N <= 64 && a.hidden == DIST_HS;
+}
+
+// How the C51 / QR actor kernels open: wave wv takes env row e = 4 blockIdx.x + wv (past E: the last row again,
+// live = false) and leaves its logits in its slice of `smem`, returned, behind a block barrier.
+__device__ __forceinline__ float* dist_actor_open(const ActorIO& a, int N, float* smem, int lane, int wv, int& e,
+                                                  bool& live) {
+  const int AN = a.A * N, J = N + AN, Jp = (J + 3) & ~3;
+  const int e_raw = blockIdx.x * 4 + wv;
+  live = e_raw < a.E;
+  e = min(e_raw, a.E - 1);
+  float* L = smem + wv * Jp;
+  dist_actor_logits(a.H, a.H_lo, a.P, e, a.A, N, lane, L);
+  __syncthreads();
+  return L;
 }

@@ -38,7 +38,7 @@ struct IsNorm {
   unsigned long long* valid_count;   // DP: += rows of this batch the rank drew (weight > 0); or null
 };
 
-// What every struct-argument loss head takes (C51Args, QRArgs, IqnArgs, MdqnArgs: their first
+// What every loss head takes (DdqnArgs, C51Args, QRArgs, IqnArgs, MdqnArgs: their first
 // member `io`; ops/_lib.py HeadIO is the mirror).  Row plans: Hon [2B] = the online net at S_t,
 // S_t+n and Htg [B] = the target net at S_t+n; the Munchausen head Hon [B] = S_t and Htg [2B] =
 // S_t+n, S_t.
@@ -83,6 +83,59 @@ static inline bool head_io_ok(const HeadIO& a) {
        (uintptr_t)a.lo.dH) & 7)
     return false;
   return true;
+}
+
+// The batch-max IS statistic (IsNorm), by one wave: every head kernel calls it under its own block / wave condition.
+__device__ __forceinline__ void head_is_norm(const HeadIO& a, int lane) {
+  float m = 0.f;
+  int nv = 0;
+  for (int i = lane; i < a.B; i += 64) {
+    m = fmaxf(m, a.isw[i]);
+    nv += a.isw[i] > 0.f ? 1 : 0;
+  }
+  m = wave_max(m);
+  nv = wave_sum(nv);
+  if (lane == 0) {
+    const float ws = a.isn.wscale != nullptr ? a.isn.wscale[0] : 1.f;
+    if (a.isn.out != nullptr) a.isn.out[0] = ws > 0.f ? (double)m / (double)ws : 0.0;
+    if (a.isn.valid_count != nullptr) atomicAdd(a.isn.valid_count, (unsigned long long)nv);
+  }
+}
+
+// What every actor head takes (the scalar head alone, else first member `io`; ops/_lib.py ActorIO is the mirror)
+struct ActorIO {
+  const bf16_t* H;      // [E][2 hidden] stream activations
+  const bf16_t* H_lo;   // split mode (fp32 learner): their lo plane, so q is fp32-accurate; else null
+  HeadParams P;
+  int E, A, hidden;
+  const float* eps;     // [E]
+  uint64_t seed;        // the draw's counter-RNG words: (seed, ctr[0], 2 e) and (seed, ctr[0], 2 e + 1)
+  const uint64_t* ctr;  // null: 0
+  float* q_out;         // [E][A]
+  int32_t* a_out;       // [E]
+};
+static_assert(std::is_standard_layout_v<ActorIO> && std::is_trivially_copyable_v<ActorIO>);
+
+// The checks the actor-head launchers share; each adds the conditions of its own.
+static inline bool actor_io_ok(const ActorIO& a) {
+  if (a.A < 1 || a.A > HEAD_MAXA || a.E < 1) return false;
+  if (a.H == nullptr || a.eps == nullptr || a.q_out == nullptr || a.a_out == nullptr) return false;
+  if (a.P.wv == nullptr || a.P.bv == nullptr || a.P.wa == nullptr || a.P.ba == nullptr) return false;
+  // float4 weight loads; 8-byte row loads of the activation planes (the C51 / QR kernels' and the 256-wide scalar
+  // one's; the 512-wide scalar launcher asks for 16, the IQN kernel reads per element and would need 2)
+  return ((((uintptr_t)a.P.wv | (uintptr_t)a.P.wa) & 15) | (((uintptr_t)a.H | (uintptr_t)a.H_lo) & 7)) == 0;
+}
+
+// The actor heads' epsilon-greedy draw: lane 0 of a live row e, `best` its greedy action.  The callers unpack
+// their ActorIO: `__restrict__` counts on parameters only.
+__device__ __forceinline__ void dist_actor_draw(int best, int e, int A, const float* __restrict__ eps, uint64_t seed,
+                                                const uint64_t* __restrict__ ctr, int32_t* __restrict__ a_out) {
+  const uint64_t c = ctr ? ctr[0] : 0;
+  const float u = apex_uniform(seed, c, 2 * (uint64_t)e);
+  const float rr = apex_uniform(seed, c, 2 * (uint64_t)e + 1);
+  int act = best;
+  if (u < eps[e]) act = min((int)(rr * (float)A), A - 1);
+  a_out[e] = act;
 }
 
 // NPL consecutive fp32 weights (16-B aligned: NPL is 4 or 8) as float4 loads
@@ -349,24 +402,23 @@ struct MdqnTarget {
 // compared with the parent's, docs/PERF_NOTES.md).  The deferred fc epilogue (hp.part) is not laid out for the
 // MDQN row plan: apex_mdqn_head refuses it.
 // RESCALE (Runtime.value_rescale; ddqn_head_kernel only): the double-DQN target becomes T = h(rew + gam h^-1(
-// q_target[a*])) of csrc/value_rescale.h with eps = `rescale_eps`, one fp64 evaluation per sample; loss, dhead and
+// q_target[a*])) of csrc/value_rescale.h with eps = io.rescale_eps, one fp64 evaluation per sample; loss, dhead and
 // dH are as before.  Again an `if constexpr`: the off instantiations are the code of before.
-template <int HS, int MAXA = HEAD_MAXA, bool MDQN = false, bool RESCALE = false>
-__device__ __forceinline__ bool ddqn_head_body(
+// The kernels call ddqn_head_body (below) with their HeadIO block; it unpacks the block into the parameters here:
+// hipcc honours `__restrict__` on the parameters of an inlined function, not on a local, and without it every store
+// may alias every load (the wave-uniform loads behind a store then become vector loads).
+template <int HS, int MAXA, bool MDQN, bool RESCALE>
+__device__ __forceinline__ bool ddqn_head_rows(
     const bf16_t* __restrict__ Hon, const bf16_t* __restrict__ Htg, HeadParams Pon, HeadParams Ptg,
     const int32_t* __restrict__ act, const float* __restrict__ rew, const float* __restrict__ gam,
     const float* __restrict__ isw, int B, int A, int huber, float kappa, float grad_scale,
     float* __restrict__ td_abs, float* __restrict__ loss, float* __restrict__ q_out,
     bf16_t* __restrict__ dH, float* __restrict__ dhead, float* __restrict__ zero_ptr, int zero_n,
-    float* ad_out, HeadLo lo, const HeadPart& hp, const MdqnTarget* mt = nullptr, float rescale_eps = 0.f) {
+    float* ad_out, HeadLo lo, const HeadPart& hp, const MdqnTarget* mt, float rescale_eps) {
   static_assert(!(MDQN && RESCALE), "the Munchausen target is not rescaled");
   __shared__ float qs[2][MAXA];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int b = blockIdx.x;
-  // zero the head-gradient region that head_wgrad accumulates into (stream-ordered)
-  if (zero_ptr != nullptr) {   // B blocks (a launch may carry extra side-job blocks)
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < zero_n; i += B * blockDim.x) zero_ptr[i] = 0.f;
-  }
   constexpr int NPL = HS / 64, ROW = 2 * HS;
   float q_t[MAXA], q_n[MAXA], q_g[MAXA];
   float hv_t[NPL], ha_t[NPL];
@@ -417,6 +469,11 @@ __device__ __forceinline__ bool ddqn_head_body(
     }
   }
   __syncthreads();
+  // zero the head-gradient region that head_wgrad accumulates into (stream-ordered); behind the block's global loads
+  // (at the top, the <256, 32> instantiation needed 36 bytes of scratch once its arguments came in a block)
+  if (zero_ptr != nullptr) {   // B blocks (a launch may carry extra side-job blocks)
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < zero_n; i += B * blockDim.x) zero_ptr[i] = 0.f;
+  }
   if (wv != 0) return false;
 #pragma unroll
   for (int j = 0; j < MAXA; ++j) {
@@ -536,6 +593,14 @@ __device__ __forceinline__ bool ddqn_head_body(
   }
   *ad_out = ad;
   return true;
+}
+
+template <int HS, int MAXA = HEAD_MAXA, bool MDQN = false, bool RESCALE = false>
+__device__ __forceinline__ bool ddqn_head_body(const HeadIO& io, int huber, float kappa, float* ad_out,
+                                               const HeadPart& hp, const MdqnTarget* mt = nullptr) {
+  return ddqn_head_rows<HS, MAXA, MDQN, RESCALE>(io.Hon, io.Htg, io.Pon, io.Ptg, io.act, io.rew, io.gam, io.isw, io.B,
+                                                 io.A, huber, kappa, io.grad_scale, io.td_abs, io.loss, io.q_out, io.dH,
+                                                 io.dhead, io.zero_ptr, io.zero_n, ad_out, io.lo, hp, mt, io.rescale_eps);
 }
 
 // head weight/bias gradients: dW[j][k] += sum_b dhead[b][j] * h[b][stream(j)][k]

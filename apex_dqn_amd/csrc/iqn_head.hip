@@ -35,12 +35,7 @@
 //
 // iqn_actor_head_kernel: one block per env row, the same logits, q = mean over the K samples
 // and the epsilon-greedy draw of actor_head_kernel (same counter-RNG words).
-#include "iqn_wgrad.h"     // (IQN_E; the weight-gradient body lives there)
-
-struct IqnEmbed {
-  const float* w;       // We [2 HS][64]
-  const float* b;       // be [2 HS]
-};
+#include "iqn_wgrad.h"     // (IQN_E, IqnEmbed, IqnActorArgs; the weight-gradient body lives there)
 
 struct IqnArgs {
   HeadIO io;            // Hon [2B], Htg [B]; dhead [B][(A + 1) N]
@@ -364,11 +359,6 @@ static inline bool iqn_embed_ok(const IqnEmbed& E) {
   return E.w != nullptr && E.b != nullptr && ((uintptr_t)E.w & 15) == 0;
 }
 
-static inline bool iqn_ptrs16(const HeadParams& P, const IqnEmbed& E) {
-  return (((uintptr_t)P.wv | (uintptr_t)P.wa) & 15) == 0 && P.bv != nullptr && P.ba != nullptr && P.wv != nullptr &&
-         P.wa != nullptr && iqn_embed_ok(E);
-}
-
 static int iqn_cu_count() {
   static int cus = 0;
   if (cus == 0) {
@@ -406,34 +396,17 @@ APEX_EXPORT int apex_iqn_head(IqnArgs a, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------ actors
-struct IqnActorArgs {
-  const bf16_t* H;      // [E][2 HS]
-  const bf16_t* H_lo;   // split mode: lo plane, or null
-  HeadParams P;
-  IqnEmbed Em;
-  int E, A, K, hidden;
-  int midpoint;         // 1: tau_k = (2 k + 1) / (2 K), no draw
-  const float* eps;
-  uint64_t seed;        // the epsilon-greedy draw's (actor_head_kernel's words)
-  const uint64_t* ctr;
-  uint64_t seed_q;
-  const int64_t* tau_ctr;   // t: c = 64 t + stream
-  int stream;
-  float* q_out;         // [E][A]
-  int32_t* a_out;       // [E]
-  float* tau_out;       // [E][K] or null
-};
-
 static inline size_t iqn_actor_lds(int A, int K) {
   const int J = (A + 1) * K, Jp = (J + 3) & ~3;
   return (size_t)((1 + DIST_NT / 64) * Jp + K * IQN_E + 64) * sizeof(float);
 }
 
-__global__ void __launch_bounds__(DIST_NT) iqn_actor_head_kernel(IqnActorArgs a) {
+__global__ void __launch_bounds__(DIST_NT) iqn_actor_head_kernel(IqnActorArgs ka) {
+  const ActorIO& a = ka.io;
   extern __shared__ __attribute__((aligned(16))) float iqn_smem[];
   constexpr int HS = DIST_HS, ROW = 2 * HS, NW = DIST_NT / 64;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int A = a.A, K = a.K, J = (A + 1) * K, Jp = (J + 3) & ~3;
+  const int A = a.A, K = ka.K, J = (A + 1) * K, Jp = (J + 3) & ~3;
   float* L = iqn_smem;               // [Jp]
   float* Pw = L + Jp;                // [NW][Jp]
   float* Cs = Pw + NW * Jp;          // [K][64]
@@ -442,9 +415,9 @@ __global__ void __launch_bounds__(DIST_NT) iqn_actor_head_kernel(IqnActorArgs a)
   if (tid < 64) {
     float tau = 0.f;
     if (tid < K) {
-      if (a.midpoint) tau = (2.f * (float)tid + 1.f) / (2.f * (float)K);
-      else tau = apex_uniform(a.seed_q, 64ull * (uint64_t)a.tau_ctr[0] + (uint64_t)a.stream, (uint64_t)e * 64ull + (uint64_t)tid);
-      if (a.tau_out != nullptr) a.tau_out[(int64_t)e * K + tid] = tau;
+      if (ka.midpoint) tau = (2.f * (float)tid + 1.f) / (2.f * (float)K);
+      else tau = apex_uniform(ka.seed_q, 64ull * (uint64_t)ka.tau_ctr[0] + (uint64_t)ka.stream, (uint64_t)e * 64ull + (uint64_t)tid);
+      if (ka.tau_out != nullptr) ka.tau_out[(int64_t)e * K + tid] = tau;
     }
     Ts[tid] = tau;
   }
@@ -454,7 +427,7 @@ __global__ void __launch_bounds__(DIST_NT) iqn_actor_head_kernel(IqnActorArgs a)
     ha += bf16_to_f32(a.H_lo[(int64_t)e * ROW + HS + tid]);
   }
   float wev[IQN_E], wea[IQN_E], bev, bea;
-  iqn_load_we(a.Em, tid, wev, wea, bev, bea);
+  iqn_load_we(ka.Em, tid, wev, wea, bev, bea);
   __syncthreads();
   iqn_fill_cos(Ts, K, Cs, nullptr, tid);
   __syncthreads();
@@ -473,13 +446,12 @@ __global__ void __launch_bounds__(DIST_NT) iqn_actor_head_kernel(IqnActorArgs a)
   if (lane == 0) dist_actor_draw(best, e, A, a.eps, a.seed, a.ctr, a.a_out);
 }
 
-APEX_EXPORT int apex_iqn_actor_head(IqnActorArgs a, hipStream_t st) {
-  if (a.A < 1 || a.A > HEAD_MAXA || a.E < 1 || a.K < 1 || a.K > 64 || a.hidden != DIST_HS)
+APEX_EXPORT int apex_iqn_actor_head(IqnActorArgs ka, hipStream_t st) {
+  const ActorIO& a = ka.io;
+  if (!actor_io_ok(a) || ka.K < 1 || ka.K > 64 || a.hidden != DIST_HS || !iqn_embed_ok(ka.Em) ||
+      (!ka.midpoint && ka.tau_ctr == nullptr))
     return (int)hipErrorInvalidValue;
-  if (!iqn_ptrs16(a.P, a.Em) || a.H == nullptr || a.eps == nullptr || a.q_out == nullptr || a.a_out == nullptr)
-    return (int)hipErrorInvalidValue;
-  if (!a.midpoint && a.tau_ctr == nullptr) return (int)hipErrorInvalidValue;
-  const size_t lds = iqn_actor_lds(a.A, a.K);
+  const size_t lds = iqn_actor_lds(a.A, ka.K);
   if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
   static size_t lds_set = 64 * 1024;      // raised once per size: not again inside a captured step
   if (lds > lds_set) {
@@ -488,6 +460,6 @@ APEX_EXPORT int apex_iqn_actor_head(IqnActorArgs a, hipStream_t st) {
     if (e != hipSuccess) return (int)e;
     lds_set = lds;
   }
-  iqn_actor_head_kernel<<<a.E, DIST_NT, lds, st>>>(a);
+  iqn_actor_head_kernel<<<a.E, DIST_NT, lds, st>>>(ka);
   APEX_CHECK_LAUNCH();
 }

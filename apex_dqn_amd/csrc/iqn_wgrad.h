@@ -28,6 +28,23 @@ struct IqnWgArgs {
   float* part;          // [IQN_WG_S][2 HS 64 + 2 HS] partials of G[wtau | btau]
 };
 
+// One net's cosine embedding and iqn_actor_head_kernel's arguments: here, where apex_abi_struct_sizes sees them
+struct IqnEmbed {
+  const float* w;       // We [2 HS][64]
+  const float* b;       // be [2 HS]
+};
+
+struct IqnActorArgs {
+  ActorIO io;           // seed / ctr: the epsilon-greedy draw's (actor_head_kernel's words)
+  IqnEmbed Em;
+  int K, midpoint;      // midpoint 1: tau_k = (2 k + 1) / (2 K), no draw
+  uint64_t seed_q;
+  const int64_t* tau_ctr;   // t: c = 64 t + stream
+  int stream;
+  float* tau_out;       // [E][K] or null
+};
+static_assert(std::is_standard_layout_v<IqnActorArgs> && std::is_trivially_copyable_v<IqnActorArgs>);
+
 static inline int iqn_wgrad_blocks(int A) {
   return IQN_WG_S * (2 * DIST_HS / IQN_WG_CT) + (1 + (A + IQN_WG_AT - 1) / IQN_WG_AT) * (DIST_HS / 64);
 }

@@ -41,25 +41,10 @@ __global__ void __launch_bounds__(192) mdqn_head_kernel(MdqnArgs ka) {
   const HeadIO& a = ka.io;
   float ad;
   const MdqnTarget mt{ka.alpha, ka.tau, ka.clip, ka.aux};
-  const bool w0 = ddqn_head_body<HS, MAXA, true>(a.Hon, a.Htg, a.Pon, a.Ptg, a.act, a.rew, a.gam, a.isw, a.B, a.A, ka.huber,
-                                                 ka.kappa, a.grad_scale, a.td_abs, a.loss, a.q_out, a.dH, a.dhead, a.zero_ptr,
-                                                 a.zero_n, &ad, a.lo, ka.hp, &mt);
+  const bool w0 = ddqn_head_body<HS, MAXA, true>(a, ka.huber, ka.kappa, &ad, ka.hp, &mt);
   // batch-max IS normalisation: block 0's second wave (csrc/ddqn_head.hip, same semantics)
-  if (!w0 && (a.isn.out != nullptr || a.isn.valid_count != nullptr) && blockIdx.x == 0 && (threadIdx.x >> 6) == 1) {
-    float m = 0.f;
-    int nv = 0;
-    for (int i = threadIdx.x & 63; i < a.B; i += 64) {
-      m = fmaxf(m, a.isw[i]);
-      nv += a.isw[i] > 0.f ? 1 : 0;
-    }
-    m = wave_max(m);
-    nv = wave_sum(nv);
-    if ((threadIdx.x & 63) == 0) {
-      const float ws = a.isn.wscale != nullptr ? a.isn.wscale[0] : 1.f;
-      if (a.isn.out != nullptr) a.isn.out[0] = ws > 0.f ? (double)m / (double)ws : 0.0;
-      if (a.isn.valid_count != nullptr) atomicAdd(a.isn.valid_count, (unsigned long long)nv);
-    }
-  }
+  if (!w0 && (a.isn.out != nullptr || a.isn.valid_count != nullptr) && blockIdx.x == 0 && (threadIdx.x >> 6) == 1)
+    head_is_norm(a, threadIdx.x & 63);
 }
 
 APEX_EXPORT int apex_mdqn_head(MdqnArgs a, hipStream_t st) {

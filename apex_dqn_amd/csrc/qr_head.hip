@@ -152,40 +152,28 @@ APEX_EXPORT int apex_qr_head(QRArgs a, hipStream_t st) {
 
 // Actor side: q = mean of the quantiles + epsilon-greedy, one wave per env row (four per
 // block; a wave past E repeats the last row and stores nothing).
-__global__ void __launch_bounds__(256) qr_actor_head_kernel(const bf16_t* __restrict__ H, HeadParams P, int E, int A,
-                                                            int N, const float* __restrict__ eps, uint64_t seed,
-                                                            const uint64_t* __restrict__ ctr,
-                                                            float* __restrict__ q_out, int32_t* __restrict__ a_out,
-                                                            const bf16_t* __restrict__ H_lo) {
+__global__ void __launch_bounds__(256) qr_actor_head_kernel(QRActorArgs ka) {
+  const ActorIO& a = ka.io;
   extern __shared__ __attribute__((aligned(16))) float qr_smem[];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int AN = A * N, J = N + AN, Jp = (J + 3) & ~3;
-  const int e_raw = blockIdx.x * 4 + wv;
-  const bool live = e_raw < E;
-  const int e = min(e_raw, E - 1);
-  float* L = qr_smem + wv * Jp;
-  dist_actor_logits(H, H_lo, P, e, A, N, lane, L);
-  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int A = a.A, N = ka.N;
+  int e; bool live;
+  const float* L = dist_actor_open(a, N, qr_smem, lane, threadIdx.x >> 6, e, live);
   const float invN = 1.0f / (float)N;
-  const DistRow r = dist_row(L, P, A, N, lane);
+  const DistRow r = dist_row(L, a.P, A, N, lane);
   int best = 0;
   float bq = -3.4e38f;
   for (int j = 0; j < A; ++j) {
     const float q = wave_sum_dpp(qr_theta(r, j, N, lane)) * invN;
     if (q > bq) { bq = q; best = j; }
-    if (live && lane == 0) q_out[(int64_t)e * A + j] = q;
+    if (live && lane == 0) a.q_out[(int64_t)e * A + j] = q;
   }
-  if (live && lane == 0) dist_actor_draw(best, e, A, eps, seed, ctr, a_out);
+  if (live && lane == 0) dist_actor_draw(best, e, A, a.eps, a.seed, a.ctr, a.a_out);
 }
 
-APEX_EXPORT int apex_qr_actor_head(const bf16_t* H, HeadParams P, int E, int A, int N, const float* eps, uint64_t seed,
-                                   const uint64_t* ctr, float* q_out, int32_t* a_out, int hidden,
-                                   const bf16_t* H_lo, hipStream_t st) {
-  if (A < 1 || A > HEAD_MAXA || E < 1 || N < 2 || N > 64 || hidden != DIST_HS) return (int)hipErrorInvalidValue;
-  if ((((uintptr_t)P.wv | (uintptr_t)P.wa) & 15) || (((uintptr_t)H | (uintptr_t)H_lo) & 7))
-    return (int)hipErrorInvalidValue;
-  const int J = (A + 1) * N, Jp = (J + 3) & ~3;
-  qr_actor_head_kernel<<<(E + 3) / 4, 256, (size_t)4 * Jp * sizeof(float), st>>>(H, P, E, A, N, eps, seed, ctr, q_out,
-                                                                                 a_out, H_lo);
+APEX_EXPORT int apex_qr_actor_head(QRActorArgs a, hipStream_t st) {
+  size_t lds = 0;
+  if (!dist_actor_args_ok(a.io, a.N, &lds)) return (int)hipErrorInvalidValue;
+  qr_actor_head_kernel<<<(a.io.E + 3) / 4, 256, lds, st>>>(a);
   APEX_CHECK_LAUNCH();
 }

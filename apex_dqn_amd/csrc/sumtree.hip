@@ -14,7 +14,7 @@
 // Duplicate indices in one update batch: last occurrence wins (deterministic).
 #include "apex_common.h"
 #include <stdlib.h>
-#include "head_common.h"
+#include "ddqn_args.h"
 #include "igemm_wgrad.h"
 #include "rmsprop_common.h"
 #include "pack_rows.h"
@@ -780,13 +780,14 @@ APEX_EXPORT int apex_fill16(void* p, int64_t n, int nt, hipStream_t st) {
   APEX_CHECK_LAUNCH();
 }
 
-APEX_EXPORT int apex_abi_version() { return 16; }
+APEX_EXPORT int apex_abi_version() { return 17; }
 
 // sizeof of every block that crosses the ABI by value in the launchers below, in the order of ops/_lib.py
 // ABI_STRUCTS (host only): a mirror that drifts by a field would otherwise only shift kernarg contents
 APEX_EXPORT int apex_abi_struct_sizes(int* out, int cap) {
   const int sz[] = {(int)sizeof(RmspropArgs), (int)sizeof(SampleArgs), (int)sizeof(RmsSegs), (int)sizeof(TreeUpdArgs),
-                    (int)sizeof(HeadWgArgs), (int)sizeof(IqnWgArgs), (int)sizeof(WgradDesc)};
+                    (int)sizeof(HeadWgArgs), (int)sizeof(IqnWgArgs), (int)sizeof(WgradDesc), (int)sizeof(DdqnArgs),
+                    (int)sizeof(ActorIO), (int)sizeof(C51ActorArgs), (int)sizeof(QRActorArgs), (int)sizeof(IqnActorArgs)};
   const int n = (int)(sizeof(sz) / sizeof(sz[0]));
   for (int i = 0; i < n && i < cap; ++i) out[i] = sz[i];
   return n;

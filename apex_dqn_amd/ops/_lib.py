@@ -58,7 +58,7 @@ class IsNorm(ctypes.Structure):
 
 
 class HeadIO(ctypes.Structure):
-    """What every struct-argument loss head takes (``HeadIO``, csrc/head_common.h): the first member ``io`` of
+    """What every loss head takes (``HeadIO``, csrc/head_common.h): the first member ``io`` of ``DdqnArgs``,
     ``C51Args``, ``QRArgs``, ``IqnArgs`` and ``MdqnArgs``."""
     _fields_ = [("Hon", c_p), ("Htg", c_p), ("Pon", HeadParams), ("Ptg", HeadParams), ("act", c_p), ("rew", c_p),
                 ("gam", c_p), ("isw", c_p), ("B", c_i), ("A", c_i), ("hidden", c_i), ("grad_scale", c_f),
@@ -77,7 +77,7 @@ class QRArgs(ctypes.Structure):
 
 
 class IqnEmbed(ctypes.Structure):
-    """The cosine embedding of one net (``IqnEmbed``, csrc/iqn_head.hip): ``We (2 HS, 64)``, ``be (2 HS,)``."""
+    """The cosine embedding of one net (``IqnEmbed``, csrc/iqn_wgrad.h): ``We (2 HS, 64)``, ``be (2 HS,)``."""
     _fields_ = [("w", c_p), ("b", c_p)]
 
 
@@ -95,11 +95,26 @@ class IqnWgArgs(ctypes.Structure):
                 ("part", c_p)]
 
 
+class ActorIO(ctypes.Structure):
+    """What every actor head takes (``ActorIO``, csrc/head_common.h): the scalar head alone, else first member ``io``."""
+    _fields_ = [("H", c_p), ("H_lo", c_p), ("P", HeadParams), ("E", c_i), ("A", c_i), ("hidden", c_i), ("eps", c_p),
+                ("seed", c_u64), ("ctr", c_p), ("q_out", c_p), ("a_out", c_p)]
+
+
+class C51ActorArgs(ctypes.Structure):
+    """Arguments of ``c51_actor_head_kernel`` (``C51ActorArgs``, csrc/dist_head.h)."""
+    _fields_ = [("io", ActorIO), ("N", c_i), ("vmin", c_f), ("vmax", c_f)]
+
+
+class QRActorArgs(ctypes.Structure):
+    """Arguments of ``qr_actor_head_kernel`` (``QRActorArgs``, csrc/dist_head.h)."""
+    _fields_ = [("io", ActorIO), ("N", c_i)]
+
+
 class IqnActorArgs(ctypes.Structure):
-    """Arguments of ``iqn_actor_head_kernel`` (``IqnActorArgs``, csrc/iqn_head.hip)."""
-    _fields_ = [("H", c_p), ("H_lo", c_p), ("P", HeadParams), ("Em", IqnEmbed), ("E", c_i), ("A", c_i), ("K", c_i),
-                ("hidden", c_i), ("midpoint", c_i), ("eps", c_p), ("seed", c_u64), ("ctr", c_p), ("seed_q", c_u64),
-                ("tau_ctr", c_p), ("stream", c_i), ("q_out", c_p), ("a_out", c_p), ("tau_out", c_p)]
+    """Arguments of ``iqn_actor_head_kernel`` (``IqnActorArgs``, csrc/iqn_wgrad.h)."""
+    _fields_ = [("io", ActorIO), ("Em", IqnEmbed), ("K", c_i), ("midpoint", c_i), ("seed_q", c_u64), ("tau_ctr", c_p),
+                ("stream", c_i), ("tau_out", c_p)]
 
 
 class MdqnArgs(ctypes.Structure):
@@ -193,6 +208,11 @@ class C2dPack(ctypes.Structure):
     _fields_ = [("w", c_p), ("w_lo", c_p), ("out", c_p)]
 
 
+class DdqnArgs(ctypes.Structure):
+    """Arguments of the scalar head kernel (``DdqnArgs``, csrc/ddqn_args.h)."""
+    _fields_ = [("io", HeadIO), ("huber", c_i), ("kappa", c_f), ("hp", HeadPart), ("pk", C2dPack)]
+
+
 class ConvDesc(ctypes.Structure):
     """Implicit-GEMM forward/dgrad problem (mirrors ``ConvDesc`` in csrc/conv_mfma.hip)."""
     _fields_ = [("x", c_p), ("frame_slots", c_p), ("w", c_p), ("bias", c_p), ("y", c_p), ("mask", c_p),
@@ -265,15 +285,14 @@ _SIGS = {
     "apex_spin_hold": ([c_i, c_i, c_i, c_p, c_p], c_i),
     "apex_grad_finalize": ([FinalizeDesc, c_p], c_i),
     "apex_norm_total": ([c_p, c_i, c_p, c_p], c_i),
-    "apex_ddqn_head": ([c_p, c_p, HeadParams, HeadParams, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p,
-                        c_p, c_p, c_p, c_p, c_p, c_i, c_i, HeadLo, HeadPart, C2dPack, IsNorm, c_f, c_p], c_i),
+    "apex_ddqn_head": ([DdqnArgs, c_p], c_i),
     "apex_value_rescale_probe": ([c_p, c_p, c_p, c_f, c_p, c_i64, c_p], c_i),
     "apex_opt_sample": ([RmspropArgs, SampleArgs, c_p, c_p], c_i),
     "apex_head_wgrad_prio": ([HeadWgArgs, TreeUpdArgs, c_p, c_p, c_p, c_i, c_i, c_p, c_i64, c_p], c_i),
     "apex_fc_wgrad_head_prio": ([WgradDesc, HeadWgArgs, TreeUpdArgs, c_p], c_i),
     "apex_head_wgrad": ([HeadWgArgs, c_p], c_i),
     "apex_c51_head": ([C51Args, c_p], c_i),
-    "apex_c51_actor_head": ([c_p, HeadParams, c_i, c_i, c_i, c_f, c_f, c_p, c_u64, c_p, c_p, c_p, c_i, c_p, c_p], c_i),
+    "apex_c51_actor_head": ([C51ActorArgs, c_p], c_i),
     "apex_qr_head": ([QRArgs, c_p], c_i),
     "apex_mdqn_head": ([MdqnArgs, c_p], c_i),
     "apex_iqn_head": ([IqnArgs, c_p], c_i),
@@ -281,8 +300,8 @@ _SIGS = {
     "apex_iqn_wgrad_part_floats": ([], c_i),
     "apex_iqn_wgrad_prio": ([IqnWgArgs, TreeUpdArgs, c_p], c_i),
     "apex_iqn_actor_head": ([IqnActorArgs, c_p], c_i),
-    "apex_qr_actor_head": ([c_p, HeadParams, c_i, c_i, c_i, c_p, c_u64, c_p, c_p, c_p, c_i, c_p, c_p], c_i),
-    "apex_actor_head": ([c_p, HeadParams, c_i, c_i, c_p, c_u64, c_p, c_p, c_p, c_i, c_p, c_p], c_i),
+    "apex_qr_actor_head": ([QRActorArgs, c_p], c_i),
+    "apex_actor_head": ([ActorIO, c_p], c_i),
     "apex_conv1_s2d_fwd": ([Conv1S2DDesc, c_i, c_p], c_i),
     "apex_conv1_wgrad_img": ([Conv1WgDesc, c_i, c_p], c_i),
     "apex_slab_reduce": ([c_p, c_i, c_i64, c_f, c_p, c_p, c_i, c_p, c_i, c_i, c_p], c_i),
@@ -314,10 +333,11 @@ def _declare(lib: ctypes.CDLL) -> None:
     conv_sigs.declare(lib)
 
 
-ABI_VERSION = 16    # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
+ABI_VERSION = 17    # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
 SQNORM_PARTIALS = 1024   # what apex_grad_sqnorm_partials writes (csrc/rmsprop_common.h SQNORM_NPART)
 # the blocks that cross the ABI by value, in the order of csrc/sumtree.hip apex_abi_struct_sizes()
-ABI_STRUCTS = (RmspropArgs, SampleArgs, RmsSegs, TreeUpdArgs, HeadWgArgs, IqnWgArgs, WgradDesc)
+ABI_STRUCTS = (RmspropArgs, SampleArgs, RmsSegs, TreeUpdArgs, HeadWgArgs, IqnWgArgs, WgradDesc, DdqnArgs, ActorIO,
+               C51ActorArgs, QRActorArgs, IqnActorArgs)
 
 
 def check_struct_sizes(sizes, where: str = "libapex_kernels") -> None:

@@ -997,19 +997,16 @@ class HipBackend(TorchBackend):
 
     def head(self, Hon, Htg, Pon, Ptg, act, rew, gam, isw, huber, kappa, grad_scale, td_abs, loss, dH,
              dhead, q_out=None, zero=None, lo=None, isn=None, rescale_eps=None):
-        B = act.shape[0]
-        A = Pon["wa"].shape[0]
-        args = (Hon.data_ptr(), Htg.data_ptr(), self._hp(Pon), self._hp(Ptg), act.data_ptr(), rew.data_ptr(),
-                gam.data_ptr(), _lib.ptr(isw), B, A, int(huber), float(kappa), float(grad_scale),
-                td_abs.data_ptr(), loss.data_ptr(), _lib.ptr(q_out), dH.data_ptr(), dhead.data_ptr(),
-                _lib.ptr(zero), 0 if zero is None else zero.numel(), Pon["wv"].numel())
-        hl = _lib.head_lo(*(lo if lo is not None else (None, None, None)))
-        hp, pk = _lib.HeadPart(), _lib.C2dPack()
+        a = _lib.DdqnArgs()
+        self._head_io(a.io, Hon, Htg, Pon, Ptg, act, rew, gam, isw, Pon["wa"].shape[0], Pon["wv"].numel(), grad_scale,
+                      td_abs, loss, dH, dhead, q_out, zero, lo, isn, rescale_eps)
+        a.huber, a.kappa = int(huber), float(kappa)
+        hp, pk = a.hp, a.pk
         fp = getattr(self, "_fc_part", None)
         if fp is not None:
             # the deferred fc epilogue: h rows [0, B) (+ lo plane) are written by this launch
             self._fc_part = None
-            assert fp["out"].data_ptr() == Hon.data_ptr() and fp["two_b"] == 2 * B
+            assert fp["out"].data_ptr() == Hon.data_ptr() and fp["two_b"] == 2 * a.io.B
             hp.part, hp.zstride, hp.nz = fp["part"].data_ptr(), int(fp["zstride"]), int(fp["nz"])
             hp.bias_on, hp.bias_tg, hp.two_b = fp["b"].data_ptr(), fp["b2"].data_ptr(), int(fp["two_b"])
             hp.hon, hp.hon_lo = Hon.data_ptr(), _lib.ptr(None if lo is None else lo[0])
@@ -1017,8 +1014,7 @@ class HipBackend(TorchBackend):
                 pk.w, pk.w_lo = fp["c2d"][0].data_ptr(), _lib.ptr(fp["c2d"][1])
                 pk.out = C.c2d_wfrag_buffer(self.ws, Hon.device).data_ptr()
                 self._c2d_packed = (fp["c2d"][0].data_ptr(), _lib.ptr(fp["c2d"][1]))
-        _lib.check(self.lib.apex_ddqn_head(*args, hl, hp, pk, _lib.is_norm(isn), _lib.rescale_eps_arg(rescale_eps),
-                                           _lib.stream_ptr()), "ddqn_head")
+        _lib.check(self.lib.apex_ddqn_head(a, _lib.stream_ptr()), "ddqn_head")
 
     def value_rescale_probe(self, y, R, Gamma, eps, out) -> None:
         """csrc/ddqn_head.hip ``value_rescale_probe_kernel``: ``out[i] = T(R[i], Gamma[i], y[i], eps)`` of
@@ -1072,12 +1068,18 @@ class HipBackend(TorchBackend):
         assert dhead.shape == (B, (A + 1) * N) and dhead.is_contiguous()
         _lib.check(self.lib.apex_c51_head(a, _lib.stream_ptr()), "c51_head")
 
+    def _actor_io(self, io, H, P, eps, ctr, seed, q_out, a_out, H_lo) -> None:
+        """Fill ``io``, the block every actor head takes (``_lib.ActorIO``); ``E`` and ``A`` are ``q_out``'s."""
+        io.H, io.H_lo, io.P = H.data_ptr(), _lib.ptr(H_lo), self._hp(P)
+        (io.E, io.A), io.hidden = q_out.shape, P["wv"].shape[-1]
+        io.eps, io.seed, io.ctr = eps.data_ptr(), int(seed), ctr.data_ptr()
+        io.q_out, io.a_out = q_out.data_ptr(), a_out.data_ptr()
+
     def c51_actor_head(self, H, P, eps, ctr, seed, num_atoms, v_min, v_max, q_out, a_out, H_lo=None):
-        E, A = q_out.shape
-        _lib.check(self.lib.apex_c51_actor_head(H.data_ptr(), self._hp(P), E, A, int(num_atoms), float(v_min),
-                                                float(v_max), eps.data_ptr(), int(seed), ctr.data_ptr(),
-                                                q_out.data_ptr(), a_out.data_ptr(), P["wv"].shape[-1],
-                                                _lib.ptr(H_lo), _lib.stream_ptr()), "c51_actor_head")
+        a = _lib.C51ActorArgs()
+        self._actor_io(a.io, H, P, eps, ctr, seed, q_out, a_out, H_lo)
+        a.N, a.vmin, a.vmax = int(num_atoms), float(v_min), float(v_max)
+        _lib.check(self.lib.apex_c51_actor_head(a, _lib.stream_ptr()), "c51_actor_head")
 
     def qr_head(self, Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, kappa, grad_scale, td_abs, loss,
                 dH, dhead, q_out=None, zero=None, lo=None, isn=None, rescale_eps=None):
@@ -1093,10 +1095,10 @@ class HipBackend(TorchBackend):
         _lib.check(self.lib.apex_qr_head(a, _lib.stream_ptr()), "qr_head")
 
     def qr_actor_head(self, H, P, eps, ctr, seed, num_atoms, q_out, a_out, H_lo=None):
-        E, A = q_out.shape
-        _lib.check(self.lib.apex_qr_actor_head(H.data_ptr(), self._hp(P), E, A, int(num_atoms), eps.data_ptr(),
-                                               int(seed), ctr.data_ptr(), q_out.data_ptr(), a_out.data_ptr(),
-                                               P["wv"].shape[-1], _lib.ptr(H_lo), _lib.stream_ptr()), "qr_actor_head")
+        a = _lib.QRActorArgs()
+        self._actor_io(a.io, H, P, eps, ctr, seed, q_out, a_out, H_lo)
+        a.N = int(num_atoms)
+        _lib.check(self.lib.apex_qr_actor_head(a, _lib.stream_ptr()), "qr_actor_head")
 
     @staticmethod
     def _embed(E):
@@ -1173,12 +1175,10 @@ class HipBackend(TorchBackend):
         """csrc/iqn_head.hip ``iqn_actor_head_kernel``."""
         a = _lib.IqnActorArgs()
         n_e, A = q_out.shape
-        a.H, a.H_lo, a.P, a.Em = H.data_ptr(), _lib.ptr(H_lo), self._hp(P), self._embed(E)
-        a.E, a.A, a.K, a.hidden, a.midpoint = n_e, A, int(num_samples), P["wv"].shape[-1], int(bool(midpoint))
-        a.eps, a.seed, a.ctr = eps.data_ptr(), int(seed), ctr.data_ptr()
-        a.seed_q, a.tau_ctr, a.stream = int(seed_q), _lib.ptr(tau_ctr), int(stream)
-        a.q_out, a.a_out, a.tau_out = q_out.data_ptr(), a_out.data_ptr(), _lib.ptr(tau_out)
-        assert H.shape[0] >= n_e and H.shape[1] == 2 * a.hidden and H.is_contiguous() and P["wa"].shape[0] == A
+        self._actor_io(a.io, H, P, eps, ctr, seed, q_out, a_out, H_lo)
+        a.Em, a.K, a.midpoint = self._embed(E), int(num_samples), int(bool(midpoint))
+        a.seed_q, a.tau_ctr, a.stream, a.tau_out = int(seed_q), _lib.ptr(tau_ctr), int(stream), _lib.ptr(tau_out)
+        assert H.shape[0] >= n_e and H.shape[1] == 2 * a.io.hidden and H.is_contiguous() and P["wa"].shape[0] == A
         assert eps.numel() >= n_e and a_out.numel() >= n_e and q_out.is_contiguous()
         assert tau_ctr is None or tau_ctr.dtype == torch.int64
         assert tau_out is None or (tau_out.shape == (n_e, a.K) and tau_out.is_contiguous())
@@ -1219,10 +1219,9 @@ class HipBackend(TorchBackend):
         return nslots
 
     def actor_head(self, H, P, eps, ctr, seed, q_out, a_out, H_lo=None):
-        E, A = q_out.shape
-        _lib.check(self.lib.apex_actor_head(H.data_ptr(), self._hp(P), E, A, eps.data_ptr(), int(seed),
-                                            ctr.data_ptr(), q_out.data_ptr(), a_out.data_ptr(),
-                                            P["wv"].numel(), _lib.ptr(H_lo), _lib.stream_ptr()), "actor_head")
+        a = _lib.ActorIO()
+        self._actor_io(a, H, P, eps, ctr, seed, q_out, a_out, H_lo)
+        _lib.check(self.lib.apex_actor_head(a, _lib.stream_ptr()), "actor_head")
 
     @staticmethod
     def _opt_sched(opt) -> "_lib.OptSched":

@@ -98,7 +98,8 @@ def test_struct_size_mismatch_names_the_struct():
     from apex_dqn_amd.ops import _lib
     good = [ctypes.sizeof(c) for c in _lib.ABI_STRUCTS]
     assert [c.__name__ for c in _lib.ABI_STRUCTS] == ["RmspropArgs", "SampleArgs", "RmsSegs", "TreeUpdArgs",
-                                                      "HeadWgArgs", "IqnWgArgs", "WgradDesc"]
+                                                      "HeadWgArgs", "IqnWgArgs", "WgradDesc", "DdqnArgs", "ActorIO",
+                                                      "C51ActorArgs", "QRActorArgs", "IqnActorArgs"]
     _lib.check_struct_sizes(good)
     for k, cls in enumerate(_lib.ABI_STRUCTS):
         bad = list(good)
@@ -107,3 +108,16 @@ def test_struct_size_mismatch_names_the_struct():
             _lib.check_struct_sizes(bad)
     with pytest.raises(RuntimeError, match="argument blocks"):
         _lib.check_struct_sizes(good[:-1])
+
+
+def test_shared_blocks_lead_their_argument_blocks():
+    """Every block that begins with a ``HeadIO`` / ``ActorIO`` has it as its member ``io`` at offset 0 (the
+    kernels read it as ``ka.io``), and is at least as large as it."""
+    from apex_dqn_amd.ops import _lib
+    for shared, blocks in ((_lib.HeadIO, (_lib.DdqnArgs, _lib.C51Args, _lib.QRArgs, _lib.IqnArgs, _lib.MdqnArgs)),
+                           (_lib.ActorIO, (_lib.C51ActorArgs, _lib.QRActorArgs, _lib.IqnActorArgs))):
+        for cls in blocks:
+            name, typ = cls._fields_[0][:2]
+            assert (name, typ) == ("io", shared), cls.__name__
+            assert cls.io.offset == 0 and cls.io.size == ctypes.sizeof(shared), cls.__name__
+            assert ctypes.sizeof(cls) >= ctypes.sizeof(shared) and ctypes.sizeof(cls) % 8 == 0, cls.__name__

@@ -257,6 +257,71 @@ def test_is_norm_without_weights_is_refused():
     torch.cuda.synchronize()
 
 
+# ------------------------------------------------------- what the launcher refuses
+def _spoil_null(field):
+    def f(io):
+        setattr(io, field, None)
+    return f
+
+
+def _spoil_pon_wa(io):
+    io.Pon.wa = None
+
+
+def _spoil_hon(io):
+    io.Hon += 4
+
+
+def _spoil_actions(io):
+    io.A = 33
+
+
+def _spoil_eps(io):
+    io.rescale_eps = 1.5
+
+
+def _spoil_rescaled_256(io):
+    io.rescale_eps, io.hidden = 0.01, 256
+
+
+@pytest.mark.parametrize("spoil", [None, _spoil_null("td_abs"), _spoil_null("dhead"), _spoil_pon_wa, _spoil_hon,
+                                   _spoil_actions, _spoil_eps, _spoil_rescaled_256],
+                         ids=["control", "null_td_abs", "null_dhead", "null_Pon_wa", "Hon_plus_4_bytes", "A_33",
+                              "rescale_eps_1.5", "rescaled_hidden_256"])
+def test_spoiled_argument_block_is_refused_and_writes_nothing(spoil):
+    """B = 2, A = 3, hidden 512: a ``DdqnArgs`` filled by the backend's own ``_head_io`` launches (the control:
+    every output leaves its sentinel); with one field spoiled ``apex_ddqn_head`` returns an error and every
+    output, the zero region included, keeps its sentinel."""
+    from apex_dqn_amd.ops import _lib
+    from apex_dqn_amd.ops.fused_ops import HipBackend
+    B, A, HS = 2, 3, 512
+    fx = F.fixture(B, A, HS, False)
+    c = F.case_inputs(fx, "plain")
+    be = HipBackend()
+    Pon, Ptg = {k: _dev(v) for k, v in c["Pon"].items()}, {k: _dev(v) for k, v in c["Ptg"].items()}
+    ins = [_dev(fx["Hon"]), _dev(fx["Htg"]), Pon, Ptg, _dev(c["act"]), _dev(c["rew"]), _dev(c["gam"]), _dev(c["isw"])]
+    out = dict(td=torch.full((B,), -1.0, device=DEV), loss=torch.full((B,), -1.0, device=DEV),
+               dH=torch.full((B, 2 * HS), 9.0, device=DEV, dtype=torch.bfloat16), dhead=torch.full((B, A + 1), 7.0, device=DEV),
+               q=torch.full((B, A), 11.0, device=DEV), zero=torch.full((HS + 1 + A * HS + A,), 3.0, device=DEV))
+    before = {k: v.clone() for k, v in out.items()}
+    a = _lib.DdqnArgs()
+    be._head_io(a.io, *ins, A, HS, 1.0 / B, out["td"], out["loss"], out["dH"], out["dhead"], out["q"], out["zero"], None,
+                None)
+    a.huber, a.kappa = int(c["huber"]), float(c["kappa"])
+    if spoil is not None:
+        spoil(a.io)
+    rc = be.lib.apex_ddqn_head(a, _lib.stream_ptr())
+    torch.cuda.synchronize()
+    if spoil is None:
+        assert rc == 0
+        assert all(not bool((out[k] == before[k]).any()) for k in ("td", "loss", "dhead", "q"))
+        assert bool((out["zero"] == 0).all())
+        return
+    assert rc != 0
+    for k in out:
+        assert torch.equal(out[k], before[k]), k
+
+
 # ---------------------------------------------------------------- head_wgrad alone
 @pytest.mark.parametrize("HS", F.HIDDEN)
 @pytest.mark.parametrize("split", [False, True])
@@ -459,3 +524,64 @@ def test_actor_head_consecutive_counters_differ():
         acts.append(want)
     assert not np.array_equal(acts[0], acts[1])
     assert len(set(acts[0].tolist())) == A               # 257 uniform draws reach all 18 actions
+
+
+# --------------------------------------------- what the four actor launchers refuse
+def _actor_block(be, kind, H, eps, ctr, q, a_out):
+    """The argument block of actor launcher ``kind`` at N = 2 (IQN: two midpoint fractions), filled by the
+    backend's own ``_actor_io``; (launcher, block, its ``ActorIO``, the tensors it points to)."""
+    from apex_dqn_amd.ops import _lib
+    A, HS, N = q.shape[1], H.shape[1] // 2, 2
+    nv = N if kind in ("c51", "qr") else 1
+    g = torch.Generator().manual_seed(3)
+    P = {"wv": torch.randn(nv, HS, generator=g) * 0.05, "bv": torch.randn(nv, generator=g),
+         "wa": torch.randn(A * nv, HS, generator=g) * 0.05, "ba": torch.randn(A * nv, generator=g)}
+    keep = [{k: _dev(v) for k, v in P.items()}]
+    blk = {"scalar": _lib.ActorIO, "c51": _lib.C51ActorArgs, "qr": _lib.QRActorArgs, "iqn": _lib.IqnActorArgs}[kind]()
+    io = blk if kind == "scalar" else blk.io
+    be._actor_io(io, H, keep[0], eps, ctr, 5, q, a_out, None)
+    if kind == "c51":
+        blk.N, blk.vmin, blk.vmax = N, -2.0, 2.0
+    elif kind == "qr":
+        blk.N = N
+    elif kind == "iqn":
+        keep.append({"wtau": _dev(torch.randn(2 * HS, 64, generator=g) * 0.05), "btau": _dev(torch.randn(2 * HS, generator=g))})
+        blk.Em, blk.K, blk.midpoint = be._embed(keep[1]), N, 1
+    fn = {"scalar": be.lib.apex_actor_head, "c51": be.lib.apex_c51_actor_head, "qr": be.lib.apex_qr_actor_head,
+          "iqn": be.lib.apex_iqn_actor_head}[kind]
+    return fn, blk, io, keep
+
+
+def _spoil_envs(io):
+    io.E = 0
+
+
+def _spoil_h(io):
+    io.H += 4
+
+
+@pytest.mark.parametrize("spoil", [None, _spoil_envs, _spoil_actions, _spoil_null("eps"), _spoil_null("a_out"), _spoil_h],
+                         ids=["control", "E_0", "A_33", "null_eps", "null_a_out", "H_plus_4_bytes"])
+@pytest.mark.parametrize("kind", ["scalar", "c51", "qr", "iqn"])
+def test_spoiled_actor_block_is_refused_and_a_out_untouched(kind, spoil):
+    """E = 3, A = 3, N = 2, every actor launcher: the block filled by ``_actor_io`` launches (the control: q_out
+    and a_out leave their sentinels, the actions are in range); with one field spoiled the launcher returns an
+    error and a_out (and q_out) keep their sentinels."""
+    from apex_dqn_amd.ops import _lib
+    from apex_dqn_amd.ops.fused_ops import HipBackend
+    E, A, HS = 3, 3, 512
+    be = HipBackend()
+    H = _dev(F.actor_fixture(E, A, HS)["H"])
+    eps, ctr = torch.full((E,), 0.5, device=DEV), torch.tensor([7], dtype=torch.int64, device=DEV)
+    q, a_out = torch.full((E, A), 11.0, device=DEV), torch.full((E,), -3, dtype=torch.int32, device=DEV)
+    fn, blk, io, keep = _actor_block(be, kind, H, eps, ctr, q, a_out)
+    if spoil is not None:
+        spoil(io)
+    rc = fn(blk, _lib.stream_ptr())
+    torch.cuda.synchronize()
+    if spoil is None:
+        assert rc == 0 and not bool((q == 11.0).any())
+        assert bool(((a_out >= 0) & (a_out < A)).all())
+        return
+    assert rc != 0
+    assert bool((a_out == -3).all()) and bool((q == 11.0).all())
