@@ -145,6 +145,14 @@ class RuntimeConf:
     # the DP step or the graph learner
     value_rescale: bool = False
     value_rescale_eps: float = 1e-3
+    # random-shift (DrQ) augmentation of the sampled frames (Kostrikov et al. 2020; learner/augment.py,
+    # csrc/augment.hip): every sampled S_t and S_t+n is padded by augment_shift pixels with edge replication and
+    # cropped back to 84 x 84 at an offset drawn per (sample, state, update), at the head of every update inside the
+    # captured step.  0 = off (the launches and the bits of before), at most 8.  Single-rank NatureCNN with every
+    # head kind, noisy layers, the Munchausen target, Adam, the schedules, the soft target and value rescaling, and
+    # the torch learner on 84 x 84 stacks; not IMPALA, the DP step or the graph learner.  Actors and evaluation
+    # see the frames as they are
+    augment_shift: int = 0
     # Atari wrappers clip rewards to {-1, 0, +1} (envs/vector_envs.py AtariWrapperVec); false keeps the raw rewards
     # (with value_rescale; the two keys are independent)
     clip_rewards: bool = True
@@ -416,6 +424,21 @@ class ApexConfig:
             if int(rt.world_size) > 1 or rt.force_dp:
                 raise ValueError("Runtime.value_rescale runs on a single rank: the data-parallel step (world_size > 1, "
                                  "force_dp) has no rescaled target")
+        P = rt.augment_shift
+        if isinstance(P, bool) or not isinstance(P, int) or not 0 <= P <= 8:
+            raise ValueError(f"Runtime.augment_shift (the random shift's pad in pixels) must be an integer in [0, 8], "
+                             f"got {P!r}")
+        if P >= 1:
+            if net == "impala":
+                raise ValueError("Runtime.augment_shift: the IMPALA step has no frame augmentation (it is the "
+                                 "NatureCNN learner's)")
+            if net not in ("nature64", "nature32"):
+                raise ValueError(f"Runtime.augment_shift needs network nature64 or nature32, got {net!r}")
+            if len(ss) != 3 or tuple(ss[1:]) != (84, 84):
+                raise ValueError(f"Runtime.augment_shift shifts 84x84 frames, got state_shape {ss}")
+            if int(rt.world_size) > 1 or rt.force_dp:
+                raise ValueError("Runtime.augment_shift runs on a single rank: the data-parallel step (world_size > 1, "
+                                 "force_dp) has no frame augmentation")
         if net in ("nature64", "nature32", "impala") and len(ss) != 3:
             raise ValueError(f"network {net} needs an image state_shape [C,H,W], got {ss}")
         if net in ("nature64", "nature32") and tuple(ss[1:]) != (84, 84):

@@ -292,7 +292,8 @@ class DataParallelStep:
                 self._conv3_wgrad(jobs)
             self._conv2_wgrad(jobs)
         jobs1 = []
-        ops.conv1_wgrad_ring(self.dY1, self.replay.frames, self.slots[:B], self.frames, rt.obs_scale, G["w1"],
+        ring, slots = self._frame_src()
+        ops.conv1_wgrad_ring(self.dY1, ring, slots[:B], self.frames, rt.obs_scale, G["w1"],
                              G["b1"], jobs=jobs1, **self._lo(dy_lo=self.dY1_lo))
         with br.branch():
             if factors and not shard:

@@ -2,6 +2,8 @@
 
 Per step (B = local batch), entirely on device, one stream, no host sync:
 
+  (Runtime.augment_shift) random-shift copies    csrc/augment.hip: 2B C shifted frames in the ring's
+  of the sampled S_t / S_t+n frame stacks        layout, read below in the ring's place (_frame_src)
   online fwd on 2B rows, target fwd on B rows    conv1_s2d (reads the uint8 replay ring
                                                  by slot) / conv2 / conv3 / fc
   DDQN target + Huber*IS loss + |delta| + dH     csrc/ddqn_head.hip (Runtime.munchausen: the online
@@ -150,6 +152,15 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         if self.ema and self._dp:
             raise ValueError("Runtime.target_ema_rate: the soft target is averaged on a single rank, not in the "
                              "data-parallel step (world > 1, Runtime.force_dp, the emulated world)")
+        # random-shift (DrQ) augmentation of the sampled frames (learner/augment.py, csrc/augment.hip): one launch at
+        # the head of every update writes shifted copies of the S_t / S_t+n stacks, which every frame consumer of
+        # the step then reads in the ring's place (_frame_src); 0 = no buffer, no launch
+        self.aug_pad = int(self.rt.augment_shift)
+        if self.aug_pad and self._dp:
+            raise ValueError("Runtime.augment_shift: the frames are augmented on a single rank, not in the "
+                             "data-parallel step (world > 1, Runtime.force_dp, the emulated world)")
+        if self.aug_pad and tuple(cfg.env_conf.state_shape[1:]) != (84, 84):
+            raise ValueError(f"Runtime.augment_shift shifts 84x84 frames, got state_shape {cfg.env_conf.state_shape}")
         if self.rt.dtype not in ("fp32", "bf16"):
             raise ValueError("Runtime.dtype must be fp32 or bf16")
         self.precision = self.rt.dtype
@@ -450,6 +461,15 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         self.S["nxt"] = self.slots[B:2 * B]
         self.frames = torch.zeros(3 * B, C, 84, 84, dtype=torch.uint8, device=d) if self.ops.name != "hip" \
             else torch.zeros(1, C, 84, 84, dtype=torch.uint8, device=d)
+        self.aug_frames = self.aug_slots = self.aug_off = None
+        if self.aug_pad:
+            # the shifted copies of rows [0, 2B) in the ring's layout, the static slot table of the 3B forward rows
+            # into them (the third block repeats the rows it shows) and the offsets of the last update
+            from .augment import aug_seed, aug_slot_table
+            self.aug_frames = torch.zeros(2 * B * C, 84, 84, dtype=torch.uint8, device=d)
+            self.aug_slots = aug_slot_table(B, C, self.munchausen).to(d)
+            self.aug_off = torch.zeros(2 * B, 2, dtype=torch.int32, device=d)
+            self._seed_a = aug_seed(self.rt.seed)
 
         def act(*shape):
             """hi buffer (+ its lo plane in split mode)"""
@@ -490,6 +510,20 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         # head's 2.5 K values), or by the wide head weight gradient's own blocks (N >= 2)
         self._head_norm_range = self.g_head_region if self.N == 1 else None
 
+    def _frame_src(self):
+        """(ring, slots [3B, C]) the step's frame consumers read: the replay ring by the sampled slots, or with
+        ``Runtime.augment_shift`` the augmented copies by their static table."""
+        if self.aug_pad:
+            return self.aug_frames, self.aug_slots
+        return self.replay.frames, self.slots
+
+    def _augment_step(self) -> None:
+        """The shifted copies of this update's S_t / S_t+n stacks, at the head of the update on the main stream
+        (the update index read on the device, before the priority write-back bumps the draw counter)."""
+        if self.aug_pad:
+            self.ops.augment_shift(self.replay.frames, self.slots[:2 * self.B], self.aug_pad, self._seed_a,
+                                   self.replay.ctr, self.upd_base, self.aug_frames, self.aug_off)
+
     def _lo(self, **kw) -> Dict[str, Any]:
         """Split-mode keyword arguments of an op (empty in bf16 / plain fp32 mode)."""
         return kw if self.split else {}
@@ -514,6 +548,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         Pb, P, Tb, T, Pl, Tl = self.Pb, self.P, self.Tb, self.T, self.Pl, self.Tl
         sp = self.split
         n, r1 = 3 * B, self._rows_first
+        ring, slots = self._frame_src()
         # c2f: conv2's weights packed for its forward in the same launch (csrc/conv2_wfrag.h)
         if self._c12:
             # conv1 -> conv2 in one launch, y1 kept in LDS; only the S_t rows' y1 (the
@@ -524,13 +559,13 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             online = 0 if self._frag_out is not None else 1     # (stored by the last optimizer launch)
             # conv3 in the same launch from y2 in LDS (SW.conv123_fused)
             c3 = self._conv3_weights() if self._conv123 else None
-            ops.conv12_fwd(self.replay.frames, self.slots, self.frames, rt.obs_scale, self.y1, self.y1_lo, self.y2,
+            ops.conv12_fwd(ring, slots, self.frames, rt.obs_scale, self.y1, self.y1_lo, self.y2,
                            self.y2_lo, c1, c2, rows_first=r1, copy_n=B,
                            pack_sets=online | (0 if self._tgt_current() else 2), c3=c3, y3=self.y3,
                            y3_lo=self.y3_lo)
         else:
             c2f = (Pb["w2"], None, Tb["w2"], None)
-            ops.conv1_fwd_ring(self.replay.frames, self.slots, self.frames, Pb["w1"], P["b1"], rt.obs_scale, self.y1,
+            ops.conv1_fwd_ring(ring, slots, self.frames, Pb["w1"], P["b1"], rt.obs_scale, self.y1,
                                Tb["w1"], T["b1"], r1, c2f=c2f)
             ops.conv_fwd(self.y1, Pb["w2"], P["b2"], 2, self.y2, Tb["w2"], T["b2"], r1)
         self._issue_params()      # sharded DP update: a deferred fc-row all-gather (learner/dp_step.py)
@@ -655,6 +690,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         S = self.S
         self._mark("sample")
         self._noisy_compose_step()
+        self._augment_step()
         # conv1 reads the uint8 frame stacks straight from the replay ring by slot
         self.forward_all(defer_head=self._defer_fc_epilogue)
         self._mark("forward")
@@ -706,7 +742,8 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         ops.conv_wgrad(self.dY2, self.y1[:B], 4, 2, G["w2"], G["b2"], jobs=jobs,
                        **self._lo(dy_lo=self.dY2_lo, x_lo=sp and self.y1_lo[:B]))
         jobs1 = []
-        ops.conv2_dgrad_conv1_wgrad(self.dY2, Pb["w2"], self.y1[:B], self.dY1, self.replay.frames, self.slots[:B],
+        ring, slots = self._frame_src()
+        ops.conv2_dgrad_conv1_wgrad(self.dY2, Pb["w2"], self.y1[:B], self.dY1, ring, slots[:B],
                                     self.frames, rt.obs_scale, G["w1"], G["b1"], jobs=jobs1,
                                     **self._lo(dy2_lo=self.dY2_lo, w2_lo=sp and Pl["w2"], dy1_lo=self.dY1_lo))
         # two finalisations, as the branched step runs them (conv3 / conv2 + the head
@@ -836,14 +873,15 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         jobs1 = []
         # conv2's data gradient + conv1's weight gradient as one kernel where the backend has
         # it; else the pair, conv1's weight gradient enqueued after the branch's conv2 wgrad
-        fuse21 = ops.conv21_fused_ok(self.dY2, self.slots[:B], **self._lo(dy2_lo=self.dY2_lo, w2_lo=sp and Pl["w2"]))
+        ring, slots = self._frame_src()
+        fuse21 = ops.conv21_fused_ok(self.dY2, slots[:B], **self._lo(dy2_lo=self.dY2_lo, w2_lo=sp and Pl["w2"]))
         self._conv32_branched(main, side, jobs, jobs1=jobs1 if fuse21 else None)
         if fc_main and self.noisy:
             # (the branch has waited for the main stream past the fc weight gradient by now)
             with torch.cuda.stream(side):
                 self._noisy_sigma_grad()
         if not fuse21:
-            ops.conv1_wgrad_ring(self.dY1, self.replay.frames, self.slots[:B], self.frames, rt.obs_scale, G["w1"],
+            ops.conv1_wgrad_ring(self.dY1, ring, slots[:B], self.frames, rt.obs_scale, G["w1"],
                                  G["b1"], jobs=jobs1, **self._lo(dy_lo=self.dY1_lo))
         fuse = self._fuse_norm
         with torch.cuda.stream(side):
@@ -888,8 +926,9 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             ops.conv_dgrad(self.dY2, Pb["w2"], 2, self.y1[:B], self.dY1,
                            **self._lo(dy_lo=self.dY2_lo, w_lo=sp and Pl["w2"], dx_lo=self.dY1_lo))
         else:
-            ops.conv2_dgrad_conv1_wgrad(self.dY2, Pb["w2"], self.y1[:B], self.dY1, self.replay.frames,
-                                        self.slots[:B], self.frames, rt.obs_scale, G["w1"], G["b1"], jobs=jobs1,
+            ring, slots = self._frame_src()
+            ops.conv2_dgrad_conv1_wgrad(self.dY2, Pb["w2"], self.y1[:B], self.dY1, ring,
+                                        slots[:B], self.frames, rt.obs_scale, G["w1"], G["b1"], jobs=jobs1,
                                         **self._lo(dy2_lo=self.dY2_lo, w2_lo=sp and Pl["w2"], dy1_lo=self.dY1_lo))
         side.wait_event(ev2)
         if wgrad2:
@@ -1229,6 +1268,8 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         if self.munchausen:     # the last update's mean bonus (<= 0) and mean soft value of S_t+n
             mean = self.mdqn_aux.double().mean(0)
             m["munchausen_bonus_mean"], m["soft_value_mean"] = float(mean[0]), float(mean[1])
+        if self.aug_pad:        # the last update's mean shift offset (expected: augment_shift)
+            m["augment_offset_mean"] = float(self.aug_off.double().mean())
         return m
 
     def q_values(self, frames_u8: torch.Tensor) -> torch.Tensor:

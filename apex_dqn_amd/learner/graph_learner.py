@@ -74,6 +74,9 @@ class GraphLearner(StepIndexMixin):
         if self.rt.value_rescale:
             raise ValueError("Runtime.value_rescale: the graph learner (Runtime.use_hip_kernels = false on the GPU) "
                              "has no rescaled target; run the HIP kernels or value_rescale = false")
+        if int(self.rt.augment_shift) >= 1:
+            raise ValueError("Runtime.augment_shift: the graph learner (Runtime.use_hip_kernels = false on the GPU) "
+                             "has no frame augmentation; run the HIP kernels or augment_shift = 0")
         self.device = torch.device(device)
         self.replay = replay
         self.comm = comm

@@ -84,6 +84,9 @@ class FusedImpalaLearner(IsNormMixin, StepIndexMixin):
         if self.rt.value_rescale:
             raise ValueError("Runtime.value_rescale: the IMPALA step has no rescaled target (it is the NatureCNN "
                              "learner's and the torch learners')")
+        if int(self.rt.augment_shift) >= 1:
+            raise ValueError("Runtime.augment_shift: the IMPALA step has no frame augmentation (it is the NatureCNN "
+                             "learner's)")
         self.world, _, self.B, self.mcap = dp_layout(cfg, comm, batch_size, allow_force=False)
         self.C = cfg.frame_stack
         if self.C != 4 or tuple(cfg.env_conf.state_shape[1:]) != (84, 84):

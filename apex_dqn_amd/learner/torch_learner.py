@@ -66,6 +66,15 @@ class TorchLearner:
     def compute_loss_and_priorities(self, batch: Dict[str, Any]):
         S_t = self._to(batch["S_t"])
         S_tpn = self._to(batch["S_tpn"])
+        P = int(self.rt.augment_shift)
+        if P >= 1 and S_t.dim() == 4 and tuple(S_t.shape[2:]) == (84, 84):
+            # random-shift augmentation by the fused learner's convention (learner/augment.py: update index =
+            # num_q_updates, rows b = S_t, B + b = S_t+n), so both see the same shifted frames
+            from .augment import aug_seed, shift_frames, shift_offsets
+            B = S_t.shape[0]
+            off = shift_offsets(aug_seed(self.rt.seed), self.num_q_updates, 2 * B, P)
+            self.last_aug_off = off
+            S_t, S_tpn = shift_frames(S_t, off[:B], P), shift_frames(S_tpn, off[B:], P)
         A = self._to(batch["A_t"], torch.long)
         R = self._to(batch["R"], torch.float32)
         G = self._to(batch["Gamma"], torch.float32)

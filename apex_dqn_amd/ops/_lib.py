@@ -141,6 +141,12 @@ class NoisyGradArgs(ctypes.Structure):
                 ("n_g", c_i64)]
 
 
+class AugArgs(ctypes.Structure):
+    """Arguments of ``augment_shift_kernel`` (``AugArgs``, csrc/augment.hip)."""
+    _fields_ = [("ring", c_p), ("F", c_i64), ("slots", c_p), ("rows", c_i), ("C", c_i), ("pad", c_i), ("seed", c_u64),
+                ("ctr", c_p), ("base", c_p), ("out", c_p), ("n_out", c_i64), ("off_out", c_p)]
+
+
 class CfFragOut(ctypes.Structure):
     """The optimizer's stores of the fused forward's online operands (``CfFragOut``,
     csrc/cf_pack.h); all-zero = off."""
@@ -315,6 +321,8 @@ _SIGS = {
     "apex_noisy_xi_len": ([c_i, c_i], c_i),
     "apex_noisy_compose": ([NoisyArgs, c_p], c_i),
     "apex_noisy_sigma_grad": ([NoisyGradArgs, c_p], c_i),
+    "apex_augment_shift": ([AugArgs, c_p], c_i),
+    "apex_augment_debug_errors": ([c_p, c_p, c_i], c_i),
 }
 
 _LIB: Optional[ctypes.CDLL] = None

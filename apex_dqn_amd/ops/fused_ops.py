@@ -779,6 +779,32 @@ class TorchBackend:
             gm = plan.seg(g32, name).double()
             plan.seg(g32, NZ.SIGMA[name]).copy_((gm * NZ.outer(v, name, gm.shape).to(gm.device)).float())
 
+    # ------------------------------------------------- frame augmentation
+    @staticmethod
+    def _augment_check(ring, slots, pad, ctr, base, out, off_out):
+        rows, C = slots.shape
+        assert ring.dtype == torch.uint8 and ring.is_contiguous() and tuple(ring.shape[1:]) == (84, 84)
+        assert slots.dtype == torch.int32 and slots.is_contiguous()
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= rows * C * 7056
+        assert off_out.dtype == torch.int32 and off_out.is_contiguous() and off_out.numel() >= 2 * rows
+        assert ctr.dtype == torch.int64 and (base is None or base.dtype == torch.int64)
+        return int(rows), int(C)
+
+    def augment_shift(self, ring, slots, pad, seed, ctr, base, out, off_out) -> None:
+        """Random-shift augmentation of the frame stacks ``slots`` [rows, C] name in ``ring`` (learner/augment.py;
+        the oracle of csrc/augment.hip ``augment_shift_kernel``): ``out`` gets the rows C shifted frames in the
+        ring's space-to-depth layout, ``off_out`` [rows, 2] the offsets, drawn with ``seed`` (seed_a) at the update
+        index ``ctr - base`` read back from the device."""
+        from ..learner import augment as AU
+        from ..replay.gpu_replay import from_s2d, to_s2d
+        rows, C = self._augment_check(ring, slots, pad, ctr, base, out, off_out)
+        u = max(int(ctr.reshape(-1)[0].item()) - (0 if base is None else int(base.reshape(-1)[0].item())), 0)
+        off = AU.shift_offsets(seed, u, rows, pad)
+        nat = from_s2d(ring[slots.long()].reshape(rows * C, 84, 84)).reshape(rows, C, 84, 84)
+        sh = AU.shift_frames(nat, off, pad)
+        out.reshape(-1)[:rows * C * 7056].copy_(to_s2d(sh.reshape(rows * C, 84, 84)).reshape(-1))
+        off_out.reshape(-1)[:2 * rows].copy_(off.reshape(-1))
+
     # ------------------------------------------- data-parallel gradient factors
     def pack_rows(self, dst: torch.Tensor, segs) -> None:
         """dst[:, c0:c0 + n] = seg for the 2-D ``segs`` laid side by side (same row count)."""
@@ -807,7 +833,7 @@ class HipBackend(TorchBackend):
         self.native_conv = native_conv and hasattr(self.lib, "apex_conv_fwd")
         self.kernels = ["replay", "head", "head_wgrad", "optimizer", "actor_head", "c51_head", "c51_actor_head", "qr_head",
                         "qr_actor_head", "noisy_compose", "noisy_sigma_grad", "mdqn_head", "iqn_head", "iqn_wgrad",
-                        "iqn_actor_head"]
+                        "iqn_actor_head", "augment_shift"]
         if self.native_conv:
             self.kernels += ["conv_fwd", "conv_dgrad", "conv_wgrad", "fc_fwd", "fc_bwd"]
         self.ws = C.Workspace()
@@ -1372,6 +1398,20 @@ class HipBackend(TorchBackend):
         a.g, a.xi, a.A, a.N, a.n_g = g32.data_ptr(), xi.data_ptr(), int(plan.A), int(plan.N), int(g32.numel())
         self._noisy_offsets(plan, a.mu, a.sg)
         _lib.check(self.lib.apex_noisy_sigma_grad(a, _lib.stream_ptr()), "noisy_sigma_grad")
+
+    def augment_args(self, ring, slots, pad, seed, ctr, base, out, off_out) -> "_lib.AugArgs":
+        """The argument block of ``apex_augment_shift`` (tests pass altered copies to the launcher)."""
+        rows, C = self._augment_check(ring, slots, pad, ctr, base, out, off_out)
+        a = _lib.AugArgs()
+        a.ring, a.F, a.slots, a.rows, a.C, a.pad = ring.data_ptr(), int(ring.shape[0]), slots.data_ptr(), rows, C, int(pad)
+        a.seed, a.ctr, a.base = int(seed), ctr.data_ptr(), _lib.ptr(base)
+        a.out, a.n_out, a.off_out = out.data_ptr(), int(out.numel()), off_out.data_ptr()
+        return a
+
+    def augment_shift(self, ring, slots, pad, seed, ctr, base, out, off_out) -> None:
+        """csrc/augment.hip ``augment_shift_kernel``: one launch; the update index is read on the device."""
+        a = self.augment_args(ring, slots, pad, seed, ctr, base, out, off_out)
+        _lib.check(self.lib.apex_augment_shift(a, _lib.stream_ptr()), "augment_shift")
 
     def cast_bf16(self, x32, hi, lo=None) -> None:
         """hi = bf16(x32) (and lo = bf16(x32 - hi)) with one kernel."""
