@@ -113,6 +113,12 @@ class RuntimeConf:
     # head's loss with sampled fractions (learner/losses.py iqn_loss, learner/iqn.py the draws' mirror).
     # iqn_actor_samples = K: the samples behind the actors' and the greedy evaluation's q
     iqn_actor_samples: int = 32
+    # "hl_gauss" (the Gaussian histogram loss, Imani & White 2018 / Farebrother et al. 2024; csrc/c51_head.hip
+    # hlg_head_kernel): the categorical head, its support, weights, checkpoint keys and actor head, trained against
+    # the scalar double-DQN target spread over the bins as a Gaussian of sigma = hl_gauss_sigma_ratio bin widths
+    # (finite, > 0; the paper's 0.75) instead of the projected target distribution; the priority is |y - q| against
+    # that scalar target (learner/losses.py hl_gauss_loss).  loss / huber_delta do not apply; C51's refusals
+    hl_gauss_sigma_ratio: float = 0.75
     # factorised NoisyNet fc and head layers (Fortunato et al. 2018; learner/noisy.py, csrc/noisy.hip): the two
     # stream layers and the two heads carry W = mu + sigma * (xi_out (x) xi_in), one draw per update for the online
     # net and one for the target net, one per noisy_actor_resample batched inference calls for an actor group;
@@ -340,8 +346,14 @@ class ApexConfig:
             raise ValueError(f"Runtime.num_atoms must be 1 or an integer in [2, 64] (one lane per atom), got {na!r}")
         if not float(rt.v_min) < float(rt.v_max):
             raise ValueError(f"Runtime.v_min must be below Runtime.v_max, got {rt.v_min} / {rt.v_max}")
-        if rt.dist_head not in ("categorical", "quantile", "implicit"):
-            raise ValueError(f"Runtime.dist_head must be 'categorical', 'quantile' or 'implicit', got {rt.dist_head!r}")
+        if rt.dist_head not in ("categorical", "quantile", "implicit", "hl_gauss"):
+            raise ValueError(f"Runtime.dist_head must be 'categorical', 'quantile', 'implicit' or 'hl_gauss', got "
+                             f"{rt.dist_head!r}")
+        sr = rt.hl_gauss_sigma_ratio
+        if na >= 2 and rt.dist_head == "hl_gauss" and (
+                isinstance(sr, bool) or not isinstance(sr, (int, float)) or not 0.0 < float(sr) < float("inf")):
+            raise ValueError(f"Runtime.hl_gauss_sigma_ratio (the histogram loss's sigma in bin widths) must be a "
+                             f"finite number > 0, got {sr!r}")
         ks = rt.iqn_actor_samples
         if isinstance(ks, bool) or not isinstance(ks, int) or not 1 <= ks <= 64:
             raise ValueError(f"Runtime.iqn_actor_samples must be an integer in [1, 64] (one lane per sample), got {ks!r}")
@@ -480,6 +492,11 @@ class ApexConfig:
     def quantile(self) -> bool:
         """The distributional head is the quantile-regression one (Runtime.dist_head)."""
         return self.distributional and self.Runtime.dist_head == "quantile"
+
+    @property
+    def hl_gauss(self) -> bool:
+        """The categorical head is trained with the histogram loss (Runtime.dist_head)."""
+        return self.distributional and self.Runtime.dist_head == "hl_gauss"
 
     @property
     def implicit(self) -> bool:

@@ -144,6 +144,118 @@ APEX_EXPORT int apex_c51_head(C51Args a, hipStream_t st) {
   APEX_CHECK_LAUNCH();
 }
 
+// Histogram-loss (HL-Gauss) target on the same head (Runtime.dist_head = "hl_gauss"; Imani & White 2018,
+// Farebrother et al. 2024): the softmax, the support, q, a* and the gradient are the categorical head's; the
+// target row is the scalar double-DQN target spread over the bins as a Gaussian (no projection):
+//
+//   sigma = sigma_ratio delta,   e_i = v_min + (i - 1/2) delta, i = 0..N   (bin i = [e_i, e_i+1], centre z_i)
+//   y     = clamp(R + G q_target(S_t+n)[a*], v_min, v_max)      (RESCALE: T(R, G, q_target[a*]), value_rescale.h)
+//   E_i   = erf((e_i - y) / (sigma sqrt 2)),   m_i = (E_i+1 - E_i) / (E_N - E_0)
+//   loss_b = -w_b sum_i m_i log p(S_t)[a_b,i],  td_abs_b = |y - q(S_t)[a_b]|,  g_i = w_b (p - m_i) grad_scale
+//
+// e_i, sigma, E_i and the quotient are fp64 on the fp32 v_min, v_max, sigma_ratio and y; m_i is rounded to fp32
+// once (value_rescale.h's convention).  y is clamped, so E_N - E_0 is at least the mass of half a bin.  A lane
+// evaluates its bin's two edges: (i + 1) - 1/2 and i + 1/2 are the same fp64 number, so the masses telescope.
+struct HlgArgs {
+  HeadIO io;            // as C51Args
+  int N;
+  float vmin, vmax, sigma_ratio;
+};
+static_assert(std::is_standard_layout_v<HlgArgs> && std::is_trivially_copyable_v<HlgArgs>);
+
+template <bool RESCALE>
+__global__ void __launch_bounds__(DIST_NT) hlg_head_kernel(HlgArgs ka) {
+  const HeadIO& a = ka.io;
+  extern __shared__ __attribute__((aligned(16))) float c51_smem[];
+  constexpr int HS = DIST_HS, ROW = 2 * HS, SPB = DIST_SPB, NR = 3 * SPB;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int B = a.B, A = a.A, N = ka.N, AN = A * N, J = N + AN;
+  const int Jp = (J + 3) & ~3;
+  float* Hs = c51_smem;                  // as c51_head_kernel
+  float* Ls = c51_smem + NR * ROW;
+  const int b0 = blockIdx.x * SPB;
+  const bool split = a.lo.Hon != nullptr;
+
+  dist_head_side(a, tid, lane, wv);
+  dist_head_stage(a, Hs, b0, tid, split);
+  __syncthreads();
+  dist_head_logits(a, N, Hs, Ls, Jp, lane, wv);
+  __syncthreads();
+
+  // ---- phase 2: wave s finishes sample s (lane = bin)
+  if (wv < SPB) {
+    const int s = wv;
+    const bool live = b0 + s < B;
+    const int b = min(b0 + s, B - 1);
+    const bool valid = lane < N;
+    const float delta = (ka.vmax - ka.vmin) / (float)(N - 1);
+    const float z = ka.vmin + (float)lane * delta;
+    const int a_b = a.act[b];
+    const float rew_b = a.rew[b], gam_b = a.gam[b];
+    const float w_b = a.isw != nullptr ? a.isw[b] : 1.f;
+    float p, lp;
+    // double DQN: a* from the online net at S_t+n (first maximum wins)
+    int astar = 0;
+    {
+      const DistRow rn = dist_row(Ls + (SPB + s) * Jp, a.Pon, A, N, lane);
+      float best = -3.4e38f;
+      for (int j = 0; j < A; ++j) {
+        const float q = c51_action(rn, j, N, lane, z, p, lp);
+        if (q > best) { best = q; astar = j; }
+      }
+      astar = __builtin_amdgcn_readfirstlane(astar);
+    }
+    // the scalar target from the target net's expectation of a*, then its Gaussian mass per bin
+    float y, m;
+    {
+      const DistRow rg = dist_row(Ls + (2 * SPB + s) * Jp, a.Ptg, A, N, lane);
+      const float qg = c51_action(rg, astar, N, lane, z, p, lp);
+      float y0;
+      if constexpr (RESCALE) y0 = value_rescale_target(rew_b, gam_b, qg, a.rescale_eps);
+      else y0 = rew_b + gam_b * qg;
+      y = fminf(fmaxf(y0, ka.vmin), ka.vmax);
+      const double vmin = (double)ka.vmin;
+      const double dl = ((double)ka.vmax - vmin) / (double)(N - 1);
+      const double inv = 1.0 / ((double)ka.sigma_ratio * dl * 1.4142135623730951);
+      const double i0 = (double)min(lane, N - 1);            // (a lane past N repeats the last bin)
+      const double Elo = erf((vmin + (i0 - 0.5) * dl - (double)y) * inv);
+      const double Ehi = erf((vmin + (i0 + 0.5) * dl - (double)y) * inv);
+      const double E0 = __shfl(Elo, 0, 64), EN = __shfl(Ehi, N - 1, 64);
+      m = valid ? (float)((Ehi - Elo) / (EN - E0)) : 0.f;
+    }
+    // S_t: expected q of every action, the taken action's distribution
+    float p_sa = 0.f, lp_sa = 0.f, q_sa = 0.f;
+    {
+      const DistRow rt = dist_row(Ls + s * Jp, a.Pon, A, N, lane);
+      for (int j = 0; j < A; ++j) {
+        const float q = c51_action(rt, j, N, lane, z, p, lp);
+        if (a.q_out != nullptr && live && lane == 0) a.q_out[(int64_t)b * A + j] = q;
+        if (j == a_b) { p_sa = p; lp_sa = lp; q_sa = q; }
+      }
+    }
+    const float ce = -wave_sum_dpp(m * lp_sa);
+    const float g = valid ? w_b * (p_sa - m) * a.grad_scale : 0.f;
+    if (live && lane == 0) {
+      a.td_abs[b] = fabsf(y - q_sa);
+      a.loss[b] = w_b * ce;
+    }
+    dist_head_store_dhead(g, live, valid, a_b, A, N, lane, Ls + s * Jp, a.dhead + (int64_t)b * J);
+  }
+  __syncthreads();
+
+  dist_head_dh(a, N, Hs, Ls, Jp, b0, tid, split);
+}
+
+APEX_EXPORT int apex_hlg_head(HlgArgs a, hipStream_t st) {
+  size_t lds = 0;
+  if (!dist_head_args_ok(a.io, a.N, &lds) || !(a.vmin < a.vmax) || !(a.sigma_ratio > 0.f) || !std::isfinite(a.sigma_ratio))
+    return (int)hipErrorInvalidValue;
+  const int grid = (a.io.B + DIST_SPB - 1) / DIST_SPB;
+  if (a.io.rescale_eps > 0.f) hlg_head_kernel<true><<<grid, DIST_NT, lds, st>>>(a);
+  else hlg_head_kernel<false><<<grid, DIST_NT, lds, st>>>(a);
+  APEX_CHECK_LAUNCH();
+}
+
 // Actor side: expected q of the distributional head + epsilon-greedy, one wave per env row
 // (four per block; a wave past E repeats the last row and stores nothing).
 __global__ void __launch_bounds__(256) c51_actor_head_kernel(C51ActorArgs ka) {

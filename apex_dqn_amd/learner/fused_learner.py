@@ -10,7 +10,8 @@ Per step (B = local batch), entirely on device, one stream, no host sync:
                                                  net on B rows, the target net on 2B, and the
                                                  Munchausen target, csrc/mdqn_head.hip;
                                                  Runtime.num_atoms >= 2:
-                                                 csrc/c51_head.hip, projected cross-entropy,
+                                                 csrc/c51_head.hip, projected cross-entropy
+                                                 or the histogram loss (hlg_head_kernel),
                                                  or csrc/qr_head.hip, quantile Huber loss,
                                                  then head wgrad + write-back and fc wgrad as
                                                  two launches on the backward's branch;
@@ -661,6 +662,10 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             # quantile regression: the quantile Huber loss, kappa = huber_delta (Runtime.loss, v_min / v_max
             # do not apply)
             ops.qr_head(*h, *data, self.N, rt.huber_delta, *out, **kw)
+        elif self.N >= 2 and self.cfg.hl_gauss:
+            # the categorical head against the Gaussian histogram of the scalar target (csrc/c51_head.hip
+            # hlg_head_kernel; Runtime.loss / huber_delta do not apply)
+            ops.hlg_head(*h, *data, self.N, rt.v_min, rt.v_max, rt.hl_gauss_sigma_ratio, *out, **kw)
         elif self.N >= 2:
             # categorical projection + cross-entropy (Runtime.loss / huber_delta do not apply)
             ops.c51_head(*h, *data, self.N, rt.v_min, rt.v_max, *out, **kw)

@@ -84,6 +84,74 @@ def c51_loss(logp_t: torch.Tensor, q_online_next: torch.Tensor, p_target_next: t
     return per.mean(), td
 
 
+def _f32(x: float) -> float:
+    return float(torch.tensor(float(x), dtype=torch.float32))
+
+
+def hl_gauss_target(y0: torch.Tensor, v_min: float, v_max: float, num_atoms: int,
+                    sigma_ratio: float = 0.75) -> torch.Tensor:
+    """The Gaussian histogram (HL-Gauss) target row of the scalar target ``y0`` [B] on the categorical head's
+    support (Imani & White 2018; Farebrother et al. 2024), ``Runtime.dist_head = "hl_gauss"``.  Bins are centred
+    on the C51 atoms z_i = v_min + i delta, delta = (v_max - v_min) / (N - 1)::
+
+        sigma = sigma_ratio delta
+        e_i   = v_min + (i - 1/2) delta,  i = 0..N          (N + 1 edges; bin i = [e_i, e_i+1], centre z_i)
+        y     = clamp(y0, v_min, v_max)
+        E_i   = erf((e_i - y) / (sigma sqrt 2))
+        m_i   = (E_i+1 - E_i) / (E_N - E_0)                 (Gaussian mass of bin i, renormalised to the covered
+                                                             range: sum_i m_i = 1)
+
+    Evaluated in fp64 on the fp32 values of ``v_min``, ``v_max`` and ``sigma_ratio`` and on ``y`` as given, and
+    rounded to ``y0``'s dtype once (csrc/value_rescale.h's convention; csrc/c51_head.hip ``hlg_head_kernel``).
+    y is clamped, so the denominator is at least the mass of half a bin.  The mean sum_i m_i z_i is y in the
+    interior and biased towards the middle within a few sigma of either end (the Gaussian is truncated there):
+    priorities are taken against y, not against that mean.  y0 [B] -> m [B, N]."""
+    N = int(num_atoms)
+    sr = _f32(sigma_ratio)
+    if not (sr > 0.0 and sr < float("inf")):
+        raise ValueError(f"hl_gauss_sigma_ratio must be finite and > 0, got {sigma_ratio}")
+    lo, hi = _f32(v_min), _f32(v_max)
+    delta = (hi - lo) / (N - 1)
+    y = y0.clamp(float(v_min), float(v_max)).double()
+    edges = lo + (torch.arange(N + 1, dtype=torch.float64, device=y0.device) - 0.5) * delta
+    E = torch.erf((edges[None, :] - y[:, None]) / (sr * delta * 1.4142135623730951))
+    m = (E[:, 1:] - E[:, :-1]) / (E[:, -1:] - E[:, :1])
+    return m.to(y0.dtype)
+
+
+def hl_gauss_loss(logp_t: torch.Tensor, q_online_next: torch.Tensor, q_target_next: torch.Tensor,
+                  A: torch.Tensor, R: torch.Tensor, Gamma: torch.Tensor, v_min: float, v_max: float,
+                  sigma_ratio: float = 0.75, weights: torch.Tensor = None,
+                  rescale_eps: float = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Histogram-loss (HL-Gauss) double-DQN loss of the categorical head.  ``logp_t`` [B, A, N]: log p(S_t) of the
+    online net; ``q_online_next`` [B, A]: its expected q at S_{t+n} (picks a*, first maximum); ``q_target_next``
+    [B, A]: the target net's expected q at S_{t+n}.  y0 = R + Gamma q_target[a*] (:func:`ddqn_targets`; with
+    ``rescale_eps`` T(R, Gamma, q_target[a*]), fp64 on the given values and rounded once), y its clamp onto
+    [v_min, v_max], m = :func:`hl_gauss_target`.  Returns (mean over the batch of -w sum_i m_i log p(S_t)[a, i],
+    |y - q(S_t)[a]| per sample): the priority is the TD error against the scalar target the row was built from.
+    Computes in ``logp_t``'s dtype (fp64 inputs: the tests' reference)."""
+    B, _, N = logp_t.shape
+    dt = logp_t.dtype
+    ar = torch.arange(B, device=logp_t.device)
+    with torch.no_grad():
+        if rescale_eps is not None:
+            y0 = ddqn_targets(q_online_next, q_target_next.to(dt).double(), R.to(dt).double(), Gamma.to(dt).double(),
+                              rescale_eps).to(dt)
+        else:
+            y0 = ddqn_targets(q_online_next, q_target_next.to(dt), R.to(dt), Gamma.to(dt))
+        y = y0.clamp(float(v_min), float(v_max))
+        m = hl_gauss_target(y, v_min, v_max, N, sigma_ratio)
+        delta = (float(v_max) - float(v_min)) / (N - 1)
+        z = float(v_min) + torch.arange(N, dtype=dt, device=logp_t.device) * delta
+    lp = logp_t[ar, A.long().view(-1)]
+    per = -(m * lp).sum(-1)
+    if weights is not None:
+        per = per * weights.to(dt)
+    with torch.no_grad():
+        td = (y - (lp.exp() * z).sum(-1)).abs()
+    return per.mean(), td
+
+
 def quantile_huber_terms(theta: torch.Tensor, T: torch.Tensor, kappa: float,
                          tau: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """The quantile Huber loss of N quantiles ``theta`` [B, N] at tau_i = (2 i + 1) / (2 N)

@@ -20,7 +20,7 @@ import torch
 from ..config import ApexConfig
 from ..models.dueling import build_network
 from ..utils.checkpoint import adopt_obs_scale, check_dist_head, check_noisy, load_checkpoint, save_checkpoint
-from .losses import c51_loss, ddqn_loss, munchausen_loss, munchausen_targets, quantile_huber_loss
+from .losses import c51_loss, ddqn_loss, hl_gauss_loss, munchausen_loss, munchausen_targets, quantile_huber_loss
 from .schedules import lr_scheduled, rt_lr, target_ema_on
 
 
@@ -101,6 +101,13 @@ class TorchLearner:
                 th_next_target = self.Q_target.quantiles(S_tpn)
             return quantile_huber_loss(self.Q.quantiles(S_t), q_next_online, th_next_target, A, R, G,
                                        self.rt.huber_delta, w, rescale_eps=rs)
+        if self.cfg.hl_gauss:
+            # HL-Gauss: cross-entropy against the Gaussian histogram of the scalar target (learner/losses.py)
+            with torch.no_grad():
+                q_next_online = self.Q(S_tpn)[2]
+                q_next_target = self.Q_target(S_tpn)[2]
+            return hl_gauss_loss(self.Q.log_probs(S_t), q_next_online, q_next_target, A, R, G, self.rt.v_min,
+                                 self.rt.v_max, self.rt.hl_gauss_sigma_ratio, w, rescale_eps=rs)
         if self.cfg.distributional:
             # C51: cross-entropy against the projected target distribution (learner/losses.py)
             with torch.no_grad():

@@ -76,15 +76,20 @@ class _C51Head:
 
     ``dist_head = "quantile"`` (QR-DQN): the same weights, keys and shapes, read as N
     quantiles per action, theta[a, i] = v[i] + adv[a, i] - mean_a' adv[a', i] at tau_i =
-    (2 i + 1) / (2 N); q is their mean; no support buffer (v_min / v_max are ignored)."""
+    (2 i + 1) / (2 N); q is their mean; no support buffer (v_min / v_max are ignored).
+
+    ``dist_head = "hl_gauss"`` (the histogram loss, learner/losses.py ``hl_gauss_loss``) changes the training
+    target only: the module is the categorical one (log-probabilities, the expectation, noisy layers)."""
 
     def _init_head(self, hidden: int, num_atoms: int, v_min: float, v_max: float,
                    dist_head: str = "categorical", noisy: bool = False, sigma0: float = 0.5,
                    iqn_actor_samples: int = 32) -> None:
-        if dist_head not in ("categorical", "quantile", "implicit"):
-            raise ValueError(f"dist_head must be 'categorical', 'quantile' or 'implicit', got {dist_head!r}")
+        if dist_head not in ("categorical", "quantile", "implicit", "hl_gauss"):
+            raise ValueError(f"dist_head must be 'categorical', 'quantile', 'implicit' or 'hl_gauss', got "
+                             f"{dist_head!r}")
         self.num_atoms = int(num_atoms)
-        self.dist_head = dist_head if self.num_atoms > 1 else "categorical"
+        # "hl_gauss" (the histogram loss) is another target for the categorical head: the module is the same
+        self.dist_head = dist_head if self.num_atoms > 1 and dist_head != "hl_gauss" else "categorical"
         self.v_min, self.v_max = float(v_min), float(v_max)
         self.noisy = bool(noisy)
         self.implicit = self.dist_head == "implicit"

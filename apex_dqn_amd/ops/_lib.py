@@ -59,7 +59,7 @@ class IsNorm(ctypes.Structure):
 
 class HeadIO(ctypes.Structure):
     """What every loss head takes (``HeadIO``, csrc/head_common.h): the first member ``io`` of ``DdqnArgs``,
-    ``C51Args``, ``QRArgs``, ``IqnArgs`` and ``MdqnArgs``."""
+    ``C51Args``, ``HlgArgs``, ``QRArgs``, ``IqnArgs`` and ``MdqnArgs``."""
     _fields_ = [("Hon", c_p), ("Htg", c_p), ("Pon", HeadParams), ("Ptg", HeadParams), ("act", c_p), ("rew", c_p),
                 ("gam", c_p), ("isw", c_p), ("B", c_i), ("A", c_i), ("hidden", c_i), ("grad_scale", c_f),
                 ("td_abs", c_p), ("loss", c_p), ("q_out", c_p), ("dH", c_p), ("dhead", c_p), ("zero_ptr", c_p),
@@ -69,6 +69,11 @@ class HeadIO(ctypes.Structure):
 class C51Args(ctypes.Structure):
     """Arguments of the distributional head kernel (``C51Args``, csrc/c51_head.hip)."""
     _fields_ = [("io", HeadIO), ("N", c_i), ("vmin", c_f), ("vmax", c_f)]
+
+
+class HlgArgs(ctypes.Structure):
+    """Arguments of the histogram-loss (HL-Gauss) head kernel (``HlgArgs``, csrc/c51_head.hip)."""
+    _fields_ = [("io", HeadIO), ("N", c_i), ("vmin", c_f), ("vmax", c_f), ("sigma_ratio", c_f)]
 
 
 class QRArgs(ctypes.Structure):
@@ -298,6 +303,7 @@ _SIGS = {
     "apex_fc_wgrad_head_prio": ([WgradDesc, HeadWgArgs, TreeUpdArgs, c_p], c_i),
     "apex_head_wgrad": ([HeadWgArgs, c_p], c_i),
     "apex_c51_head": ([C51Args, c_p], c_i),
+    "apex_hlg_head": ([HlgArgs, c_p], c_i),
     "apex_c51_actor_head": ([C51ActorArgs, c_p], c_i),
     "apex_qr_head": ([QRArgs, c_p], c_i),
     "apex_mdqn_head": ([MdqnArgs, c_p], c_i),
@@ -341,7 +347,7 @@ def _declare(lib: ctypes.CDLL) -> None:
     conv_sigs.declare(lib)
 
 
-ABI_VERSION = 17    # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
+ABI_VERSION = 18    # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
 SQNORM_PARTIALS = 1024   # what apex_grad_sqnorm_partials writes (csrc/rmsprop_common.h SQNORM_NPART)
 # the blocks that cross the ABI by value, in the order of csrc/sumtree.hip apex_abi_struct_sizes()
 ABI_STRUCTS = (RmspropArgs, SampleArgs, RmsSegs, TreeUpdArgs, HeadWgArgs, IqnWgArgs, WgradDesc, DdqnArgs, ActorIO,

@@ -345,6 +345,43 @@ class TorchBackend:
             m = m + p_g[:, j:j + 1] * (1.0 - (b[:, j:j + 1] - idx[None, :]).abs()).clamp_min(0.0)
         return m
 
+    def hlg_head(self, Hon, Htg, Pon: Dict[str, torch.Tensor], Ptg: Dict[str, torch.Tensor], act, rew, gam, isw,
+                 num_atoms: int, v_min: float, v_max: float, sigma_ratio: float, grad_scale: float, td_abs, loss, dH,
+                 dhead, q_out=None, zero: Optional[torch.Tensor] = None, lo=None, isn=None, rescale_eps=None):
+        """:meth:`c51_head` with the histogram-loss (HL-Gauss) target (the oracle of csrc/c51_head.hip
+        ``hlg_head_kernel``): y = clamp(rew + gam q_target(S_t+n)[a*]) from the target net's expectation of the
+        double-DQN action (with ``rescale_eps`` T(rew, gam, q_target[a*])), m its Gaussian mass per bin
+        (learner/losses.py ``hl_gauss_target``: fp64 on y, rounded to the head's dtype once), loss = -w sum_i m_i
+        log p(S_t)[a, i], td_abs = |y - q(S_t)[a]|; every output laid out as :meth:`c51_head`'s."""
+        from ..learner.losses import hl_gauss_target
+        B, N = act.shape[0], int(num_atoms)
+        A = Pon["wa"].shape[0] // N
+        dt = _head_dtype(Pon["wv"])
+        lo = lo if lo is not None else (None, None, None)
+        Hon, Htg = join(Hon, lo[0], dt), join(Htg, lo[1], dt)
+        delta = (float(v_max) - float(v_min)) / (N - 1)
+        z = float(v_min) + torch.arange(N, dtype=dt, device=Hon.device) * delta
+        ar = torch.arange(B, device=Hon.device)
+        lp_t = self._c51_logp(Hon[:B], Pon, A, N, dt)
+        q_t = (lp_t.exp() * z).sum(-1)
+        a_star = (self._c51_logp(Hon[B:2 * B], Pon, A, N, dt).exp() * z).sum(-1).argmax(1)
+        q_g = (self._c51_logp(Htg[:B], Ptg, A, N, dt)[ar, a_star].exp() * z).sum(-1)
+        if rescale_eps is None:
+            y0 = rew.to(dt) + gam.to(dt) * q_g
+        else:
+            y0 = rescale_target(rew.to(dt).double(), gam.to(dt).double(), q_g.double(),
+                                _lib.rescale_eps_arg(rescale_eps)).to(dt)
+        y = y0.clamp(float(v_min), float(v_max))
+        m = hl_gauss_target(y, v_min, v_max, N, sigma_ratio)
+        lp = lp_t[ar, act.long()]
+        p = lp.exp()
+        w = isw.to(dt) if isw is not None else torch.ones(B, dtype=dt, device=Hon.device)
+        td_abs.copy_((y - (p * z).sum(-1)).abs())
+        loss.copy_(-w * (m * lp).sum(-1))
+        g = w[:, None] * (p - m) * grad_scale                      # d loss / d logits of (a_b, .)
+        self._dueling_bwd(g, act, Pon, Hon[:B], dH, dhead, lo[2], dt)
+        self._head_close(q_out, q_t, zero, isn, w.float())
+
     def c51_actor_head(self, H, P, eps, ctr, seed, num_atoms: int, v_min: float, v_max: float, q_out, a_out,
                        H_lo=None):
         """Expected q of the distributional head + epsilon-greedy per row (the oracle of
@@ -833,7 +870,7 @@ class HipBackend(TorchBackend):
         self.native_conv = native_conv and hasattr(self.lib, "apex_conv_fwd")
         self.kernels = ["replay", "head", "head_wgrad", "optimizer", "actor_head", "c51_head", "c51_actor_head", "qr_head",
                         "qr_actor_head", "noisy_compose", "noisy_sigma_grad", "mdqn_head", "iqn_head", "iqn_wgrad",
-                        "iqn_actor_head", "augment_shift"]
+                        "iqn_actor_head", "augment_shift", "hlg_head"]
         if self.native_conv:
             self.kernels += ["conv_fwd", "conv_dgrad", "conv_wgrad", "fc_fwd", "fc_bwd"]
         self.ws = C.Workspace()
@@ -1093,6 +1130,19 @@ class HipBackend(TorchBackend):
         a.N, a.vmin, a.vmax = N, float(v_min), float(v_max)
         assert dhead.shape == (B, (A + 1) * N) and dhead.is_contiguous()
         _lib.check(self.lib.apex_c51_head(a, _lib.stream_ptr()), "c51_head")
+
+    def hlg_head(self, Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, v_min, v_max, sigma_ratio, grad_scale,
+                 td_abs, loss, dH, dhead, q_out=None, zero=None, lo=None, isn=None, rescale_eps=None):
+        """csrc/c51_head.hip ``hlg_head_kernel`` (reads h: the fc epilogue is not deferred)."""
+        assert getattr(self, "_fc_part", None) is None, "the distributional head reads h: fc epilogue deferred"
+        N = int(num_atoms)
+        a = _lib.HlgArgs()
+        B, A = act.shape[0], Pon["wa"].shape[0] // N
+        self._head_io(a.io, Hon, Htg, Pon, Ptg, act, rew, gam, isw, A, Pon["wv"].shape[-1], grad_scale, td_abs, loss,
+                      dH, dhead, q_out, zero, lo, isn, rescale_eps)
+        a.N, a.vmin, a.vmax, a.sigma_ratio = N, float(v_min), float(v_max), float(sigma_ratio)
+        assert dhead.shape == (B, (A + 1) * N) and dhead.is_contiguous()
+        _lib.check(self.lib.apex_hlg_head(a, _lib.stream_ptr()), "hlg_head")
 
     def _actor_io(self, io, H, P, eps, ctr, seed, q_out, a_out, H_lo) -> None:
         """Fill ``io``, the block every actor head takes (``_lib.ActorIO``); ``E`` and ``A`` are ``q_out``'s."""
