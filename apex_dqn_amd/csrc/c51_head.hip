@@ -17,12 +17,12 @@
 // transformed space, b_j = (clamp(h(R + G h^-1(z_j))) - v_min) / delta (csrc/value_rescale.h); the projection and
 // td_abs are as above.
 //
-// c51_head_kernel: one block of DIST_NT threads per DIST_SPB samples.  Staging the
-// activation rows, the logits and dH (phases 0, 1 and 3) are csrc/dist_head.h's, shared
-// with the quantile head (csrc/qr_head.hip); phase 2 is this head's own:
-//   2. Wave s finishes sample s with lane = atom: softmax per action, expectations, a*, the
-//      projection (p'_j and b_j by lane shuffles), loss, priority and the dhead row, which
-//      it also leaves in LDS.
+// c51_head_kernel: one block of DIST_NT threads per DIST_SPB samples, run by csrc/dist_head.h's
+// dist_head_frame (staging the activation rows, the logits, the sample's batch row, the dhead
+// row and dH: shared with the quantile head, csrc/qr_head.hip).  The kernel hands the frame
+// its phase 2, per sample with lane = atom: a* (c51_astar), the projection (p'_j and b_j by
+// lane shuffles), then the S_t pass (c51_st_pass: softmax per action, expectations, loss,
+// priority, g).  hlg_head_kernel below shares both helpers and differs in the target row.
 // Nothing depends on the order blocks run in (no float atomics).
 //
 // c51_actor_head_kernel: one wave per env row, the logits as in phase 1 with the row in
@@ -50,98 +50,76 @@ __device__ __forceinline__ float c51_action(const DistRow& r, int a, int N, int 
   return wave_sum_dpp(p * z);
 }
 
+// double DQN: a* = the first maximum of the expected q over the actions of logits row L (wave-uniform)
+__device__ __forceinline__ int c51_astar(const float* L, const HeadParams& P, int A, int N, int lane, float z) {
+  const DistRow rn = dist_row(L, P, A, N, lane);
+  float best = -3.4e38f, p, lp;
+  int astar = 0;
+  for (int j = 0; j < A; ++j) {
+    const float q = c51_action(rn, j, N, lane, z, p, lp);
+    if (q > best) { best = q; astar = j; }
+  }
+  return __builtin_amdgcn_readfirstlane(astar);
+}
+
+// The S_t pass of both categorical heads against the target row m (this lane's mass): the expected q of every
+// action (q_out), the taken action's distribution, loss = -w sum_i m_i log p_i and td_abs = |ref - q[a_b]|
+// (ref(): sum_i m_i z_i for C51, y for HL-Gauss; a callable so that C51's wave sum stands beside the loss's and
+// the two reductions share packed adds); returns this lane's g.
+template <class Ref>
+__device__ __forceinline__ float c51_st_pass(const HeadIO& a, const DistSample& d, const float* L, int N, int lane,
+                                             float z, float m, Ref ref) {
+  const int A = a.A;
+  float p, lp, p_sa = 0.f, lp_sa = 0.f, q_sa = 0.f;
+  const DistRow rt = dist_row(L, a.Pon, A, N, lane);
+  for (int j = 0; j < A; ++j) {
+    const float q = c51_action(rt, j, N, lane, z, p, lp);
+    if (a.q_out != nullptr && d.live && lane == 0) a.q_out[(int64_t)d.b * A + j] = q;
+    if (j == d.a_b) { p_sa = p; lp_sa = lp; q_sa = q; }
+  }
+  const float ce = -wave_sum_dpp(m * lp_sa);
+  const float r = ref();
+  if (d.live && lane == 0) {
+    a.td_abs[d.b] = fabsf(r - q_sa);
+    a.loss[d.b] = d.w * ce;
+  }
+  return d.valid ? d.w * (p_sa - m) * a.grad_scale : 0.f;
+}
+
 template <bool RESCALE>
 __global__ void __launch_bounds__(DIST_NT) c51_head_kernel(C51Args ka) {
-  const HeadIO& a = ka.io;
   extern __shared__ __attribute__((aligned(16))) float c51_smem[];
-  constexpr int HS = DIST_HS, ROW = 2 * HS, SPB = DIST_SPB, NR = 3 * SPB;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int B = a.B, A = a.A, N = ka.N, AN = A * N, J = N + AN;
-  const int Jp = (J + 3) & ~3;
-  float* Hs = c51_smem;                  // [NR][ROW]: rows s (S_t), SPB + s (online S_t+n), 2 SPB + s (target)
-  float* Ls = c51_smem + NR * ROW;       // [NR][Jp] logits (no biases); rows s later hold the dhead rows
-  const int b0 = blockIdx.x * SPB;
-  const bool split = a.lo.Hon != nullptr;
-
-  dist_head_side(a, tid, lane, wv);
-  dist_head_stage(a, Hs, b0, tid, split);
-  __syncthreads();
-  dist_head_logits(a, N, Hs, Ls, Jp, lane, wv);
-  __syncthreads();
-
-  // ---- phase 2: wave s finishes sample s (lane = atom)
-  if (wv < SPB) {
-    const int s = wv;
-    const bool live = b0 + s < B;
-    const int b = min(b0 + s, B - 1);
-    const bool valid = lane < N;
+  const HeadIO& a = ka.io;
+  const int N = ka.N;
+  dist_head_frame(a, N, c51_smem, [&](const DistSample& d, const float* Ls, int Jp, int lane) {
+    constexpr int SPB = DIST_SPB;
     const float delta = (ka.vmax - ka.vmin) / (float)(N - 1);
     const float z = ka.vmin + (float)lane * delta;
-    const int a_b = a.act[b];
-    const float rew_b = a.rew[b], gam_b = a.gam[b];
-    const float w_b = a.isw != nullptr ? a.isw[b] : 1.f;
-    float p, lp;
-    // double DQN: a* from the online net at S_t+n (first maximum wins)
-    int astar = 0;
-    {
-      const DistRow rn = dist_row(Ls + (SPB + s) * Jp, a.Pon, A, N, lane);
-      float best = -3.4e38f;
-      for (int j = 0; j < A; ++j) {
-        const float q = c51_action(rn, j, N, lane, z, p, lp);
-        if (q > best) { best = q; astar = j; }
-      }
-      astar = __builtin_amdgcn_readfirstlane(astar);
-    }
+    const int astar = c51_astar(Ls + (SPB + d.s) * Jp, a.Pon, a.A, N, lane, z);
     // the target net's distribution of a*, projected onto the support
-    float m = 0.f;
-    {
-      const DistRow rg = dist_row(Ls + (2 * SPB + s) * Jp, a.Ptg, A, N, lane);
-      c51_action(rg, astar, N, lane, z, p, lp);
-      const float pj = valid ? p : 0.f;
-      float tz0;
-      if constexpr (RESCALE) tz0 = value_rescale_target(rew_b, gam_b, z, a.rescale_eps);
-      else tz0 = rew_b + gam_b * z;
-      const float tz = fminf(fmaxf(tz0, ka.vmin), ka.vmax);
-      const float bj = (tz - ka.vmin) / delta;
-      const float fi = (float)lane;
-      for (int j = 0; j < N; ++j) {      // increasing j: the oracle's order
-        const float pp = __shfl(pj, j, 64), bb = __shfl(bj, j, 64);
-        m += pp * fmaxf(0.f, 1.f - fabsf(bb - fi));
-      }
-      if (!valid) m = 0.f;
+    const DistRow rg = dist_row(Ls + (2 * SPB + d.s) * Jp, a.Ptg, a.A, N, lane);
+    float p, lp, m = 0.f;
+    c51_action(rg, astar, N, lane, z, p, lp);
+    const float pj = d.valid ? p : 0.f;
+    float tz0;
+    if constexpr (RESCALE) tz0 = value_rescale_target(d.rew, d.gam, z, a.rescale_eps);
+    else tz0 = d.rew + d.gam * z;
+    const float tz = fminf(fmaxf(tz0, ka.vmin), ka.vmax);
+    const float bj = (tz - ka.vmin) / delta;
+    const float fi = (float)lane;
+    for (int j = 0; j < N; ++j) {      // increasing j: the oracle's order
+      const float pp = __shfl(pj, j, 64), bb = __shfl(bj, j, 64);
+      m += pp * fmaxf(0.f, 1.f - fabsf(bb - fi));
     }
-    // S_t: expected q of every action, the taken action's distribution
-    float p_sa = 0.f, lp_sa = 0.f, q_sa = 0.f;
-    {
-      const DistRow rt = dist_row(Ls + s * Jp, a.Pon, A, N, lane);
-      for (int j = 0; j < A; ++j) {
-        const float q = c51_action(rt, j, N, lane, z, p, lp);
-        if (a.q_out != nullptr && live && lane == 0) a.q_out[(int64_t)b * A + j] = q;
-        if (j == a_b) { p_sa = p; lp_sa = lp; q_sa = q; }
-      }
-    }
-    const float ce = -wave_sum_dpp(m * lp_sa);
-    const float em = wave_sum_dpp(m * z);
-    const float g = valid ? w_b * (p_sa - m) * a.grad_scale : 0.f;
-    if (live && lane == 0) {
-      a.td_abs[b] = fabsf(em - q_sa);
-      a.loss[b] = w_b * ce;
-    }
-    // the dhead row: to memory, and into LDS (over the consumed S_t logits) for phase 3
-    dist_head_store_dhead(g, live, valid, a_b, A, N, lane, Ls + s * Jp, a.dhead + (int64_t)b * J);
-  }
-  __syncthreads();
-
-  dist_head_dh(a, N, Hs, Ls, Jp, b0, tid, split);
+    if (!d.valid) m = 0.f;
+    return c51_st_pass(a, d, Ls + d.s * Jp, N, lane, z, m, [&] { return wave_sum_dpp(m * z); });
+  });
 }
 
 APEX_EXPORT int apex_c51_head(C51Args a, hipStream_t st) {
   size_t lds = 0;
   if (!dist_head_args_ok(a.io, a.N, &lds) || !(a.vmin < a.vmax)) return (int)hipErrorInvalidValue;
-  const int grid = (a.io.B + DIST_SPB - 1) / DIST_SPB;
-  if (a.io.rescale_eps > 0.f) c51_head_kernel<true><<<grid, DIST_NT, lds, st>>>(a);
-  else c51_head_kernel<false><<<grid, DIST_NT, lds, st>>>(a);
-  APEX_CHECK_LAUNCH();
+  return dist_head_launch(c51_head_kernel<true>, c51_head_kernel<false>, a, lds, st);
 }
 
 // Histogram-loss (HL-Gauss) target on the same head (Runtime.dist_head = "hl_gauss"; Imani & White 2018,
@@ -165,95 +143,39 @@ static_assert(std::is_standard_layout_v<HlgArgs> && std::is_trivially_copyable_v
 
 template <bool RESCALE>
 __global__ void __launch_bounds__(DIST_NT) hlg_head_kernel(HlgArgs ka) {
-  const HeadIO& a = ka.io;
   extern __shared__ __attribute__((aligned(16))) float c51_smem[];
-  constexpr int HS = DIST_HS, ROW = 2 * HS, SPB = DIST_SPB, NR = 3 * SPB;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int B = a.B, A = a.A, N = ka.N, AN = A * N, J = N + AN;
-  const int Jp = (J + 3) & ~3;
-  float* Hs = c51_smem;                  // as c51_head_kernel
-  float* Ls = c51_smem + NR * ROW;
-  const int b0 = blockIdx.x * SPB;
-  const bool split = a.lo.Hon != nullptr;
-
-  dist_head_side(a, tid, lane, wv);
-  dist_head_stage(a, Hs, b0, tid, split);
-  __syncthreads();
-  dist_head_logits(a, N, Hs, Ls, Jp, lane, wv);
-  __syncthreads();
-
-  // ---- phase 2: wave s finishes sample s (lane = bin)
-  if (wv < SPB) {
-    const int s = wv;
-    const bool live = b0 + s < B;
-    const int b = min(b0 + s, B - 1);
-    const bool valid = lane < N;
+  const HeadIO& a = ka.io;
+  const int N = ka.N;
+  dist_head_frame(a, N, c51_smem, [&](const DistSample& d, const float* Ls, int Jp, int lane) {
+    constexpr int SPB = DIST_SPB;
     const float delta = (ka.vmax - ka.vmin) / (float)(N - 1);
     const float z = ka.vmin + (float)lane * delta;
-    const int a_b = a.act[b];
-    const float rew_b = a.rew[b], gam_b = a.gam[b];
-    const float w_b = a.isw != nullptr ? a.isw[b] : 1.f;
-    float p, lp;
-    // double DQN: a* from the online net at S_t+n (first maximum wins)
-    int astar = 0;
-    {
-      const DistRow rn = dist_row(Ls + (SPB + s) * Jp, a.Pon, A, N, lane);
-      float best = -3.4e38f;
-      for (int j = 0; j < A; ++j) {
-        const float q = c51_action(rn, j, N, lane, z, p, lp);
-        if (q > best) { best = q; astar = j; }
-      }
-      astar = __builtin_amdgcn_readfirstlane(astar);
-    }
+    const int astar = c51_astar(Ls + (SPB + d.s) * Jp, a.Pon, a.A, N, lane, z);
     // the scalar target from the target net's expectation of a*, then its Gaussian mass per bin
-    float y, m;
-    {
-      const DistRow rg = dist_row(Ls + (2 * SPB + s) * Jp, a.Ptg, A, N, lane);
-      const float qg = c51_action(rg, astar, N, lane, z, p, lp);
-      float y0;
-      if constexpr (RESCALE) y0 = value_rescale_target(rew_b, gam_b, qg, a.rescale_eps);
-      else y0 = rew_b + gam_b * qg;
-      y = fminf(fmaxf(y0, ka.vmin), ka.vmax);
-      const double vmin = (double)ka.vmin;
-      const double dl = ((double)ka.vmax - vmin) / (double)(N - 1);
-      const double inv = 1.0 / ((double)ka.sigma_ratio * dl * 1.4142135623730951);
-      const double i0 = (double)min(lane, N - 1);            // (a lane past N repeats the last bin)
-      const double Elo = erf((vmin + (i0 - 0.5) * dl - (double)y) * inv);
-      const double Ehi = erf((vmin + (i0 + 0.5) * dl - (double)y) * inv);
-      const double E0 = __shfl(Elo, 0, 64), EN = __shfl(Ehi, N - 1, 64);
-      m = valid ? (float)((Ehi - Elo) / (EN - E0)) : 0.f;
-    }
-    // S_t: expected q of every action, the taken action's distribution
-    float p_sa = 0.f, lp_sa = 0.f, q_sa = 0.f;
-    {
-      const DistRow rt = dist_row(Ls + s * Jp, a.Pon, A, N, lane);
-      for (int j = 0; j < A; ++j) {
-        const float q = c51_action(rt, j, N, lane, z, p, lp);
-        if (a.q_out != nullptr && live && lane == 0) a.q_out[(int64_t)b * A + j] = q;
-        if (j == a_b) { p_sa = p; lp_sa = lp; q_sa = q; }
-      }
-    }
-    const float ce = -wave_sum_dpp(m * lp_sa);
-    const float g = valid ? w_b * (p_sa - m) * a.grad_scale : 0.f;
-    if (live && lane == 0) {
-      a.td_abs[b] = fabsf(y - q_sa);
-      a.loss[b] = w_b * ce;
-    }
-    dist_head_store_dhead(g, live, valid, a_b, A, N, lane, Ls + s * Jp, a.dhead + (int64_t)b * J);
-  }
-  __syncthreads();
-
-  dist_head_dh(a, N, Hs, Ls, Jp, b0, tid, split);
+    const DistRow rg = dist_row(Ls + (2 * SPB + d.s) * Jp, a.Ptg, a.A, N, lane);
+    float p, lp;
+    const float qg = c51_action(rg, astar, N, lane, z, p, lp);
+    float y0;
+    if constexpr (RESCALE) y0 = value_rescale_target(d.rew, d.gam, qg, a.rescale_eps);
+    else y0 = d.rew + d.gam * qg;
+    const float y = fminf(fmaxf(y0, ka.vmin), ka.vmax);
+    const double vmin = (double)ka.vmin;
+    const double dl = ((double)ka.vmax - vmin) / (double)(N - 1);
+    const double inv = 1.0 / ((double)ka.sigma_ratio * dl * 1.4142135623730951);
+    const double i0 = (double)min(lane, N - 1);            // (a lane past N repeats the last bin)
+    const double Elo = erf((vmin + (i0 - 0.5) * dl - (double)y) * inv);
+    const double Ehi = erf((vmin + (i0 + 0.5) * dl - (double)y) * inv);
+    const double E0 = __shfl(Elo, 0, 64), EN = __shfl(Ehi, N - 1, 64);
+    const float m = d.valid ? (float)((Ehi - Elo) / (EN - E0)) : 0.f;
+    return c51_st_pass(a, d, Ls + d.s * Jp, N, lane, z, m, [&] { return y; });
+  });
 }
 
 APEX_EXPORT int apex_hlg_head(HlgArgs a, hipStream_t st) {
   size_t lds = 0;
   if (!dist_head_args_ok(a.io, a.N, &lds) || !(a.vmin < a.vmax) || !(a.sigma_ratio > 0.f) || !std::isfinite(a.sigma_ratio))
     return (int)hipErrorInvalidValue;
-  const int grid = (a.io.B + DIST_SPB - 1) / DIST_SPB;
-  if (a.io.rescale_eps > 0.f) hlg_head_kernel<true><<<grid, DIST_NT, lds, st>>>(a);
-  else hlg_head_kernel<false><<<grid, DIST_NT, lds, st>>>(a);
-  APEX_CHECK_LAUNCH();
+  return dist_head_launch(hlg_head_kernel<true>, hlg_head_kernel<false>, a, lds, st);
 }
 
 // Actor side: expected q of the distributional head + epsilon-greedy, one wave per env row

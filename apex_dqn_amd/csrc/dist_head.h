@@ -2,7 +2,9 @@
 // quantile regression).  Both read the head weights as wv [N][HS], bv [N], wa [A N][HS] (row
 // a N + i = action a, atom / quantile i), ba [A N]; HS = 512, N <= 64 (lane = atom), and both
 // leave dhead [B][(A + 1) N] and dH.  A head kernel is one block of DIST_NT threads per
-// DIST_SPB samples:
+// DIST_SPB samples, and its body is dist_head_frame: the LDS carve-up, the phases below with
+// their barriers, and between phases 1 and 3 the head's own phase 2, a callable the kernel
+// hands in.  A kernel is its shared-memory declaration, that call and its phase 2.
 //
 //   dist_head_side     zeroes the head-gradient region, leaves the batch-max IS statistic
 //   dist_head_stage    phase 0: the 3 DIST_SPB activation rows (online S_t, online S_t+n,
@@ -16,8 +18,10 @@
 //                      four DPP steps.  A block reads both weight sets once for DIST_SPB
 //                      samples; the next group's weights are loaded while the current one
 //                      is multiplied.
-//   (phase 2 is the kernel's own: wave s finishes sample s with lane = atom and leaves the
-//    dhead row of sample s in LDS over the consumed S_t logits)
+//   phase 2            wave s finishes sample s with lane = atom: the frame reads the sample's
+//                      row of the batch (DistSample), calls the head's callable for td_abs,
+//                      loss, q_out and this lane's g, and leaves the dhead row in memory and in
+//                      LDS over the consumed S_t logits (dist_head_store_dhead)
 //   dist_head_dh       phase 3: dH for the block's samples: the threads form four groups of
 //                      128, a thread holds four columns, group q adds rows q, q + 4, .. of
 //                      dhead . W (float4 weight loads, the coefficients broadcast from LDS);
@@ -283,12 +287,67 @@ __device__ __forceinline__ void dist_head_dh(const HeadIO& a, int N, float* Hs, 
   }
 }
 
+// What phase 2 is handed: wave s finishes sample s = row b of the batch (a sample past the batch repeats the
+// last row with live = false and stores nothing); valid = lane < N.
+struct DistSample {
+  int s, b, a_b;
+  bool live, valid;
+  float rew, gam, w;    // R, Gamma and the IS weight (1 without one) of row b
+};
+
+// A head kernel's body.  `smem`: dist_head_lds floats.  `finish(d, Ls, Jp, lane)` is the head's phase 2 for one
+// sample: rows d.s, SPB + d.s and 2 SPB + d.s of Ls [3 SPB][Jp] hold the logits of S_t, online S_t+n and target
+// S_t+n; it stores td_abs, loss and q_out of a live sample and returns this lane's g.
+template <class Finish>
+__device__ __forceinline__ void dist_head_frame(const HeadIO& a, int N, float* smem, Finish finish) {
+  constexpr int ROW = 2 * DIST_HS, SPB = DIST_SPB, NR = 3 * SPB;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int J = N + a.A * N, Jp = (J + 3) & ~3;
+  float* Hs = smem;                      // [NR][ROW]: rows s (S_t), SPB + s (online S_t+n), 2 SPB + s (target)
+  float* Ls = smem + NR * ROW;           // [NR][Jp] logits (no biases); rows s later hold the dhead rows
+  const int b0 = blockIdx.x * SPB;
+  const bool split = a.lo.Hon != nullptr;
+
+  dist_head_side(a, tid, lane, wv);
+  dist_head_stage(a, Hs, b0, tid, split);
+  __syncthreads();
+  dist_head_logits(a, N, Hs, Ls, Jp, lane, wv);
+  __syncthreads();
+
+  if (wv < SPB) {
+    DistSample d;
+    d.s = wv;
+    d.live = b0 + d.s < a.B;
+    d.b = min(b0 + d.s, a.B - 1);
+    d.valid = lane < N;
+    d.a_b = a.act[d.b];
+    d.rew = a.rew[d.b];
+    d.gam = a.gam[d.b];
+    d.w = a.isw != nullptr ? a.isw[d.b] : 1.f;
+    const float g = finish(d, Ls, Jp, lane);
+    dist_head_store_dhead(g, d.live, d.valid, d.a_b, a.A, N, lane, Ls + d.s * Jp, a.dhead + (int64_t)d.b * J);
+  }
+  __syncthreads();
+
+  dist_head_dh(a, N, Hs, Ls, Jp, b0, tid, split);
+}
+
 // head_io_ok plus what the C51 / QR launchers share of their own: the N range, the stream width
 // and the LDS bound; the LDS in `lds`.
 static inline bool dist_head_args_ok(const HeadIO& a, int N, size_t* lds) {
   if (!head_io_ok(a) || N < 2 || N > 64 || a.hidden != DIST_HS) return false;
   *lds = dist_head_lds(a.A, N);
   return *lds <= 65536;     // (A + 1) N <= 1706 logits per row
+}
+
+// How the three launchers close: one block per DIST_SPB samples, the kernel instantiated for value rescaling
+// when HeadIO.rescale_eps > 0.
+template <class Args>
+static inline int dist_head_launch(void (*rescale)(Args), void (*plain)(Args), const Args& a, size_t lds,
+                                   hipStream_t st) {
+  const int grid = (a.io.B + DIST_SPB - 1) / DIST_SPB;
+  (a.io.rescale_eps > 0.f ? rescale : plain)<<<grid, DIST_NT, lds, st>>>(a);
+  APEX_CHECK_LAUNCH();
 }
 
 // Actor heads: the logits (no biases) of env row `e` -> L [Jp], one wave, the row's

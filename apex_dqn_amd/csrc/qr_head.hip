@@ -21,9 +21,9 @@
 // transformed T_j, summed in increasing j -- the shortcut through q_target no longer equals it.
 //   dH         = dhead . W, masked by the stream ReLUs (bf16, or hi / lo planes)
 //
-// qr_head_kernel: one block of DIST_NT threads per DIST_SPB samples.  Staging the
-// activation rows, the logits and dH (phases 0, 1 and 3) are csrc/dist_head.h's, shared
-// with the categorical head; phase 2 is this head's own:
+// qr_head_kernel: one block of DIST_NT threads per DIST_SPB samples, run by csrc/dist_head.h's
+// dist_head_frame (staging the activation rows, the logits, the sample's batch row, the dhead
+// row and dH: shared with the categorical heads).  The kernel hands the frame its phase 2:
 //   2. Wave s finishes sample s with lane = quantile.  The three theta rows come from the
 //      LDS logits; q per action is one wave sum; a* is made wave-uniform; each lane keeps
 //      its T_j, and the j loop reads lane j of it (j is wave-uniform: a lane read, no
@@ -51,38 +51,18 @@ __device__ __forceinline__ float qr_theta(const DistRow& r, int a, int N, int la
 
 template <bool RESCALE>
 __global__ void __launch_bounds__(DIST_NT) qr_head_kernel(QRArgs ka) {
-  const HeadIO& a = ka.io;
   extern __shared__ __attribute__((aligned(16))) float qr_smem[];
-  constexpr int HS = DIST_HS, ROW = 2 * HS, SPB = DIST_SPB, NR = 3 * SPB;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int B = a.B, A = a.A, N = ka.N, AN = A * N, J = N + AN;
-  const int Jp = (J + 3) & ~3;
-  float* Hs = qr_smem;                   // [NR][ROW]: rows s (S_t), SPB + s (online S_t+n), 2 SPB + s (target)
-  float* Ls = qr_smem + NR * ROW;        // [NR][Jp] logits (no biases); rows s later hold the dhead rows
-  const int b0 = blockIdx.x * SPB;
-  const bool split = a.lo.Hon != nullptr;
-
-  dist_head_side(a, tid, lane, wv);
-  dist_head_stage(a, Hs, b0, tid, split);
-  __syncthreads();
-  dist_head_logits(a, N, Hs, Ls, Jp, lane, wv);
-  __syncthreads();
-
-  // ---- phase 2: wave s finishes sample s (lane = quantile)
-  if (wv < SPB) {
-    const int s = wv;
-    const bool live = b0 + s < B;
-    const int b = min(b0 + s, B - 1);
-    const bool valid = lane < N;
+  const HeadIO& a = ka.io;
+  const int N = ka.N;
+  dist_head_frame(a, N, qr_smem, [&](const DistSample& d, const float* Ls, int Jp, int lane) {
+    constexpr int SPB = DIST_SPB;
+    const int A = a.A;
     const float invN = 1.0f / (float)N;
-    const int a_b = a.act[b];
-    const float rew_b = a.rew[b], gam_b = a.gam[b];
-    const float w_b = a.isw != nullptr ? a.isw[b] : 1.f;
     const float kappa = ka.kappa;
     // double DQN: a* from the online net at S_t+n (first maximum wins)
     int astar = 0;
     {
-      const DistRow rn = dist_row(Ls + (SPB + s) * Jp, a.Pon, A, N, lane);
+      const DistRow rn = dist_row(Ls + (SPB + d.s) * Jp, a.Pon, A, N, lane);
       float best = -3.4e38f;
       for (int j = 0; j < A; ++j) {
         const float q = wave_sum_dpp(qr_theta(rn, j, N, lane)) * invN;
@@ -93,21 +73,21 @@ __global__ void __launch_bounds__(DIST_NT) qr_head_kernel(QRArgs ka) {
     // the target samples: lane j holds T_j
     float T;
     {
-      const DistRow rg = dist_row(Ls + (2 * SPB + s) * Jp, a.Ptg, A, N, lane);
+      const DistRow rg = dist_row(Ls + (2 * SPB + d.s) * Jp, a.Ptg, A, N, lane);
       if constexpr (RESCALE)
-        T = valid ? value_rescale_target(rew_b, gam_b, qr_theta(rg, astar, N, lane), a.rescale_eps) : 0.f;
+        T = d.valid ? value_rescale_target(d.rew, d.gam, qr_theta(rg, astar, N, lane), a.rescale_eps) : 0.f;
       else
-        T = valid ? rew_b + gam_b * qr_theta(rg, astar, N, lane) : 0.f;
+        T = d.valid ? d.rew + d.gam * qr_theta(rg, astar, N, lane) : 0.f;
     }
     // S_t: q of every action, the taken action's quantiles
     float th_sa = 0.f, q_sa = 0.f;
     {
-      const DistRow rt = dist_row(Ls + s * Jp, a.Pon, A, N, lane);
+      const DistRow rt = dist_row(Ls + d.s * Jp, a.Pon, A, N, lane);
       for (int j = 0; j < A; ++j) {
         const float th = qr_theta(rt, j, N, lane);
         const float q = wave_sum_dpp(th) * invN;
-        if (a.q_out != nullptr && live && lane == 0) a.q_out[(int64_t)b * A + j] = q;
-        if (j == a_b) { th_sa = th; q_sa = q; }
+        if (a.q_out != nullptr && d.live && lane == 0) a.q_out[(int64_t)d.b * A + j] = q;
+        if (j == d.a_b) { th_sa = th; q_sa = q; }
       }
     }
     // this lane's quantile against every target sample, in increasing j
@@ -124,30 +104,22 @@ __global__ void __launch_bounds__(DIST_NT) qr_head_kernel(QRArgs ka) {
       c += wgt * fminf(fmaxf(u, -kappa), kappa);
     }
     const float sc = invN / kappa;
-    const float ls = wave_sum_dpp(valid ? rho * sc : 0.f);
+    const float ls = wave_sum_dpp(d.valid ? rho * sc : 0.f);
     float et;
     if constexpr (RESCALE) et = tsum * invN;
     else et = wave_sum_dpp(T) * invN;
-    const float g = valid ? -w_b * a.grad_scale * (c * sc) : 0.f;
-    if (live && lane == 0) {
-      a.td_abs[b] = fabsf(et - q_sa);
-      a.loss[b] = w_b * ls;
+    if (d.live && lane == 0) {
+      a.td_abs[d.b] = fabsf(et - q_sa);
+      a.loss[d.b] = d.w * ls;
     }
-    // the dhead row: to memory, and into LDS (over the consumed S_t logits) for phase 3
-    dist_head_store_dhead(g, live, valid, a_b, A, N, lane, Ls + s * Jp, a.dhead + (int64_t)b * J);
-  }
-  __syncthreads();
-
-  dist_head_dh(a, N, Hs, Ls, Jp, b0, tid, split);
+    return d.valid ? -d.w * a.grad_scale * (c * sc) : 0.f;
+  });
 }
 
 APEX_EXPORT int apex_qr_head(QRArgs a, hipStream_t st) {
   size_t lds = 0;
   if (!dist_head_args_ok(a.io, a.N, &lds) || !(a.kappa > 0.f)) return (int)hipErrorInvalidValue;
-  const int grid = (a.io.B + DIST_SPB - 1) / DIST_SPB;
-  if (a.io.rescale_eps > 0.f) qr_head_kernel<true><<<grid, DIST_NT, lds, st>>>(a);
-  else qr_head_kernel<false><<<grid, DIST_NT, lds, st>>>(a);
-  APEX_CHECK_LAUNCH();
+  return dist_head_launch(qr_head_kernel<true>, qr_head_kernel<false>, a, lds, st);
 }
 
 // Actor side: q = mean of the quantiles + epsilon-greedy, one wave per env row (four per

@@ -301,28 +301,47 @@ class TorchBackend:
         |sum_i m_i z_i - q(S_t)[a]|, ``dhead [B, (A + 1) N]`` (value atoms, then action a's
         atoms at N + a N), ``q_out`` the expected q(S_t).  Computes in the head weights'
         dtype when that is fp64 (the tests' reference), else fp32."""
+        def target(p_g, z):
+            m = self._c51_m(p_g, rew, gam, v_min, v_max, rescale_eps)
+            return m, (m * z).sum(-1)
+        self._categorical_head(Hon, Htg, Pon, Ptg, act, isw, num_atoms, v_min, v_max, grad_scale, td_abs, loss, dH,
+                               dhead, q_out, zero, lo, isn, target)
+
+    def _dist_head(self, Hon, Htg, Pon, act, isw, num_atoms, td_abs, loss, dH, dhead, q_out, zero, lo, isn, rows):
+        """What :meth:`c51_head`, :meth:`hlg_head` and :meth:`qr_head` share: the planes joined in the head's
+        dtype, then ``rows(Hon, Htg, A, N, dt, ar, w)`` -> ``(q_t [B, A], td [B], loss [B], g [B, N])`` of the
+        head (``ar`` = arange(B), ``w`` the IS weights or ones), then the outputs and the dueling backward."""
         B, N = act.shape[0], int(num_atoms)
         A = Pon["wa"].shape[0] // N
         dt = _head_dtype(Pon["wv"])
         lo = lo if lo is not None else (None, None, None)
         Hon, Htg = join(Hon, lo[0], dt), join(Htg, lo[1], dt)
-        delta = (float(v_max) - float(v_min)) / (N - 1)
-        z = float(v_min) + torch.arange(N, dtype=dt, device=Hon.device) * delta
         ar = torch.arange(B, device=Hon.device)
-        lp_t = self._c51_logp(Hon[:B], Pon, A, N, dt)
-        q_t = (lp_t.exp() * z).sum(-1)
-        q_n = (self._c51_logp(Hon[B:2 * B], Pon, A, N, dt).exp() * z).sum(-1)
-        a_star = q_n.argmax(1)
-        p_g = self._c51_logp(Htg[:B], Ptg, A, N, dt)[ar, a_star].exp()
-        m = self._c51_m(p_g, rew, gam, v_min, v_max, rescale_eps)
-        lp = lp_t[ar, act.long()]
-        p = lp.exp()
         w = isw.to(dt) if isw is not None else torch.ones(B, dtype=dt, device=Hon.device)
-        td_abs.copy_(((m * z).sum(-1) - (p * z).sum(-1)).abs())
-        loss.copy_(-w * (m * lp).sum(-1))
-        g = w[:, None] * (p - m) * grad_scale                      # d loss / d logits of (a_b, .)
+        q_t, td, loss_row, g = rows(Hon, Htg, A, N, dt, ar, w)
+        td_abs.copy_(td)
+        loss.copy_(loss_row)
         self._dueling_bwd(g, act, Pon, Hon[:B], dH, dhead, lo[2], dt)
         self._head_close(q_out, q_t, zero, isn, w.float())
+
+    def _categorical_head(self, Hon, Htg, Pon, Ptg, act, isw, num_atoms, v_min, v_max, grad_scale, td_abs, loss, dH,
+                          dhead, q_out, zero, lo, isn, target):
+        """The categorical rows of :meth:`c51_head` and :meth:`hlg_head`: ``target(p_g, z)`` -> ``(m [B, N], ref
+        [B])`` from the target net's distribution of the double-DQN action; loss = -w sum_i m_i log p(S_t)[a, i],
+        td_abs = |ref - q(S_t)[a]|."""
+        def rows(Hon, Htg, A, N, dt, ar, w):
+            B = ar.shape[0]
+            delta = (float(v_max) - float(v_min)) / (N - 1)
+            z = float(v_min) + torch.arange(N, dtype=dt, device=Hon.device) * delta
+            lp_t = self._c51_logp(Hon[:B], Pon, A, N, dt)
+            q_t = (lp_t.exp() * z).sum(-1)
+            a_star = (self._c51_logp(Hon[B:2 * B], Pon, A, N, dt).exp() * z).sum(-1).argmax(1)
+            m, ref = target(self._c51_logp(Htg[:B], Ptg, A, N, dt)[ar, a_star].exp(), z)
+            lp = lp_t[ar, act.long()]
+            p = lp.exp()
+            g = w[:, None] * (p - m) * grad_scale                      # d loss / d logits of (a_b, .)
+            return q_t, (ref - (p * z).sum(-1)).abs(), -w * (m * lp).sum(-1), g
+        self._dist_head(Hon, Htg, Pon, act, isw, num_atoms, td_abs, loss, dH, dhead, q_out, zero, lo, isn, rows)
 
     @staticmethod
     def _c51_m(p_g, rew, gam, v_min, v_max, rescale_eps):
@@ -354,33 +373,18 @@ class TorchBackend:
         (learner/losses.py ``hl_gauss_target``: fp64 on y, rounded to the head's dtype once), loss = -w sum_i m_i
         log p(S_t)[a, i], td_abs = |y - q(S_t)[a]|; every output laid out as :meth:`c51_head`'s."""
         from ..learner.losses import hl_gauss_target
-        B, N = act.shape[0], int(num_atoms)
-        A = Pon["wa"].shape[0] // N
-        dt = _head_dtype(Pon["wv"])
-        lo = lo if lo is not None else (None, None, None)
-        Hon, Htg = join(Hon, lo[0], dt), join(Htg, lo[1], dt)
-        delta = (float(v_max) - float(v_min)) / (N - 1)
-        z = float(v_min) + torch.arange(N, dtype=dt, device=Hon.device) * delta
-        ar = torch.arange(B, device=Hon.device)
-        lp_t = self._c51_logp(Hon[:B], Pon, A, N, dt)
-        q_t = (lp_t.exp() * z).sum(-1)
-        a_star = (self._c51_logp(Hon[B:2 * B], Pon, A, N, dt).exp() * z).sum(-1).argmax(1)
-        q_g = (self._c51_logp(Htg[:B], Ptg, A, N, dt)[ar, a_star].exp() * z).sum(-1)
-        if rescale_eps is None:
-            y0 = rew.to(dt) + gam.to(dt) * q_g
-        else:
-            y0 = rescale_target(rew.to(dt).double(), gam.to(dt).double(), q_g.double(),
-                                _lib.rescale_eps_arg(rescale_eps)).to(dt)
-        y = y0.clamp(float(v_min), float(v_max))
-        m = hl_gauss_target(y, v_min, v_max, N, sigma_ratio)
-        lp = lp_t[ar, act.long()]
-        p = lp.exp()
-        w = isw.to(dt) if isw is not None else torch.ones(B, dtype=dt, device=Hon.device)
-        td_abs.copy_((y - (p * z).sum(-1)).abs())
-        loss.copy_(-w * (m * lp).sum(-1))
-        g = w[:, None] * (p - m) * grad_scale                      # d loss / d logits of (a_b, .)
-        self._dueling_bwd(g, act, Pon, Hon[:B], dH, dhead, lo[2], dt)
-        self._head_close(q_out, q_t, zero, isn, w.float())
+
+        def target(p_g, z):
+            q_g = (p_g * z).sum(-1)
+            if rescale_eps is None:
+                y0 = rew.to(z.dtype) + gam.to(z.dtype) * q_g
+            else:
+                y0 = rescale_target(rew.to(z.dtype).double(), gam.to(z.dtype).double(), q_g.double(),
+                                    _lib.rescale_eps_arg(rescale_eps)).to(z.dtype)
+            y = y0.clamp(float(v_min), float(v_max))
+            return hl_gauss_target(y, v_min, v_max, int(num_atoms), sigma_ratio), y
+        self._categorical_head(Hon, Htg, Pon, Ptg, act, isw, num_atoms, v_min, v_max, grad_scale, td_abs, loss, dH,
+                               dhead, q_out, zero, lo, isn, target)
 
     def c51_actor_head(self, H, P, eps, ctr, seed, num_atoms: int, v_min: float, v_max: float, q_out, a_out,
                        H_lo=None):
@@ -415,26 +419,19 @@ class TorchBackend:
         q(S_t)[a]|, ``dhead`` / ``dH`` / ``q_out`` laid out as :meth:`c51_head`'s.  Computes in
         the head weights' dtype when that is fp64 (the tests' reference), else fp32."""
         from ..learner.losses import quantile_huber_terms
-        B, N = act.shape[0], int(num_atoms)
-        A = Pon["wa"].shape[0] // N
-        dt = _head_dtype(Pon["wv"])
         if not float(kappa) > 0.0:
             raise ValueError(f"qr_head: kappa must be > 0, got {kappa}")
-        lo = lo if lo is not None else (None, None, None)
-        Hon, Htg = join(Hon, lo[0], dt), join(Htg, lo[1], dt)
-        ar = torch.arange(B, device=Hon.device)
-        th_t = self._qr_theta(Hon[:B], Pon, A, N, dt)
-        q_t = th_t.mean(-1)
-        a_star = self._qr_theta(Hon[B:2 * B], Pon, A, N, dt).mean(-1).argmax(1)
-        T = self._quantile_T(rew.to(dt), gam.to(dt), self._qr_theta(Htg[:B], Ptg, A, N, dt)[ar, a_star], rescale_eps)
-        th = th_t[ar, act.long()]
-        rho, c = quantile_huber_terms(th, T, kappa)
-        w = isw.to(dt) if isw is not None else torch.ones(B, dtype=dt, device=Hon.device)
-        td_abs.copy_((T.mean(-1) - th.mean(-1)).abs())
-        loss.copy_(w * rho.sum(-1))
-        g = -w[:, None] * grad_scale * c                           # d loss / d theta of (a_b, .)
-        self._dueling_bwd(g, act, Pon, Hon[:B], dH, dhead, lo[2], dt)
-        self._head_close(q_out, q_t, zero, isn, w.float())
+
+        def rows(Hon, Htg, A, N, dt, ar, w):
+            B = ar.shape[0]
+            th_t = self._qr_theta(Hon[:B], Pon, A, N, dt)
+            a_star = self._qr_theta(Hon[B:2 * B], Pon, A, N, dt).mean(-1).argmax(1)
+            T = self._quantile_T(rew.to(dt), gam.to(dt), self._qr_theta(Htg[:B], Ptg, A, N, dt)[ar, a_star], rescale_eps)
+            th = th_t[ar, act.long()]
+            rho, c = quantile_huber_terms(th, T, kappa)
+            g = -w[:, None] * grad_scale * c                           # d loss / d theta of (a_b, .)
+            return th_t.mean(-1), (T.mean(-1) - th.mean(-1)).abs(), w * rho.sum(-1), g
+        self._dist_head(Hon, Htg, Pon, act, isw, num_atoms, td_abs, loss, dH, dhead, q_out, zero, lo, isn, rows)
 
     @staticmethod
     def _quantile_T(rew, gam, theta, rescale_eps):
@@ -1118,31 +1115,33 @@ class HipBackend(TorchBackend):
         assert q_out is None or (q_out.shape == (B, A) and q_out.is_contiguous())
         _lib.check(self.lib.apex_mdqn_head(a, _lib.stream_ptr()), "mdqn_head")
 
-    def c51_head(self, Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, v_min, v_max, grad_scale, td_abs, loss,
-                 dH, dhead, q_out=None, zero=None, lo=None, isn=None, rescale_eps=None):
-        """csrc/c51_head.hip ``c51_head_kernel`` (reads h: the fc epilogue is not deferred)."""
+    def _dist_head_launch(self, a, symbol, Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, grad_scale, td_abs, loss,
+                          dH, dhead, q_out, zero, lo, isn, rescale_eps) -> None:
+        """Launch ``apex_<symbol>`` with the argument struct ``a``, whose scalar fields but ``N`` the caller has
+        set (the three heads of csrc/dist_head.h's frame; they read h: the fc epilogue is not deferred)."""
         assert getattr(self, "_fc_part", None) is None, "the distributional head reads h: fc epilogue deferred"
-        N = int(num_atoms)
-        a = _lib.C51Args()
+        a.N = N = int(num_atoms)
         B, A = act.shape[0], Pon["wa"].shape[0] // N
         self._head_io(a.io, Hon, Htg, Pon, Ptg, act, rew, gam, isw, A, Pon["wv"].shape[-1], grad_scale, td_abs, loss,
                       dH, dhead, q_out, zero, lo, isn, rescale_eps)
-        a.N, a.vmin, a.vmax = N, float(v_min), float(v_max)
         assert dhead.shape == (B, (A + 1) * N) and dhead.is_contiguous()
-        _lib.check(self.lib.apex_c51_head(a, _lib.stream_ptr()), "c51_head")
+        _lib.check(getattr(self.lib, "apex_" + symbol)(a, _lib.stream_ptr()), symbol)
+
+    def c51_head(self, Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, v_min, v_max, grad_scale, td_abs, loss,
+                 dH, dhead, q_out=None, zero=None, lo=None, isn=None, rescale_eps=None):
+        """csrc/c51_head.hip ``c51_head_kernel``."""
+        a = _lib.C51Args()
+        a.vmin, a.vmax = float(v_min), float(v_max)
+        self._dist_head_launch(a, "c51_head", Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, grad_scale, td_abs,
+                               loss, dH, dhead, q_out, zero, lo, isn, rescale_eps)
 
     def hlg_head(self, Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, v_min, v_max, sigma_ratio, grad_scale,
                  td_abs, loss, dH, dhead, q_out=None, zero=None, lo=None, isn=None, rescale_eps=None):
-        """csrc/c51_head.hip ``hlg_head_kernel`` (reads h: the fc epilogue is not deferred)."""
-        assert getattr(self, "_fc_part", None) is None, "the distributional head reads h: fc epilogue deferred"
-        N = int(num_atoms)
+        """csrc/c51_head.hip ``hlg_head_kernel``."""
         a = _lib.HlgArgs()
-        B, A = act.shape[0], Pon["wa"].shape[0] // N
-        self._head_io(a.io, Hon, Htg, Pon, Ptg, act, rew, gam, isw, A, Pon["wv"].shape[-1], grad_scale, td_abs, loss,
-                      dH, dhead, q_out, zero, lo, isn, rescale_eps)
-        a.N, a.vmin, a.vmax, a.sigma_ratio = N, float(v_min), float(v_max), float(sigma_ratio)
-        assert dhead.shape == (B, (A + 1) * N) and dhead.is_contiguous()
-        _lib.check(self.lib.apex_hlg_head(a, _lib.stream_ptr()), "hlg_head")
+        a.vmin, a.vmax, a.sigma_ratio = float(v_min), float(v_max), float(sigma_ratio)
+        self._dist_head_launch(a, "hlg_head", Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, grad_scale, td_abs,
+                               loss, dH, dhead, q_out, zero, lo, isn, rescale_eps)
 
     def _actor_io(self, io, H, P, eps, ctr, seed, q_out, a_out, H_lo) -> None:
         """Fill ``io``, the block every actor head takes (``_lib.ActorIO``); ``E`` and ``A`` are ``q_out``'s."""
@@ -1159,16 +1158,11 @@ class HipBackend(TorchBackend):
 
     def qr_head(self, Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, kappa, grad_scale, td_abs, loss,
                 dH, dhead, q_out=None, zero=None, lo=None, isn=None, rescale_eps=None):
-        """csrc/qr_head.hip ``qr_head_kernel`` (reads h: the fc epilogue is not deferred)."""
-        assert getattr(self, "_fc_part", None) is None, "the distributional head reads h: fc epilogue deferred"
-        N = int(num_atoms)
+        """csrc/qr_head.hip ``qr_head_kernel``."""
         a = _lib.QRArgs()
-        B, A = act.shape[0], Pon["wa"].shape[0] // N
-        self._head_io(a.io, Hon, Htg, Pon, Ptg, act, rew, gam, isw, A, Pon["wv"].shape[-1], grad_scale, td_abs, loss,
-                      dH, dhead, q_out, zero, lo, isn, rescale_eps)
-        a.N, a.kappa = N, float(kappa)
-        assert dhead.shape == (B, (A + 1) * N) and dhead.is_contiguous()
-        _lib.check(self.lib.apex_qr_head(a, _lib.stream_ptr()), "qr_head")
+        a.kappa = float(kappa)
+        self._dist_head_launch(a, "qr_head", Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, grad_scale, td_abs,
+                               loss, dH, dhead, q_out, zero, lo, isn, rescale_eps)
 
     def qr_actor_head(self, H, P, eps, ctr, seed, num_atoms, q_out, a_out, H_lo=None):
         a = _lib.QRActorArgs()

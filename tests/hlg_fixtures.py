@@ -4,6 +4,7 @@ tests/test_hlgauss_cpu.py (the fixture and tolerance checks that need no GPU) an
 import functools
 
 import torch
+from head_fixtures import split_planes
 
 VMIN, VMAX = -10.0, 10.0
 SIGMA = 0.75            # Runtime.hl_gauss_sigma_ratio's default
@@ -11,8 +12,10 @@ EPS = 1e-3              # Runtime.value_rescale_eps of the rescaled case
 WSCALE = 2.0            # the sampler's factor handed to the IS statistic (a power of two: the division is exact)
 SHAPES = [(64, 4, 51), (64, 18, 51), (64, 6, 21), (64, 3, 64), (5, 4, 51), (3, 3, 2)]
 EDGE = (8, 4, 51)
+FRAME_EDGE = (3, 2, 2)  # a block whose second sample is past the batch, fewer weight-row tasks (4) than waves
 EDGE_CASES = ("rew_hi", "rew_lo", "terminal", "no_isw")
 # tests/test_gpu_c51.py's seeds: generator seed 2, and 3 where seed 2 leaves a near-tie in the online argmax
+# (FRAME_EDGE keeps seed 2: top-2 gap 1.18 in both input modes, fp64 on the CPU)
 SEEDS = {(6, 21): 3, (3, 64): 3}
 
 # Every head problem the GPU file runs: (B, A, N, split, case, sigma_ratio, rescale_eps)
@@ -33,12 +36,6 @@ TOL = dict(td=(1e-4, 1e-4), loss=(1e-4, 1e-5), dH=(1e-2, 1e-6), dhead=(1e-4, DHE
            g=(1e-3, 1e-6))      # (rtol, atol); g: the four head weight gradients
 
 
-def _split_planes(x32):
-    hi = x32.to(torch.bfloat16)
-    lo = (x32 - hi.float()).to(torch.bfloat16)
-    return hi, lo
-
-
 @functools.lru_cache(maxsize=None)
 def fixture(B, A, N, split=False):
     """Inputs (CPU) of one head problem, drawn as tests/test_gpu_c51.py draws them: Hon, Htg, online head,
@@ -57,7 +54,7 @@ def fixture(B, A, N, split=False):
     gam[::7] = 0.0
     isw = torch.rand(B, generator=g)
     if split:
-        (Hon, Hon_lo), (Htg, Htg_lo) = _split_planes(Hon), _split_planes(Htg)
+        (Hon, Hon_lo), (Htg, Htg_lo) = split_planes(Hon), split_planes(Htg)
     else:
         Hon, Htg, Hon_lo, Htg_lo = Hon.to(torch.bfloat16), Htg.to(torch.bfloat16), None, None
     return dict(Hon=Hon, Htg=Htg, Hon_lo=Hon_lo, Htg_lo=Htg_lo, Pon=Pon, Ptg=Ptg, act=act, rew=rew, gam=gam, isw=isw)

@@ -3,6 +3,7 @@
 import functools
 
 import torch
+from head_fixtures import split_planes
 
 KAPPA = 1.0
 SEED = 12345            # Runtime.seed of the head problems
@@ -15,12 +16,6 @@ KINK = 1e-5             # |pre| below this in the fp64 oracle: a ReLU-mask flip 
 def seed_q():
     from apex_dqn_amd.learner.iqn import iqn_seed
     return iqn_seed(SEED)
-
-
-def _split_planes(x32):
-    hi = x32.to(torch.bfloat16)
-    lo = (x32 - hi.float()).to(torch.bfloat16)
-    return hi, lo
 
 
 @functools.lru_cache(maxsize=None)
@@ -46,7 +41,7 @@ def fixture(B, A, split=False):
         return {"wtau": torch.randn(1024, 64, generator=g) * 0.125, "btau": torch.randn(1024, generator=g) * 0.1 ** 0.5}
     Eon, Etg = E(), E()
     if split:
-        (Hon, Hon_lo), (Htg, Htg_lo) = _split_planes(Hon), _split_planes(Htg)
+        (Hon, Hon_lo), (Htg, Htg_lo) = split_planes(Hon), split_planes(Htg)
     else:
         Hon, Htg, Hon_lo, Htg_lo = Hon.to(torch.bfloat16), Htg.to(torch.bfloat16), None, None
     return dict(Hon=Hon, Htg=Htg, Hon_lo=Hon_lo, Htg_lo=Htg_lo, Pon=Pon, Ptg=Ptg, Eon=Eon, Etg=Etg, act=act, rew=rew,

@@ -5,6 +5,7 @@ resume and the GPU loop."""
 import numpy as np
 import pytest
 import torch
+from head_fixtures import fill_replay
 
 pytestmark = pytest.mark.gpu
 
@@ -180,15 +181,6 @@ def test_launcher_refusals(ring):
 
 
 # -------------------------------------------------------------- 4. whole step
-def _fill_replay(rp, K, A=6, seed=0):
-    rng = np.random.default_rng(seed)
-    seqs = rp.append_frames(rng.integers(0, 255, (K + 8, 84, 84), dtype=np.uint8))
-    st = np.stack([seqs[i:i + 4] for i in range(K)])
-    rp.insert(dict(S_t=st, S_tpn=st + 3, A_t=rng.integers(0, A, K), R=rng.normal(size=K).astype(np.float32),
-                   Gamma=np.where(rng.random(K) < 0.1, 0.0, 0.97).astype(np.float32),
-                   priority=rng.random(K).astype(np.float32) * 3 + 0.01))
-
-
 def _cfg(B, **rt):
     from apex_dqn_amd.config import ApexConfig
     learner = rt.pop("learner", {})
@@ -212,7 +204,7 @@ def test_augmented_learner_step_hip_vs_torch_backend(dtype, rt):
     for be in ("hip", "torch"):
         torch.manual_seed(0)
         rp = GpuReplayShard(2000, 2000, 2100, 4, device=DEV, seed=7)
-        _fill_replay(rp, 1500, seed=11)
+        fill_replay(rp, 1500, seed=11)
         L = FusedNatureLearner(cfg, DEV, rp, backend=be, split=split)
         assert L.aug_pad == 4 and L.split == split and L.munchausen == bool(rt.get("munchausen"))
         if be == "torch":
@@ -250,7 +242,7 @@ def test_augmented_graph_steps_match_eager_steps():
         cfg = _cfg(64, use_graphs=graphs, graph_steps=4, learner={"q_target_sync_freq": 1000})
         torch.manual_seed(0)
         rp = GpuReplayShard(2000, 2000, 2100, 4, device=DEV, seed=3)
-        _fill_replay(rp, 1500, seed=1)
+        fill_replay(rp, 1500, seed=1)
         L = FusedNatureLearner(cfg, DEV, rp, backend="hip")
         u0 = L.update_index()
         if graphs:
@@ -282,7 +274,7 @@ def test_augmented_resume_matches_uninterrupted_run(tmp_path):
 
     def replay():
         rp = GpuReplayShard(2000, 2000, 2100, 4, device=DEV, seed=5)
-        _fill_replay(rp, 1500, seed=2)
+        fill_replay(rp, 1500, seed=2)
         return rp
 
     cfg = _cfg(32, use_graphs=True, learner={"q_target_sync_freq": 3})

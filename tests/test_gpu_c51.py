@@ -6,6 +6,7 @@ import functools
 import numpy as np
 import pytest
 import torch
+from head_fixtures import fill_replay, split_planes
 
 pytestmark = pytest.mark.gpu
 
@@ -14,16 +15,11 @@ VMIN, VMAX = -10.0, 10.0
 
 
 # --------------------------------------------------------------------- fixture
-def _split_planes(x32):
-    hi = x32.to(torch.bfloat16)
-    lo = (x32 - hi.float()).to(torch.bfloat16)
-    return hi, lo
-
-
 # Generator seed 2 everywhere but at (A, N) = (6, 21) and (3, 64): there seed 2 leaves a
 # near-tie in the fp64 oracle's online next-state q (top-2 gaps 2.7e-4 and 2.6e-6, under the
 # 1e-3 the tests ask for so that no sample has to be left out), so those two shapes draw from
-# the next seed, 3 (gaps 4.7e-2 / 1.3e-2; measured on the CPU in fp64).
+# the next seed, 3 (gaps 4.7e-2 / 1.3e-2; measured on the CPU in fp64).  (B, A, N) = (3, 2, 2) keeps seed 2: gap
+# 1.18 in both input modes.
 SEEDS = {(6, 21): 3, (3, 64): 3}
 
 
@@ -45,7 +41,7 @@ def _fixture(B, A, N, split=False):
     gam[::7] = 0.0
     isw = torch.rand(B, generator=g)
     if split:
-        (Hon, Hon_lo), (Htg, Htg_lo) = _split_planes(Hon), _split_planes(Htg)
+        (Hon, Hon_lo), (Htg, Htg_lo) = split_planes(Hon), split_planes(Htg)
     else:
         Hon, Htg, Hon_lo, Htg_lo = Hon.to(torch.bfloat16), Htg.to(torch.bfloat16), None, None
     return dict(Hon=Hon, Htg=Htg, Hon_lo=Hon_lo, Htg_lo=Htg_lo, Pon=Pon, Ptg=Ptg, act=act, rew=rew, gam=gam, isw=isw)
@@ -134,13 +130,14 @@ def _compare(h, r):
 
 # --------------------------------------------------------- 1. kernel vs oracle
 @pytest.mark.parametrize("split", [False, True])
-@pytest.mark.parametrize("B,A,N", [(64, 4, 51), (64, 18, 51), (64, 6, 21), (64, 3, 64), (5, 4, 51)])
+@pytest.mark.parametrize("B,A,N", [(64, 4, 51), (64, 18, 51), (64, 6, 21), (64, 3, 64), (5, 4, 51), (3, 2, 2)])
 def test_c51_head_kernel_vs_fp64_oracle(B, A, N, split):
     """bf16 single plane and split hi / lo inputs (built from fp32 activations; the oracle
-    works on the joined values).  B = 5: not a multiple of the samples per block."""
+    works on the joined values).  B = 5: not a multiple of the samples per block.  (3, 2, 2): a
+    block whose second sample is past the batch in a head with fewer weight-row tasks (4) than waves."""
     fx = _fixture(B, A, N, split)
     r = _oracle(fx, A, N)
-    if B == 64:
+    if B != 5:
         # no near-tie in the online argmax: every sample is compared (fix the fixture, not the test)
         assert r["gap"] >= 1e-3, r["gap"]
     h = _run_hip(fx, A, N)
@@ -231,15 +228,6 @@ def test_c51_actor_head_vs_oracle():
 
 
 # -------------------------------------------------------------- 4. whole step
-def _fill_replay(rp, K, A=6, seed=0):
-    rng = np.random.default_rng(seed)
-    seqs = rp.append_frames(rng.integers(0, 255, (K + 8, 84, 84), dtype=np.uint8))
-    st = np.stack([seqs[i:i + 4] for i in range(K)])
-    rp.insert(dict(S_t=st, S_tpn=st + 3, A_t=rng.integers(0, A, K), R=rng.normal(size=K).astype(np.float32),
-                   Gamma=np.where(rng.random(K) < 0.1, 0.0, 0.97).astype(np.float32),
-                   priority=rng.random(K).astype(np.float32) * 3 + 0.01))
-
-
 def _cfg(B, **rt):
     from apex_dqn_amd.config import ApexConfig
     learner = rt.pop("learner", {})
@@ -261,7 +249,7 @@ def test_c51_learner_step_hip_vs_torch_backend(dtype):
     for be in ("hip", "torch"):
         torch.manual_seed(0)
         rp = GpuReplayShard(2000, 2000, 2100, 4, device=DEV, seed=7)
-        _fill_replay(rp, 1500, seed=11)
+        fill_replay(rp, 1500, seed=11)
         L = FusedNatureLearner(cfg, DEV, rp, backend=be, split=split)
         assert L.N == 51 and L.split == split
         if be == "torch":
@@ -298,7 +286,7 @@ def test_c51_graph_steps_match_eager_steps():
                    learner={"q_target_sync_freq": 1000})
         torch.manual_seed(0)
         rp = GpuReplayShard(2000, 2000, 2100, 4, device=DEV, seed=3)
-        _fill_replay(rp, 1500, seed=1)
+        fill_replay(rp, 1500, seed=1)
         L = FusedNatureLearner(cfg, DEV, rp, backend="hip")
         u0 = L.update_index()
         if graphs:

@@ -5,6 +5,7 @@ import hlg_fixtures as F
 import numpy as np
 import pytest
 import torch
+from head_fixtures import fill_replay
 
 pytestmark = pytest.mark.gpu
 
@@ -57,11 +58,13 @@ def _check(prob, **kw):
 
 # --------------------------------------------------------- 1. kernel vs oracle
 @pytest.mark.parametrize("split", [False, True])
-@pytest.mark.parametrize("B,A,N", F.SHAPES)
+@pytest.mark.parametrize("B,A,N", F.SHAPES + [F.FRAME_EDGE])
 def test_hlg_head_kernel_vs_fp64_oracle(B, A, N, split):
     """bf16 single plane and split hi / lo inputs at sigma_ratio = 0.75.  B = 5: a ragged last block; (3, 3, 2):
-    the smallest head and the widest Gaussian (delta = 20, sigma = 15)."""
-    _check((B, A, N, split, "plain", F.SIGMA, None))
+    the smallest head and the widest Gaussian (delta = 20, sigma = 15); (3, 2, 2): tests/hlg_fixtures.py
+    FRAME_EDGE."""
+    h, r = _check((B, A, N, split, "plain", F.SIGMA, None))
+    assert r["gap"] >= 1e-3, r["gap"]         # no near-tie in the online argmax: every sample is compared
 
 
 @pytest.mark.parametrize("split", [False, True])
@@ -123,15 +126,6 @@ def test_launcher_refuses_wrong_arguments():
 
 
 # -------------------------------------------------------------- 5. whole step
-def _fill_replay(rp, K, A=6, seed=0):
-    rng = np.random.default_rng(seed)
-    seqs = rp.append_frames(rng.integers(0, 255, (K + 8, 84, 84), dtype=np.uint8))
-    st = np.stack([seqs[i:i + 4] for i in range(K)])
-    rp.insert(dict(S_t=st, S_tpn=st + 3, A_t=rng.integers(0, A, K), R=rng.normal(size=K).astype(np.float32),
-                   Gamma=np.where(rng.random(K) < 0.1, 0.0, 0.97).astype(np.float32),
-                   priority=rng.random(K).astype(np.float32) * 3 + 0.01))
-
-
 def _cfg(B, **rt):
     from apex_dqn_amd.config import ApexConfig
     learner = rt.pop("learner", {})
@@ -152,7 +146,7 @@ def test_hlg_learner_step_hip_vs_torch_backend(dtype, rt):
     for be in ("hip", "torch"):
         torch.manual_seed(0)
         rp = GpuReplayShard(2000, 2000, 2100, 4, device=DEV, seed=7)
-        _fill_replay(rp, 1500, seed=11)
+        fill_replay(rp, 1500, seed=11)
         L = FusedNatureLearner(cfg, DEV, rp, backend=be, split=split)
         assert L.N == 51 and L.cfg.hl_gauss and L.split == split and L.noisy == bool(rt.get("noisy"))
         if be == "torch":
@@ -182,7 +176,7 @@ def test_graph_of_four_updates_is_bit_identical_to_four_eager_steps():
                    learner={"q_target_sync_freq": 1000})
         torch.manual_seed(0)
         rp = GpuReplayShard(2000, 2000, 2100, 4, device=DEV, seed=3)
-        _fill_replay(rp, 1500, seed=1)
+        fill_replay(rp, 1500, seed=1)
         L = FusedNatureLearner(cfg, DEV, rp, backend="hip")
         if graphs:
             L.steps(4)
@@ -204,7 +198,7 @@ def test_gpu_resume_is_bit_identical(tmp_path):
 
     def replay():
         rp = GpuReplayShard(2000, 2000, 2100, 4, device=DEV, seed=5)
-        _fill_replay(rp, 1500, seed=2)
+        fill_replay(rp, 1500, seed=2)
         return rp
     cfg = _cfg(32, use_graphs=True, graph_steps=4, learner={"q_target_sync_freq": 3})
     rp = replay()

@@ -7,6 +7,7 @@ import math
 import numpy as np
 import pytest
 import torch
+from head_fixtures import fill_replay, split_planes
 
 pytestmark = pytest.mark.gpu
 
@@ -15,12 +16,6 @@ ALPHA, TAU, CLIP, KAPPA = 0.9, 0.03, -1.0, 1.0
 
 
 # --------------------------------------------------------------------- fixture
-def _split_planes(x32):
-    hi = x32.to(torch.bfloat16)
-    lo = (x32 - hi.float()).to(torch.bfloat16)
-    return hi, lo
-
-
 @functools.lru_cache(maxsize=None)
 def _fixture(B, A, split=False):
     """Inputs (CPU) of one head problem: Hon [B, 1024] (online S_t), Htg [2B, 1024] (target S_t+n, then
@@ -39,7 +34,7 @@ def _fixture(B, A, split=False):
     gam[::7] = 0.0
     isw = torch.rand(B, generator=g)
     if split:
-        (Hon, Hon_lo), (Htg, Htg_lo) = _split_planes(Hon), _split_planes(Htg)
+        (Hon, Hon_lo), (Htg, Htg_lo) = split_planes(Hon), split_planes(Htg)
     else:
         Hon, Htg, Hon_lo, Htg_lo = Hon.to(torch.bfloat16), Htg.to(torch.bfloat16), None, None
     return dict(Hon=Hon, Htg=Htg, Hon_lo=Hon_lo, Htg_lo=Htg_lo, Pon=Pon, Ptg=Ptg, act=act, rew=rew, gam=gam, isw=isw)
@@ -273,15 +268,6 @@ def test_q_out_bit_equal_to_the_ddqn_head(B, A):
 
 
 # ----------------------------------------------------------------- 4. sampler
-def _fill_replay(rp, K, A=6, seed=0):
-    rng = np.random.default_rng(seed)
-    seqs = rp.append_frames(rng.integers(0, 255, (K + 8, 84, 84), dtype=np.uint8))
-    st = np.stack([seqs[i:i + 4] for i in range(K)])
-    rp.insert(dict(S_t=st, S_tpn=st + 3, A_t=rng.integers(0, A, K), R=rng.normal(size=K).astype(np.float32),
-                   Gamma=np.where(rng.random(K) < 0.1, 0.0, 0.97).astype(np.float32),
-                   priority=rng.random(K).astype(np.float32) * 3 + 0.01))
-
-
 @pytest.mark.parametrize("fused", [False, True])
 def test_sampler_obs2(fused):
     """obs2 is bit-equal to obs from tree_sample_kernel and from the optimizer + sample launch; without it
@@ -295,7 +281,7 @@ def test_sampler_obs2(fused):
     res = {}
     for with_obs2 in (True, False):
         rp = GpuReplayShard(2000, 2000, 2100, 4, device=DEV, seed=4)
-        _fill_replay(rp, 1500, seed=2)
+        fill_replay(rp, 1500, seed=2)
         S = rp.alloc_sample_buffers(B)
         nxt2 = torch.full((B, 4), -7, dtype=torch.int32, device=DEV)
         obs2 = torch.full((B, 4), -7, dtype=torch.int32, device=DEV)
@@ -338,7 +324,7 @@ def test_mdqn_learner_step_hip_vs_torch_backend(dtype, noisy):
     for be in ("hip", "torch"):
         torch.manual_seed(0)
         rp = GpuReplayShard(2000, 2000, 2100, 4, device=DEV, seed=7)
-        _fill_replay(rp, 1500, seed=11)
+        fill_replay(rp, 1500, seed=11)
         L = FusedNatureLearner(cfg, DEV, rp, backend=be, split=split)
         assert L.munchausen and L.N == 1 and L.split == split and L.noisy == noisy and L._rows_first == 32
         L.t32.mul_(1.25)                       # a target net that differs from the online net
@@ -379,7 +365,7 @@ def test_mdqn_graph_steps_match_eager_steps():
         cfg = _cfg(64, use_graphs=graphs, graph_steps=4, learner={"q_target_sync_freq": 1000})
         torch.manual_seed(0)
         rp = GpuReplayShard(2000, 2000, 2100, 4, device=DEV, seed=3)
-        _fill_replay(rp, 1500, seed=1)
+        fill_replay(rp, 1500, seed=1)
         L = FusedNatureLearner(cfg, DEV, rp, backend="hip")
         assert L.munchausen and L._presample
         p0 = L.p32.clone()
@@ -409,7 +395,7 @@ def test_mdqn_gpu_resume_matches_uninterrupted_run(tmp_path):
 
     def replay():
         rp = GpuReplayShard(2000, 2000, 2100, 4, device=DEV, seed=5)
-        _fill_replay(rp, 1500, seed=2)
+        fill_replay(rp, 1500, seed=2)
         return rp
 
     cfg = _cfg(32, use_graphs=True, learner={"q_target_sync_freq": 2})

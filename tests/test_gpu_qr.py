@@ -6,6 +6,7 @@ import functools
 import numpy as np
 import pytest
 import torch
+from head_fixtures import fill_replay, split_planes
 
 pytestmark = pytest.mark.gpu
 
@@ -14,12 +15,6 @@ KAPPA = 1.0
 
 
 # --------------------------------------------------------------------- fixture
-def _split_planes(x32):
-    hi = x32.to(torch.bfloat16)
-    lo = (x32 - hi.float()).to(torch.bfloat16)
-    return hi, lo
-
-
 @functools.lru_cache(maxsize=None)
 def _fixture(B, A, N, split=False):
     """Inputs (CPU) of one head problem, drawn as tests/test_gpu_c51.py draws them: generator
@@ -38,7 +33,7 @@ def _fixture(B, A, N, split=False):
     gam[::7] = 0.0
     isw = torch.rand(B, generator=g)
     if split:
-        (Hon, Hon_lo), (Htg, Htg_lo) = _split_planes(Hon), _split_planes(Htg)
+        (Hon, Hon_lo), (Htg, Htg_lo) = split_planes(Hon), split_planes(Htg)
     else:
         Hon, Htg, Hon_lo, Htg_lo = Hon.to(torch.bfloat16), Htg.to(torch.bfloat16), None, None
     return dict(Hon=Hon, Htg=Htg, Hon_lo=Hon_lo, Htg_lo=Htg_lo, Pon=Pon, Ptg=Ptg, act=act, rew=rew, gam=gam, isw=isw)
@@ -141,15 +136,18 @@ def _compare(h, r):
 
 # --------------------------------------------------------- 1. kernel vs oracle
 @pytest.mark.parametrize("split", [False, True])
-@pytest.mark.parametrize("B,A,N", [(64, 4, 32), (64, 18, 64), (64, 6, 21), (64, 3, 51), (64, 2, 2), (5, 4, 32)])
+@pytest.mark.parametrize("B,A,N", [(64, 4, 32), (64, 18, 64), (64, 6, 21), (64, 3, 51), (64, 2, 2), (5, 4, 32),
+                                   (3, 2, 2)])
 def test_qr_head_kernel_vs_fp64_oracle(B, A, N, split):
     """bf16 single plane and split hi / lo inputs (built from fp32 activations; the oracle
     works on the joined values).  B = 5: not a multiple of the samples per block.  The
     fixture's smallest top-2 gap of the online next-state q (fp64, measured on the CPU) is
     4.3e-3, 1.8e-3, 4.3e-3, 1.6e-3 and 3.5e-1 at the B = 64 shapes in this order, in both
-    input modes: no near-tie, every sample is compared."""
+    input modes: no near-tie, every sample is compared.  (3, 2, 2): a block whose second sample
+    is past the batch in a head with fewer weight-row tasks (4) than waves; generator seed 2 as
+    everywhere, gap 5.0e-1 in both input modes."""
     r = _oracle(B, A, N, split)
-    if B == 64:
+    if B != 5:
         assert r["gap"] >= 1e-3, r["gap"]
     h = _run_hip(B, A, N, split)
     print(f"B {B} A {A} N {N} split {split}: oracle gap {r['gap']:.3e}, "
@@ -237,15 +235,6 @@ def test_qr_actor_head_vs_oracle():
 
 
 # -------------------------------------------------------------- 4. whole step
-def _fill_replay(rp, K, A=6, seed=0):
-    rng = np.random.default_rng(seed)
-    seqs = rp.append_frames(rng.integers(0, 255, (K + 8, 84, 84), dtype=np.uint8))
-    st = np.stack([seqs[i:i + 4] for i in range(K)])
-    rp.insert(dict(S_t=st, S_tpn=st + 3, A_t=rng.integers(0, A, K), R=rng.normal(size=K).astype(np.float32),
-                   Gamma=np.where(rng.random(K) < 0.1, 0.0, 0.97).astype(np.float32),
-                   priority=rng.random(K).astype(np.float32) * 3 + 0.01))
-
-
 def _cfg(B, **rt):
     from apex_dqn_amd.config import ApexConfig
     learner = rt.pop("learner", {})
@@ -267,7 +256,7 @@ def test_qr_learner_step_hip_vs_torch_backend(dtype):
     for be in ("hip", "torch"):
         torch.manual_seed(0)
         rp = GpuReplayShard(2000, 2000, 2100, 4, device=DEV, seed=7)
-        _fill_replay(rp, 1500, seed=11)
+        fill_replay(rp, 1500, seed=11)
         L = FusedNatureLearner(cfg, DEV, rp, backend=be, split=split)
         assert L.N == 32 and L.quantile and L.split == split
         if be == "torch":
@@ -300,7 +289,7 @@ def test_qr_graph_steps_match_eager_steps():
                    learner={"q_target_sync_freq": 1000})
         torch.manual_seed(0)
         rp = GpuReplayShard(2000, 2000, 2100, 4, device=DEV, seed=3)
-        _fill_replay(rp, 1500, seed=1)
+        fill_replay(rp, 1500, seed=1)
         L = FusedNatureLearner(cfg, DEV, rp, backend="hip")
         u0 = L.update_index()
         if graphs:

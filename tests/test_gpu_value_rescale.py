@@ -235,7 +235,7 @@ def _cfg(B, **rt):
 
 
 def _fill_replay(rp, K, A=6, seed=0):
-    """tests/test_gpu_qr.py ``_fill_replay`` with raw rewards of either sign up to about 100."""
+    """tests/head_fixtures.py ``fill_replay`` with raw rewards of either sign up to about 100."""
     rng = np.random.default_rng(seed)
     seqs = rp.append_frames(rng.integers(0, 255, (K + 8, 84, 84), dtype=np.uint8))
     st = np.stack([seqs[i:i + 4] for i in range(K)])
