@@ -159,6 +159,18 @@ class RuntimeConf:
     # the torch learner on 84 x 84 stacks; not IMPALA, the DP step or the graph learner.  Actors and evaluation
     # see the frames as they are
     augment_shift: int = 0
+    # periodic shrink-and-perturb resets (Nikishin et al. 2022; SR-SPR, D'Oro et al. 2023; BBF, Schwarzer et al.
+    # 2023; learner/reset.py, csrc/reset.hip): after every update whose count is a positive multiple of
+    # reset_interval every parameter becomes alpha * old + (1 - alpha) * a fresh draw from its layer's initial
+    # distribution -- alpha = reset_shrink_encoder for the conv layers, reset_shrink_head for everything behind
+    # them -- in both nets with the same draw, the optimizer moments are zeroed and Adam's step count restarts; the
+    # replay carries the knowledge across.  0 = off (no buffer, no launch, the launches and the bits of before).
+    # Single-rank NatureCNN with every head kind, noisy layers, the Munchausen target, value rescaling, the random
+    # shift, Adam, the schedules and either target, and the torch learners (mlp); not IMPALA, the DP step or the
+    # graph learner
+    reset_interval: int = 0
+    reset_shrink_encoder: float = 0.5
+    reset_shrink_head: float = 0.0
     # Atari wrappers clip rewards to {-1, 0, +1} (envs/vector_envs.py AtariWrapperVec); false keeps the raw rewards
     # (with value_rescale; the two keys are independent)
     clip_rewards: bool = True
@@ -451,6 +463,24 @@ class ApexConfig:
             if int(rt.world_size) > 1 or rt.force_dp:
                 raise ValueError("Runtime.augment_shift runs on a single rank: the data-parallel step (world_size > 1, "
                                  "force_dp) has no frame augmentation")
+        ri = rt.reset_interval
+        if isinstance(ri, bool) or not isinstance(ri, int) or ri < 0:
+            raise ValueError(f"Runtime.reset_interval (updates between shrink-and-perturb resets, 0 = off) must be an "
+                             f"integer >= 0, got {ri!r}")
+        for key in ("reset_shrink_encoder", "reset_shrink_head"):
+            al = getattr(rt, key)
+            if isinstance(al, bool) or not isinstance(al, (int, float)) or not 0.0 <= float(al) <= 1.0:
+                raise ValueError(f"Runtime.{key} (the share of the old value a reset keeps) must be a number in "
+                                 f"[0, 1], got {al!r}")
+        if ri > 0:
+            if net == "impala":
+                raise ValueError("Runtime.reset_interval: the IMPALA step has no periodic resets (they are the "
+                                 "NatureCNN learner's)")
+            if net not in ("nature64", "nature32", "mlp"):
+                raise ValueError(f"Runtime.reset_interval needs network nature64, nature32 or mlp, got {net!r}")
+            if int(rt.world_size) > 1 or rt.force_dp:
+                raise ValueError("Runtime.reset_interval runs on a single rank: the data-parallel step (world_size > 1, "
+                                 "force_dp) has no periodic resets")
         if net in ("nature64", "nature32", "impala") and len(ss) != 3:
             raise ValueError(f"network {net} needs an image state_shape [C,H,W], got {ss}")
         if net in ("nature64", "nature32") and tuple(ss[1:]) != (84, 84):

@@ -106,4 +106,9 @@ __device__ __forceinline__ float apex_uniform(uint64_t seed, uint64_t ctr, uint6
   return (float)(r >> 40) * (1.0f / 16777216.0f);  // [0,1)
 }
 
+// the 24-bit integer behind apex_uniform(seed, ctr, i): apex_uniform * 2^24, exactly
+__device__ __forceinline__ uint32_t apex_u24(uint64_t seed, uint64_t ctr, uint64_t i) {
+  return (uint32_t)(apex_mix64(seed ^ apex_mix64(ctr * 0x100000001b3ull + i)) >> 40);
+}
+
 #define APEX_CHECK_LAUNCH() return (int)hipGetLastError()

@@ -43,11 +43,6 @@ __device__ int aug_dbg_count;
 __device__ long long aug_dbg_first;
 #endif
 
-// the 24-bit integer behind apex_uniform(seed, ctr, i): apex_uniform * 2^24, exactly
-__device__ __forceinline__ uint32_t aug_u24(uint64_t seed, uint64_t ctr, uint64_t i) {
-  return (uint32_t)(apex_mix64(seed ^ apex_mix64(ctr * 0x100000001b3ull + i)) >> 40);
-}
-
 // the dword of cell `cell` in one source pixel row (`rowp`: that row's dword of cell 0, cells 4
 // dwords apart); cells off the frame replicate the edge pixel
 __host__ __device__ __forceinline__ uint32_t aug_cell_word(const uint32_t* rowp, int cell) {
@@ -83,8 +78,8 @@ __global__ void __launch_bounds__(256) augment_shift_kernel(AugArgs a) {
   u = u < 0 ? 0 : u;
   const uint64_t c = (uint64_t)AUG_STREAMS * (uint64_t)u;
   const uint32_t span = 2u * (uint32_t)a.pad + 1u;     // k < 2^24, span <= 17: the product fits 32 bits
-  const int oy = (int)((aug_u24(a.seed, c, 2ull * (uint64_t)r) * span) >> 24);
-  const int ox = (int)((aug_u24(a.seed, c, 2ull * (uint64_t)r + 1ull) * span) >> 24);
+  const int oy = (int)((apex_u24(a.seed, c, 2ull * (uint64_t)r) * span) >> 24);
+  const int ox = (int)((apex_u24(a.seed, c, 2ull * (uint64_t)r + 1ull) * span) >> 24);
   int32_t s = a.slots[f];
 #ifdef APEX_DEBUG_BOUNDS
   if (!(s >= 0 && (int64_t)s < a.F)) {

@@ -105,7 +105,7 @@ __device__ __forceinline__ double pow_u64(double b, uint64_t t) {
 
 #define OPT_RMSPROP 0        // RMSprop, lr = RmspropArgs.lr
 #define OPT_RMSPROP_SCHED 1  // RMSprop, lr(u)
-#define OPT_ADAM 2           // Adam, lr(u), bias corrections from t = u + 1
+#define OPT_ADAM 2           // Adam, lr(u), bias corrections from t = u + 1 - t0
 
 struct OptSched {
   const uint64_t* ctr;   // the replay's draw counter, or null (OPT_RMSPROP)
@@ -114,6 +114,8 @@ struct OptSched {
   int64_t warmup, decay; // lr schedule (0: off)
   double lr0, lr_end;
   double beta1, beta2;
+  const int64_t* t0;     // device word: the updates completed at the last shrink-and-perturb reset (learner/reset.py:
+                         // the moments restart at zero there, so Adam's step count does); null = 0
 };
 
 __host__ __device__ inline int opt_mode(const OptSched& s) {
@@ -217,8 +219,10 @@ __device__ __forceinline__ void rmsprop_body(const RmspropArgs& A_, int bid, int
       u = u < 0 ? 0 : u;
       sh[2] = sched_lr(u, os.lr0, os.lr_end, os.warmup, os.decay);
       if constexpr (MODE == OPT_ADAM) {
-        sh[3] = (float)(1.0 - pow_u64(os.beta1, (uint64_t)u + 1));
-        sh[4] = (float)(1.0 - pow_u64(os.beta2, (uint64_t)u + 1));
+        int64_t t = u + 1 - (os.t0 != nullptr ? os.t0[0] : 0);
+        t = t < 1 ? 1 : t;
+        sh[3] = (float)(1.0 - pow_u64(os.beta1, (uint64_t)t));
+        sh[4] = (float)(1.0 - pow_u64(os.beta2, (uint64_t)t));
       }
     }
   }
@@ -383,6 +387,7 @@ inline bool opt_args_ok(const RmspropArgs& a, int64_t n0, int64_t first) {
   if (((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.v | (uintptr_t)a.m) & 15) return false;
   if (((uintptr_t)a.pb | (uintptr_t)a.pb_lo) & 7) return false;
   if (opt_mode(a.os) != OPT_RMSPROP && (a.os.ctr == nullptr || a.os.base == nullptr)) return false;
+  if (a.os.t0 != nullptr && (opt_mode(a.os) != OPT_ADAM || ((uintptr_t)a.os.t0 & 7))) return false;
   return opt_target_check(a.tg, a.pb_lo, a.fo, n0, first) == 0;
 }
 

@@ -780,7 +780,7 @@ APEX_EXPORT int apex_fill16(void* p, int64_t n, int nt, hipStream_t st) {
   APEX_CHECK_LAUNCH();
 }
 
-APEX_EXPORT int apex_abi_version() { return 18; }
+APEX_EXPORT int apex_abi_version() { return 19; }
 
 // sizeof of every block that crosses the ABI by value in the launchers below, in the order of ops/_lib.py
 // ABI_STRUCTS (host only): a mirror that drifts by a field would otherwise only shift kernarg contents

@@ -45,7 +45,8 @@ Precision (``Runtime.dtype``):
 
 Periodic host work between steps: target sync (D2D copy, every
 ``q_target_sync_freq``; none with ``Runtime.target_ema_rate`` > 0, where the optimizer launch
-averages the target after every update), FIFO eviction + exact tree rebuild (every
+averages the target after every update), the shrink-and-perturb reset (one launch and the
+fragment repacks, every ``Runtime.reset_interval``; learner/reset.py), FIFO eviction + exact tree rebuild (every
 ``remove_old_xp_freq``), checkpoint (rank 0).
 
 Reference parity: ``Learner.learn`` / ``compute_loss_and_priorities`` /
@@ -162,6 +163,12 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
                              "data-parallel step (world > 1, Runtime.force_dp, the emulated world)")
         if self.aug_pad and tuple(cfg.env_conf.state_shape[1:]) != (84, 84):
             raise ValueError(f"Runtime.augment_shift shifts 84x84 frames, got state_shape {cfg.env_conf.state_shape}")
+        # periodic shrink-and-perturb resets (learner/reset.py, csrc/reset.hip): one eager launch between graph
+        # replays after every reset_interval-th update (reset_now); 0 = no table, no launch, no new kernel argument
+        self.reset_I = int(self.rt.reset_interval)
+        if self.reset_I and self._dp:
+            raise ValueError("Runtime.reset_interval: the resets run on a single rank, not in the data-parallel step "
+                             "(world > 1, Runtime.force_dp, the emulated world)")
         if self.rt.dtype not in ("fp32", "bf16"):
             raise ValueError("Runtime.dtype must be fp32 or bf16")
         self.precision = self.rt.dtype
@@ -339,6 +346,10 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         self._init_step_index()
         if self.noisy:
             self._init_noisy()
+        if self.reset_I:
+            from .reset import reset_seed, reset_table
+            self._reset_table = reset_table(self.layout, cfg)
+            self._seed_r = reset_seed(self.rt.seed)
         ls = cfg.Learner.load_saved_state
         if ls:
             self.load(ls)
@@ -979,16 +990,36 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         else:
             self._body()
         self.num_q_updates += 1
-        L = self.cfg.Learner
-        if not self.ema and self.num_q_updates % L.q_target_sync_freq == 0:
+        self._boundary_work()
+
+    def _boundary_work(self) -> None:
+        """The eager work between updates: the hard target sync every ``q_target_sync_freq`` updates, then (a
+        coinciding boundary: the sync first) the shrink-and-perturb reset every ``Runtime.reset_interval``."""
+        if not self.ema and self.num_q_updates % self.cfg.Learner.q_target_sync_freq == 0:
             self.sync_target()
+        if self.reset_I and self.num_q_updates % self.reset_I == 0:
+            self.reset_now(self.num_q_updates // self.reset_I)
+
+    def reset_now(self, r: int) -> None:
+        """Reset number ``r`` (learner/reset.py): one launch rewrites both nets' fp32 parameters and bf16 planes and
+        zeroes the moments, then the derived formats follow as in :meth:`load` -- the fused forward's fragment
+        buffers of both nets, the noisy shadows -- and Adam's step count restarts (``upd_t0``).  Eager, between graph
+        replays: every pointer a captured graph holds is unchanged, the pre-sampled batch stays valid and the
+        replay is not touched."""
+        if not self.reset_I:
+            raise ValueError("reset_now needs Runtime.reset_interval > 0")
+        self.ops.reset_perturb(self._reset_table, self._seed_r, int(r), self.p32, self.t32, self.rms_v, self.rms_m,
+                               (self.pbf, self.pbf_lo), (self.tbf, self.tbf_lo))
+        self._online_changed()
+        self._target_changed()
+        self._sync_update_index()
 
     def steps(self, n: int) -> None:
         """``n`` learner updates.  With HIP graphs, chunks of ``Runtime.graph_steps``
         updates replay ONE graph holding that many steps (each graph launch costs
         ~9 us of idle GPU at its boundary); chunks never straddle a target-network
-        sync (the soft target has none: it is averaged inside every update).  Same updates
-        as ``n`` calls of :meth:`step`."""
+        sync (the soft target has none: it is averaged inside every update) or a reset
+        (``Runtime.reset_interval``).  Same updates as ``n`` calls of :meth:`step`."""
         k = int(self.rt.graph_steps)
         if k <= 1 or not self._graphs_enabled():
             for _ in range(n):
@@ -997,6 +1028,8 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         f = self.cfg.Learner.q_target_sync_freq
         while n > 0:
             to_sync = k if self.ema else f - self.num_q_updates % f
+            if self.reset_I:
+                to_sync = min(to_sync, self.reset_I - self.num_q_updates % self.reset_I)
             if n < k or to_sync < k:
                 self.step()
                 n -= 1
@@ -1011,8 +1044,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             self._multi.replay()
             self.num_q_updates += k
             n -= k
-            if not self.ema and self.num_q_updates % f == 0:
-                self.sync_target()
+            self._boundary_work()
 
     def prepare_graphs(self, multi: bool = True) -> int:
         """Capture every graph :meth:`step` / :meth:`steps` will replay (the one-update
@@ -1275,6 +1307,8 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             m["munchausen_bonus_mean"], m["soft_value_mean"] = float(mean[0]), float(mean[1])
         if self.aug_pad:        # the last update's mean shift offset (expected: augment_shift)
             m["augment_offset_mean"] = float(self.aug_off.double().mean())
+        if self.reset_I:        # shrink-and-perturb resets so far
+            m["resets"] = self.num_q_updates // self.reset_I
         return m
 
     def q_values(self, frames_u8: torch.Tensor) -> torch.Tensor:

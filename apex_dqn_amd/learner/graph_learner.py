@@ -77,6 +77,9 @@ class GraphLearner(StepIndexMixin):
         if int(self.rt.augment_shift) >= 1:
             raise ValueError("Runtime.augment_shift: the graph learner (Runtime.use_hip_kernels = false on the GPU) "
                              "has no frame augmentation; run the HIP kernels or augment_shift = 0")
+        if int(self.rt.reset_interval) > 0:
+            raise ValueError("Runtime.reset_interval: the graph learner (Runtime.use_hip_kernels = false on the GPU) "
+                             "has no periodic resets; run the HIP kernels or reset_interval = 0")
         self.device = torch.device(device)
         self.replay = replay
         self.comm = comm

@@ -87,6 +87,9 @@ class FusedImpalaLearner(IsNormMixin, StepIndexMixin):
         if int(self.rt.augment_shift) >= 1:
             raise ValueError("Runtime.augment_shift: the IMPALA step has no frame augmentation (it is the NatureCNN "
                              "learner's)")
+        if int(self.rt.reset_interval) > 0:
+            raise ValueError("Runtime.reset_interval: the IMPALA step has no periodic resets (they are the NatureCNN "
+                             "learner's)")
         self.world, _, self.B, self.mcap = dp_layout(cfg, comm, batch_size, allow_force=False)
         self.C = cfg.frame_stack
         if self.C != 4 or tuple(cfg.env_conf.state_shape[1:]) != (84, 84):

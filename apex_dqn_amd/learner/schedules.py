@@ -56,9 +56,10 @@ def pow_int(b: float, t: int) -> np.float64:
     return r
 
 
-def adam_corrections(u: int, beta1: float, beta2: float):
-    """(c1, c2) = fp32(1 - beta^t), t = u + 1."""
-    t = int(u) + 1
+def adam_corrections(u: int, beta1: float, beta2: float, t0: int = 0):
+    """(c1, c2) = fp32(1 - beta^t), t = u + 1 - t0 (``t0``: the updates completed at the last shrink-and-perturb
+    reset, learner/reset.py -- the moments restart at zero there, so the step count does)."""
+    t = max(int(u) + 1 - int(t0), 1)
     return np.float32(np.float64(1.0) - pow_int(beta1, t)), np.float32(np.float64(1.0) - pow_int(beta2, t))
 
 
@@ -116,6 +117,7 @@ class OptSpec:
     beta1: float = 0.9
     beta2: float = 0.999
     adam_eps: float = 1.5e-4
+    t0: Optional[torch.Tensor] = None   # int64 [1]: the updates completed at the last reset (None: 0), Adam only
 
     @property
     def adam(self) -> bool:
@@ -141,19 +143,23 @@ class OptSpec:
         """Adam's (c1, c2) as fp32 tensors (torch's fp64 pow: within an ulp of the kernels'
         product chain before the rounding to fp32)."""
         t = self.index().double() + 1
+        if self.t0 is not None:
+            t = (t - self.t0.reshape(-1)[0].double()).clamp_min(1)
         one = torch.ones_like(t)
         return ((one - torch.full_like(t, self.beta1) ** t).float(),
                 (one - torch.full_like(t, self.beta2) ** t).float())
 
 
-def opt_spec(rt, replay, base: torch.Tensor) -> Optional[OptSpec]:
+def opt_spec(rt, replay, base: torch.Tensor, t0: Optional[torch.Tensor] = None) -> Optional[OptSpec]:
     """The :class:`OptSpec` of a ``Runtime`` section, or None for the default (RMSprop,
-    constant lr): the step then issues exactly the launches of before."""
+    constant lr): the step then issues exactly the launches of before.  ``t0``: the reset word, which only
+    Adam reads."""
     if rt.optimizer == "rmsprop" and not lr_scheduled(rt):
         return None
+    t0 = t0 if rt.optimizer == "adam" else None
     return OptSpec(kind=rt.optimizer, ctr=replay.ctr, base=base, lr=float(rt.lr), warmup=int(rt.lr_warmup_steps),
                    decay=int(rt.lr_decay_steps), lr_end=None if rt.lr_end is None else float(rt.lr_end),
-                   beta1=float(rt.adam_beta1), beta2=float(rt.adam_beta2), adam_eps=float(rt.adam_eps))
+                   beta1=float(rt.adam_beta1), beta2=float(rt.adam_beta2), adam_eps=float(rt.adam_eps), t0=t0)
 
 
 class StepIndexMixin:
@@ -162,18 +168,26 @@ class StepIndexMixin:
     update boundary (the priority write-back bumps the counter once per update; snapshots
     and restores carry the counter).  :meth:`_init_step_index` goes after ``num_q_updates``
     is set, :meth:`_sync_update_index` after every host-side change of either number
-    (``load``)."""
+    (``load``).  With ``Runtime.reset_interval`` = I > 0 it also owns ``upd_t0``, the updates completed at the last
+    reset, (num_q_updates // I) I -- derived, so a checkpoint needs no key for it."""
+
+    upd_t0 = None
 
     def _init_step_index(self) -> None:
         rt, rp = self.rt, self.replay
         self.upd_base = torch.zeros(1, dtype=torch.int64, device=rp.ctr.device)
-        self._opt = opt_spec(rt, rp, self.upd_base)
+        if int(getattr(rt, "reset_interval", 0)) > 0:
+            self.upd_t0 = torch.zeros(1, dtype=torch.int64, device=rp.ctr.device)
+        self._opt = opt_spec(rt, rp, self.upd_base, self.upd_t0)
         if beta_scheduled(rt):
             rp.set_beta_schedule(self.upd_base, rt.is_beta_end, rt.is_beta_anneal_steps)
         self._sync_update_index()
 
     def _sync_update_index(self) -> None:
         self.upd_base.copy_(self.replay.ctr - int(self.num_q_updates))
+        if self.upd_t0 is not None:
+            I = int(self.rt.reset_interval)
+            self.upd_t0.fill_(int(self.num_q_updates) // I * I)
 
     def update_index(self) -> int:
         """The device's update index (a host read-back: tests, diagnostics)."""

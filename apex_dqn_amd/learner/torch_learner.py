@@ -149,7 +149,29 @@ class TorchLearner:
             self.ema_target()
         elif self.num_q_updates % self.cfg.Learner.q_target_sync_freq == 0:
             self.sync_target()
+        I = int(self.rt.reset_interval)
+        if I and self.num_q_updates % I == 0:
+            self.reset_now(self.num_q_updates // I)
         return gnorm
+
+    def reset_now(self, r: int) -> None:
+        """Shrink-and-perturb reset ``r`` (Runtime.reset_interval, learner/reset.py) by the fused learner's
+        convention on this module's parameters in ``named_parameters()`` order (flat index = running offset,
+        fan-in from the shape, ``module_reset_table``): both nets mixed with the same fresh values, the optimizer
+        state dropped (zero moments, Adam's step count restarts)."""
+        from .reset import apply_reset, module_reset_table, reset_seed
+        table = module_reset_table(self.Q, self.cfg)
+        tgt = dict(self.Q_target.named_parameters())
+        pairs = [(p, tgt[k]) for k, p in self.Q.named_parameters()]
+        flat = [np.concatenate([x.detach().cpu().numpy().ravel() for x in col]).astype(np.float32)
+                for col in zip(*pairs)]
+        zero = np.zeros_like(flat[0])
+        apply_reset(flat[0], flat[1], zero, zero.copy(), reset_seed(self.rt.seed), int(r), table)
+        with torch.no_grad():
+            for row, (p, t) in zip(table, pairs):
+                for x, a in ((p, flat[0]), (t, flat[1])):
+                    x.copy_(torch.from_numpy(a[row.start:row.end]).reshape(x.shape))
+        self.optimizer.state.clear()
 
     def ema_target(self) -> None:
         """The soft target (Runtime.target_ema_rate): every parameter of the target module averaged with the
@@ -184,10 +206,14 @@ class TorchLearner:
         return out
 
     def last_metrics(self) -> Dict[str, float]:
-        """Munchausen target: the last update's mean bonus and mean soft value (else empty)."""
-        if not self.rt.munchausen or getattr(self, "_mdqn", None) is None:
-            return {}
-        return {"munchausen_bonus_mean": self._mdqn[0], "soft_value_mean": self._mdqn[1]}
+        """Munchausen target: the last update's mean bonus and mean soft value; Runtime.reset_interval: the
+        resets so far (else empty)."""
+        m = {}
+        if int(self.rt.reset_interval) > 0:
+            m["resets"] = self.num_q_updates // int(self.rt.reset_interval)
+        if self.rt.munchausen and getattr(self, "_mdqn", None) is not None:
+            m.update(munchausen_bonus_mean=self._mdqn[0], soft_value_mean=self._mdqn[1])
+        return m
 
     # --------------------------------------------------------- params
     def state_dict_for_actors(self) -> Dict[str, torch.Tensor]:

@@ -152,6 +152,18 @@ class AugArgs(ctypes.Structure):
                 ("ctr", c_p), ("base", c_p), ("out", c_p), ("n_out", c_i64), ("off_out", c_p)]
 
 
+class ResetRow(ctypes.Structure):
+    """One segment of a reset (``ResetRow``, csrc/reset.hip; learner/reset.py ``ResetRow``)."""
+    _fields_ = [("start", c_i64), ("end", c_i64), ("period", c_i64), ("live", c_i64), ("bound", c_f), ("alpha", c_f),
+                ("const_flag", c_i), ("const_value", c_f)]
+
+
+class ResetArgs(ctypes.Structure):
+    """Arguments of ``reset_perturb_kernel`` (``ResetArgs``, csrc/reset.hip)."""
+    _fields_ = [("p", c_p), ("t", c_p), ("v", c_p), ("m", c_p), ("pb", c_p), ("tb", c_p), ("pb_lo", c_p),
+                ("tb_lo", c_p), ("n", c_i64), ("seed", c_u64), ("r", c_u64), ("nrows", c_i), ("rows", ResetRow * 32)]
+
+
 class CfFragOut(ctypes.Structure):
     """The optimizer's stores of the fused forward's online operands (``CfFragOut``,
     csrc/cf_pack.h); all-zero = off."""
@@ -176,7 +188,7 @@ class OptSched(ctypes.Structure):
     csrc/rmsprop_common.h); all-zero = RMSprop with the learning rate passed by value."""
     _fields_ = [("ctr", c_p), ("base", c_p), ("adam", c_i), ("warmup", c_i64), ("decay", c_i64),
                 ("lr0", ctypes.c_double), ("lr_end", ctypes.c_double), ("beta1", ctypes.c_double),
-                ("beta2", ctypes.c_double)]
+                ("beta2", ctypes.c_double), ("t0", c_p)]
 
 
 class BetaSched(ctypes.Structure):
@@ -329,6 +341,8 @@ _SIGS = {
     "apex_noisy_sigma_grad": ([NoisyGradArgs, c_p], c_i),
     "apex_augment_shift": ([AugArgs, c_p], c_i),
     "apex_augment_debug_errors": ([c_p, c_p, c_i], c_i),
+    "apex_reset_perturb": ([ResetArgs, c_p], c_i),
+    "apex_reset_args_size": ([], c_i),
 }
 
 _LIB: Optional[ctypes.CDLL] = None
@@ -347,7 +361,7 @@ def _declare(lib: ctypes.CDLL) -> None:
     conv_sigs.declare(lib)
 
 
-ABI_VERSION = 18    # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
+ABI_VERSION = 19   # csrc/sumtree.hip apex_abi_version(): the launchers' argument lists
 SQNORM_PARTIALS = 1024   # what apex_grad_sqnorm_partials writes (csrc/rmsprop_common.h SQNORM_NPART)
 # the blocks that cross the ABI by value, in the order of csrc/sumtree.hip apex_abi_struct_sizes()
 ABI_STRUCTS = (RmspropArgs, SampleArgs, RmsSegs, TreeUpdArgs, HeadWgArgs, IqnWgArgs, WgradDesc, DdqnArgs, ActorIO,

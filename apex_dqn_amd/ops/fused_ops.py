@@ -839,6 +839,35 @@ class TorchBackend:
         out.reshape(-1)[:rows * C * 7056].copy_(to_s2d(sh.reshape(rows * C, 84, 84)).reshape(-1))
         off_out.reshape(-1)[:2 * rows].copy_(off.reshape(-1))
 
+    # ------------------------------------------------------ periodic resets
+    @staticmethod
+    def _reset_check(table, p32, t32, v, m, pb, tb) -> int:
+        from ..learner import reset as RS
+        n = int(p32.numel())
+        for t in (p32, t32, v, m):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+        for hi, lo in (pb, tb):
+            assert hi.is_contiguous() and hi.numel() == n and (lo is None or (lo.is_contiguous() and lo.numel() == n
+                                                                              and lo.dtype == hi.dtype))
+        assert pb[0].dtype == tb[0].dtype and len(table) <= RS.MAX_ROWS
+        return n
+
+    def reset_perturb(self, table, seed, r, p32, t32, v, m, pb, tb) -> None:
+        """Shrink-and-perturb reset ``r`` of the flat parameters (learner/reset.py ``apply_reset``; the oracle of
+        csrc/reset.hip ``reset_perturb_kernel``): ``p32`` / ``t32`` mixed with the fresh values of ``table`` drawn
+        with ``seed`` (seed_r), the moments ``v`` / ``m`` zeroed, and the bf16 planes ``pb`` = (hi, lo or None),
+        ``tb`` of both nets rewritten from the result -- inside the table's rows only."""
+        from ..learner import reset as RS
+        self._reset_check(table, p32, t32, v, m, pb, tb)
+        arrs = [t.detach().cpu().numpy().copy() for t in (p32, t32, v, m)]
+        RS.apply_reset(*arrs, int(seed), int(r), table)
+        for row in table:
+            s = slice(row.start, row.end)
+            for t, a in zip((p32, t32, v, m), arrs):
+                t[s].copy_(torch.from_numpy(a[s]))
+            for src, (hi, lo) in ((p32, pb), (t32, tb)):
+                split_into(src[s], hi[s], None if lo is None else lo[s])
+
     # ------------------------------------------- data-parallel gradient factors
     def pack_rows(self, dst: torch.Tensor, segs) -> None:
         """dst[:, c0:c0 + n] = seg for the 2-D ``segs`` laid side by side (same row count)."""
@@ -867,7 +896,7 @@ class HipBackend(TorchBackend):
         self.native_conv = native_conv and hasattr(self.lib, "apex_conv_fwd")
         self.kernels = ["replay", "head", "head_wgrad", "optimizer", "actor_head", "c51_head", "c51_actor_head", "qr_head",
                         "qr_actor_head", "noisy_compose", "noisy_sigma_grad", "mdqn_head", "iqn_head", "iqn_wgrad",
-                        "iqn_actor_head", "augment_shift", "hlg_head"]
+                        "iqn_actor_head", "augment_shift", "hlg_head", "reset_perturb"]
         if self.native_conv:
             self.kernels += ["conv_fwd", "conv_dgrad", "conv_wgrad", "fc_fwd", "fc_bwd"]
         self.ws = C.Workspace()
@@ -1302,6 +1331,9 @@ class HipBackend(TorchBackend):
             os_.warmup, os_.decay = int(opt.warmup), int(opt.decay)
             os_.lr0, os_.lr_end = float(opt.lr), float(opt.lr if opt.lr_end is None else opt.lr_end)
             os_.beta1, os_.beta2 = float(opt.beta1), float(opt.beta2)
+            if opt.t0 is not None:     # (only with Runtime.reset_interval: else the arguments of before)
+                assert opt.adam and opt.t0.dtype == torch.int64
+                os_.t0 = opt.t0.data_ptr()
         return os_
 
     def _opt_args(self, p32, g32, v, m, pbf, lr, alpha, eps, clip, centered, norm_out, pb_lo, wnorm, frag_out,
@@ -1456,6 +1488,22 @@ class HipBackend(TorchBackend):
         """csrc/augment.hip ``augment_shift_kernel``: one launch; the update index is read on the device."""
         a = self.augment_args(ring, slots, pad, seed, ctr, base, out, off_out)
         _lib.check(self.lib.apex_augment_shift(a, _lib.stream_ptr()), "augment_shift")
+
+    def reset_args(self, table, seed, r, p32, t32, v, m, pb, tb) -> "_lib.ResetArgs":
+        """The argument block of ``apex_reset_perturb`` (tests pass altered copies to the launcher)."""
+        n = self._reset_check(table, p32, t32, v, m, pb, tb)
+        assert self.lib.apex_reset_args_size() == ctypes.sizeof(_lib.ResetArgs)
+        a = _lib.ResetArgs(p=p32.data_ptr(), t=t32.data_ptr(), v=v.data_ptr(), m=m.data_ptr(), pb=pb[0].data_ptr(),
+                           tb=tb[0].data_ptr(), pb_lo=_lib.ptr(pb[1]), tb_lo=_lib.ptr(tb[1]), n=n,
+                           seed=int(seed), r=int(r), nrows=len(table))
+        for k, row in enumerate(table):
+            a.rows[k] = _lib.ResetRow(*row)
+        return a
+
+    def reset_perturb(self, table, seed, r, p32, t32, v, m, pb, tb) -> None:
+        """csrc/reset.hip ``reset_perturb_kernel``: one launch over the flat vector."""
+        a = self.reset_args(table, seed, r, p32, t32, v, m, pb, tb)
+        _lib.check(self.lib.apex_reset_perturb(a, _lib.stream_ptr()), "reset_perturb")
 
     def cast_bf16(self, x32, hi, lo=None) -> None:
         """hi = bf16(x32) (and lo = bf16(x32 - hi)) with one kernel."""

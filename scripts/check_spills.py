@@ -20,7 +20,7 @@ HOT = ["conv12_fused_kernel", "conv2_dgrad_img", "conv3_dgrad_img", "igemm_dma_k
        "fc_gemm128_kernel", "conv1_wgrad_img_kernel", "conv21_bwd_fused_kernel", "fc_wgrad_head_prio_kernel", "rmsprop_sample_kernel",
        "grad_finalize_kernel", "actor_head_kernel", "c51_head_kernel", "hlg_head_kernel", "qr_head_kernel", "head_wgrad_prio_kernel",
        "noisy_compose_kernel", "noisy_sigma_grad_kernel", "iqn_head_kernel", "iqn_wgrad_prio_kernel", "iqn_wgrad_reduce_kernel", "sconv_", "resblock_",
-       "augment_shift_kernel", "maxpool_bwd",       # ("actor_head_kernel" also names the C51 / QR / IQN actor heads)
+       "augment_shift_kernel", "reset_perturb_kernel", "maxpool_bwd",      # ("actor_head_kernel" also names the C51 / QR / IQN actor heads)
        "mdqn_head_kernelILi512ELi8E"]          # (the MAXA = 8 instantiation: no scratch up to 8 actions)
 
 
