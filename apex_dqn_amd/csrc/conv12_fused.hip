@@ -32,7 +32,9 @@
 //     swapped so a lane holds 4 consecutive output channels of a pixel; the two
 //     kernel-row pairs meet in a 24 KB fp32 LDS buffer (the image's spent staging
 //     buffer), summed in fixed order by the kp = 0 waves, which apply bias + ReLU and
-//     store y2 as hi / lo planes.
+//     store y2 as hi / lo planes.  With conv3 fused (below: it takes y2 from LDS) only rows
+//     < y2_n store it -- the backward's rows; the others' 12 stores per wave and image and
+//     their HBM writes are skipped.
 // LDS: y1 hi + lo planes 2 x 52224 B + staging 2 x 28 KB (C = 4) + slot table = 159 KB.
 //
 // Online / target weights switch at image img_switch; each workgroup takes a contiguous
@@ -100,6 +102,8 @@ struct Conv12Desc {
   bf16_t* y3_lo;
   uint4* w3frag;           // both sets' conv3 weights in C3F fragment order (csrc/conv2_wfrag.h:
                            // set 0 hi, lo, set 1 hi, lo), packed with the other fragments
+  int y2_n;                // conv3 fused: only rows < y2_n store y2 (the rows the backward reads; the
+                           // fused conv3 takes y2 from LDS).  <= 0, or no fused conv3: every row
 };
 
 template <int C>
@@ -267,6 +271,8 @@ __global__ void __launch_bounds__(CF_THREADS, 1) conv12_fused_kernel(Conv12Desc 
   // moves ~7-25 B per cycle, so 12 stores in a row after the reduction cost ~3k cycles
   uint4 pend[3][2];
   int pend_img = -1;
+  // rows >= y2_lim keep their y2 on chip (Conv12Desc::y2_n, normalised by the launcher)
+  const int y2_lim = d.y2_n;
   // byte offset of this lane's y2 quad at (mt, jq = 0) within an image, -1 for padding
   // rows (their lanes skip; every wave has valid lanes in each mt, so the 12 store
   // instructions per wave and image that the vmcnt wait after conv1 counts always issue)
@@ -448,6 +454,8 @@ __global__ void __launch_bounds__(CF_THREADS, 1) conv12_fused_kernel(Conv12Desc 
   for (int i = 0; cur < d.N; ++i) {
     const int img = cur;
     const bool more = nxt < d.N;
+    // image i - 1's y2 leaves for HBM during this conv1 (workgroup-uniform)
+    const bool st_prev = pend_img >= 0 && pend_img < y2_lim;
     const int set = (two && img >= d.img_switch) ? 1 : 0;
     if (set != cur_set) {
 #ifdef APEX_PROBE
@@ -557,7 +565,7 @@ __global__ void __launch_bounds__(CF_THREADS, 1) conv12_fused_kernel(Conv12Desc 
         // MFMAs (that buffer's last readers -- conv1(i - 1), the reduction of image i - 1
         // -- finished before the barrier that closed image i - 1)
         if (j - 1 < NDW && more) issue_dma_piece(nsl, (i + 1) & 1, j - 1);
-        if (i > 0) store_y2(j - 1);                           // image i - 1's y2
+        if (st_prev) store_y2(j - 1);                         // image i - 1's y2
         __builtin_amdgcn_sched_barrier(0);
         mfma_tile(u[j & 1], a[j & 1], al[j & 1], j - 1, a[(j - 1) & 1], al[(j - 1) & 1]);
       }
@@ -566,9 +574,11 @@ __global__ void __launch_bounds__(CF_THREADS, 1) conv12_fused_kernel(Conv12Desc 
     }
     PROBE(d.probe, 4, i, 1);
     // image i + 1's frames (DMA pieces at tiles 1 .. NDW, each before that tile's y2 store)
-    // have landed: only the y2 stores of tiles NDW .. 12 are younger than the last piece
+    // have landed: only the y2 stores of tiles NDW .. 12 are younger than the last piece.
+    // The count holds only if those stores were issued: an image whose predecessor kept its
+    // y2 on chip (or had none) drains everything, which is the DMA pieces alone
     static_assert(NDW <= 7, "the vmcnt below assumes the last DMA piece at tile <= 7");
-    if (i > 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(cf_young_stores(NDW, SPLIT)) : "memory");
+    if (st_prev) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(cf_young_stores(NDW, SPLIT)) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();          // y1 complete; staging(i) read (free: the reduction's); staging(i + 1) visible
     const bool copy = img < d.copy_n;
@@ -710,7 +720,7 @@ __global__ void __launch_bounds__(CF_THREADS, 1) conv12_fused_kernel(Conv12Desc 
     cur = nxt;
     nxt = nn;
   }
-  if (pend_img >= 0) {
+  if (pend_img >= 0 && pend_img < y2_lim) {
 #pragma unroll
     for (int q = 0; q < 12; ++q) store_y2(q);   // the last image's y2
   }
@@ -778,6 +788,7 @@ APEX_EXPORT int apex_conv12_fused_fwd(Conv12Desc d, int grid, hipStream_t st) {
         (uintptr_t)d.w2 | (uintptr_t)d.w2_lo | (uintptr_t)d.b2 | (uintptr_t)d.y1 | (uintptr_t)d.y1_lo) & 15) ||
       (((uintptr_t)d.y2 | (uintptr_t)d.y2_lo | (uintptr_t)d.scratch) & 7) || ((uintptr_t)d.wfrag & 15))
     return (int)hipErrorInvalidValue;
+  if (d.w3 == nullptr || d.y2_n <= 0 || d.y2_n > d.N) d.y2_n = d.N;   // (the separate conv3 reads every row)
   int G = grid > 0 ? grid : 256;
   if (G > d.N) G = d.N;
   if ((d.N + G - 1) / G > CF_MAXIMG) G = (d.N + CF_MAXIMG - 1) / CF_MAXIMG;

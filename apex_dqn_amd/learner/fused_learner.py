@@ -571,10 +571,11 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             online = 0 if self._frag_out is not None else 1     # (stored by the last optimizer launch)
             # conv3 in the same launch from y2 in LDS (SW.conv123_fused)
             c3 = self._conv3_weights() if self._conv123 else None
+            # (with conv3 fused only the backward reads y2 from memory: the S_t rows)
             ops.conv12_fwd(ring, slots, self.frames, rt.obs_scale, self.y1, self.y1_lo, self.y2,
                            self.y2_lo, c1, c2, rows_first=r1, copy_n=B,
                            pack_sets=online | (0 if self._tgt_current() else 2), c3=c3, y3=self.y3,
-                           y3_lo=self.y3_lo)
+                           y3_lo=self.y3_lo, y2_n=B if (c3 is not None and SW.conv12_y2_rows) else None)
         else:
             c2f = (Pb["w2"], None, Tb["w2"], None)
             ops.conv1_fwd_ring(ring, slots, self.frames, Pb["w1"], P["b1"], rt.obs_scale, self.y1,

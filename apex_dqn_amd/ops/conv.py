@@ -308,7 +308,8 @@ def conv12_fused_fwd(lib, ws: "Workspace", ring: torch.Tensor, slots: torch.Tens
                      y1_lo: Optional[torch.Tensor] = None, copy_n: int = 0, w1b=None, b1b=None, w2b=None,
                      w2b_lo=None, b2b=None, rows_first: int = 0, grid: int = 0,
                      probe: Optional[torch.Tensor] = None, pack_sets: int = 3, probe_split: int = 0,
-                     c3=None, y3: Optional[torch.Tensor] = None, y3_lo: Optional[torch.Tensor] = None) -> None:
+                     c3=None, y3: Optional[torch.Tensor] = None, y3_lo: Optional[torch.Tensor] = None,
+                     y2_n: Optional[int] = None) -> None:
     """conv1 (fp32 OIHW weights ``w1``, exact uint8 frames from the s2d ring) + ReLU ->
     conv2 (hi / lo bf16 OHWI ``w2``, ``w2_lo``) + ReLU in one persistent launch, y1 kept
     in LDS; rows < ``copy_n`` also store y1 (hi / lo) for the backward.  Rows >=
@@ -317,7 +318,12 @@ def conv12_fused_fwd(lib, ws: "Workspace", ring: torch.Tensor, slots: torch.Tens
     see ``conv12_pack``).  ``w2_lo`` None: the bf16 kernel (one plane; ``y1_lo``,
     ``y2_lo`` unused).  ``c3 = (w3, w3_lo, b3, w3 target, w3_lo target, b3 target)``:
     conv3 (3x3 / s1, OHWI bf16 planes) + ReLU fused too, from y2 in LDS, into ``y3``
-    (``y3_lo``) [N, 7, 7, 64]; y2 is still written for every row."""
+    (``y3_lo``) [N, 7, 7, 64]; y2 is then written for rows < ``y2_n`` only (None: every
+    row) -- the fused conv3 reads it from LDS, so only a backward needs it in memory.
+    Without ``c3`` every row is written whatever ``y2_n`` says.  The contract callers rely
+    on is this one: ``y2_n`` is None or in [1, N] (asserted).  The launcher's mapping of 0 or
+    an out-of-range ``Conv12Desc::y2_n`` to "every row" only makes a zero-initialised
+    descriptor (every caller from before the field existed) behave as it did."""
     N, C = slots.shape
     sp = w2_lo is not None
     assert slots.dtype == torch.int32 and slots.is_contiguous() and int(w1.shape[1]) == C
@@ -333,6 +339,9 @@ def conv12_fused_fwd(lib, ws: "Workspace", ring: torch.Tensor, slots: torch.Tens
     d.y2, d.y2_lo = y2.data_ptr(), (y2_lo.data_ptr() if sp else 0)
     d.pack_sets = int(pack_sets)
     d.N = N
+    if y2_n is not None:
+        assert 1 <= int(y2_n) <= N      # (the descriptor's 0 means every row)
+        d.y2_n = int(y2_n)
     d.probe = _lib.ptr(probe)
     d.probe_split = int(probe_split)
     d.wq = ws.wq(("cf_wq", N, int(grid)), ring.device, overlapped=False)
@@ -601,9 +610,55 @@ def conv2_wgrad_rows_pick(x_shape, dy_shape, KH: int, stride: int, split: bool, 
     return covers and bool(SW.conv2_wgrad_rows) and x_shape[0] >= SW.conv2_wgrad_rows_min
 
 
+def conv3_wgrad_img_covers(x_shape, dy_shape, KH: int, stride: int, split: bool) -> bool:
+    """Whether the image-resident conv3 weight-gradient kernel (csrc/conv3_wgrad_img.hip)
+    covers the problem: split-mode conv3 only (y2 [N, 9, 9, 64] against dY3 [N, 7, 7, 64],
+    3 x 3 stride 1)."""
+    return (bool(split) and KH == 3 and stride == 1 and len(x_shape) == 4 and len(dy_shape) == 4
+            and tuple(x_shape[1:]) == (9, 9, 64) and tuple(dy_shape[1:]) == (7, 7, 64)
+            and x_shape[0] == dy_shape[0] and x_shape[0] > 0)
+
+
+def conv3_wgrad_img_pick(x_shape, dy_shape, KH: int, stride: int, split: bool, force: Optional[bool] = None) -> bool:
+    """The conv3 weight-gradient path: ``force`` (tests, microbenchmarks) wins, else the
+    image-resident kernel where it covers the problem, ``SW.conv3_wgrad_img`` is on and the
+    batch has at least ``SW.conv3_wgrad_img_min`` images.  Forcing it on an uncovered
+    problem is an error."""
+    covers = conv3_wgrad_img_covers(x_shape, dy_shape, KH, stride, split)
+    if force is not None:
+        if force and not covers:
+            raise ValueError("conv3_wgrad_img does not cover this problem")
+        return bool(force)
+    return covers and bool(SW.conv3_wgrad_img) and x_shape[0] >= SW.conv3_wgrad_img_min
+
+
+def _conv3_wgrad_img(lib, ws: Workspace, dy, x, dw_out, db_out, jobs, dy_lo, x_lo, grid: int) -> None:
+    """conv3's weight gradient on the image-resident kernel: ``grid`` persistent workgroups
+    (0: ``SW.conv3_wgrad_img_grid``; capped to the images, so every workgroup owns at
+    least one), one partial slab plane each, the job the same as the generic kernel's."""
+    N = dy.shape[0]
+    for t in (dy, x, dy_lo, x_lo):
+        assert t.is_contiguous() and t.dtype == torch.bfloat16
+    assert dy_lo.shape == dy.shape and x_lo.shape == x.shape
+    G = max(1, min(N, int(grid) if grid > 0 else int(SW.conv3_wgrad_img_grid)))
+    slab = ws.get(("wg3img", G), G * 64 * 576, dy.device)
+    bslab = ws.get(("wg3imgb", G), G * 64, dy.device)
+    d = _wg_desc(dy=dy.data_ptr(), x=x.data_ptr(), slab=slab.data_ptr(), bias_slab=bslab.data_ptr(), N=N, H=9, W=9,
+                 Cin=64, OH=7, OW=7, KH=3, KW=3, stride=1, mode=1, Co=64, Kc=576, ldd=64, rows_per_split=0,
+                 Mred=N * 49, dy_lo=dy_lo.data_ptr(), x_lo=x_lo.data_ptr())
+    if jobs is not None:   # reduction deferred to one grad_finalize launch
+        _lib.check(lib.apex_conv3_wgrad_img(d, None, None, G, 1.0, _lib.stream_ptr()), "conv3_wgrad_img")
+        jobs.append(dict(slab=slab, bslab=bslab, out=dw_out, bout=db_out, n=64 * 576, nsplit=G, nb=64, s2dC=0,
+                         Kc=576, scale=1.0))
+        return
+    _lib.check(lib.apex_conv3_wgrad_img(d, dw_out.data_ptr(), db_out.data_ptr(), G, 1.0, _lib.stream_ptr()),
+               "conv3_wgrad_img")
+
+
 def conv_wgrad(lib, ws: Workspace, dy: torch.Tensor, x: torch.Tensor, KH: int, stride: int,
                dw_out: torch.Tensor, db_out: torch.Tensor, target_rows: int = 0, jobs: Optional[list] = None,
-               dy_lo=None, x_lo=None, rows_kernel: Optional[bool] = None) -> None:
+               dy_lo=None, x_lo=None, rows_kernel: Optional[bool] = None, img_kernel: Optional[bool] = None,
+               img_grid: int = 0) -> None:
     """dW (OHWI, fp32) and db for an NHWC conv with 64 output channels.  With
     ``jobs``, the split-K reduction is appended there for ``finalize_grads``.
     ``target_rows``: reduction rows per split-K block (0 = tuned default: fewer
@@ -619,8 +674,15 @@ def conv_wgrad(lib, ws: Workspace, dy: torch.Tensor, x: torch.Tensor, KH: int, s
     implicit GEMM (8 blocks of two taps per split, 4 waves, 144 KB LDS: 8 x 59 blocks at 512
     images) and the row-resident kernel (csrc/conv2_wgrad_rows.hip: one 8-wave block per
     (split, kernel row), 4 x 59, each input row staged once).  ``rows_kernel`` forces one
-    (tests); the default is ``conv2_wgrad_rows_pick``."""
+    (tests); the default is ``conv2_wgrad_rows_pick``.
+    Split-mode conv3 has the image-resident kernel (csrc/conv3_wgrad_img.hip: ``img_grid``
+    persistent workgroups, one slab plane each; a different summation order, so not the
+    generic kernel's bits): ``img_kernel`` forces it on or off, the default is
+    ``conv3_wgrad_img_pick``."""
     N, OH, OW, Co = dy.shape
+    if conv3_wgrad_img_pick(x.shape, dy.shape, KH, stride, dy_lo is not None and x_lo is not None, img_kernel):
+        _conv3_wgrad_img(lib, ws, dy, x, dw_out, db_out, jobs, dy_lo, x_lo, img_grid)   # a missing kernel is an error
+        return
     if target_rows <= 0:
         small = N < 256
         target_rows = {3: SW.wg_rows3, 4: SW.wg_rows2}.get(KH) or \

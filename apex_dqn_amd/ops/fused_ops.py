@@ -93,14 +93,15 @@ class TorchBackend:
         conv3's too."""
 
     def conv12_fwd(self, ring, slots, frames_buf, scale, y1, y1_lo, y2, y2_lo, c1, c2, rows_first=0, copy_n=None,
-                   pack_sets=3, c3=None, y3=None, y3_lo=None):
+                   pack_sets=3, c3=None, y3=None, y3_lo=None, y2_n=None):
         """conv1 -> conv2 in split mode: ``c1 = (w1 fp32, b1, w1 target, b1 target)``, ``c2 =
         (w2, w2_lo, b2, w2 target, w2_lo target, b2 target)`` (target entries None: one
         set).  y1 rows < ``copy_n`` must hold conv1's output afterwards (the backward's
         input); the HIP backend keeps the other rows in LDS (csrc/conv12_fused.hip) and
         repacks the weight fragments of ``pack_sets`` first (the others come from the last
         ``conv12_pack``).  ``c3 = (w3, w3_lo, b3, w3 target, w3_lo target, b3 target)``:
-        conv3 too, into ``y3`` / ``y3_lo``."""
+        conv3 too, into ``y3`` / ``y3_lo``; the HIP backend then writes y2 for rows <
+        ``y2_n`` only (None: every row); this backend writes every row."""
         w1, b1, w1b, b1b = c1
         w2, w2l, b2, w2b, w2bl, b2b = c2
         self.conv1_fwd_ring(ring, slots, frames_buf, w1.to(y1.dtype), b1, scale, y1,
@@ -925,7 +926,7 @@ class HipBackend(TorchBackend):
                       b2b=b2b, sets=sets, c3=c3)
 
     def conv12_fwd(self, ring, slots, frames_buf, scale, y1, y1_lo, y2, y2_lo, c1, c2, rows_first=0, copy_n=None,
-                   pack_sets=3, c3=None, y3=None, y3_lo=None):
+                   pack_sets=3, c3=None, y3=None, y3_lo=None, y2_n=None):
         if not self._conv12_native():
             return super().conv12_fwd(ring, slots, frames_buf, scale, y1, y1_lo, y2, y2_lo, c1, c2, rows_first,
                                       copy_n, c3=c3, y3=y3, y3_lo=y3_lo)
@@ -934,7 +935,7 @@ class HipBackend(TorchBackend):
         n = slots.shape[0] if copy_n is None else int(copy_n)
         C.conv12_fused_fwd(self.lib, self.ws, ring, slots, w1, b1, w2, w2l, b2, scale, y2, y2_lo, y1=y1, y1_lo=y1_lo,
                            copy_n=n, w1b=w1b, b1b=b1b, w2b=w2b, w2b_lo=w2bl, b2b=b2b, rows_first=rows_first,
-                           pack_sets=pack_sets, c3=c3, y3=y3, y3_lo=y3_lo)
+                           pack_sets=pack_sets, c3=c3, y3=y3, y3_lo=y3_lo, y2_n=y2_n)
 
     def conv_fwd(self, x, w, b, stride, out, w2=None, b2=None, rows_first=0, x_lo=None, w_lo=None, w2_lo=None,
                  out_lo=None):

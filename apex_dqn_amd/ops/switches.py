@@ -37,6 +37,15 @@ class Switches:
     # 163.1-169.7 us, W = 4 192.7-193.5 vs 198.1-202.9 us (profiles/r6_ab_conv123_fused_c3f.txt;
     # with the weights read from OHWI rows it lost at 512 rows, r6_ab_conv123_fused.txt)
     conv123_max_images: int = 1 << 20
+    # with conv3 fused, the forward writes y2 to memory only for the S_t rows (the backward's
+    # input; csrc/conv12_fused.hip Conv12Desc::y2_n): the 2B rows of S_t+n keep it in LDS, 21 MB
+    # of stores per 512-row fp32 update that nothing read.  The step's results are the same
+    # bytes.  conv12_fused_kernel in the 512-row fp32 step 118.4 -> 114.8 us
+    # (profiles/pr33_step_timeline_fp32_parent.txt, pr33_step_timeline_fp32_conv3_wgrad_img.txt);
+    # parent / this tree / this tree with the switch off, 4 interleaved runs each at 20 / 5
+    # steps: 2,928-2,956 / 2,974-3,015 / 2,912-2,927 updates/s (profiles/pr33_ab_switches.txt).
+    # The 200 / 20 comparison has not been taken
+    conv12_y2_rows: bool = True
     # the fused forward's one-plane variant for the bf16 learner (4,105 vs 3,790 steps/s,
     # profiles/r3_ab_conv12_bf16_fused_4105_vs_3790.txt)
     conv12_bf16: bool = True
@@ -105,6 +114,24 @@ class Switches:
     # blocks) and 511 nobody has measured
     conv2_wgrad_rows: bool = True
     conv2_wgrad_rows_min: int = 512
+    # split-mode conv3 weight gradient on the image-resident kernel (csrc/conv3_wgrad_img.hip:
+    # dY3 and y2 staged once per image, the whole 64 x 576 gradient in the registers of
+    # conv3_wgrad_img_grid persistent workgroups, one slab plane each) for batches of at
+    # least conv3_wgrad_img_min images.  OFF: correct (tests/test_gpu_conv3_wgrad_img.py) but
+    # slower than the generic kernel at every size measured.  Isolated, 7 interleaved repeats
+    # of 50 launches, kernel (+ its grad_finalize): generic 13.4-13.7 (+ 3.4) us at 512 images;
+    # 64 workgroups 25.7-26.5 (+ 3.4), 128: 18.7-18.9 (+ 3.9), 256: 15.5-15.6 (+ 8.0); at 256
+    # images 12.6 vs 14.4 (128) / 13.0 (256), at 146 images 8.6 vs 14.1, at 74 images 8.0 vs
+    # 12.7 (profiles/pr33_conv3_wgrad_isolated.txt): ~1.7 us per image and workgroup, as
+    # modelled, on top of ~12 us per launch that the model did not have.  In the 512-row fp32
+    # step 24.1 us against the generic kernel's 18.0; on vs off in one tree, 4 interleaved
+    # runs each at 20 / 5 steps: 2,832-2,858 vs 2,912-2,927 updates/s (grid 128, the best of
+    # 64 / 128 / 256; profiles/pr33_ab_switches.txt); emulated W = 8 rank step 154.0-158.0 vs
+    # 150.7-153.2 us (profiles/pr33_emulated_ranks.txt).  docs/PERF_NOTES.md has the account.
+    # The threshold is the one size at which the step was worth asking about
+    conv3_wgrad_img: bool = False
+    conv3_wgrad_img_min: int = 512
+    conv3_wgrad_img_grid: int = 128
     # IMPALA weight gradients: workgroups per conv and the partial-slab cap (floats)
     impala_wg_target: int = 512
     impala_slab_cap: int = 8 << 20

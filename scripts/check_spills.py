@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "apex_dqn_amd", "csrc")
 # kernels on the default learner / actor paths (substring of the mangled name)
 HOT = ["conv12_fused_kernel", "conv2_dgrad_img", "conv3_dgrad_img", "igemm_dma_kernel", "igemm_wgrad_kernel",
-       "conv2_wgrad_rows_kernel",
+       "conv2_wgrad_rows_kernel", "conv3_wgrad_img_kernel",
        "fc_gemm128_kernel", "conv1_wgrad_img_kernel", "conv21_bwd_fused_kernel", "fc_wgrad_head_prio_kernel", "rmsprop_sample_kernel",
        "grad_finalize_kernel", "actor_head_kernel", "c51_head_kernel", "hlg_head_kernel", "qr_head_kernel", "head_wgrad_prio_kernel",
        "noisy_compose_kernel", "noisy_sigma_grad_kernel", "iqn_head_kernel", "iqn_wgrad_prio_kernel", "iqn_wgrad_reduce_kernel", "sconv_", "resblock_",
