@@ -299,6 +299,9 @@ class GpuActorGroup:
             ops.noisy_compose(self._nz, [(self.p32, self._e32, self._ebf[:nm], self._ebf[nm:] if self.split else None)],
                               self.xi)
             F, Fb, Fl = self.EP, self.EPb, self.EPl
+        if getattr(self.learner, "layer_norm", False):
+            # the stream layers' LayerNorm: gamma / beta of the actor's parameter slot in fp32, nothing saved
+            ks["ln"] = (P["lng"], P["lnb"], None, None, float(self.cfg.Runtime.layer_norm_eps), 0, None, None)
         if self.split:
             if c3 is None:
                 ops.conv_fwd(self.y2, Pb["w3"], P["b3"], 1, self.y3, x_lo=self.y2_lo, w_lo=Pl["w3"],

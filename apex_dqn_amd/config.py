@@ -171,6 +171,14 @@ class RuntimeConf:
     reset_interval: int = 0
     reset_shrink_encoder: float = 0.5
     reset_shrink_head: float = 0.0
+    # LayerNorm on the two stream layers, between the Linear and the ReLU (Lyle et al. 2023; PQN, Gallici et al.
+    # 2024; models/dueling.py, csrc/fc_layernorm.hip): torch's nn.LayerNorm over each stream's own features, gamma = 1
+    # and beta = 0 at the start, eps = layer_norm_eps.  false = off (no segment, no buffer, no launch, the launches and
+    # the bits of before).  Single-rank NatureCNN with every head kind, noisy layers, the Munchausen target, value
+    # rescaling, the random shift, the resets, Adam, the schedules and either target, and the torch learners (mlp);
+    # not IMPALA, the DP step or the graph learner
+    layer_norm: bool = False
+    layer_norm_eps: float = 1e-5
     # Atari wrappers clip rewards to {-1, 0, +1} (envs/vector_envs.py AtariWrapperVec); false keeps the raw rewards
     # (with value_rescale; the two keys are independent)
     clip_rewards: bool = True
@@ -481,6 +489,21 @@ class ApexConfig:
             if int(rt.world_size) > 1 or rt.force_dp:
                 raise ValueError("Runtime.reset_interval runs on a single rank: the data-parallel step (world_size > 1, "
                                  "force_dp) has no periodic resets")
+        if not isinstance(rt.layer_norm, bool):
+            raise ValueError(f"Runtime.layer_norm must be true or false, got {rt.layer_norm!r}")
+        le = rt.layer_norm_eps
+        if isinstance(le, bool) or not isinstance(le, (int, float)) or not np.isfinite(float(le)) or not float(le) > 0.0:
+            raise ValueError(f"Runtime.layer_norm_eps (the variance floor of Runtime.layer_norm) must be a finite "
+                             f"number > 0, got {le!r}")
+        if rt.layer_norm:
+            if net == "impala":
+                raise ValueError("Runtime.layer_norm: the IMPALA step has no layer normalisation (it is the "
+                                 "NatureCNN learner's)")
+            if net not in ("nature64", "nature32", "mlp"):
+                raise ValueError(f"Runtime.layer_norm needs network nature64, nature32 or mlp, got {net!r}")
+            if int(rt.world_size) > 1 or rt.force_dp:
+                raise ValueError("Runtime.layer_norm runs on a single rank: the data-parallel step (world_size > 1, "
+                                 "force_dp) has no layer normalisation")
         if net in ("nature64", "nature32", "impala") and len(ss) != 3:
             raise ValueError(f"network {net} needs an image state_shape [C,H,W], got {ss}")
         if net in ("nature64", "nature32") and tuple(ss[1:]) != (84, 84):
@@ -505,6 +528,8 @@ class ApexConfig:
             kw.update(iqn_actor_samples=int(rt.iqn_actor_samples))
         if rt.noisy:       # (only then: the non-noisy call is the one of before)
             kw.update(noisy=True, noisy_sigma0=float(rt.noisy_sigma0))
+        if rt.layer_norm:  # (only then)
+            kw.update(layer_norm=True, layer_norm_eps=float(rt.layer_norm_eps))
         return kw
 
     @property

@@ -65,8 +65,9 @@ from ..models.flat_params import (FlatLayout, flat_to_reference_state, nature_se
                                   reference_state_to_flat)
 from ..ops.fused_ops import HipBackend, TorchBackend, split_into
 from ..ops.switches import SW
-from ..utils.checkpoint import (adopt_obs_scale, check_dist_head, check_noisy, layout_segments, load_checkpoint,
-                                pack_flat_state, save_checkpoint, unpack_flat_state, checkpoint_network)
+from ..utils.checkpoint import (adopt_obs_scale, check_dist_head, check_layer_norm, check_noisy, layout_segments,
+                                load_checkpoint, pack_flat_state, save_checkpoint, unpack_flat_state,
+                                checkpoint_network)
 from .dp_step import DataParallelStep, Streams
 from .is_norm import IsNormMixin
 from .schedules import StepIndexMixin, target_ema_on
@@ -169,6 +170,13 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         if self.reset_I and self._dp:
             raise ValueError("Runtime.reset_interval: the resets run on a single rank, not in the data-parallel step "
                              "(world > 1, Runtime.force_dp, the emulated world)")
+        # LayerNorm on the two stream layers (csrc/fc_layernorm.hip): the fc forward's split-K epilogue normalises, one
+        # backward launch between the head and the fc gradients, gamma / beta as the segments lng / lnb behind
+        # everything else in the flat layout; false = no segment, no buffer, no launch, no new kernel argument
+        self.layer_norm = bool(self.rt.layer_norm)
+        if self.layer_norm and self._dp:
+            raise ValueError("Runtime.layer_norm: the stream layers are normalised on a single rank, not in the "
+                             "data-parallel step (world > 1, Runtime.force_dp, the emulated world)")
         if self.rt.dtype not in ("fp32", "bf16"):
             raise ValueError("Runtime.dtype must be fp32 or bf16")
         self.precision = self.rt.dtype
@@ -194,7 +202,8 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         # (the torch backend emulates the split kernel's contract: ops.conv12_fwd)
         self._c12 = self.split or (backend == "hip" and self.ops._conv12_native() and SW.conv12_bf16)
         d = self.device
-        self.layout = FlatLayout(nature_segments(self.C, self.A, 64, self.Nh, noisy=self.noisy, implicit=self.implicit))
+        self.layout = FlatLayout(nature_segments(self.C, self.A, 64, self.Nh, noisy=self.noisy, implicit=self.implicit,
+                                                 **({"layer_norm": True} if self.layer_norm else {})))
         n = self.layout.numel
         self.p32 = torch.zeros(n, dtype=torch.float32, device=d)
         # bf16 compute copies [hi | lo] of the online / target parameters (lo: split mode)
@@ -276,7 +285,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         # With the sigma-gradient blocks as one more producer the step measured the same within
         # its spread, profiles/pr11_ab_noisy_sigma_norm_partials_rejected.txt)
         self._fuse_norm = not self._dp and self.ops.name == "hip" and getattr(self.ops, "native_conv", False) \
-            and not self.noisy and not self.implicit
+            and not self.noisy and not self.implicit and not self.layer_norm
         # DP: the rank-local replay shards form ONE prioritized replay (replay/gpu_replay.py
         # enable_sharding): every step all-gathers the shards' (sum p^alpha, min p^alpha)
         # right after the priority write-back and the next batch is one global draw,
@@ -329,7 +338,8 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         # carries the conv2 fragment pack job)
         # (the Munchausen head reads h too: with the weight set switched at row B the fc forward keeps its
         # own epilogue, ops.fc_fwd)
-        self._defer_fc_epilogue = SW.fc_epi_in_head and self.N == 1 and not self.munchausen
+        # (Runtime.layer_norm: the LayerNorm epilogue is the fc forward's own launch, the head reads h)
+        self._defer_fc_epilogue = SW.fc_epi_in_head and self.N == 1 and not self.munchausen and not self.layer_norm
         # next-batch pre-sampling: the batch of step t+1 is drawn at the end of step t,
         # after the priority write-back -- on the HIP backend inside the optimizer launch
         # (its first blocks run the sampler: csrc/sumtree.hip rmsprop_sample_kernel), so
@@ -493,6 +503,11 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         self.y3, self.y3_lo = act(3 * B, 7, 7, 64)
         self.h, self.h_lo = act(3 * B, 1024)
         self.dH, self.dH_lo = act(B, 1024)
+        self.ln_xhat = self.ln_rstd = self._ln_tok = None
+        if self.layer_norm:
+            # what the LayerNorm epilogue leaves of the B training rows for its backward: xh and r per stream
+            self.ln_xhat = torch.zeros(B, 1024, dtype=torch.float32, device=d)
+            self.ln_rstd = torch.zeros(B, 2, dtype=torch.float32, device=d)
         self.dY3, self.dY3_lo = act(B, 7, 7, 64)
         self.dY2, self.dY2_lo = act(B, 9, 9, 64)
         self.dY1, self.dY1_lo = act(B, 20, 20, 64)
@@ -588,9 +603,26 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         self._wait_params()       # sharded DP update: the last update's fc rows (learner/dp_step.py)
         wfc, wfc_lo, bfc, wfc_t, wfc_t_lo, bfc_t = self._fc_weights()
         ops.fc_fwd(self.y3.reshape(n, 3136), wfc, bfc, self.h, wfc_t, bfc_t, r1,
-                   c2d=(Pb["w2"], Pl["w2"] if sp else None), defer_head=defer_head,
+                   c2d=(Pb["w2"], Pl["w2"] if sp else None), defer_head=defer_head, **self._ln_kw(B),
                    **self._lo(x_lo=sp and self.y3_lo.reshape(n, 3136), w_lo=wfc_lo,
                               w2_lo=wfc_t_lo, out_lo=self.h_lo))
+
+    def _ln_kw(self, save_n: int) -> Dict[str, Any]:
+        """``ln=`` of ``ops.fc_fwd`` with ``Runtime.layer_norm`` (empty without: the call of before): the fp32 gamma /
+        beta of both nets, eps, and where the first ``save_n`` rows leave xh and r."""
+        if not self.layer_norm:
+            return {}
+        P, T = self.P, self.T
+        return {"ln": (P["lng"], P["lnb"], T["lng"], T["lnb"], float(self.rt.layer_norm_eps), save_n,
+                       self.ln_xhat, self.ln_rstd)}
+
+    def _ln_backward(self) -> None:
+        """dH: the head's gradient at gamma xh + beta -> the gradient at the fc pre-activation, in place, right behind
+        the head on the main stream (fc_ln_bwd_kernel); G[lng] / G[lnb] follow where the fc and head weight gradients
+        run (:meth:`_head_fc_weight_grads`).  Everything downstream reads the same buffers as before."""
+        if self.layer_norm:
+            self._ln_tok = self.ops.fc_ln_backward(self.dH, self.ln_xhat, self.ln_rstd, self.P["lng"], self.G["lng"],
+                                                   self.G["lnb"], **self._lo(dh_lo=self.dH_lo))
 
     def _conv12_weights(self):
         P, T, Pb, Tb, Pl, Tl = self.P, self.T, self.Pb, self.Tb, self.Pl, self.Tl
@@ -638,6 +670,8 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
     def _head_fc_weight_grads(self, prio) -> None:
         """The head and fc weight gradients with the priority write-back ``prio``: one launch on the HIP backend
         (csrc/sumtree.hip fc_wgrad_head_prio_kernel), or the implicit head's own launches."""
+        if self.layer_norm:     # the small reduce of G[lng] / G[lnb]'s chunk partials (_ln_backward)
+            self.ops.fc_ln_reduce(self._ln_tok)
         if self.implicit:
             return self._iqn_weight_grads(prio)
         sp, B, G = self.split, self.B, self.G
@@ -712,6 +746,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         self.forward_all(defer_head=self._defer_fc_epilogue)
         self._mark("forward")
         self._loss_head(S["weights"] if self._isw else None)
+        self._ln_backward()
         self._mark("head")
         prio = (self.replay, S["idx"], S["gen"], self.td_abs)
         if self._branched or self._dp:
@@ -1310,6 +1345,8 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             m["augment_offset_mean"] = float(self.aug_off.double().mean())
         if self.reset_I:        # shrink-and-perturb resets so far
             m["resets"] = self.num_q_updates // self.reset_I
+        if self.layer_norm:     # the last update's mean 1 / sqrt(var + eps) over the training rows' two streams
+            m["ln_rstd_mean"] = float(self.ln_rstd.double().mean())
         return m
 
     def q_values(self, frames_u8: torch.Tensor) -> torch.Tensor:
@@ -1347,6 +1384,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             return False
         check_dist_head(ck, self.rt)
         check_noisy(ck, self.rt)
+        check_layer_norm(ck, self.rt)
         if adopt_obs_scale(ck, self.rt):
             self._graphs = self._multi = None    # the input scale is a kernel argument: recapture
             self._setup_frag_out()               # (and folded into the conv1 operands)

@@ -80,6 +80,9 @@ class GraphLearner(StepIndexMixin):
         if int(self.rt.reset_interval) > 0:
             raise ValueError("Runtime.reset_interval: the graph learner (Runtime.use_hip_kernels = false on the GPU) "
                              "has no periodic resets; run the HIP kernels or reset_interval = 0")
+        if self.rt.layer_norm:
+            raise ValueError("Runtime.layer_norm: the graph learner (Runtime.use_hip_kernels = false on the GPU) has "
+                             "no layer normalisation; run the HIP kernels or layer_norm = false")
         self.device = torch.device(device)
         self.replay = replay
         self.comm = comm

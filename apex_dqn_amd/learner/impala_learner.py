@@ -90,6 +90,9 @@ class FusedImpalaLearner(IsNormMixin, StepIndexMixin):
         if int(self.rt.reset_interval) > 0:
             raise ValueError("Runtime.reset_interval: the IMPALA step has no periodic resets (they are the NatureCNN "
                              "learner's)")
+        if self.rt.layer_norm:
+            raise ValueError("Runtime.layer_norm: the IMPALA step has no layer normalisation (it is the NatureCNN "
+                             "learner's)")
         self.world, _, self.B, self.mcap = dp_layout(cfg, comm, batch_size, allow_force=False)
         self.C = cfg.frame_stack
         if self.C != 4 or tuple(cfg.env_conf.state_shape[1:]) != (84, 84):

@@ -33,6 +33,7 @@ from ..replay.gpu_replay import _mix64
 MAX_ROWS = 32       # csrc/reset.hip RESET_MAX_ROWS
 ENCODER = ("w1", "b1", "w2", "b2", "w3", "b3")
 _SIGMA_OF = {"swv": "wv", "sbv": "wv", "swa": "wa", "sba": "wa", "swfc": "wfc", "sbfc": "wfc"}
+_LN_CONST = {"lng": 1.0, "lnb": 0.0}       # models/flat_params.py: the stream layers' LayerNorm gamma / beta
 _WEIGHT_OF = {"b1": "w1", "b2": "w2", "b3": "w3", "bfc": "wfc", "bv": "wv", "ba": "wa", "btau": "wtau"}
 
 
@@ -84,7 +85,9 @@ def reset_table(layout, cfg) -> List[ResetRow]:
         elif name in ("b1", "w2"):       # (64,), (64, 4, 4, 64): the channels >= c1 are padding
             period, live = 64, c1
         alpha = a_e if name in ENCODER else a_h
-        if name in _SIGMA_OF:
+        if name in _LN_CONST:            # the LayerNorm affine back to its start: gamma 1, beta 0 (no draw)
+            rows.append(ResetRow(start, start + n, period, live, 0.0, alpha, 1, _LN_CONST[name]))
+        elif name in _SIGMA_OF:
             p = fan[_SIGMA_OF[name]]
             rows.append(ResetRow(start, start + n, period, live, float(fan_in_bound(p)), alpha, 1,
                                  float(sigma_const(rt.noisy_sigma0, p))))
@@ -106,9 +109,13 @@ def module_reset_table(module, cfg) -> List[ResetRow]:
     for name, shape in shapes.items():
         n = int(np.prod(shape))
         stem, leaf = name.rsplit(".", 1)
+        alpha = a_e if name.startswith("layer") else a_h
+        if len(shapes[stem + ".weight"]) == 1:      # a LayerNorm's affine: gamma 1, beta 0 (no draw)
+            rows.append(ResetRow(off, off + n, n, n, 0.0, alpha, 1, 1.0 if leaf == "weight" else 0.0))
+            off += n
+            continue
         w = shapes[stem + ".weight"]
         p = int(np.prod(w[1:]))
-        alpha = a_e if name.startswith("layer") else a_h
         sig = leaf.endswith("_sigma")
         rows.append(ResetRow(off, off + n, n, n, float(fan_in_bound(p)), alpha, int(sig),
                              float(sigma_const(rt.noisy_sigma0, p)) if sig else 0.0))

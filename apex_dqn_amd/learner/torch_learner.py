@@ -19,7 +19,8 @@ import torch
 
 from ..config import ApexConfig
 from ..models.dueling import build_network
-from ..utils.checkpoint import adopt_obs_scale, check_dist_head, check_noisy, load_checkpoint, save_checkpoint
+from ..utils.checkpoint import (adopt_obs_scale, check_dist_head, check_layer_norm, check_noisy, load_checkpoint,
+                                save_checkpoint)
 from .losses import c51_loss, ddqn_loss, hl_gauss_loss, munchausen_loss, munchausen_targets, quantile_huber_loss
 from .schedules import lr_scheduled, rt_lr, target_ema_on
 
@@ -234,6 +235,7 @@ class TorchLearner:
             return False
         check_dist_head(ck, self.rt)
         check_noisy(ck, self.rt)
+        check_layer_norm(ck, self.rt)
         if adopt_obs_scale(ck, self.rt):
             for net in (self.Q, self.Q_target):
                 if hasattr(net, "pre"):

@@ -68,6 +68,16 @@ def _linear(p: int, rows: int, noisy: bool, sigma0: float) -> nn.Module:
     return NoisyLinear(p, rows, sigma0) if noisy else nn.Linear(p, rows)
 
 
+def _stream(p: int, rows: int, noisy: bool, sigma0: float, layer_norm: bool = False, eps: float = 1e-5) -> nn.Sequential:
+    """One stream layer: Linear, ReLU -- or with ``layer_norm`` (Runtime.layer_norm) Linear, LayerNorm(rows), ReLU:
+    biased variance over the stream's own ``rows`` features, per-feature affine, gamma = 1 and beta = 0 at the start
+    (csrc/fc_layernorm.hip states the arithmetic).  The Linear stays at index 0: every other key keeps its name, the
+    new ones are ``<stream>.1.weight`` / ``<stream>.1.bias``."""
+    if layer_norm:
+        return nn.Sequential(_linear(p, rows, noisy, sigma0), nn.LayerNorm(rows, eps=float(eps)), nn.ReLU())
+    return nn.Sequential(_linear(p, rows, noisy, sigma0), nn.ReLU())
+
+
 class _C51Head:
     """Distributional (C51) dueling head shared by the modules that take ``num_atoms``:
     the value head has N outputs, the advantage head A N (row a N + i = action a, atom i),
@@ -215,18 +225,19 @@ class DuellingDQN(nn.Module, _C51Head):
                  conv1_channels: int = 64, obs_scale: float = 1.0 / 255.0,
                  num_atoms: int = 1, v_min: float = -10.0, v_max: float = 10.0,
                  dist_head: str = "categorical", noisy: bool = False, noisy_sigma0: float = 0.5,
-                 iqn_actor_samples: int = 32):
+                 iqn_actor_samples: int = 32, layer_norm: bool = False, layer_norm_eps: float = 1e-5):
         super().__init__()
         self.input_shape = tuple(state_shape)
         self.action_dim = int(action_dim)
+        self.layer_norm = bool(layer_norm)
         c = int(state_shape[0])
         c1 = int(conv1_channels)
         self.pre = _ObsScale(obs_scale)
         self.layer1 = nn.Sequential(nn.Conv2d(c, c1, 8, stride=4), nn.ReLU())
         self.layer2 = nn.Sequential(nn.Conv2d(c1, 64, 4, stride=2), nn.ReLU())
         self.layer3 = nn.Sequential(nn.Conv2d(64, 64, 3, stride=1), nn.ReLU())
-        self.value_stream_layer = nn.Sequential(_linear(64 * 7 * 7, 512, noisy, noisy_sigma0), nn.ReLU())
-        self.advantage_stream_layer = nn.Sequential(_linear(64 * 7 * 7, 512, noisy, noisy_sigma0), nn.ReLU())
+        self.value_stream_layer = _stream(64 * 7 * 7, 512, noisy, noisy_sigma0, layer_norm, layer_norm_eps)
+        self.advantage_stream_layer = _stream(64 * 7 * 7, 512, noisy, noisy_sigma0, layer_norm, layer_norm_eps)
         self._init_head(512, num_atoms, v_min, v_max, dist_head, noisy, noisy_sigma0, iqn_actor_samples)
 
     def streams(self, x: torch.Tensor):
@@ -261,14 +272,15 @@ class MLPDuellingDQN(nn.Module, _C51Head):
     def __init__(self, state_shape: Sequence[int], action_dim: int, hidden: int = 128,
                  num_atoms: int = 1, v_min: float = -10.0, v_max: float = 10.0,
                  dist_head: str = "categorical", noisy: bool = False, noisy_sigma0: float = 0.5,
-                 iqn_actor_samples: int = 32):
+                 iqn_actor_samples: int = 32, layer_norm: bool = False, layer_norm_eps: float = 1e-5):
         super().__init__()
+        self.layer_norm = bool(layer_norm)
         d = int(state_shape[0]) if len(state_shape) == 1 else int(torch.tensor(state_shape).prod())
         self.input_shape = tuple(state_shape)
         self.action_dim = int(action_dim)
         self.layer1 = nn.Sequential(nn.Linear(d, hidden), nn.ReLU())
-        self.value_stream_layer = nn.Sequential(_linear(hidden, hidden, noisy, noisy_sigma0), nn.ReLU())
-        self.advantage_stream_layer = nn.Sequential(_linear(hidden, hidden, noisy, noisy_sigma0), nn.ReLU())
+        self.value_stream_layer = _stream(hidden, hidden, noisy, noisy_sigma0, layer_norm, layer_norm_eps)
+        self.advantage_stream_layer = _stream(hidden, hidden, noisy, noisy_sigma0, layer_norm, layer_norm_eps)
         self._init_head(hidden, num_atoms, v_min, v_max, dist_head, noisy, noisy_sigma0, iqn_actor_samples)
 
     def streams(self, x: torch.Tensor):
@@ -358,9 +370,12 @@ class ImpalaDuellingDQN(nn.Module):
 def build_network(kind: str, state_shape: Sequence[int], action_dim: int,
                   obs_scale: float = 1.0 / 255.0, num_atoms: int = 1, v_min: float = -10.0,
                   v_max: float = 10.0, dist_head: str = "categorical", noisy: bool = False,
-                  noisy_sigma0: float = 0.5, iqn_actor_samples: int = 32) -> nn.Module:
+                  noisy_sigma0: float = 0.5, iqn_actor_samples: int = 32, layer_norm: bool = False,
+                  layer_norm_eps: float = 1e-5) -> nn.Module:
     head = dict(num_atoms=num_atoms, v_min=v_min, v_max=v_max, dist_head=dist_head, noisy=noisy,
                 noisy_sigma0=noisy_sigma0, iqn_actor_samples=iqn_actor_samples)
+    if layer_norm:     # (only then: the call of before)
+        head.update(layer_norm=True, layer_norm_eps=layer_norm_eps)
     if kind == "nature64":
         return DuellingDQN(state_shape, action_dim, conv1_channels=64, obs_scale=obs_scale, **head)
     if kind == "nature32":
@@ -372,6 +387,8 @@ def build_network(kind: str, state_shape: Sequence[int], action_dim: int,
             raise ValueError("Runtime.num_atoms >= 2: the impala network has no distributional head")
         if noisy:
             raise ValueError("Runtime.noisy: the impala network has no noisy layers")
+        if layer_norm:
+            raise ValueError("Runtime.layer_norm: the impala network has no layer normalisation")
         return ImpalaDuellingDQN(state_shape, action_dim, obs_scale=obs_scale)
     raise ValueError(f"unknown network kind {kind!r}")
 
@@ -384,4 +401,5 @@ REFERENCE_KEYS = (
     "value.weight", "value.bias", "advantage.weight", "advantage.bias",
 )
 NOISY_LAYERS = ("value_stream_layer.0", "advantage_stream_layer.0", "value", "advantage")
+LN_KEYS = tuple(f"{s}.1.{p}" for s in ("value_stream_layer", "advantage_stream_layer") for p in ("weight", "bias"))
 SIGMA_KEYS = tuple(f"{l}.{p}_sigma" for l in NOISY_LAYERS for p in ("weight", "bias"))

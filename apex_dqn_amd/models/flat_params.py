@@ -24,7 +24,8 @@ SIGMA_SEGMENTS = (("swv", "wv"), ("sbv", "bv"), ("swa", "wa"), ("sba", "ba"), ("
 
 
 def nature_segments(C: int, A: int, c1: int = 64, num_atoms: int = 1,
-                    noisy: bool = False, implicit: bool = False) -> List[Tuple[str, Tuple[int, ...]]]:
+                    noisy: bool = False, implicit: bool = False,
+                    layer_norm: bool = False) -> List[Tuple[str, Tuple[int, ...]]]:
     """Flat order: the small tensors (convs, heads) first, the 3.2 M-parameter fc layer
     last, so the fc weights are one contiguous suffix: the data-parallel exchange treats
     [0, wfc) and [wfc, end) as its two buckets and the single-rank step updates the fc
@@ -34,7 +35,9 @@ def nature_segments(C: int, A: int, c1: int = 64, num_atoms: int = 1,
     swv, sbv, swa, sba, swfc, sbfc with the shapes of their mu segments follow the fc layer,
     so every other segment keeps its offset.  ``implicit`` (the implicit quantile head: pass
     ``num_atoms`` = 1, its heads have the scalar head's shapes): the embedding ``wtau`` (1024, 64),
-    ``btau`` (1024,) follows the fc layer in the same way."""
+    ``btau`` (1024,) follows the fc layer in the same way.  ``layer_norm`` (Runtime.layer_norm): the stream layers'
+    LayerNorm affine ``lng`` (gamma) and ``lnb`` (beta), (1024,) each as [value 512 | advantage 512], behind
+    everything else."""
     N = int(num_atoms)
     heads = [("wv", (512,)), ("bv", (1,)), ("wa", (A, 512)), ("ba", (A,))] if N == 1 else \
         [("wv", (N, 512)), ("bv", (N,)), ("wa", (A * N, 512)), ("ba", (A * N,))]
@@ -50,6 +53,8 @@ def nature_segments(C: int, A: int, c1: int = 64, num_atoms: int = 1,
         segs += [(s, shapes[m]) for s, m in SIGMA_SEGMENTS]
     if implicit:
         segs += [("wtau", (1024, 64)), ("btau", (1024,))]
+    if layer_norm:
+        segs += [("lng", (1024,)), ("lnb", (1024,))]
     return segs
 
 
@@ -115,6 +120,10 @@ def flat_to_reference_state(v: Dict[str, torch.Tensor], c1: int = 64) -> "Ordere
     if "wtau" in v:       # implicit quantile head: the cosine embedding (rows in h's column order)
         sd["tau_embed.weight"] = v["wtau"].clone()
         sd["tau_embed.bias"] = v["btau"].clone()
+    if "lng" in v:        # the stream layers' LayerNorm affine
+        for k, key in (("lng", "weight"), ("lnb", "bias")):
+            sd[f"value_stream_layer.1.{key}"] = v[k][:512].clone()
+            sd[f"advantage_stream_layer.1.{key}"] = v[k][512:].clone()
     return OrderedDict((k, t.detach().float().cpu()) for k, t in sd.items())
 
 
@@ -140,6 +149,11 @@ def reference_state_to_flat(sd: Dict[str, torch.Tensor], v: Dict[str, torch.Tens
         if has_tau != ("wtau" in v):
             raise ValueError("the state has " + ("" if has_tau else "no ") + "implicit quantile embedding (tau_embed.*) "
                              "and this layout holds " + ("none" if has_tau else "one") + ": Runtime.dist_head differs")
+        has_ln = "value_stream_layer.1.weight" in sd
+        if has_ln != ("lng" in v):
+            raise ValueError("the state has " + ("" if has_ln else "no ") + "stream LayerNorm keys "
+                             "(value_stream_layer.1.*) and this layout holds " + ("none" if has_ln else "them") +
+                             ": Runtime.layer_norm differs (a reference checkpoint has no LayerNorm)")
         for k, name in (("wv", "value.weight"), ("bv", "value.bias"), ("wa", "advantage.weight"),
                         ("ba", "advantage.bias")):
             if sd[name].numel() != v[k].numel():
@@ -166,6 +180,10 @@ def reference_state_to_flat(sd: Dict[str, torch.Tensor], v: Dict[str, torch.Tens
         if has_tau:
             v["wtau"].copy_(sd["tau_embed.weight"])
             v["btau"].copy_(sd["tau_embed.bias"])
+        if has_ln:
+            for k, key in (("lng", "weight"), ("lnb", "bias")):
+                v[k][:512].copy_(sd[f"value_stream_layer.1.{key}"])
+                v[k][512:].copy_(sd[f"advantage_stream_layer.1.{key}"])
         if has_sigma:
             v["swfc"][:512].copy_(fc_cols_to_hwc(sd["value_stream_layer.0.weight_sigma"]))
             v["sbfc"][:512].copy_(sd["value_stream_layer.0.bias_sigma"])

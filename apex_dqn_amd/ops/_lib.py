@@ -231,6 +231,24 @@ class C2dPack(ctypes.Structure):
     _fields_ = [("w", c_p), ("w_lo", c_p), ("out", c_p)]
 
 
+class FcLnSet(ctypes.Structure):
+    """The stream layers' bias, LayerNorm gamma and beta of one net (``FcLnSet``, csrc/fc_layernorm.hip)."""
+    _fields_ = [("bias", c_p), ("gamma", c_p), ("beta", c_p)]
+
+
+class FcLnEpiArgs(ctypes.Structure):
+    """Arguments of ``fc_ln_epilogue_kernel`` (``FcLnEpiArgs``, csrc/fc_layernorm.hip)."""
+    _fields_ = [("ws", c_p), ("zstride", c_i64), ("nz", c_i), ("M", c_i), ("features", c_i), ("m_switch", c_i),
+                ("in_scale", c_f), ("eps", c_f), ("set", FcLnSet * 2), ("y", c_p), ("y_lo", c_p), ("ldy", c_i),
+                ("save_n", c_i), ("xhat", c_p), ("rstd", c_p), ("pk", C2dPack)]
+
+
+class FcLnBwdArgs(ctypes.Structure):
+    """Arguments of ``fc_ln_bwd_kernel`` and its reduce (``FcLnBwdArgs``, csrc/fc_layernorm.hip)."""
+    _fields_ = [("dH", c_p), ("dH_lo", c_p), ("xhat", c_p), ("rstd", c_p), ("gamma", c_p), ("B", c_i),
+                ("features", c_i), ("part", c_p), ("part_elems", c_i64), ("g_gamma", c_p), ("g_beta", c_p)]
+
+
 class DdqnArgs(ctypes.Structure):
     """Arguments of the scalar head kernel (``DdqnArgs``, csrc/ddqn_args.h)."""
     _fields_ = [("io", HeadIO), ("huber", c_i), ("kappa", c_f), ("hp", HeadPart), ("pk", C2dPack)]
@@ -343,6 +361,12 @@ _SIGS = {
     "apex_augment_debug_errors": ([c_p, c_p, c_i], c_i),
     "apex_reset_perturb": ([ResetArgs, c_p], c_i),
     "apex_reset_args_size": ([], c_i),
+    "apex_fc_ln_epilogue": ([FcLnEpiArgs, c_p], c_i),
+    "apex_fc_ln_bwd": ([FcLnBwdArgs, c_p], c_i),
+    "apex_fc_ln_wgrad_reduce": ([FcLnBwdArgs, c_p], c_i),
+    "apex_fc_ln_status_name": ([c_i], ctypes.c_char_p),
+    "apex_fc_ln_chunk": ([], c_i),
+    "apex_fc_ln_args_size": ([c_i], c_i),
 }
 
 _LIB: Optional[ctypes.CDLL] = None
@@ -463,6 +487,14 @@ def rescale_eps_arg(rescale_eps) -> float:
         return 0.0
     from ..learner.rescale import check_eps
     return check_eps(rescale_eps)
+
+
+def check_fc_ln(lib, rc: int, what: str) -> None:
+    """``check`` for the LayerNorm launchers, whose refusals name the argument (csrc/fc_layernorm.hip)."""
+    name = lib.apex_fc_ln_status_name(int(rc)) if rc else None
+    if name:
+        raise ValueError(f"{what} refused its argument {name.decode()!r} (status {rc})")
+    check(rc, what)
 
 
 def check(rc: int, what: str) -> None:

@@ -59,6 +59,11 @@ HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-f
              "-mllvm", "-amdgpu-mfma-vgpr-form", "-Wno-unused-result", "-I", CSRC]
 CXX_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-I", CSRC]
 COMM_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-I", "/opt/rocm/include"]
+# flags of single sources on top of their plan's (part of that object's key only).
+# fc_layernorm.hip: scalar fp32 instructions only (no v_pk_*_f32 pairing of its elementwise
+# adds / multiplies) -- 42/43, 61/63 VGPRs against 44, 68/72 with pairing, the same 8 waves per
+# SIMD and no scratch either way (profiles/pr35_layer_norm_resource_usage.txt)
+SOURCE_FLAGS = {"fc_layernorm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 _STAMP_RE = re.compile(rb"APEX_BUILD_ID:([0-9a-f]{64})")
 _COMPILER_IDS: Dict[str, str] = {}
@@ -156,16 +161,19 @@ class _Plan:
         hdrs = sorted(hdrs)
         # the checkout's absolute path (an include flag) is not content: the tree builds
         # to the same keys wherever it is copied (a GPU box runs it from a scratch path)
-        kflags = [_rel_flag(f) for f in self.flags]
         self.objs = []
         for s in srcs:
             o = os.path.join(OUT, os.path.basename(s) + obj_suffix)
+            kflags = [_rel_flag(f) for f in self.flags_of(s)]
             self.objs.append((s, o, _digest([s] + hdrs, kflags + [cid])))
         h = hashlib.sha256((BUILD_SCHEMA + tag).encode())
         for _, o, k in self.objs:
             h.update(os.path.basename(o).encode() + b"=" + k.encode())
         h.update(" ".join(self.link + self.link_libs + [cid]).encode())
         self.build_id = h.hexdigest()
+
+    def flags_of(self, src: str) -> List[str]:
+        return self.flags + SOURCE_FLAGS.get(os.path.basename(src), [])
 
     def stale_objects(self, force: bool = False):
         return [(s, o, k) for s, o, k in self.objs
@@ -252,11 +260,11 @@ def _compile(job) -> None:
 
 def _build_plan(p: _Plan, force: bool, jobs: int, verbose: bool) -> str:
     os.makedirs(OUT, exist_ok=True)
-    todo = [([p.cc] + p.flags + ["-c", s], o, k) for s, o, k in p.stale_objects(force)]
+    todo = [([p.cc] + p.flags_of(s) + ["-c", s], o, k) for s, o, k in p.stale_objects(force)]
     for rp in getattr(p, "release_part", ()):   # debug library: release objects it links
         s, o, k = rp
         if force or not os.path.exists(o) or _read_key(o + ".key") != k:
-            todo.append(([HIPCC] + HIP_FLAGS + ["-c", s], o, k))
+            todo.append(([HIPCC] + HIP_FLAGS + SOURCE_FLAGS.get(os.path.basename(s), []) + ["-c", s], o, k))
     if todo:
         with ThreadPoolExecutor(max_workers=jobs) as ex:
             list(ex.map(_compile, todo))

@@ -124,14 +124,73 @@ class TorchBackend:
             split_into(R.conv_fwd(xf[r:], join(w2, w2_lo), b2, stride, dt), out[r:],
                        None if out_lo is None else out_lo[r:])
 
+    @staticmethod
+    def fc_ln_fwd(a, gamma, beta, eps: float):
+        """The stream layers' LayerNorm + ReLU on the fc pre-activations ``a`` [M, 2 F] (the definition, dtype-generic:
+        fp64 is the reference, fp32 a stand-in for csrc/fc_layernorm.hip's precision): per row and stream of F features
+        mu, d = a - mu, v = mean d^2 (two passes), r = 1 / sqrt(v + eps) in fp64 rounded once, xh = d r,
+        h = max(gamma xh + beta, 0).  ``eps`` enters as its fp32 value, the one the kernel's argument block carries.
+        ``gamma`` / ``beta``: [2 F], or per row [M, 2 F].  Returns (h [M, 2 F], xh [M, 2 F], r [M, 2])."""
+        M, F = a.shape[0], a.shape[1] // 2
+        eps = float(np.float32(eps))
+        x = a.reshape(M, 2, F)
+        d = x - x.mean(-1, keepdim=True)
+        v = (d * d).mean(-1, keepdim=True)
+        r = (1.0 / torch.sqrt(v.double() + float(eps))).to(a.dtype)
+        xh = (d * r).reshape(M, 2 * F)
+        return torch.relu(gamma.to(a.dtype) * xh + beta.to(a.dtype)), xh, r.reshape(M, 2)
+
+    @staticmethod
+    def fc_ln_bwd(dz, xh, r, gamma):
+        """Backward of :meth:`fc_ln_fwd` from ``dz`` [B, 2 F], the gradient at gamma xh + beta (zero where h = 0):
+        g = gamma dz, s1 = mean g, s2 = mean g xh per (row, stream), da = r (g - s1 - xh s2); returns (da,
+        G[gamma] = sum_b dz xh, G[beta] = sum_b dz), in ``dz``'s dtype."""
+        B, F = dz.shape[0], dz.shape[1] // 2
+        dt = dz.dtype
+        xh3 = xh.to(dt).reshape(B, 2, F)
+        g = (gamma.to(dt) * dz).reshape(B, 2, F)
+        s1 = g.mean(-1, keepdim=True)
+        s2 = (g * xh3).mean(-1, keepdim=True)
+        da = r.to(dt).reshape(B, 2, 1) * (g - s1 - xh3 * s2)
+        return da.reshape(B, 2 * F), (dz * xh.to(dt)).sum(0), dz.sum(0)
+
+    def fc_ln_backward(self, dh, xhat, rstd, gamma, g_gamma, g_beta, dh_lo=None):
+        """``dh`` (+ ``dh_lo``): dz in, da out in place; G[gamma], G[beta] overwritten (:meth:`fc_ln_bwd`).
+        Returns what :meth:`fc_ln_reduce` takes (the HIP backend writes G there, on the weight gradients' stream)."""
+        da, gg, gb = self.fc_ln_bwd(join(dh, dh_lo), xhat, rstd, gamma)
+        split_into(da, dh, dh_lo)
+        g_gamma.copy_(gg)
+        g_beta.copy_(gb)
+        return None
+
+    def fc_ln_reduce(self, token) -> None:
+        """Nothing left to add here (HIP: the chunk partials of :meth:`fc_ln_backward` into G)."""
+
     def fc_fwd(self, x, w, b, out, w2=None, b2=None, rows_first=0, x_lo=None, w_lo=None, w2_lo=None, out_lo=None,
-               c2d=None, defer_head=False, ksplit=0):
+               c2d=None, defer_head=False, ksplit=0, ln=None):
         """``c2d = (conv2 weight, lo plane)``: weights of this step's conv2 data gradient,
         which the HIP backend pre-packs inside the fc launch; ``defer_head``: the HIP
-        backend may leave the epilogue to the next :meth:`head` (both ignored here)."""
+        backend may leave the epilogue to the next :meth:`head` (both ignored here).
+        ``ln = (gamma, beta, gamma2, beta2, eps, save_n, xhat, rstd)``: the stream layers' LayerNorm between
+        the Linear and the ReLU (Runtime.layer_norm; :meth:`fc_ln_fwd`), the second pair for rows >=
+        ``rows_first``; rows < ``save_n`` leave xh in ``xhat`` [save_n, 2 F] and r in ``rstd`` [save_n, 2]."""
         dt = torch.float32 if x_lo is not None else self.dtype
         x = x.reshape(x.shape[0], -1)
         xf = join(x, x_lo.reshape(x.shape)) if x_lo is not None else x
+        if ln is not None:
+            gm, bt, gm2, bt2, eps, save_n, xhat, rstd = ln
+            a = xf.to(dt) @ join(w, w_lo).to(dt).t() + b.to(dt)
+            if w2 is not None:
+                r = rows_first
+                a[r:] = xf[r:].to(dt) @ join(w2, w2_lo).to(dt).t() + b2.to(dt)
+                second = (torch.arange(a.shape[0], device=a.device) >= r)[:, None]
+                gm, bt = torch.where(second, gm2, gm), torch.where(second, bt2, bt)
+            h, xh, rs = self.fc_ln_fwd(a, gm, bt, eps)
+            split_into(h, out, out_lo)
+            if save_n:
+                xhat.copy_(xh[:save_n])
+                rstd.copy_(rs[:save_n])
+            return
         if w2 is None:
             split_into(R.fc_fwd(xf, join(w, w_lo), b, dt), out, out_lo)
         else:
@@ -899,7 +958,10 @@ class HipBackend(TorchBackend):
                         "qr_actor_head", "noisy_compose", "noisy_sigma_grad", "mdqn_head", "iqn_head", "iqn_wgrad",
                         "iqn_actor_head", "augment_shift", "hlg_head", "reset_perturb"]
         if self.native_conv:
-            self.kernels += ["conv_fwd", "conv_dgrad", "conv_wgrad", "fc_fwd", "fc_bwd"]
+            self.kernels += ["conv_fwd", "conv_dgrad", "conv_wgrad", "fc_fwd", "fc_bwd", "fc_ln_fwd", "fc_ln_bwd"]
+            for k, cls in enumerate((_lib.FcLnEpiArgs, _lib.FcLnBwdArgs)):
+                if self.lib.apex_fc_ln_args_size(k) != ctypes.sizeof(cls):
+                    raise RuntimeError(f"libapex_kernels: sizeof({cls.__name__}) differs from its mirror")
         self.ws = C.Workspace()
 
     # --------------------------------------------------- native conv family
@@ -949,12 +1011,17 @@ class HipBackend(TorchBackend):
                    out_lo=out_lo, packed=packed)
 
     def fc_fwd(self, x, w, b, out, w2=None, b2=None, rows_first=0, x_lo=None, w_lo=None, w2_lo=None, out_lo=None,
-               c2d=None, defer_head=False, ksplit=0):
+               c2d=None, defer_head=False, ksplit=0, ln=None):
         """``ksplit`` > 0: that K split instead of the one that fills the chip (the actors:
-        a throughput job beside the learner, where fewer partial planes cost less)."""
+        a throughput job beside the learner, where fewer partial planes cost less).
+        ``ln``: the split-K GEMM alone, then the LayerNorm epilogue in the plain epilogue's place
+        (csrc/fc_layernorm.hip fc_ln_epilogue_kernel), which carries the conv2 pack job too."""
         if not self.native_conv:
-            return super().fc_fwd(x, w, b, out, w2, b2, rows_first, x_lo, w_lo, w2_lo, out_lo)
+            return super().fc_fwd(x, w, b, out, w2, b2, rows_first, x_lo, w_lo, w2_lo, out_lo, ln=ln)
         M, K = x.shape[0], x[0].numel()
+        if ln is not None:
+            return self._fc_fwd_ln(x.reshape(M, K), w, b, out, w2, b2, rows_first, x_lo, w_lo, w2_lo, out_lo, c2d,
+                                   ksplit, ln)
         if w.shape[0] % 128 == 0 and K % 64 == 0 and hasattr(self.lib, "apex_fc_gemm128"):
             # 128x128 tiles, K split in two, loader waves: fc forward 40.6 -> 36.2 us
             # (split) / 25.7 -> 22.5 (bf16) at the learner shape (scripts/bench_fc128.py)
@@ -987,6 +1054,64 @@ class HipBackend(TorchBackend):
                     rows_first=rows_first, ws=self.ws,
                     x_lo=None if x_lo is None else x_lo.reshape(x.shape[0], -1), w_lo=w_lo, w2_lo=w2_lo,
                     out_lo=out_lo)
+
+    def _fc_fwd_ln(self, x, w, b, out, w2, b2, rows_first, x_lo, w_lo, w2_lo, out_lo, c2d, ksplit, ln) -> None:
+        gm, bt, gm2, bt2, eps, save_n, xhat, rstd = ln
+        M, K = x.shape
+        if w.shape[0] != 1024 or K % 64 or b is None or (w2 is not None and (b2 is None or gm2 is None or bt2 is None)):
+            raise ValueError("fc_fwd(ln=): the LayerNorm epilogue serves two 512-feature streams with a bias, gamma "
+                             f"and beta per weight set, got {w.shape[0]} features")
+        tiles = C.row_tiles_host(M, rows_first if w2 is not None else None, 128) * (w.shape[0] // 128)
+        ks = int(ksplit) if ksplit > 0 else max(2, 256 // max(tiles, 1))
+        if ksplit <= 0 and SW.fc_ksplit_max > 0:
+            ks = max(1, min(ks, SW.fc_ksplit_max))
+        part, nz = C.dense_fwd128(self.lib, self.ws, x, w, b, out, True, w2, b2, rows_first, ks, True,
+                                  x_lo=None if x_lo is None else x_lo.reshape(M, K), w_lo=w_lo, w2_lo=w2_lo,
+                                  out_lo=out_lo, no_epilogue=True)
+        a = _lib.FcLnEpiArgs()
+        a.ws, a.zstride, a.nz, a.M, a.features = part.data_ptr(), M * w.shape[0], nz, M, out.shape[1]
+        a.m_switch = int(rows_first) if w2 is not None else M
+        a.in_scale, a.eps = 1.0, float(eps)
+        for k, (bb, g, be) in enumerate(((b, gm, bt), (b2, gm2, bt2))):
+            a.set[k].bias, a.set[k].gamma, a.set[k].beta = _lib.ptr(bb), _lib.ptr(g), _lib.ptr(be)
+        a.y, a.y_lo, a.ldy = out.data_ptr(), _lib.ptr(out_lo), out.stride(0)
+        a.save_n = int(save_n)
+        a.xhat, a.rstd = _lib.ptr(xhat), _lib.ptr(rstd)
+        if save_n and (xhat.numel() < save_n * 1024 or rstd.numel() < save_n * 2):
+            raise ValueError(f"fc_fwd(ln=): xhat / rstd hold fewer than save_n = {save_n} rows")
+        if c2d is not None:
+            a.pk.w, a.pk.w_lo = c2d[0].data_ptr(), _lib.ptr(c2d[1])
+            a.pk.out = C.c2d_wfrag_buffer(self.ws, x.device).data_ptr()
+        _lib.check_fc_ln(self.lib, self.lib.apex_fc_ln_epilogue(a, _lib.stream_ptr()), "fc_ln_epilogue")
+        if c2d is not None:
+            self._c2d_packed = (c2d[0].data_ptr(), _lib.ptr(c2d[1]))
+
+    def fc_ln_args(self, dh, xhat, rstd, gamma, g_gamma, g_beta, dh_lo=None) -> "_lib.FcLnBwdArgs":
+        B = dh.shape[0]
+        chunks = -(-B // int(self.lib.apex_fc_ln_chunk()))
+        part = self.ws.get(("fc_ln_part", _lib.stream_ptr()), chunks * 2 * 1024, dh.device)
+        a = _lib.FcLnBwdArgs()
+        a.dH, a.dH_lo, a.xhat, a.rstd, a.gamma = dh.data_ptr(), _lib.ptr(dh_lo), xhat.data_ptr(), rstd.data_ptr(), \
+            gamma.data_ptr()
+        a.B, a.features = B, dh.shape[1]
+        a.part, a.part_elems = part.data_ptr(), part.numel()
+        a.g_gamma, a.g_beta = _lib.ptr(g_gamma), _lib.ptr(g_beta)
+        if not dh.is_contiguous() or xhat.numel() < B * 1024 or rstd.numel() < B * 2 or gamma.numel() != 1024:
+            raise ValueError("fc_ln_bwd: dH [B, 1024] contiguous, xhat / rstd of at least B rows, gamma (1024,)")
+        return a
+
+    def fc_ln_backward(self, dh, xhat, rstd, gamma, g_gamma, g_beta, dh_lo=None):
+        """dz -> da in place over dH (+ dH_lo) with the chunk partials of G[gamma] / G[beta] left in the workspace
+        (fc_ln_bwd_kernel); returns the argument block for :meth:`fc_ln_reduce`."""
+        if not self.native_conv:
+            return super().fc_ln_backward(dh, xhat, rstd, gamma, g_gamma, g_beta, dh_lo)
+        a = self.fc_ln_args(dh, xhat, rstd, gamma, g_gamma, g_beta, dh_lo)
+        _lib.check_fc_ln(self.lib, self.lib.apex_fc_ln_bwd(a, _lib.stream_ptr()), "fc_ln_bwd")
+        return a
+
+    def fc_ln_reduce(self, a) -> None:
+        if a is not None:
+            _lib.check_fc_ln(self.lib, self.lib.apex_fc_ln_wgrad_reduce(a, _lib.stream_ptr()), "fc_ln_wgrad_reduce")
 
     def fc_dgrad(self, dh, x, w, dx_out, dh_lo=None, w_lo=None, dx_lo=None):
         if not self.native_conv:

@@ -161,6 +161,19 @@ def check_noisy(ck: Dict[str, Any], runtime_conf) -> None:
                          f"runs Runtime.noisy={bool(runtime_conf.noisy)}")
 
 
+def check_layer_norm(ck: Dict[str, Any], runtime_conf) -> None:
+    """Refuse a checkpoint whose ``Q_state`` has the stream layers' LayerNorm keys (``<stream>.1.weight`` /
+    ``.bias``) when the learner has none, and the reverse (a reference checkpoint never has them): before
+    anything is copied."""
+    qs = ck.get("Q_state") if isinstance(ck, dict) else None
+    if not isinstance(qs, dict):
+        return
+    has = "value_stream_layer.1.weight" in qs
+    if has != bool(runtime_conf.layer_norm):
+        raise ValueError(f"the checkpoint has {'' if has else 'no '}stream LayerNorm keys (value_stream_layer.1.*), "
+                         f"this learner runs Runtime.layer_norm={bool(runtime_conf.layer_norm)}")
+
+
 def layout_segments(layout) -> List[Tuple[str, int, int]]:
     """Segments of a ``models.flat_params.FlatLayout``."""
     out = []
