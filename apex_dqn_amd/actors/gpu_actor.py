@@ -96,6 +96,12 @@ class GpuActorGroup:
         self.h, self.h_lo = act(self.E, 1024)
         self.q = torch.zeros(self.E, self.A, dtype=torch.float32, device=d)
         self.act = torch.zeros(self.E, dtype=torch.int32, device=d)
+        # the wide quantile actor head's logits [E, Jp] (csrc/qr_wide_head.hip): this group's own -- the groups of a
+        # pipeline run their inferences on their own streams at the same time
+        n_q = int(getattr(learner, "N", 1))
+        self.qr_L = None
+        if self.cfg.quantile and (n_q > 64 or SW.qr_wide) and hasattr(self.ops, "qr_wide_logits"):
+            self.qr_L = self.ops.qr_wide_logits(self.E, self.A, n_q, d)
         self.q_host = torch.zeros(self.E, self.A, dtype=torch.float32).pin_memory() \
             if d.type == "cuda" else torch.zeros(self.E, self.A)
         self.a_host = torch.zeros(self.E, dtype=torch.int32).pin_memory() \
@@ -330,6 +336,8 @@ class GpuActorGroup:
             own = (seed_q, self.ctr, stream, K, False)
         elif n >= 2 and self.cfg.quantile:
             op, own = ops.qr_actor_head, (n,)
+            if getattr(self, "qr_L", None) is not None:
+                return op(h, heads, self.eps, self.ctr, self.seed, n, self.q, self.act, H_lo=h_lo, logits=self.qr_L)
         elif n >= 2:
             op, own = ops.c51_actor_head, (n, rt.v_min, rt.v_max)
         else:

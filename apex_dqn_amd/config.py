@@ -362,13 +362,18 @@ class ApexConfig:
             raise ValueError("Runtime.is_beta_end anneals the IS weights: it needs Runtime.use_is_weights")
         net = self.network
         na = rt.num_atoms
-        if isinstance(na, bool) or not isinstance(na, int) or not (na == 1 or 2 <= na <= 64):
-            raise ValueError(f"Runtime.num_atoms must be 1 or an integer in [2, 64] (one lane per atom), got {na!r}")
+        if isinstance(na, bool) or not isinstance(na, int) or not (na == 1 or 2 <= na <= 256):
+            raise ValueError(f"Runtime.num_atoms must be 1 or an integer in [2, 256] ([65, 256] with "
+                             f"Runtime.dist_head='quantile' only), got {na!r}")
         if not float(rt.v_min) < float(rt.v_max):
             raise ValueError(f"Runtime.v_min must be below Runtime.v_max, got {rt.v_min} / {rt.v_max}")
         if rt.dist_head not in ("categorical", "quantile", "implicit", "hl_gauss"):
             raise ValueError(f"Runtime.dist_head must be 'categorical', 'quantile', 'implicit' or 'hl_gauss', got "
                              f"{rt.dist_head!r}")
+        if na > 64 and rt.dist_head != "quantile":
+            raise ValueError(f"Runtime.num_atoms={na} with Runtime.dist_head={rt.dist_head!r}: the range [65, 256] is "
+                             f"the quantile head's (csrc/qr_wide_head.hip); the other heads map one lane to one atom "
+                             f"and stop at 64")
         sr = rt.hl_gauss_sigma_ratio
         if na >= 2 and rt.dist_head == "hl_gauss" and (
                 isinstance(sr, bool) or not isinstance(sr, (int, float)) or not 0.0 < float(sr) < float("inf")):

@@ -532,6 +532,10 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             self.iqn_ws = self.ops.iqn_workspace(B, self.N, d)
             self.tau_out = torch.zeros(B, 3, self.N, dtype=torch.float32, device=d)
             self._seed_q = iqn_seed(self.rt.seed)
+        # the wide quantile head's fp32 logits [3B, Jp] (csrc/qr_wide_head.hip): this learner's own, allocated once
+        self.qr_L = None
+        if self.quantile and (self.N > 64 or SW.qr_wide) and hasattr(self.ops, "qr_wide_logits"):
+            self.qr_L = self.ops.qr_wide_logits(3 * B, self.A, self.N, d)
         self.g_head_region = self.g32[o0:o1]
         # its share of the producer-summed clip norm: summed by one finalize block (the scalar
         # head's 2.5 K values), or by the wide head weight gradient's own blocks (N >= 2)
@@ -707,6 +711,8 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         elif self.N >= 2 and self.quantile:
             # quantile regression: the quantile Huber loss, kappa = huber_delta (Runtime.loss, v_min / v_max
             # do not apply)
+            if self.qr_L is not None:
+                kw["logits"] = self.qr_L
             ops.qr_head(*h, *data, self.N, rt.huber_delta, *out, **kw)
         elif self.N >= 2 and self.cfg.hl_gauss:
             # the categorical head against the Gaussian histogram of the scalar target (csrc/c51_head.hip

@@ -81,6 +81,12 @@ class QRArgs(ctypes.Structure):
     _fields_ = [("io", HeadIO), ("N", c_i), ("kappa", c_f)]
 
 
+class QRWideArgs(ctypes.Structure):
+    """Arguments of the wide quantile head's launches (``QRWideArgs``, csrc/qr_wide_head.hip); ``L``: the fp32 logits
+    workspace ``[3B, apex_qr_wide_jp(A, N)]``."""
+    _fields_ = [("io", HeadIO), ("N", c_i), ("kappa", c_f), ("L", c_p)]
+
+
 class IqnEmbed(ctypes.Structure):
     """The cosine embedding of one net (``IqnEmbed``, csrc/iqn_wgrad.h): ``We (2 HS, 64)``, ``be (2 HS,)``."""
     _fields_ = [("w", c_p), ("b", c_p)]
@@ -114,6 +120,11 @@ class C51ActorArgs(ctypes.Structure):
 class QRActorArgs(ctypes.Structure):
     """Arguments of ``qr_actor_head_kernel`` (``QRActorArgs``, csrc/dist_head.h)."""
     _fields_ = [("io", ActorIO), ("N", c_i)]
+
+
+class QRWideActorArgs(ctypes.Structure):
+    """Arguments of the wide quantile actor head (``QRWideActorArgs``, csrc/qr_wide_head.hip); ``L [E, Jp]``."""
+    _fields_ = [("io", ActorIO), ("N", c_i), ("L", c_p)]
 
 
 class IqnActorArgs(ctypes.Structure):
@@ -336,6 +347,10 @@ _SIGS = {
     "apex_hlg_head": ([HlgArgs, c_p], c_i),
     "apex_c51_actor_head": ([C51ActorArgs, c_p], c_i),
     "apex_qr_head": ([QRArgs, c_p], c_i),
+    "apex_qr_wide_head": ([QRWideArgs, c_p], c_i),
+    "apex_qr_wide_actor_head": ([QRWideActorArgs, c_p], c_i),
+    "apex_qr_wide_jp": ([c_i, c_i], c_i),
+    "apex_qr_wide_args_size": ([c_i], c_i),
     "apex_mdqn_head": ([MdqnArgs, c_p], c_i),
     "apex_iqn_head": ([IqnArgs, c_p], c_i),
     "apex_iqn_wgrad": ([IqnWgArgs, c_p], c_i),

@@ -63,7 +63,9 @@ COMM_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-I", "/opt/rocm/include"]
 # fc_layernorm.hip: scalar fp32 instructions only (no v_pk_*_f32 pairing of its elementwise
 # adds / multiplies) -- 42/43, 61/63 VGPRs against 44, 68/72 with pairing, the same 8 waves per
 # SIMD and no scratch either way (profiles/pr35_layer_norm_resource_usage.txt)
-SOURCE_FLAGS = {"fc_layernorm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+# qr_wide_head.hip: scalar fp32 instructions in its elementwise phases too; the build with pairing was not compared
+SOURCE_FLAGS = {"fc_layernorm.hip": _NO_PK_F32, "qr_wide_head.hip": _NO_PK_F32}
 
 _STAMP_RE = re.compile(rb"APEX_BUILD_ID:([0-9a-f]{64})")
 _COMPILER_IDS: Dict[str, str] = {}

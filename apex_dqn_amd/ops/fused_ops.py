@@ -962,6 +962,9 @@ class HipBackend(TorchBackend):
             for k, cls in enumerate((_lib.FcLnEpiArgs, _lib.FcLnBwdArgs)):
                 if self.lib.apex_fc_ln_args_size(k) != ctypes.sizeof(cls):
                     raise RuntimeError(f"libapex_kernels: sizeof({cls.__name__}) differs from its mirror")
+        for k, cls in enumerate((_lib.QRWideArgs, _lib.QRWideActorArgs)):
+            if self.lib.apex_qr_wide_args_size(k) != ctypes.sizeof(cls):
+                raise RuntimeError(f"libapex_kernels: sizeof({cls.__name__}) differs from its mirror")
         self.ws = C.Workspace()
 
     # --------------------------------------------------- native conv family
@@ -1312,17 +1315,44 @@ class HipBackend(TorchBackend):
         _lib.check(self.lib.apex_c51_actor_head(a, _lib.stream_ptr()), "c51_actor_head")
 
     def qr_head(self, Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, kappa, grad_scale, td_abs, loss,
-                dH, dhead, q_out=None, zero=None, lo=None, isn=None, rescale_eps=None):
-        """csrc/qr_head.hip ``qr_head_kernel``."""
-        a = _lib.QRArgs()
+                dH, dhead, q_out=None, zero=None, lo=None, isn=None, rescale_eps=None, logits=None):
+        """csrc/qr_head.hip ``qr_head_kernel`` up to 64 quantiles; above, or under ``SW.qr_wide``, the three
+        launches of csrc/qr_wide_head.hip.  ``logits``: the caller's own workspace (:meth:`qr_wide_logits` with 3B
+        rows; a learner allocates it once), or None: a fresh one for this call."""
+        wide = int(num_atoms) > 64 or SW.qr_wide
+        a = _lib.QRWideArgs() if wide else _lib.QRArgs()
         a.kappa = float(kappa)
-        self._dist_head_launch(a, "qr_head", Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, grad_scale, td_abs,
-                               loss, dH, dhead, q_out, zero, lo, isn, rescale_eps)
+        if wide:
+            B, N = act.shape[0], int(num_atoms)
+            assert Hon.shape[0] >= 2 * B and Htg.shape[0] >= B and Hon.shape[1] == 1024 and Htg.shape[1] == 1024
+            assert dH.shape == (B, 1024) and Hon.is_contiguous() and Htg.is_contiguous() and dH.is_contiguous()
+            a.L = self._qr_wide_L(logits, 3 * B, Pon["wa"].shape[0] // max(N, 1), N, Hon.device)
+        self._dist_head_launch(a, "qr_wide_head" if wide else "qr_head", Hon, Htg, Pon, Ptg, act, rew, gam, isw,
+                               num_atoms, grad_scale, td_abs, loss, dH, dhead, q_out, zero, lo, isn, rescale_eps)
 
-    def qr_actor_head(self, H, P, eps, ctr, seed, num_atoms, q_out, a_out, H_lo=None):
-        a = _lib.QRActorArgs()
+    def qr_wide_logits(self, rows: int, A: int, N: int, device) -> torch.Tensor:
+        """A new fp32 logits workspace ``[rows, Jp]`` of the wide quantile head.  Every user owns one (a learner 3B
+        rows, an actor group E rows, allocated when they are built and passed as ``logits``): the launches of two
+        users may run on different streams at once."""
+        return torch.zeros(int(rows), self.lib.apex_qr_wide_jp(int(A), max(int(N), 1)), dtype=torch.float32,
+                           device=device)
+
+    def _qr_wide_L(self, logits, rows, A, N, device) -> int:
+        if logits is None:
+            logits = self.qr_wide_logits(rows, A, N, device)
+        assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.device == device
+        assert logits.shape == (rows, self.lib.apex_qr_wide_jp(int(A), max(int(N), 1))), logits.shape
+        return logits.data_ptr()
+
+    def qr_actor_head(self, H, P, eps, ctr, seed, num_atoms, q_out, a_out, H_lo=None, logits=None):
+        wide = int(num_atoms) > 64 or SW.qr_wide
+        a = _lib.QRWideActorArgs() if wide else _lib.QRActorArgs()
         self._actor_io(a.io, H, P, eps, ctr, seed, q_out, a_out, H_lo)
         a.N = int(num_atoms)
+        if wide:
+            assert H.shape[0] >= q_out.shape[0] and H.shape[1] == 1024 and H.is_contiguous()
+            a.L = self._qr_wide_L(logits, q_out.shape[0], q_out.shape[1], a.N, H.device)
+            return _lib.check(self.lib.apex_qr_wide_actor_head(a, _lib.stream_ptr()), "qr_wide_actor_head")
         _lib.check(self.lib.apex_qr_actor_head(a, _lib.stream_ptr()), "qr_actor_head")
 
     @staticmethod

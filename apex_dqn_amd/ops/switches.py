@@ -164,6 +164,11 @@ class Switches:
     # conv1's bucket summed inside the optimizer launch (no norm launch on main; emulated W =
     # 8 with the fc gradient on main: 160.5-162.1 us vs 166-169 before)
     dp_norm_split: bool = True
+    # the quantile head and its actor head on the wide MFMA path (csrc/qr_wide_head.hip) for every N in [2, 256];
+    # off, only N > 64 takes it and N <= 64 keeps qr_head_kernel.  The switch exists to compare the two on one shape
+    # (tests/test_gpu_qr_wide.py).  fp32, B = 512, forced against default in two processes: N = 51 at A = 18 1,894 vs
+    # 1,807 updates/s, at A = 4 a tie; N = 32 at A = 4 2,477 vs 2,540 (profiles/pr36_bench_qr_forced_wide_fp32.json)
+    qr_wide: bool = False
 
     @classmethod
     def from_env(cls, spec: str = None) -> "Switches":

@@ -2,7 +2,7 @@
 categorical (C51) head, by the protocol of ``scripts/bench_c51.py``: ``learner.steps(200)`` of
 the fused NatureCNN learner (B = 512, synthetic frames, the captured multi-update graphs)
 timed with device events after a warm-up.  Per action count four learners -- scalar, C51 with
-``--atoms`` atoms, quantile with ``--atoms`` and with ``--quantiles`` quantiles -- alternated
+``--atoms`` atoms, quantile with ``--atoms`` and with each of ``--quantiles`` quantiles -- alternated
 ``--reps`` times in one process so they see the same machine state; every ratio is against
 the scalar-head number of the same run.  ``--dtype`` fp32 (split) or bf16.  Prints one JSON
 line."""
@@ -31,7 +31,8 @@ def main() -> None:
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--replay", type=int, default=100000)
     ap.add_argument("--atoms", type=int, default=51)
-    ap.add_argument("--quantiles", type=int, default=32)
+    ap.add_argument("--quantiles", type=int, nargs="+", default=[32])     # e.g. 32 200: above 64, csrc/qr_wide_head.hip
+    ap.add_argument("--out", default="")       # also write the JSON line to this file
     ap.add_argument("--actions", type=int, nargs="+", default=[4, 18])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"])
     args = ap.parse_args()
@@ -41,7 +42,7 @@ def main() -> None:
     heads = {"scalar": {"num_atoms": 1},
              f"c51_{args.atoms}": {"num_atoms": args.atoms},
              f"qr_{args.atoms}": {"num_atoms": args.atoms, "dist_head": "quantile"},
-             f"qr_{args.quantiles}": {"num_atoms": args.quantiles, "dist_head": "quantile"}}
+             **{f"qr_{n}": {"num_atoms": n, "dist_head": "quantile"} for n in args.quantiles}}
     learners = {}
     for A in args.actions:
         for name, head in heads.items():
@@ -79,6 +80,9 @@ def main() -> None:
                 out[f"A{A}_{name}_vs_scalar"] = round(c / s, 4)
                 out[f"A{A}_{name}_extra_us_per_update"] = round(1e6 / c - 1e6 / s, 1)
     print(json.dumps(out), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(json.dumps(out) + "\n")
 
 
 if __name__ == "__main__":
