@@ -100,7 +100,8 @@ class GpuActorGroup:
         # pipeline run their inferences on their own streams at the same time
         n_q = int(getattr(learner, "N", 1))
         self.qr_L = None
-        if self.cfg.quantile and (n_q > 64 or SW.qr_wide) and hasattr(self.ops, "qr_wide_logits"):
+        self.wide_cat = n_q >= 2 and self.cfg.wide_categorical      # Runtime.wide_atoms: csrc/cat_wide_head.hip
+        if ((self.cfg.quantile and (n_q > 64 or SW.qr_wide)) or self.wide_cat) and hasattr(self.ops, "qr_wide_logits"):
             self.qr_L = self.ops.qr_wide_logits(self.E, self.A, n_q, d)
         self.q_host = torch.zeros(self.E, self.A, dtype=torch.float32).pin_memory() \
             if d.type == "cuda" else torch.zeros(self.E, self.A)
@@ -340,6 +341,9 @@ class GpuActorGroup:
                 return op(h, heads, self.eps, self.ctr, self.seed, n, self.q, self.act, H_lo=h_lo, logits=self.qr_L)
         elif n >= 2:
             op, own = ops.c51_actor_head, (n, rt.v_min, rt.v_max)
+            if getattr(self, "wide_cat", False):
+                return op(h, heads, self.eps, self.ctr, self.seed, *own, self.q, self.act, H_lo=h_lo, wide=True,
+                          logits=self.qr_L)
         else:
             op, own = ops.actor_head, ()
         op(h, heads, *net, self.eps, self.ctr, self.seed, *own, self.q, self.act, H_lo=h_lo)

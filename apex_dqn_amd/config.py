@@ -119,6 +119,14 @@ class RuntimeConf:
     # (finite, > 0; the paper's 0.75) instead of the projected target distribution; the priority is |y - q| against
     # that scalar target (learner/losses.py hl_gauss_loss).  loss / huber_delta do not apply; C51's refusals
     hl_gauss_sigma_ratio: float = 0.75
+    # the categorical and histogram-loss heads on the wide MFMA path (csrc/cat_wide_head.hip): num_atoms in [2, 256]
+    # (C51 with 101 / 201 atoms; HL-Gauss, whose resolution is its bin count, on a support wide enough for
+    # value_rescale / clip_rewards=false), every such N through the wide launches.  Opt-in, never automatic: that path
+    # feeds the head weights to the MFMAs as bf16 hi + lo (2^-17 relative), another rounding than the fp32 head's.
+    # false = everything as before (the narrow kernels, at most 64 atoms).  Refused with dist_head="implicit" and
+    # with num_atoms=1; without effect on "quantile", whose range is open already.  C51's refusals otherwise; the
+    # weights, the flat layout and the checkpoint keys are the narrow heads' (checkpoints load across the key)
+    wide_atoms: bool = False
     # factorised NoisyNet fc and head layers (Fortunato et al. 2018; learner/noisy.py, csrc/noisy.hip): the two
     # stream layers and the two heads carry W = mu + sigma * (xi_out (x) xi_in), one draw per update for the online
     # net and one for the target net, one per noisy_actor_resample batched inference calls for an actor group;
@@ -370,10 +378,17 @@ class ApexConfig:
         if rt.dist_head not in ("categorical", "quantile", "implicit", "hl_gauss"):
             raise ValueError(f"Runtime.dist_head must be 'categorical', 'quantile', 'implicit' or 'hl_gauss', got "
                              f"{rt.dist_head!r}")
-        if na > 64 and rt.dist_head != "quantile":
+        if not isinstance(rt.wide_atoms, bool):
+            raise ValueError(f"Runtime.wide_atoms must be true or false, got {rt.wide_atoms!r}")
+        if rt.wide_atoms and (na == 1 or rt.dist_head == "implicit"):
+            raise ValueError(f"Runtime.wide_atoms is the categorical / hl_gauss heads' wide path "
+                             f"(csrc/cat_wide_head.hip): not Runtime.num_atoms={na} with Runtime.dist_head="
+                             f"{rt.dist_head!r}")
+        if na > 64 and rt.dist_head != "quantile" and not (rt.wide_atoms and rt.dist_head != "implicit"):
             raise ValueError(f"Runtime.num_atoms={na} with Runtime.dist_head={rt.dist_head!r}: the range [65, 256] is "
-                             f"the quantile head's (csrc/qr_wide_head.hip); the other heads map one lane to one atom "
-                             f"and stop at 64")
+                             f"the quantile head's (csrc/qr_wide_head.hip) and, with Runtime.wide_atoms, the "
+                             f"categorical / hl_gauss heads' (csrc/cat_wide_head.hip); their narrow kernels and the "
+                             f"implicit head map one lane to one atom and stop at 64")
         sr = rt.hl_gauss_sigma_ratio
         if na >= 2 and rt.dist_head == "hl_gauss" and (
                 isinstance(sr, bool) or not isinstance(sr, (int, float)) or not 0.0 < float(sr) < float("inf")):
@@ -557,6 +572,12 @@ class ApexConfig:
     def hl_gauss(self) -> bool:
         """The categorical head is trained with the histogram loss (Runtime.dist_head)."""
         return self.distributional and self.Runtime.dist_head == "hl_gauss"
+
+    @property
+    def wide_categorical(self) -> bool:
+        """The categorical / hl_gauss head runs the wide launches (Runtime.wide_atoms, csrc/cat_wide_head.hip)."""
+        return (self.distributional and bool(self.Runtime.wide_atoms)
+                and self.Runtime.dist_head in ("categorical", "hl_gauss"))
 
     @property
     def implicit(self) -> bool:

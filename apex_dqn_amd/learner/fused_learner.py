@@ -532,9 +532,11 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             self.iqn_ws = self.ops.iqn_workspace(B, self.N, d)
             self.tau_out = torch.zeros(B, 3, self.N, dtype=torch.float32, device=d)
             self._seed_q = iqn_seed(self.rt.seed)
-        # the wide quantile head's fp32 logits [3B, Jp] (csrc/qr_wide_head.hip): this learner's own, allocated once
+        # the wide heads' fp32 logits [3B, Jp] (csrc/qr_wide_head.hip; with Runtime.wide_atoms csrc/cat_wide_head.hip):
+        # this learner's own, allocated once
         self.qr_L = None
-        if self.quantile and (self.N > 64 or SW.qr_wide) and hasattr(self.ops, "qr_wide_logits"):
+        self.wide_cat = self.cfg.wide_categorical and not self.quantile and not self.implicit
+        if ((self.quantile and (self.N > 64 or SW.qr_wide)) or self.wide_cat) and hasattr(self.ops, "qr_wide_logits"):
             self.qr_L = self.ops.qr_wide_logits(3 * B, self.A, self.N, d)
         self.g_head_region = self.g32[o0:o1]
         # its share of the producer-summed clip norm: summed by one finalize block (the scalar
@@ -714,6 +716,14 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             if self.qr_L is not None:
                 kw["logits"] = self.qr_L
             ops.qr_head(*h, *data, self.N, rt.huber_delta, *out, **kw)
+        elif self.N >= 2 and self.wide_cat:
+            # Runtime.wide_atoms: either categorical head through csrc/cat_wide_head.hip (only then: the other
+            # calls are the ones of before)
+            kw.update(wide=True, logits=self.qr_L)
+            if self.cfg.hl_gauss:
+                ops.hlg_head(*h, *data, self.N, rt.v_min, rt.v_max, rt.hl_gauss_sigma_ratio, *out, **kw)
+            else:
+                ops.c51_head(*h, *data, self.N, rt.v_min, rt.v_max, *out, **kw)
         elif self.N >= 2 and self.cfg.hl_gauss:
             # the categorical head against the Gaussian histogram of the scalar target (csrc/c51_head.hip
             # hlg_head_kernel; Runtime.loss / huber_delta do not apply)

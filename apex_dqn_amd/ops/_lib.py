@@ -87,6 +87,17 @@ class QRWideArgs(ctypes.Structure):
     _fields_ = [("io", HeadIO), ("N", c_i), ("kappa", c_f), ("L", c_p)]
 
 
+class C51WideArgs(ctypes.Structure):
+    """``C51Args`` with the fp32 logits workspace ``L [3B, apex_qr_wide_jp(A, N)]`` appended (``C51WideArgs``,
+    csrc/cat_wide_head.hip)."""
+    _fields_ = [("io", HeadIO), ("N", c_i), ("vmin", c_f), ("vmax", c_f), ("L", c_p)]
+
+
+class HlgWideArgs(ctypes.Structure):
+    """``HlgArgs`` with the logits workspace appended (``HlgWideArgs``, csrc/cat_wide_head.hip)."""
+    _fields_ = [("io", HeadIO), ("N", c_i), ("vmin", c_f), ("vmax", c_f), ("sigma_ratio", c_f), ("L", c_p)]
+
+
 class IqnEmbed(ctypes.Structure):
     """The cosine embedding of one net (``IqnEmbed``, csrc/iqn_wgrad.h): ``We (2 HS, 64)``, ``be (2 HS,)``."""
     _fields_ = [("w", c_p), ("b", c_p)]
@@ -125,6 +136,12 @@ class QRActorArgs(ctypes.Structure):
 class QRWideActorArgs(ctypes.Structure):
     """Arguments of the wide quantile actor head (``QRWideActorArgs``, csrc/qr_wide_head.hip); ``L [E, Jp]``."""
     _fields_ = [("io", ActorIO), ("N", c_i), ("L", c_p)]
+
+
+class C51WideActorArgs(ctypes.Structure):
+    """``C51ActorArgs`` with the logits workspace ``L [E, Jp]`` appended (``C51WideActorArgs``,
+    csrc/cat_wide_head.hip)."""
+    _fields_ = [("io", ActorIO), ("N", c_i), ("vmin", c_f), ("vmax", c_f), ("L", c_p)]
 
 
 class IqnActorArgs(ctypes.Structure):
@@ -351,6 +368,10 @@ _SIGS = {
     "apex_qr_wide_actor_head": ([QRWideActorArgs, c_p], c_i),
     "apex_qr_wide_jp": ([c_i, c_i], c_i),
     "apex_qr_wide_args_size": ([c_i], c_i),
+    "apex_c51_wide_head": ([C51WideArgs, c_p], c_i),
+    "apex_hlg_wide_head": ([HlgWideArgs, c_p], c_i),
+    "apex_c51_wide_actor_head": ([C51WideActorArgs, c_p], c_i),
+    "apex_cat_wide_args_size": ([c_i], c_i),
     "apex_mdqn_head": ([MdqnArgs, c_p], c_i),
     "apex_iqn_head": ([IqnArgs, c_p], c_i),
     "apex_iqn_wgrad": ([IqnWgArgs, c_p], c_i),

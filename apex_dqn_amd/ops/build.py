@@ -65,7 +65,11 @@ COMM_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-I", "/opt/rocm/include"]
 # SIMD and no scratch either way (profiles/pr35_layer_norm_resource_usage.txt)
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 # qr_wide_head.hip: scalar fp32 instructions in its elementwise phases too; the build with pairing was not compared
-SOURCE_FLAGS = {"fc_layernorm.hip": _NO_PK_F32, "qr_wide_head.hip": _NO_PK_F32}
+# cat_wide_head.hip: the same flags, so that its copy of csrc/wide_head.h's two GEMM kernels is the code of
+# qr_wide_head.hip's.  Register counts of the two builds of this file (no scratch in either): the dH GEMM 102 VGPRs
+# against 98 with pairing, the logits GEMM 84 / 84, the finish kernels within 2 of each other (C51 38..65 / 38..67,
+# HL-Gauss 47..90 both, NQ = 1..4); their run times were not compared
+SOURCE_FLAGS = {"fc_layernorm.hip": _NO_PK_F32, "qr_wide_head.hip": _NO_PK_F32, "cat_wide_head.hip": _NO_PK_F32}
 
 _STAMP_RE = re.compile(rb"APEX_BUILD_ID:([0-9a-f]{64})")
 _COMPILER_IDS: Dict[str, str] = {}

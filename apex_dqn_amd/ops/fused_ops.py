@@ -353,14 +353,17 @@ class TorchBackend:
 
     def c51_head(self, Hon, Htg, Pon: Dict[str, torch.Tensor], Ptg: Dict[str, torch.Tensor], act, rew, gam, isw,
                  num_atoms: int, v_min: float, v_max: float, grad_scale: float, td_abs, loss, dH, dhead,
-                 q_out=None, zero: Optional[torch.Tensor] = None, lo=None, isn=None, rescale_eps=None):
+                 q_out=None, zero: Optional[torch.Tensor] = None, lo=None, isn=None, rescale_eps=None, wide=False,
+                 logits=None):
         """The distributional counterpart of :meth:`head` (the oracle of csrc/c51_head.hip
         ``c51_head_kernel``): head weights ``wv (N, HS)``, ``bv (N,)``, ``wa (A N, HS)``, ``ba
         (A N,)``; loss = -w sum_i m_i log p(S_t)[a, i] with m the projected target
         distribution of the double-DQN action (learner/losses.py ``c51_project``), td_abs =
         |sum_i m_i z_i - q(S_t)[a]|, ``dhead [B, (A + 1) N]`` (value atoms, then action a's
         atoms at N + a N), ``q_out`` the expected q(S_t).  Computes in the head weights'
-        dtype when that is fp64 (the tests' reference), else fp32."""
+        dtype when that is fp64 (the tests' reference), else fp32.  ``wide`` / ``logits`` are the HIP backend's
+        (csrc/cat_wide_head.hip); this one is N-generic and ignores them, here and in :meth:`hlg_head` and
+        :meth:`c51_actor_head`."""
         def target(p_g, z):
             m = self._c51_m(p_g, rew, gam, v_min, v_max, rescale_eps)
             return m, (m * z).sum(-1)
@@ -426,7 +429,8 @@ class TorchBackend:
 
     def hlg_head(self, Hon, Htg, Pon: Dict[str, torch.Tensor], Ptg: Dict[str, torch.Tensor], act, rew, gam, isw,
                  num_atoms: int, v_min: float, v_max: float, sigma_ratio: float, grad_scale: float, td_abs, loss, dH,
-                 dhead, q_out=None, zero: Optional[torch.Tensor] = None, lo=None, isn=None, rescale_eps=None):
+                 dhead, q_out=None, zero: Optional[torch.Tensor] = None, lo=None, isn=None, rescale_eps=None,
+                 wide=False, logits=None):
         """:meth:`c51_head` with the histogram-loss (HL-Gauss) target (the oracle of csrc/c51_head.hip
         ``hlg_head_kernel``): y = clamp(rew + gam q_target(S_t+n)[a*]) from the target net's expectation of the
         double-DQN action (with ``rescale_eps`` T(rew, gam, q_target[a*])), m its Gaussian mass per bin
@@ -447,7 +451,7 @@ class TorchBackend:
                                dhead, q_out, zero, lo, isn, target)
 
     def c51_actor_head(self, H, P, eps, ctr, seed, num_atoms: int, v_min: float, v_max: float, q_out, a_out,
-                       H_lo=None):
+                       H_lo=None, wide=False, logits=None):
         """Expected q of the distributional head + epsilon-greedy per row (the oracle of
         csrc/c51_head.hip ``c51_actor_head_kernel``)."""
         N = int(num_atoms)
@@ -965,6 +969,9 @@ class HipBackend(TorchBackend):
         for k, cls in enumerate((_lib.QRWideArgs, _lib.QRWideActorArgs)):
             if self.lib.apex_qr_wide_args_size(k) != ctypes.sizeof(cls):
                 raise RuntimeError(f"libapex_kernels: sizeof({cls.__name__}) differs from its mirror")
+        for k, cls in enumerate((_lib.C51WideArgs, _lib.HlgWideArgs, _lib.C51WideActorArgs)):
+            if self.lib.apex_cat_wide_args_size(k) != ctypes.sizeof(cls):
+                raise RuntimeError(f"libapex_kernels: sizeof({cls.__name__}) differs from its mirror")
         self.ws = C.Workspace()
 
     # --------------------------------------------------- native conv family
@@ -1285,21 +1292,34 @@ class HipBackend(TorchBackend):
         assert dhead.shape == (B, (A + 1) * N) and dhead.is_contiguous()
         _lib.check(getattr(self.lib, "apex_" + symbol)(a, _lib.stream_ptr()), symbol)
 
+    def _wide_head_L(self, a, logits, Hon, Htg, Pon, act, dH, num_atoms) -> None:
+        """The wide launches' own preconditions, and ``a.L``: the caller's workspace or a fresh one."""
+        B, N = act.shape[0], int(num_atoms)
+        assert Hon.shape[0] >= 2 * B and Htg.shape[0] >= B and Hon.shape[1] == 1024 and Htg.shape[1] == 1024
+        assert dH.shape == (B, 1024) and Hon.is_contiguous() and Htg.is_contiguous() and dH.is_contiguous()
+        a.L = self._qr_wide_L(logits, 3 * B, Pon["wa"].shape[0] // max(N, 1), N, Hon.device)
+
     def c51_head(self, Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, v_min, v_max, grad_scale, td_abs, loss,
-                 dH, dhead, q_out=None, zero=None, lo=None, isn=None, rescale_eps=None):
-        """csrc/c51_head.hip ``c51_head_kernel``."""
-        a = _lib.C51Args()
+                 dH, dhead, q_out=None, zero=None, lo=None, isn=None, rescale_eps=None, wide=False, logits=None):
+        """csrc/c51_head.hip ``c51_head_kernel`` (up to 64 atoms); with ``wide`` (``Runtime.wide_atoms``) the three
+        launches of csrc/cat_wide_head.hip for any N in [2, 256].  ``logits``: as :meth:`qr_head`'s."""
+        a = _lib.C51WideArgs() if wide else _lib.C51Args()
         a.vmin, a.vmax = float(v_min), float(v_max)
-        self._dist_head_launch(a, "c51_head", Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, grad_scale, td_abs,
-                               loss, dH, dhead, q_out, zero, lo, isn, rescale_eps)
+        if wide:
+            self._wide_head_L(a, logits, Hon, Htg, Pon, act, dH, num_atoms)
+        self._dist_head_launch(a, "c51_wide_head" if wide else "c51_head", Hon, Htg, Pon, Ptg, act, rew, gam, isw,
+                               num_atoms, grad_scale, td_abs, loss, dH, dhead, q_out, zero, lo, isn, rescale_eps)
 
     def hlg_head(self, Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, v_min, v_max, sigma_ratio, grad_scale,
-                 td_abs, loss, dH, dhead, q_out=None, zero=None, lo=None, isn=None, rescale_eps=None):
-        """csrc/c51_head.hip ``hlg_head_kernel``."""
-        a = _lib.HlgArgs()
+                 td_abs, loss, dH, dhead, q_out=None, zero=None, lo=None, isn=None, rescale_eps=None, wide=False,
+                 logits=None):
+        """csrc/c51_head.hip ``hlg_head_kernel``; with ``wide`` csrc/cat_wide_head.hip, as :meth:`c51_head`."""
+        a = _lib.HlgWideArgs() if wide else _lib.HlgArgs()
         a.vmin, a.vmax, a.sigma_ratio = float(v_min), float(v_max), float(sigma_ratio)
-        self._dist_head_launch(a, "hlg_head", Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, grad_scale, td_abs,
-                               loss, dH, dhead, q_out, zero, lo, isn, rescale_eps)
+        if wide:
+            self._wide_head_L(a, logits, Hon, Htg, Pon, act, dH, num_atoms)
+        self._dist_head_launch(a, "hlg_wide_head" if wide else "hlg_head", Hon, Htg, Pon, Ptg, act, rew, gam, isw,
+                               num_atoms, grad_scale, td_abs, loss, dH, dhead, q_out, zero, lo, isn, rescale_eps)
 
     def _actor_io(self, io, H, P, eps, ctr, seed, q_out, a_out, H_lo) -> None:
         """Fill ``io``, the block every actor head takes (``_lib.ActorIO``); ``E`` and ``A`` are ``q_out``'s."""
@@ -1308,10 +1328,15 @@ class HipBackend(TorchBackend):
         io.eps, io.seed, io.ctr = eps.data_ptr(), int(seed), ctr.data_ptr()
         io.q_out, io.a_out = q_out.data_ptr(), a_out.data_ptr()
 
-    def c51_actor_head(self, H, P, eps, ctr, seed, num_atoms, v_min, v_max, q_out, a_out, H_lo=None):
-        a = _lib.C51ActorArgs()
+    def c51_actor_head(self, H, P, eps, ctr, seed, num_atoms, v_min, v_max, q_out, a_out, H_lo=None, wide=False,
+                       logits=None):
+        a = _lib.C51WideActorArgs() if wide else _lib.C51ActorArgs()
         self._actor_io(a.io, H, P, eps, ctr, seed, q_out, a_out, H_lo)
         a.N, a.vmin, a.vmax = int(num_atoms), float(v_min), float(v_max)
+        if wide:
+            assert H.shape[0] >= q_out.shape[0] and H.shape[1] == 1024 and H.is_contiguous()
+            a.L = self._qr_wide_L(logits, q_out.shape[0], q_out.shape[1], a.N, H.device)
+            return _lib.check(self.lib.apex_c51_wide_actor_head(a, _lib.stream_ptr()), "c51_wide_actor_head")
         _lib.check(self.lib.apex_c51_actor_head(a, _lib.stream_ptr()), "c51_actor_head")
 
     def qr_head(self, Hon, Htg, Pon, Ptg, act, rew, gam, isw, num_atoms, kappa, grad_scale, td_abs, loss,

@@ -49,13 +49,16 @@ def main() -> None:
     ap.add_argument("--kernel-iters", type=int, default=200)
     ap.add_argument("--actions", type=int, nargs="+", default=[4, 18])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"])
+    # Runtime.wide_atoms for every learner (csrc/cat_wide_head.hip; needed above 64 atoms).  Compare with the narrow
+    # kernels at --atoms <= 64 in a second process
+    ap.add_argument("--wide", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_hlgauss.py needs a GPU")
     dev = torch.device("cuda", 0)
-    c51 = {"num_atoms": args.atoms}
+    c51 = {"num_atoms": args.atoms, "wide_atoms": args.wide}
     heads = {"c51_a": c51, "c51_b": c51,
-             "hlgauss": {"num_atoms": args.atoms, "dist_head": "hl_gauss", "hl_gauss_sigma_ratio": args.sigma_ratio}}
+             "hlgauss": {**c51, "dist_head": "hl_gauss", "hl_gauss_sigma_ratio": args.sigma_ratio}}
     learners = {}
     for A in args.actions:
         for name, head in heads.items():
@@ -81,7 +84,8 @@ def main() -> None:
             assert L.graph_captures == caps, "a graph capture landed in the timed window"
             rates[name].append(round(args.steps / (e0.elapsed_time(e1) * 1e-3), 1))
     out = {"metric": "updates_per_s", "batch": args.batch, "steps": args.steps, "dtype": args.dtype,
-           "atoms": args.atoms, "sigma_ratio": args.sigma_ratio, "device": torch.cuda.get_device_name(0)}
+           "atoms": args.atoms, "wide": args.wide, "sigma_ratio": args.sigma_ratio,
+           "device": torch.cuda.get_device_name(0)}
     for name, r in rates.items():
         out[name] = {"runs": r, "median": float(np.median(r)), "min": min(r), "max": max(r)}
         assert np.isfinite(learners[name].last_metrics()["loss"])
