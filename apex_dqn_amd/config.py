@@ -113,6 +113,13 @@ class RuntimeConf:
     # head's loss with sampled fractions (learner/losses.py iqn_loss, learner/iqn.py the draws' mirror).
     # iqn_actor_samples = K: the samples behind the actors' and the greedy evaluation's q
     iqn_actor_samples: int = 32
+    # the implicit head's loss on the MFMA path (csrc/iqn_wide_head.hip): num_atoms = N in [2, 256], every such N
+    # through the wide launches (so at N <= 64 the key compares the two paths on one shape, with the same fractions).
+    # Opt-in: the embedding and head products take bf16 hi + lo operands (2^-17 relative), another rounding than
+    # the fp32 kernel's.  false = everything as before (csrc/iqn_head.hip, at most 64 samples).  Refused with any
+    # other dist_head and with num_atoms=1; the actors keep iqn_actor_samples in [1, 64] and their kernel.  The
+    # weights, the flat layout and the checkpoint keys do not depend on N (checkpoints load across the key)
+    iqn_wide: bool = False
     # "hl_gauss" (the Gaussian histogram loss, Imani & White 2018 / Farebrother et al. 2024; csrc/c51_head.hip
     # hlg_head_kernel): the categorical head, its support, weights, checkpoint keys and actor head, trained against
     # the scalar double-DQN target spread over the bins as a Gaussian of sigma = hl_gauss_sigma_ratio bin widths
@@ -384,11 +391,18 @@ class ApexConfig:
             raise ValueError(f"Runtime.wide_atoms is the categorical / hl_gauss heads' wide path "
                              f"(csrc/cat_wide_head.hip): not Runtime.num_atoms={na} with Runtime.dist_head="
                              f"{rt.dist_head!r}")
-        if na > 64 and rt.dist_head != "quantile" and not (rt.wide_atoms and rt.dist_head != "implicit"):
+        if not isinstance(rt.iqn_wide, bool):
+            raise ValueError(f"Runtime.iqn_wide must be true or false, got {rt.iqn_wide!r}")
+        if rt.iqn_wide and (na == 1 or rt.dist_head != "implicit"):
+            raise ValueError(f"Runtime.iqn_wide is the implicit head's wide path (csrc/iqn_wide_head.hip): not "
+                             f"Runtime.num_atoms={na} with Runtime.dist_head={rt.dist_head!r}")
+        if na > 64 and rt.dist_head != "quantile" and not (rt.wide_atoms and rt.dist_head != "implicit") and not (
+                rt.iqn_wide and rt.dist_head == "implicit"):
             raise ValueError(f"Runtime.num_atoms={na} with Runtime.dist_head={rt.dist_head!r}: the range [65, 256] is "
                              f"the quantile head's (csrc/qr_wide_head.hip) and, with Runtime.wide_atoms, the "
-                             f"categorical / hl_gauss heads' (csrc/cat_wide_head.hip); their narrow kernels and the "
-                             f"implicit head map one lane to one atom and stop at 64")
+                             f"categorical / hl_gauss heads' (csrc/cat_wide_head.hip) and, with Runtime.iqn_wide, the "
+                             f"implicit head's (csrc/iqn_wide_head.hip); their narrow kernels map one lane to one "
+                             f"atom and stop at 64")
         sr = rt.hl_gauss_sigma_ratio
         if na >= 2 and rt.dist_head == "hl_gauss" and (
                 isinstance(sr, bool) or not isinstance(sr, (int, float)) or not 0.0 < float(sr) < float("inf")):
@@ -583,6 +597,11 @@ class ApexConfig:
     def implicit(self) -> bool:
         """The distributional head is the implicit quantile one (Runtime.dist_head)."""
         return self.distributional and self.Runtime.dist_head == "implicit"
+
+    @property
+    def wide_implicit(self) -> bool:
+        """The implicit head's loss runs the wide launches (Runtime.iqn_wide, csrc/iqn_wide_head.hip)."""
+        return self.implicit and bool(self.Runtime.iqn_wide)
 
     @property
     def env_backend(self) -> str:

@@ -35,32 +35,7 @@
 //
 // iqn_actor_head_kernel: one block per env row, the same logits, q = mean over the K samples
 // and the epsilon-greedy draw of actor_head_kernel (same counter-RNG words).
-#include "iqn_wgrad.h"     // (IQN_E, IqnEmbed, IqnActorArgs; the weight-gradient body lives there)
-
-struct IqnArgs {
-  HeadIO io;            // Hon [2B], Htg [B]; dhead [B][(A + 1) N]
-  IqnEmbed Eon, Etg;    // (right behind io: with them after `base` iqn_head_kernel measured 0.5 % slower at A = 4)
-  int N;
-  float kappa;
-  uint64_t seed_q;
-  const int64_t* ctr;   // draw counter; u = ctr - base
-  const int64_t* base;  // null: 0
-  float* tau_out;       // [B][3][N] or null
-  float* dpre;          // [B][N][2 HS]
-  float* cosT;          // [B][N][64]
-  float* xg;            // [B][2 HS]
-  float* gsum;          // [B]
-  int max_blocks;       // <= 0: the CU count
-};
-static_assert(std::is_standard_layout_v<IqnArgs> && std::is_trivially_copyable_v<IqnArgs>);
-
-// cos(pi i tau): the fp32 product i tau rounds; its exact residual (one fma) enters to first order
-__device__ __forceinline__ float iqn_cos(int i, float tau) {
-  const float fi = (float)i;
-  const float p = __fmul_rn(fi, tau);
-  const float r = fmaf(fi, tau, -p);
-  return fmaf(-3.14159265358979323846f * r, sinpif(p), cospif(p));
-}
+#include "iqn_wgrad.h"     // (IQN_E, IqnEmbed, IqnArgs, IqnActorArgs, iqn_cos; the weight-gradient body lives there)
 
 __device__ __forceinline__ void iqn_load_we(const IqnEmbed& E, int tid, float* wev, float* wea, float& bev, float& bea) {
   const float4* pv = reinterpret_cast<const float4*>(E.w + (int64_t)tid * IQN_E);
@@ -353,22 +328,6 @@ __global__ void __launch_bounds__(DIST_NT) iqn_head_kernel(IqnArgs ka) {
       }
     }
   }
-}
-
-static inline bool iqn_embed_ok(const IqnEmbed& E) {
-  return E.w != nullptr && E.b != nullptr && ((uintptr_t)E.w & 15) == 0;
-}
-
-static int iqn_cu_count() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        n < 1)
-      n = 256;
-    cus = n;
-  }
-  return cus;
 }
 
 APEX_EXPORT int apex_iqn_head(IqnArgs a, hipStream_t st) {

@@ -45,6 +45,48 @@ struct IqnActorArgs {
 };
 static_assert(std::is_standard_layout_v<IqnActorArgs> && std::is_trivially_copyable_v<IqnActorArgs>);
 
+// iqn_head_kernel's arguments (csrc/iqn_head.hip); csrc/iqn_wide_head.hip appends its logits workspace
+struct IqnArgs {
+  HeadIO io;            // Hon [2B], Htg [B]; dhead [B][(A + 1) N]
+  IqnEmbed Eon, Etg;    // (right behind io: with them after `base` iqn_head_kernel measured 0.5 % slower at A = 4)
+  int N;
+  float kappa;
+  uint64_t seed_q;
+  const int64_t* ctr;   // draw counter; u = ctr - base
+  const int64_t* base;  // null: 0
+  float* tau_out;       // [B][3][N] or null
+  float* dpre;          // [B][N][2 HS]
+  float* cosT;          // [B][N][64]
+  float* xg;            // [B][2 HS]
+  float* gsum;          // [B]
+  int max_blocks;       // <= 0: the CU count
+};
+static_assert(std::is_standard_layout_v<IqnArgs> && std::is_trivially_copyable_v<IqnArgs>);
+
+// cos(pi i tau): the fp32 product i tau rounds; its exact residual (one fma) enters to first order
+__device__ __forceinline__ float iqn_cos(int i, float tau) {
+  const float fi = (float)i;
+  const float p = __fmul_rn(fi, tau);
+  const float r = fmaf(fi, tau, -p);
+  return fmaf(-3.14159265358979323846f * r, sinpif(p), cospif(p));
+}
+
+static inline bool iqn_embed_ok(const IqnEmbed& E) {
+  return E.w != nullptr && E.b != nullptr && ((uintptr_t)E.w & 15) == 0;
+}
+
+static inline int iqn_cu_count() {
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        n < 1)
+      n = 256;
+    cus = n;
+  }
+  return cus;
+}
+
 static inline int iqn_wgrad_blocks(int A) {
   return IQN_WG_S * (2 * DIST_HS / IQN_WG_CT) + (1 + (A + IQN_WG_AT - 1) / IQN_WG_AT) * (DIST_HS / 64);
 }
@@ -162,7 +204,7 @@ __device__ __forceinline__ void iqn_wgrad_body(const IqnWgArgs& h, int blk) {
 }
 
 static inline bool iqn_wgrad_args_ok(const IqnWgArgs& h) {
-  if (h.A < 1 || h.A > HEAD_MAXA || h.B < 1 || h.N < 2 || h.N > 64) return false;
+  if (h.A < 1 || h.A > HEAD_MAXA || h.B < 1 || h.N < 2 || h.N > 256) return false;
   if (h.dpre == nullptr || h.cosT == nullptr || h.xg == nullptr || h.gsum == nullptr || h.act == nullptr ||
       h.gwv == nullptr || h.gbv == nullptr || h.gwa == nullptr || h.gba == nullptr || h.gwtau == nullptr ||
       h.gbtau == nullptr || h.part == nullptr)

@@ -532,11 +532,14 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             self.iqn_ws = self.ops.iqn_workspace(B, self.N, d)
             self.tau_out = torch.zeros(B, 3, self.N, dtype=torch.float32, device=d)
             self._seed_q = iqn_seed(self.rt.seed)
-        # the wide heads' fp32 logits [3B, Jp] (csrc/qr_wide_head.hip; with Runtime.wide_atoms csrc/cat_wide_head.hip):
+        # the wide heads' fp32 logits [3B, Jp] (csrc/qr_wide_head.hip; with Runtime.wide_atoms csrc/cat_wide_head.hip,
+        # with Runtime.iqn_wide csrc/iqn_wide_head.hip):
         # this learner's own, allocated once
         self.qr_L = None
         self.wide_cat = self.cfg.wide_categorical and not self.quantile and not self.implicit
-        if ((self.quantile and (self.N > 64 or SW.qr_wide)) or self.wide_cat) and hasattr(self.ops, "qr_wide_logits"):
+        self.iqn_wide = self.implicit and self.cfg.wide_implicit      # Runtime.iqn_wide: csrc/iqn_wide_head.hip
+        if (((self.quantile and (self.N > 64 or SW.qr_wide)) or self.wide_cat or self.iqn_wide)
+                and hasattr(self.ops, "qr_wide_logits")):
             self.qr_L = self.ops.qr_wide_logits(3 * B, self.A, self.N, d)
         self.g_head_region = self.g32[o0:o1]
         # its share of the producer-summed clip norm: summed by one finalize block (the scalar
@@ -707,6 +710,8 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         elif self.implicit:
             # implicit quantiles: the quantile Huber loss at fractions drawn for this update (the index read on
             # the device: replay.ctr - upd_base, as the noisy layers' compose reads it)
+            if self.iqn_wide:       # (only then: the narrow call is the one of before)
+                kw.update(wide=True, logits=self.qr_L)
             ops.iqn_head(*h, self._embed(self.P), self._embed(self.T), *data, self.N, rt.huber_delta, out[0],
                          self._seed_q, self.replay.ctr, self.upd_base, *out[1:], self.iqn_ws, tau_out=self.tau_out,
                          **kw)

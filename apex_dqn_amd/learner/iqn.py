@@ -9,7 +9,8 @@ Nothing is drawn from a kernel's private state: every fraction is
 with ``apex_uniform`` the replay's counter RNG (csrc/apex_common.h, replay/gpu_replay.py) and
 ``seed_q`` a mixed word of ``Runtime.seed`` (:func:`iqn_seed`), never the noise seed's.
 
-  learner, update u:           c = 64 u,                    idx = (3 b + set) 64 + k
+  learner, update u:           c = 64 u,                    idx = (3 b + set) stride + k
+                               stride = 64 for N <= 64, 256 above (Runtime.iqn_wide, csrc/iqn_wide_head.hip)
   actor group g, call t:       c = 64 t + actor_stream(g),  idx = e 64 + k
   greedy evaluation:           tau_k = (2 k + 1) / (2 K)    (no draw)
 
@@ -26,7 +27,8 @@ from ..replay.gpu_replay import _mix64, apex_uniform
 from .noisy import STREAMS_PER_INDEX, actor_stream
 
 EMBED = 64          # cosines of the embedding (the paper's n = 64): a constant, not a key
-MAX_SAMPLES = 64    # one lane per sample; also the stride of a row's draws
+MAX_SAMPLES = 64    # one lane per sample (the narrow kernels); also the stride of a row's draws up to here
+MAX_WIDE = 256      # the learner's samples under Runtime.iqn_wide, and the stride of a row's draws above 64
 SETS = 3
 
 
@@ -37,11 +39,16 @@ def iqn_seed(seed: int) -> int:
         return int(_mix64(np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF) ^ np.uint64(0x49514E746175))) & ((1 << 63) - 1)
 
 
+def learner_stride(N: int) -> int:
+    """Draws between two tau sets of the learner: 64 for N <= 64, 256 above (no two sets share an index)."""
+    return MAX_SAMPLES if int(N) <= MAX_SAMPLES else MAX_WIDE
+
+
 def learner_taus(seed: int, u: int, B: int, N: int) -> torch.Tensor:
     """[B, 3, N] float32: the three tau sets of every batch row at update ``u`` (``seed`` is
-    seed_q)."""
-    assert 1 <= int(N) <= MAX_SAMPLES
-    row = np.arange(int(B) * SETS, dtype=np.uint64)[:, None] * np.uint64(MAX_SAMPLES)
+    seed_q).  The stride between two sets is 64 up to N = 64 (the bits of before) and 256 above."""
+    assert 1 <= int(N) <= MAX_WIDE
+    row = np.arange(int(B) * SETS, dtype=np.uint64)[:, None] * np.uint64(learner_stride(N))
     idx = row + np.arange(int(N), dtype=np.uint64)[None, :]
     t = apex_uniform(seed, STREAMS_PER_INDEX * int(u), idx)
     return torch.from_numpy(t.reshape(int(B), SETS, int(N)).copy())

@@ -110,6 +110,12 @@ class IqnArgs(ctypes.Structure):
                 ("gsum", c_p), ("max_blocks", c_i)]
 
 
+class IqnWideArgs(ctypes.Structure):
+    """``IqnArgs`` with the fp32 logits workspace ``L [3B, apex_qr_wide_jp(A, N)]`` appended (``IqnWideArgs``,
+    csrc/iqn_wide_head.hip)."""
+    _fields_ = [("h", IqnArgs), ("L", c_p)]
+
+
 class IqnWgArgs(ctypes.Structure):
     """Arguments of ``iqn_wgrad_prio_kernel`` (``IqnWgArgs``, csrc/iqn_wgrad.h; launched from csrc/sumtree.hip)."""
     _fields_ = [("dpre", c_p), ("cosT", c_p), ("xg", c_p), ("gsum", c_p), ("act", c_p), ("B", c_i), ("A", c_i),
@@ -374,6 +380,8 @@ _SIGS = {
     "apex_cat_wide_args_size": ([c_i], c_i),
     "apex_mdqn_head": ([MdqnArgs, c_p], c_i),
     "apex_iqn_head": ([IqnArgs, c_p], c_i),
+    "apex_iqn_wide_head": ([IqnWideArgs, c_p], c_i),
+    "apex_iqn_wide_args_size": ([], c_i),
     "apex_iqn_wgrad": ([IqnWgArgs, c_p], c_i),
     "apex_iqn_wgrad_part_floats": ([], c_i),
     "apex_iqn_wgrad_prio": ([IqnWgArgs, TreeUpdArgs, c_p], c_i),

@@ -548,7 +548,7 @@ class TorchBackend:
                  Eon: Dict[str, torch.Tensor], Etg: Dict[str, torch.Tensor], act, rew, gam, isw, num_samples: int,
                  kappa: float, grad_scale: float, seed_q: int, ctr, base, td_abs, loss, dH, dhead, ws, q_out=None,
                  tau_out=None, zero: Optional[torch.Tensor] = None, lo=None, isn=None, max_blocks=None,
-                 rescale_eps=None):
+                 rescale_eps=None, wide=False, logits=None):
         """The implicit quantile counterpart of :meth:`qr_head` (the oracle of csrc/iqn_head.hip
         ``iqn_head_kernel``): the scalar head's weights ``P`` gated by the cosine embedding
         ``E`` (:meth:`_iqn_theta`) at three tau sets of N fractions per sample, drawn by the
@@ -556,7 +556,8 @@ class TorchBackend:
         S_t, set 1 the online net at S_t+n (a* = first maximum of the mean), set 2 the target
         net at S_t+n (T_j).  loss, g, td_abs and ``dhead [B, (A + 1) N]`` as :meth:`qr_head`
         with tau_i of set 0; ``dH`` = [h > 0] sum_k phi_k dx_k; ``ws`` (:meth:`iqn_workspace`)
-        receives what :meth:`iqn_wgrad` needs; ``tau_out [B, 3, N]`` the fractions used."""
+        receives what :meth:`iqn_wgrad` needs; ``tau_out [B, 3, N]`` the fractions used.  ``wide`` / ``logits``
+        select the HIP backend's launches (csrc/iqn_wide_head.hip); this one is N-generic and ignores them."""
         from ..learner.iqn import learner_taus
         from ..learner.losses import quantile_huber_terms
         B, N = act.shape[0], int(num_samples)
@@ -969,6 +970,8 @@ class HipBackend(TorchBackend):
         for k, cls in enumerate((_lib.QRWideArgs, _lib.QRWideActorArgs)):
             if self.lib.apex_qr_wide_args_size(k) != ctypes.sizeof(cls):
                 raise RuntimeError(f"libapex_kernels: sizeof({cls.__name__}) differs from its mirror")
+        if self.lib.apex_iqn_wide_args_size() != ctypes.sizeof(_lib.IqnWideArgs):
+            raise RuntimeError("libapex_kernels: sizeof(IqnWideArgs) differs from its mirror")
         for k, cls in enumerate((_lib.C51WideArgs, _lib.HlgWideArgs, _lib.C51WideActorArgs)):
             if self.lib.apex_cat_wide_args_size(k) != ctypes.sizeof(cls):
                 raise RuntimeError(f"libapex_kernels: sizeof({cls.__name__}) differs from its mirror")
@@ -1396,12 +1399,14 @@ class HipBackend(TorchBackend):
 
     def iqn_head(self, Hon, Htg, Pon, Ptg, Eon, Etg, act, rew, gam, isw, num_samples, kappa, grad_scale, seed_q, ctr,
                  base, td_abs, loss, dH, dhead, ws, q_out=None, tau_out=None, zero=None, lo=None, isn=None,
-                 max_blocks=None, rescale_eps=None):
+                 max_blocks=None, rescale_eps=None, wide=False, logits=None):
         """csrc/iqn_head.hip ``iqn_head_kernel`` (reads h: the fc epilogue is not deferred).  ``max_blocks``
-        caps the persistent grid (default: the CU count)."""
+        caps the persistent grid (default: the CU count).  With ``wide`` (``Runtime.iqn_wide``) the three launches
+        of csrc/iqn_wide_head.hip for any N in [2, 256]; ``logits``: as :meth:`qr_head`'s."""
         assert getattr(self, "_fc_part", None) is None, "the distributional head reads h: fc epilogue deferred"
         N = int(num_samples)
-        a = _lib.IqnArgs()
+        aw = _lib.IqnWideArgs() if wide else None
+        a = aw.h if wide else _lib.IqnArgs()
         B, A, hidden = act.shape[0], Pon["wa"].shape[0], Pon["wv"].shape[-1]
         self._head_io(a.io, Hon, Htg, Pon, Ptg, act, rew, gam, isw, A, hidden, grad_scale, td_abs, loss, dH, dhead,
                       q_out, zero, lo, isn, rescale_eps)
@@ -1422,6 +1427,10 @@ class HipBackend(TorchBackend):
         assert tau_out is None or (tau_out.shape == (B, 3, N) and tau_out.is_contiguous()
                                    and tau_out.dtype == torch.float32)
         assert q_out is None or (q_out.shape == (B, A) and q_out.is_contiguous())
+        if wide:
+            assert hidden == 512 and Hon.shape[1] == 1024 and Htg.shape[1] == 1024
+            aw.L = self._qr_wide_L(logits, 3 * B, A, N, Hon.device)
+            return _lib.check(self.lib.apex_iqn_wide_head(aw, _lib.stream_ptr()), "iqn_wide_head")
         _lib.check(self.lib.apex_iqn_head(a, _lib.stream_ptr()), "iqn_head")
 
     def iqn_wgrad(self, act, ws, g, prio=None) -> None:

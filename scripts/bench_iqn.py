@@ -51,7 +51,10 @@ def steps_main(args) -> None:
     heads = {"scalar": {"num_atoms": 1}}
     for N in args.samples:
         heads[f"qr_{N}"] = {"num_atoms": N, "dist_head": "quantile"}
-        heads[f"iqn_{N}"] = {"num_atoms": N, "dist_head": "implicit"}
+        if N <= 64:
+            heads[f"iqn_{N}"] = {"num_atoms": N, "dist_head": "implicit"}
+        # Runtime.iqn_wide (csrc/iqn_wide_head.hip): any N in [2, 256]
+        heads[f"iqnw_{N}"] = {"num_atoms": N, "dist_head": "implicit", "iqn_wide": True}
     learners = {}
     for A in args.actions:
         for name, head in heads.items():
@@ -83,9 +86,11 @@ def steps_main(args) -> None:
         assert np.isfinite(learners[name].last_metrics()["loss"])
     for A in args.actions:
         for N in args.samples:
-            q, i = out[f"A{A}_qr_{N}"]["median"], out[f"A{A}_iqn_{N}"]["median"]
-            out[f"A{A}_iqn_{N}_vs_qr"] = round(i / q, 4)
-            out[f"A{A}_iqn_{N}_extra_us_per_update"] = round(1e6 / i - 1e6 / q, 1)
+            q = out[f"A{A}_qr_{N}"]["median"]
+            for kind in ("iqn", "iqnw") if N <= 64 else ("iqnw",):
+                i = out[f"A{A}_{kind}_{N}"]["median"]
+                out[f"A{A}_{kind}_{N}_vs_qr"] = round(i / q, 4)
+                out[f"A{A}_{kind}_{N}_extra_us_per_update"] = round(1e6 / i - 1e6 / q, 1)
     print(json.dumps(out), flush=True)
 
 
@@ -122,9 +127,12 @@ def main() -> None:
             gi = {"wv": z(1, 512), "bv": z(1), "wa": z(A, 512), "ba": z(A), "wtau": z(1024, 64), "btau": z(1024)}
             gq = {"wv": z(N, 512), "bv": z(N), "wa": z(A * N, 512), "ba": z(A * N)}
             ctr = torch.zeros(1, dtype=torch.int64, device=dev)
+            L = be.qr_wide_logits(3 * B, A, N, dev)
+            iqn = lambda **kw: be.iqn_head(p["Hon"], p["Htg"], *p["P1"], *p["E"], p["act"], p["rew"], p["gam"],      # noqa: E731
+                                           p["isw"], N, 1.0, 1.0 / B, 99, ctr, None, td, loss, dH, dhead, ws, lo=lo, **kw)
             launches = {
-                "iqn_head": lambda: be.iqn_head(p["Hon"], p["Htg"], *p["P1"], *p["E"], p["act"], p["rew"], p["gam"],
-                                                p["isw"], N, 1.0, 1.0 / B, 99, ctr, None, td, loss, dH, dhead, ws, lo=lo),
+                "iqn_head": iqn if N <= 64 else lambda: None,        # (the narrow kernel stops at 64)
+                "iqn_wide_head": lambda: iqn(wide=True, logits=L),
                 "iqn_wgrad": lambda: be.iqn_wgrad(p["act"], ws, gi),
                 "qr_head": lambda: be.qr_head(p["Hon"], p["Htg"], *p["PN"], p["act"], p["rew"], p["gam"], p["isw"], N, 1.0,
                                               1.0 / B, td, loss, dH, dhead, lo=lo),
