@@ -22,6 +22,9 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+# Runtime.dist_head values that run the implicit quantile network (the second: the Munchausen target, M-IQN)
+IMPLICIT_KINDS = ("implicit", "implicit_munchausen")
+
 
 @dataclass
 class EnvConf:
@@ -112,6 +115,11 @@ class RuntimeConf:
     # the head at the scalar head's shapes gated by a 64-cosine embedding of tau after the fc layer; the quantile
     # head's loss with sampled fractions (learner/losses.py iqn_loss, learner/iqn.py the draws' mirror).
     # iqn_actor_samples = K: the samples behind the actors' and the greedy evaluation's q
+    # "implicit_munchausen" (M-IQN, Vieillard et al. 2020; csrc/iqn_wide_head.hip miqn_wide_finish_kernel): the
+    # implicit head, its network, layout, checkpoint keys, draws and actors, trained on the Munchausen target
+    # (learner/losses.py miqn_targets) with munchausen_alpha / munchausen_tau / munchausen_clip; the 3B rows follow
+    # the Munchausen plan (target net at S_t+n and at S_t, no online net at S_t+n).  Needs iqn_wide; Runtime.munchausen
+    # stays the scalar head's key and is refused here; not rescaled; a checkpoint of the other implicit kind is refused
     iqn_actor_samples: int = 32
     # the implicit head's loss on the MFMA path (csrc/iqn_wide_head.hip): num_atoms = N in [2, 256], every such N
     # through the wide launches (so at N <= 64 the key compares the two paths on one shape, with the same fractions).
@@ -382,22 +390,25 @@ class ApexConfig:
                              f"Runtime.dist_head='quantile' only), got {na!r}")
         if not float(rt.v_min) < float(rt.v_max):
             raise ValueError(f"Runtime.v_min must be below Runtime.v_max, got {rt.v_min} / {rt.v_max}")
-        if rt.dist_head not in ("categorical", "quantile", "implicit", "hl_gauss"):
-            raise ValueError(f"Runtime.dist_head must be 'categorical', 'quantile', 'implicit' or 'hl_gauss', got "
-                             f"{rt.dist_head!r}")
+        if rt.dist_head not in ("categorical", "quantile", "implicit", "hl_gauss", "implicit_munchausen"):
+            raise ValueError(f"Runtime.dist_head must be 'categorical', 'quantile', 'implicit', 'hl_gauss' or "
+                             f"'implicit_munchausen', got {rt.dist_head!r}")
+        imp = rt.dist_head in IMPLICIT_KINDS
         if not isinstance(rt.wide_atoms, bool):
             raise ValueError(f"Runtime.wide_atoms must be true or false, got {rt.wide_atoms!r}")
-        if rt.wide_atoms and (na == 1 or rt.dist_head == "implicit"):
+        if rt.wide_atoms and (na == 1 or imp):
             raise ValueError(f"Runtime.wide_atoms is the categorical / hl_gauss heads' wide path "
                              f"(csrc/cat_wide_head.hip): not Runtime.num_atoms={na} with Runtime.dist_head="
                              f"{rt.dist_head!r}")
         if not isinstance(rt.iqn_wide, bool):
             raise ValueError(f"Runtime.iqn_wide must be true or false, got {rt.iqn_wide!r}")
-        if rt.iqn_wide and (na == 1 or rt.dist_head != "implicit"):
+        if rt.iqn_wide and (na == 1 or not imp):
             raise ValueError(f"Runtime.iqn_wide is the implicit head's wide path (csrc/iqn_wide_head.hip): not "
                              f"Runtime.num_atoms={na} with Runtime.dist_head={rt.dist_head!r}")
-        if na > 64 and rt.dist_head != "quantile" and not (rt.wide_atoms and rt.dist_head != "implicit") and not (
-                rt.iqn_wide and rt.dist_head == "implicit"):
+        if na >= 2 and rt.dist_head == "implicit_munchausen" and not rt.iqn_wide:
+            raise ValueError("Runtime.dist_head='implicit_munchausen' (M-IQN) runs on the wide path only "
+                             "(miqn_wide_finish_kernel, csrc/iqn_wide_head.hip): set Runtime.iqn_wide = true")
+        if na > 64 and rt.dist_head != "quantile" and not (rt.wide_atoms and not imp) and not (rt.iqn_wide and imp):
             raise ValueError(f"Runtime.num_atoms={na} with Runtime.dist_head={rt.dist_head!r}: the range [65, 256] is "
                              f"the quantile head's (csrc/qr_wide_head.hip) and, with Runtime.wide_atoms, the "
                              f"categorical / hl_gauss heads' (csrc/cat_wide_head.hip) and, with Runtime.iqn_wide, the "
@@ -414,16 +425,17 @@ class ApexConfig:
         if na == 1 and rt.dist_head != "categorical":
             raise ValueError(f"Runtime.dist_head={rt.dist_head!r} needs Runtime.num_atoms >= 2 (the scalar head has "
                              f"no distribution)")
-        if na >= 2 and rt.dist_head in ("quantile", "implicit") and not float(rt.huber_delta) > 0.0:
+        if na >= 2 and (rt.dist_head == "quantile" or imp) and not float(rt.huber_delta) > 0.0:
             raise ValueError(f"Runtime.dist_head={rt.dist_head!r} needs Runtime.huber_delta > 0 (the quantile Huber "
                              f"loss's kappa), got {rt.huber_delta}")
-        if na >= 2 and rt.dist_head == "implicit":
+        if na >= 2 and imp:
             if rt.noisy is True:
-                raise ValueError("Runtime.noisy with Runtime.dist_head='implicit' is not built: the noisy layers "
+                raise ValueError(f"Runtime.noisy with Runtime.dist_head={rt.dist_head!r} is not built: the noisy layers "
                                  "compose the categorical and quantile heads only")
             if rt.munchausen is True:
-                raise ValueError("Runtime.munchausen with Runtime.dist_head='implicit' (M-IQN) is not built: the "
-                                 "Munchausen target is the scalar head's")
+                raise ValueError(f"Runtime.munchausen with Runtime.dist_head={rt.dist_head!r}: Runtime.munchausen is "
+                                 "the scalar head's key; M-IQN is Runtime.dist_head='implicit_munchausen' with "
+                                 "Runtime.iqn_wide")
         if na >= 2:
             if net not in ("nature64", "nature32", "mlp"):
                 raise ValueError(f"Runtime.num_atoms={na} needs network nature64, nature32 or mlp, got {net!r}")
@@ -482,9 +494,9 @@ class ApexConfig:
         if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 < float(eps) <= 1.0:
             raise ValueError(f"Runtime.value_rescale_eps (the linear term of h) must be a number in (0, 1], got {eps!r}")
         if rt.value_rescale:
-            if rt.munchausen:
-                raise ValueError("Runtime.value_rescale with Runtime.munchausen is not built: the Munchausen target "
-                                 "is not rescaled")
+            if rt.munchausen or (na >= 2 and rt.dist_head == "implicit_munchausen"):
+                raise ValueError("Runtime.value_rescale with Runtime.munchausen or Runtime.dist_head="
+                                 "'implicit_munchausen' is not built: the Munchausen target is not rescaled")
             if net not in ("nature64", "nature32", "mlp"):
                 raise ValueError(f"Runtime.value_rescale needs network nature64, nature32 or mlp, got {net!r}")
             if int(rt.world_size) > 1 or rt.force_dp:
@@ -557,7 +569,7 @@ class ApexConfig:
         """The dueling modules' head arguments (models/dueling.py)."""
         rt = self.Runtime
         kw = dict(num_atoms=int(rt.num_atoms), v_min=float(rt.v_min), v_max=float(rt.v_max),
-                  dist_head=str(rt.dist_head))
+                  dist_head="implicit" if self.implicit else str(rt.dist_head))   # (M-IQN: the implicit module)
         if self.implicit:  # (only then: the other heads' call is the one of before)
             kw.update(iqn_actor_samples=int(rt.iqn_actor_samples))
         if rt.noisy:       # (only then: the non-noisy call is the one of before)
@@ -595,8 +607,14 @@ class ApexConfig:
 
     @property
     def implicit(self) -> bool:
-        """The distributional head is the implicit quantile one (Runtime.dist_head)."""
-        return self.distributional and self.Runtime.dist_head == "implicit"
+        """The distributional head is the implicit quantile one, with either target (Runtime.dist_head)."""
+        return self.distributional and self.Runtime.dist_head in IMPLICIT_KINDS
+
+    @property
+    def miqn(self) -> bool:
+        """The implicit head is trained on the Munchausen target (M-IQN, learner/losses.py miqn_loss); alpha, tau and
+        clip are :meth:`munchausen_kw`'s."""
+        return self.distributional and self.Runtime.dist_head == "implicit_munchausen"
 
     @property
     def wide_implicit(self) -> bool:

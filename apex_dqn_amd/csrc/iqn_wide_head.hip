@@ -37,6 +37,10 @@
 //                            S: a lane adds its samples in increasing k, then the 16 lanes of a DPP row are added in
 //                            a fixed order.
 //
+// Munchausen-IQN (dist_head = "implicit_munchausen", apex_miqn_wide_head): the logits kernel's MPLAN instantiation
+// (online S_t, target S_t+n, target S_t; the net switch at row B), miqn_wide_finish_kernel in the finish kernel's
+// place, the same backward.
+//
 // Nothing depends on the order blocks run in (no float atomics).
 #include "iqn_wgrad.h"
 #include "wide_head.h"
@@ -164,6 +168,10 @@ __device__ __forceinline__ uint64_t iqw_cword(const IqnArgs& ka) {
 }
 
 // ------------------------------------------------------------------------------------------------ logits
+// MPLAN (the Munchausen target, miqn_wide_finish_kernel): rows [0, B) the online net at S_t (set 0), [B, 2B) the
+// target net at S_t+n (set 2, the plain plan's draws), [2B, 3B) the target net at S_t (set 1); Hon [B], Htg [2B] read
+// at r - B; the one net switch of a walk is at row B.  Every difference is an `if constexpr`.
+template <bool MPLAN>
 __global__ void __launch_bounds__(IQW_NT) iqn_wide_logits_kernel(IqnWideArgs wa) {
   const IqnArgs& ka = wa.h;
   const HeadIO& a = ka.io;
@@ -183,7 +191,8 @@ __global__ void __launch_bounds__(IQW_NT) iqn_wide_logits_kernel(IqnWideArgs wa)
   uint4 whi[2][2], wmi[2][2], wlo[2][2];                       // head weights [column-tile pair][row tile], three terms
   int cur = -1, buf = 0;
   for (int r = blockIdx.x; r < 3 * B; r += gridDim.x) {
-    const int set = r < B ? 0 : (r < 2 * B ? 1 : 2), b = r - set * B, tg = set == 2;
+    const int blk = r < B ? 0 : (r < 2 * B ? 1 : 2), b = r - blk * B;
+    const int set = MPLAN ? (3 - blk) % 3 : blk, tg = MPLAN ? blk != 0 : blk == 2;
     if (tg != cur) {
       cur = tg;
       iqw_load_embed(tg ? ka.Etg : ka.Eon, c0, lane, f);
@@ -209,7 +218,7 @@ __global__ void __launch_bounds__(IQW_NT) iqn_wide_logits_kernel(IqnWideArgs wa)
         }
     }
     float h[4][4];
-    iqw_load_h(tg ? a.Htg : a.Hon, tg ? a.lo.Htg : a.lo.Hon, tg ? b : r, c0, lane, h);
+    iqw_load_h(tg ? a.Htg : a.Hon, tg ? a.lo.Htg : a.lo.Hon, tg ? (MPLAN ? r - B : b) : r, c0, lane, h);
     iqw_stage_cos(ka, cword, b, set, N, Ts, Chi, Clo, st == 0 ? ka.tau_out : nullptr, nullptr, tid);
     float* __restrict__ Lrow = wa.L + (int64_t)r * Jp + (st ? Nv4 : 0);
     for (int t = 0; t < NT; ++t) {
@@ -296,21 +305,25 @@ __device__ __forceinline__ float iqw_q(const QWRow<NQ>& r, int j, int N, int lan
   return wave_sum_dpp(p) * invN;
 }
 
+// What the finish kernels share once this lane's target samples T (0 past N) stand: the online row b of L (q_out, theta
+// of a_b), the pairwise quantile Huber loop against the drawn tau of set 0, td_abs, loss, gsum, dhead, the IS statistic
+template <bool RESCALE, int NQ>
+__device__ __forceinline__ void iqw_finish_tail(const IqnWideArgs& wa, const float (&T)[NQ], int b, bool live, int lane,
+                                                int wv);
+
 template <bool RESCALE, int NQ>
 __global__ void __launch_bounds__(QW_NT) iqn_wide_finish_kernel(IqnWideArgs wa) {
   const IqnArgs& ka = wa.h;
   const HeadIO& a = ka.io;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int B = a.B, A = a.A, N = ka.N, J = (A + 1) * N, Jp = qr_wide_jp(A, N);
+  const int B = a.B, A = a.A, N = ka.N, Jp = qr_wide_jp(A, N);
   if (a.zero_ptr != nullptr)
     for (int i = blockIdx.x * QW_NT + tid; i < a.zero_n; i += gridDim.x * QW_NT) a.zero_ptr[i] = 0.f;
   const int b_raw = blockIdx.x * 4 + wv;
   const bool live = b_raw < B;
   const int b = min(b_raw, B - 1);
-  const int a_b = a.act[b];
   const float rew = a.rew[b], gam = a.gam[b];
-  const float w = a.isw != nullptr ? a.isw[b] : 1.f;
-  const float invN = 1.0f / (float)N, kappa = ka.kappa;
+  const float invN = 1.0f / (float)N;
   float th[NQ];
   int astar = 0;
   {
@@ -333,6 +346,19 @@ __global__ void __launch_bounds__(QW_NT) iqn_wide_finish_kernel(IqnWideArgs wa) 
       else T[s] = ok ? rew + gam * th[s] : 0.f;
     }
   }
+  iqw_finish_tail<RESCALE, NQ>(wa, T, b, live, lane, wv);
+}
+
+template <bool RESCALE, int NQ>
+__device__ __forceinline__ void iqw_finish_tail(const IqnWideArgs& wa, const float (&T)[NQ], int b, bool live, int lane,
+                                                int wv) {
+  const IqnArgs& ka = wa.h;
+  const HeadIO& a = ka.io;
+  const int A = a.A, N = ka.N, J = (A + 1) * N, Jp = qr_wide_jp(A, N);
+  const int a_b = a.act[b];
+  const float w = a.isw != nullptr ? a.isw[b] : 1.f;
+  const float invN = 1.0f / (float)N, kappa = ka.kappa;
+  float th[NQ];
   float th_sa[NQ], q_sa = 0.f;
 #pragma unroll
   for (int s = 0; s < NQ; ++s) th_sa[s] = 0.f;
@@ -408,6 +434,97 @@ __global__ void __launch_bounds__(QW_NT) iqn_wide_finish_kernel(IqnWideArgs wa) 
   }
   if ((a.isn.out != nullptr || a.isn.valid_count != nullptr) && blockIdx.x == 0 && wv == QW_NT / 64 - 1)
     head_is_norm(a, lane);
+}
+
+// ------------------------------------------------------------------------------------------------ M-IQN finish
+// Munchausen-IQN (Runtime.dist_head = "implicit_munchausen"; learner/losses.py miqn_targets is the definition): the
+// logits kernel's M plan left rows b (online S_t), B + b (target S_t+n), 2B + b (target S_t) of L.
+struct MiqnWideArgs {
+  IqnWideArgs w;
+  float alpha, tau, clip;   // bonus scale, softmax temperature, lower clip of tau ln pi
+  float* aux;               // [B][2] (bonus, vsoft)
+};
+static_assert(std::is_standard_layout_v<MiqnWideArgs> && std::is_trivially_copyable_v<MiqnWideArgs>);
+
+// tau ln softmax(g / tau) of the A values g held one per lane (lane j = action j; lanes past A pass anything):
+// (g - max g) - tau ln sum_a exp((g - max g) / tau), max-subtracted as csrc/head_common.h's MDQN body, accurate expf /
+// logf.  Lanes past A return 0.
+__device__ __forceinline__ float miqn_tlp(float g, int A, int lane, float tau) {
+  const bool on = lane < A;
+  const float m = wave_max(on ? g : -3.4e38f);
+  const float c = on ? g - m : 0.f;
+  const float s = wave_sum_dpp(on ? expf(c / tau) : 0.f);
+  return on ? c - tau * logf(s) : 0.f;
+}
+
+// One wave per sample as iqn_wide_finish_kernel.  The two target rows' expectations g1[a] / g0[a] are wave sums over
+// each action's theta, kept one action per lane (A <= 32); the softmax terms are wave reductions over those lanes and
+// reach the second walk over the S_t+n row as v_readlane broadcasts.  That walk re-reads the A logit rows (the L2
+// holds them) instead of keeping A x NQ thetas in registers.
+template <int NQ>
+__global__ void __launch_bounds__(QW_NT) miqn_wide_finish_kernel(MiqnWideArgs ma) {
+  const IqnWideArgs& wa = ma.w;
+  const IqnArgs& ka = wa.h;
+  const HeadIO& a = ka.io;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int B = a.B, A = a.A, N = ka.N, Jp = qr_wide_jp(A, N);
+  if (a.zero_ptr != nullptr)
+    for (int i = blockIdx.x * QW_NT + tid; i < a.zero_n; i += gridDim.x * QW_NT) a.zero_ptr[i] = 0.f;
+  const int b_raw = blockIdx.x * 4 + wv;
+  const bool live = b_raw < B;
+  const int b = min(b_raw, B - 1);
+  const int a_b = __builtin_amdgcn_readfirstlane(a.act[b]);
+  const float rew = a.rew[b], gam = a.gam[b];
+  const float invN = 1.0f / (float)N, tau_m = ma.tau;
+  float th[NQ];
+  // target net at S_t+n: g1, tau ln pi1 and pi1 per lane, then the mixture sum_a pi1[a] (theta[a] - tlp1[a]) per owned
+  // sample in increasing a
+  float mix[NQ], vsoft;
+  {
+    const QWRow<NQ> r1 = iqw_row<NQ>(wa.L + (int64_t)(B + b) * Jp, a.Ptg, A, N, lane);
+    float g1 = 0.f;
+    for (int j = 0; j < A; ++j) {
+      const float q = iqw_q(r1, j, N, lane, invN, th);
+      if (lane == j) g1 = q;
+    }
+    const float tl1 = miqn_tlp(g1, A, lane, tau_m);
+    const float pi1 = lane < A ? expf(tl1 / tau_m) : 0.f;
+    vsoft = wave_sum_dpp(pi1 * (g1 - tl1));
+#pragma unroll
+    for (int s = 0; s < NQ; ++s) mix[s] = 0.f;
+    for (int j = 0; j < A; ++j) {
+      const float pj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pi1), j));
+      const float tj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tl1), j));
+      const float bj = r1.ba[j];
+#pragma unroll
+      for (int s = 0; s < NQ; ++s) {
+        const int i = 64 * s + lane;
+        const float t = i < N ? r1.v[s] + (r1.L[j * N + i] + bj) - r1.mean[s] : 0.f;
+        mix[s] += pj * (t - tj);
+      }
+    }
+  }
+  // target net at S_t: g0 and the bonus alpha clamp(tau ln pi0[a_b], clip, 0)
+  float bonus;
+  {
+    const QWRow<NQ> r0 = iqw_row<NQ>(wa.L + (int64_t)(2 * B + b) * Jp, a.Ptg, A, N, lane);
+    float g0 = 0.f;
+    for (int j = 0; j < A; ++j) {
+      const float q = iqw_q(r0, j, N, lane, invN, th);
+      if (lane == j) g0 = q;
+    }
+    const float tl0 = miqn_tlp(g0, A, lane, tau_m);
+    const float t0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tl0), a_b));
+    bonus = ma.alpha * fminf(fmaxf(t0, ma.clip), 0.f);
+  }
+  float T[NQ];
+#pragma unroll
+  for (int s = 0; s < NQ; ++s) T[s] = 64 * s + lane < N ? rew + bonus + gam * mix[s] : 0.f;
+  if (live && lane == 0) {
+    ma.aux[2 * (int64_t)b] = bonus;
+    ma.aux[2 * (int64_t)b + 1] = vsoft;
+  }
+  iqw_finish_tail<false, NQ>(wa, T, b, live, lane, wv);
 }
 
 // ------------------------------------------------------------------------------------------------ backward
@@ -514,7 +631,18 @@ static inline void iqw_finish_launch(const IqnWideArgs& a, hipStream_t st) {
   }
 }
 
-APEX_EXPORT int apex_iqn_wide_head(IqnWideArgs wa, hipStream_t st) {
+static inline void miqn_finish_launch(const MiqnWideArgs& a, hipStream_t st) {
+  const int grid = (a.w.h.io.B + 3) / 4;
+  switch ((a.w.h.N + 63) / 64) {
+    case 1: miqn_wide_finish_kernel<1><<<grid, QW_NT, 0, st>>>(a); break;
+    case 2: miqn_wide_finish_kernel<2><<<grid, QW_NT, 0, st>>>(a); break;
+    case 3: miqn_wide_finish_kernel<3><<<grid, QW_NT, 0, st>>>(a); break;
+    default: miqn_wide_finish_kernel<4><<<grid, QW_NT, 0, st>>>(a); break;
+  }
+}
+
+// The three launches of either head: `ma` null = the plain row plan and target, else the Munchausen ones.
+static int iqw_launch(const IqnWideArgs& wa, const MiqnWideArgs* ma, hipStream_t st) {
   const IqnArgs& a = wa.h;
   if (!qw_head_ok(a.io, a.N, wa.L) || !(a.kappa > 0.f)) return (int)hipErrorInvalidValue;
   if (!iqn_embed_ok(a.Eon) || !iqn_embed_ok(a.Etg)) return (int)hipErrorInvalidValue;
@@ -525,7 +653,8 @@ APEX_EXPORT int apex_iqn_wide_head(IqnWideArgs wa, hipStream_t st) {
   if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
   static bool lds_set = false;             // raised once, to the largest N's: not again inside a captured step
   if (!lds_set) {
-    for (const void* fn : {reinterpret_cast<const void*>(iqn_wide_logits_kernel),
+    for (const void* fn : {reinterpret_cast<const void*>(iqn_wide_logits_kernel<false>),
+                           reinterpret_cast<const void*>(iqn_wide_logits_kernel<true>),
                            reinterpret_cast<const void*>(iqn_wide_bwd_kernel)}) {
       const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)iqw_lds(256));
       if (e != hipSuccess) return (int)e;
@@ -535,11 +664,29 @@ APEX_EXPORT int apex_iqn_wide_head(IqnWideArgs wa, hipStream_t st) {
   // one block per CU: half the CUs walk each stream
   const int cap = a.max_blocks > 0 ? a.max_blocks : (iqn_cu_count() + 1) / 2;
   const int B = a.io.B;
-  iqn_wide_logits_kernel<<<dim3((unsigned)(3 * B < cap ? 3 * B : cap), 2), IQW_NT, lds, st>>>(wa);
-  if (a.io.rescale_eps > 0.f) iqw_finish_launch<true>(wa, st);
-  else iqw_finish_launch<false>(wa, st);
+  const dim3 lgrid((unsigned)(3 * B < cap ? 3 * B : cap), 2);
+  if (ma != nullptr) {
+    iqn_wide_logits_kernel<true><<<lgrid, IQW_NT, lds, st>>>(wa);
+    miqn_finish_launch(*ma, st);
+  } else {
+    iqn_wide_logits_kernel<false><<<lgrid, IQW_NT, lds, st>>>(wa);
+    if (a.io.rescale_eps > 0.f) iqw_finish_launch<true>(wa, st);
+    else iqw_finish_launch<false>(wa, st);
+  }
   iqn_wide_bwd_kernel<<<dim3((unsigned)(B < cap ? B : cap), 2), IQW_NT, lds, st>>>(wa);
   APEX_CHECK_LAUNCH();
 }
 
+APEX_EXPORT int apex_iqn_wide_head(IqnWideArgs wa, hipStream_t st) { return iqw_launch(wa, nullptr, st); }
+
 APEX_EXPORT int apex_iqn_wide_args_size() { return (int)sizeof(IqnWideArgs); }
+
+// Hon [B] (online S_t), Htg [2B] (target S_t+n, S_t); refuses what apex_iqn_wide_head refuses, a rescaled target, and
+// alpha / tau / clip outside the Munchausen target's ranges (csrc/mdqn_head.hip)
+APEX_EXPORT int apex_miqn_wide_head(MiqnWideArgs ma, hipStream_t st) {
+  if (!(ma.tau > 0.f) || !(ma.clip < 0.f) || !(ma.alpha >= 0.f && ma.alpha <= 1.f)) return (int)hipErrorInvalidValue;
+  if (ma.aux == nullptr || ma.w.h.io.rescale_eps != 0.f) return (int)hipErrorInvalidValue;
+  return iqw_launch(ma.w, &ma, st);
+}
+
+APEX_EXPORT int apex_miqn_wide_args_size() { return (int)sizeof(MiqnWideArgs); }

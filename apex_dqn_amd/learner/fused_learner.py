@@ -141,11 +141,18 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         if self.munchausen and self._dp:
             raise ValueError("Runtime.munchausen: the Munchausen target runs on a single rank, not in the "
                              "data-parallel step (world > 1, Runtime.force_dp, the emulated world)")
+        # M-IQN (Runtime.dist_head = "implicit_munchausen"): the implicit head on the same row plan with the
+        # Munchausen target of csrc/iqn_wide_head.hip miqn_wide_finish_kernel; m_plan: either of the two
+        self.miqn = cfg.miqn
+        if self.miqn and not self.rt.iqn_wide:
+            raise ValueError("Runtime.dist_head='implicit_munchausen' needs Runtime.iqn_wide = true (the wide path)")
+        self.m_plan = self.munchausen or self.miqn
         # rescaled n-step target T = h(R + Gamma h^-1(.)) (csrc/value_rescale.h): a variant of every head but the
         # Munchausen one, eps riding in the head's argument block; None = the launches and the bits of before
         self.rescale_eps = cfg.rescale_eps
-        if self.rescale_eps is not None and self.munchausen:
-            raise ValueError("Runtime.value_rescale: the Munchausen target (Runtime.munchausen) is not rescaled")
+        if self.rescale_eps is not None and self.m_plan:
+            raise ValueError("Runtime.value_rescale: the Munchausen target (Runtime.munchausen, Runtime.dist_head="
+                             "'implicit_munchausen') is not rescaled")
         if self.rescale_eps is not None and self._dp:
             raise ValueError("Runtime.value_rescale: the rescaled target runs on a single rank, not in the "
                              "data-parallel step (world > 1, Runtime.force_dp, the emulated world)")
@@ -339,7 +346,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         # (the Munchausen head reads h too: with the weight set switched at row B the fc forward keeps its
         # own epilogue, ops.fc_fwd)
         # (Runtime.layer_norm: the LayerNorm epilogue is the fc forward's own launch, the head reads h)
-        self._defer_fc_epilogue = SW.fc_epi_in_head and self.N == 1 and not self.munchausen and not self.layer_norm
+        self._defer_fc_epilogue = SW.fc_epi_in_head and self.N == 1 and not self.m_plan and not self.layer_norm
         # next-batch pre-sampling: the batch of step t+1 is drawn at the end of step t,
         # after the priority write-back -- on the HIP backend inside the optimizer launch
         # (its first blocks run the sampler: csrc/sumtree.hip rmsprop_sample_kernel), so
@@ -475,7 +482,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         # rows [0,B) = S_t, [B,2B) = S_{t+n} (online net), [2B,3B) = S_{t+n} (target net):
         # every forward layer is ONE launch over 3B images with the weight set
         # switched at row 2B (block-uniform)
-        # (Runtime.munchausen: [0,B) = S_t (online net), [B,2B) = S_{t+n}, [2B,3B) = S_t (both target net),
+        # (Runtime.munchausen, M-IQN: [0,B) = S_t (online net), [B,2B) = S_{t+n}, [2B,3B) = S_t (both target net),
         # switched at row B: _rows_first)
         self.S = self.replay.alloc_sample_buffers(B)
         self.slots = torch.zeros(3 * B, C, dtype=torch.int32, device=d)
@@ -489,7 +496,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             # into them (the third block repeats the rows it shows) and the offsets of the last update
             from .augment import aug_seed, aug_slot_table
             self.aug_frames = torch.zeros(2 * B * C, 84, 84, dtype=torch.uint8, device=d)
-            self.aug_slots = aug_slot_table(B, C, self.munchausen).to(d)
+            self.aug_slots = aug_slot_table(B, C, self.m_plan).to(d)
             self.aug_off = torch.zeros(2 * B, 2, dtype=torch.int32, device=d)
             self._seed_a = aug_seed(self.rt.seed)
 
@@ -516,7 +523,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         self.td_abs = torch.zeros(B, dtype=torch.float32, device=d)
         self.loss_b = torch.zeros(B, dtype=torch.float32, device=d)
         # Munchausen target: (bonus, soft value) per row, for the metrics
-        self.mdqn_aux = torch.zeros(B, 2, dtype=torch.float32, device=d) if self.munchausen else None
+        self.mdqn_aux = torch.zeros(B, 2, dtype=torch.float32, device=d) if self.m_plan else None
         self.partials = torch.zeros(1024, dtype=torch.float64, device=d)
         # single rank, HIP: the clip norm is summed by the gradient producers (fc wgrad
         # epilogue + grad_finalize blocks) instead of a separate pass over g32
@@ -573,7 +580,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
     @property
     def _rows_first(self) -> int:
         """The first row of the target net in the 3B-row forward: 2B, or B with the Munchausen target."""
-        return self.B if self.munchausen else 2 * self.B
+        return self.B if self.m_plan else 2 * self.B
 
     def forward_all(self, defer_head: bool = False) -> None:
         """Online net on rows [0,2B), target net on rows [2B,3B) (``_rows_first``): one launch per layer.
@@ -707,6 +714,12 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             mk = self.cfg.munchausen_kw()
             ops.mdqn_head(*h, *data, rt.loss == "huber", rt.huber_delta, mk["alpha"], mk["tau"], mk["clip"], *out,
                           aux=self.mdqn_aux, **kw)
+        elif self.miqn:
+            # M-IQN: the implicit head's call with the Munchausen row plan and target (always the wide launches)
+            mk = self.cfg.munchausen_kw()
+            ops.miqn_head(*h, self._embed(self.P), self._embed(self.T), *data, self.N, rt.huber_delta, mk["alpha"],
+                          mk["tau"], mk["clip"], out[0], self._seed_q, self.replay.ctr, self.upd_base, *out[1:],
+                          self.iqn_ws, aux=self.mdqn_aux, tau_out=self.tau_out, logits=self.qr_L, **kw)
         elif self.implicit:
             # implicit quantiles: the quantile Huber loss at fractions drawn for this update (the index read on
             # the device: replay.ctr - upd_base, as the noisy layers' compose reads it)
@@ -790,7 +803,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
         """The sampler's destination for the third row block ``slots[2B:]``: the S_{t+n} slots a second time,
         or with the Munchausen target the S_t slots."""
         third = self.slots[2 * self.B:]
-        return dict(obs2=third) if self.munchausen else dict(nxt2=third)
+        return dict(obs2=third) if self.m_plan else dict(nxt2=third)
 
     def _seg2(self, after_first=None) -> None:
         """fc dgrad + conv backward (with DP, all of it overlaps the fc/heads bucket
@@ -1359,7 +1372,7 @@ class FusedNatureLearner(IsNormMixin, StepIndexMixin, DataParallelStep):
             m["noisy_sigma_mean"] = float(self.P["swfc"].abs().mean())
         if self.ema:       # mean |online - target| of the fc weights (syncs, as the noisy metric)
             m["target_gap"] = float((self.P["wfc"] - self.T["wfc"]).abs().mean())
-        if self.munchausen:     # the last update's mean bonus (<= 0) and mean soft value of S_t+n
+        if self.m_plan:     # the last update's mean bonus (<= 0) and mean soft value of S_t+n
             mean = self.mdqn_aux.double().mean(0)
             m["munchausen_bonus_mean"], m["soft_value_mean"] = float(mean[0]), float(mean[1])
         if self.aug_pad:        # the last update's mean shift offset (expected: augment_shift)

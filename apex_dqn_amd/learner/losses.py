@@ -290,6 +290,54 @@ def munchausen_loss(q_t: torch.Tensor, q_target_t: torch.Tensor, q_target_next: 
     return per.mean(), delta.detach().abs()
 
 
+def miqn_targets(theta_target_t: torch.Tensor, theta_target_next: torch.Tensor, A: torch.Tensor, R: torch.Tensor,
+                 Gamma: torch.Tensor, alpha: float, tau: float,
+                 clip: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(T [B, N'], bonus [B], vsoft [B]) of the Munchausen-IQN target (Vieillard et al. 2020), in
+    ``theta_target_next``'s dtype.  ``theta_target_t`` [B, A, N''] / ``theta_target_next`` [B, A, N']: the target net's
+    quantiles at S_t / S_t+n, each at its own fractions; g0 / g1 [B, A] their means over the samples, pi = softmax(g /
+    tau) through :func:`tau_log_policy`:
+
+        bonus = alpha clamp(tlp(g0)[a_b], clip, 0)
+        T_j   = R + bonus + Gamma sum_a pi1[a] (theta_target_next[a, j] - tlp(g1)[a])      (a in increasing order)
+        vsoft = sum_a pi1[a] (g1[a] - tlp(g1)[a]),   so mean_j T_j = R + bonus + Gamma vsoft
+
+    Gamma = 0 at terminals needs no special case; with n-step returns the bonus is paid on the first transition
+    only, as in :func:`munchausen_targets`."""
+    th1 = theta_target_next
+    dt = th1.dtype
+    tl0 = tau_log_policy(theta_target_t.to(dt).mean(-1), tau).gather(1, A.long().view(-1, 1)).squeeze(1)
+    bonus = float(alpha) * tl0.clamp(float(clip), 0.0)
+    g1 = th1.mean(-1)
+    tl1 = tau_log_policy(g1, tau)
+    pi1 = (tl1 / float(tau)).exp()
+    mix = torch.zeros_like(th1[:, 0])
+    for a in range(th1.shape[1]):          # fixed order: the kernel's sum
+        mix = mix + pi1[:, a:a + 1] * (th1[:, a] - tl1[:, a:a + 1])
+    vsoft = (pi1 * (g1 - tl1)).sum(-1)
+    return R.to(dt)[:, None] + bonus[:, None] + Gamma.to(dt)[:, None] * mix, bonus, vsoft
+
+
+def miqn_loss(theta_t: torch.Tensor, tau_t: torch.Tensor, theta_target_t: torch.Tensor,
+              theta_target_next: torch.Tensor, A: torch.Tensor, R: torch.Tensor, Gamma: torch.Tensor, kappa: float,
+              weights: torch.Tensor = None, alpha: float = 0.9, tau: float = 0.03,
+              clip: float = -1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Munchausen-IQN loss: :func:`iqn_loss` with the detached target samples of :func:`miqn_targets` (no online
+    argmax).  ``theta_t`` [B, A, N]: the online net at S_t at the fractions ``tau_t`` [B, N].  Returns (mean over
+    the batch of w sum_i rho_i, |mean_j T_j - mean_i theta_i| per sample); computes in ``theta_t``'s dtype."""
+    B = theta_t.shape[0]
+    dt = theta_t.dtype
+    with torch.no_grad():
+        T = miqn_targets(theta_target_t.to(dt), theta_target_next.to(dt), A, R, Gamma, alpha, tau, clip)[0]
+    th = theta_t[torch.arange(B, device=theta_t.device), A.long().view(-1)]
+    per = quantile_huber_terms(th, T, kappa, tau_t)[0].sum(-1)
+    if weights is not None:
+        per = per * weights.to(dt)
+    with torch.no_grad():
+        td = (T.mean(-1) - th.mean(-1)).abs()
+    return per.mean(), td
+
+
 def ddqn_loss(q_online_t: torch.Tensor, q_online_next: torch.Tensor,
               q_target_next: torch.Tensor, A: torch.Tensor, R: torch.Tensor,
               Gamma: torch.Tensor, weights: torch.Tensor = None, loss: str = "huber",

@@ -90,6 +90,17 @@ class TorchLearner:
             taus = learner_taus(iqn_seed(self.rt.seed), self.num_q_updates, S_t.shape[0],
                                 int(self.rt.num_atoms)).to(self.device)
             self.last_taus = taus
+            if self.cfg.miqn:
+                # M-IQN: set 2 the target net at S_t+n, set 1 the target net at S_t, no online argmax
+                from .losses import miqn_loss, miqn_targets
+                kw = self.cfg.munchausen_kw()
+                with torch.no_grad():
+                    th0 = self.Q_target.quantiles_at(S_t, taus[:, 1])
+                    th1 = self.Q_target.quantiles_at(S_tpn, taus[:, 2])
+                    _, bonus, vsoft = miqn_targets(th0, th1, A, R, G, **kw)
+                    self._mdqn = (float(bonus.mean()), float(vsoft.mean()))
+                return miqn_loss(self.Q.quantiles_at(S_t, taus[:, 0]), taus[:, 0], th0, th1, A, R, G,
+                                 self.rt.huber_delta, w, **kw)
             with torch.no_grad():
                 q_next_online = self.Q.quantiles_at(S_tpn, taus[:, 1]).mean(-1)
                 th_next_target = self.Q_target.quantiles_at(S_tpn, taus[:, 2])
@@ -212,7 +223,7 @@ class TorchLearner:
         m = {}
         if int(self.rt.reset_interval) > 0:
             m["resets"] = self.num_q_updates // int(self.rt.reset_interval)
-        if self.rt.munchausen and getattr(self, "_mdqn", None) is not None:
+        if (self.rt.munchausen or self.cfg.miqn) and getattr(self, "_mdqn", None) is not None:
             m.update(munchausen_bonus_mean=self._mdqn[0], soft_value_mean=self._mdqn[1])
         return m
 

@@ -116,6 +116,12 @@ class IqnWideArgs(ctypes.Structure):
     _fields_ = [("h", IqnArgs), ("L", c_p)]
 
 
+class MiqnWideArgs(ctypes.Structure):
+    """``IqnWideArgs`` with the Munchausen target's alpha, tau, clip and ``aux [B, 2]`` appended (``MiqnWideArgs``,
+    csrc/iqn_wide_head.hip)."""
+    _fields_ = [("w", IqnWideArgs), ("alpha", c_f), ("tau", c_f), ("clip", c_f), ("aux", c_p)]
+
+
 class IqnWgArgs(ctypes.Structure):
     """Arguments of ``iqn_wgrad_prio_kernel`` (``IqnWgArgs``, csrc/iqn_wgrad.h; launched from csrc/sumtree.hip)."""
     _fields_ = [("dpre", c_p), ("cosT", c_p), ("xg", c_p), ("gsum", c_p), ("act", c_p), ("B", c_i), ("A", c_i),
@@ -382,6 +388,8 @@ _SIGS = {
     "apex_iqn_head": ([IqnArgs, c_p], c_i),
     "apex_iqn_wide_head": ([IqnWideArgs, c_p], c_i),
     "apex_iqn_wide_args_size": ([], c_i),
+    "apex_miqn_wide_head": ([MiqnWideArgs, c_p], c_i),
+    "apex_miqn_wide_args_size": ([], c_i),
     "apex_iqn_wgrad": ([IqnWgArgs, c_p], c_i),
     "apex_iqn_wgrad_part_floats": ([], c_i),
     "apex_iqn_wgrad_prio": ([IqnWgArgs, TreeUpdArgs, c_p], c_i),

@@ -559,11 +559,8 @@ class TorchBackend:
         receives what :meth:`iqn_wgrad` needs; ``tau_out [B, 3, N]`` the fractions used.  ``wide`` / ``logits``
         select the HIP backend's launches (csrc/iqn_wide_head.hip); this one is N-generic and ignores them."""
         from ..learner.iqn import learner_taus
-        from ..learner.losses import quantile_huber_terms
         B, N = act.shape[0], int(num_samples)
-        A = Pon["wa"].shape[0]
         dt = _head_dtype(Pon["wv"])
-        HS = Pon["wv"].shape[-1]
         if not float(kappa) > 0.0:
             raise ValueError(f"iqn_head: kappa must be > 0, got {kappa}")
         lo = lo if lo is not None else (None, None, None)
@@ -573,13 +570,25 @@ class TorchBackend:
             tau_out.copy_(taus)
         ar = torch.arange(B, device=Hon.device)
         th_t, pre, cf = self._iqn_theta(Hon[:B], Pon, Eon, taus[:, 0], dt)
-        q_t = th_t.mean(-1)
         a_star = self._iqn_theta(Hon[B:2 * B], Pon, Eon, taus[:, 1], dt)[0].mean(-1).argmax(1)
         T = self._quantile_T(rew.to(dt), gam.to(dt), self._iqn_theta(Htg[:B], Ptg, Etg, taus[:, 2], dt)[0][ar, a_star],
                              rescale_eps)
-        th = th_t[ar, act.long()]
-        rho, c = quantile_huber_terms(th, T, kappa, taus[:, 0])
-        w = isw.to(dt) if isw is not None else torch.ones(B, dtype=dt, device=Hon.device)
+        self._iqn_tail(T, th_t, pre, cf, taus[:, 0], Hon[:B], Pon, act, isw, kappa, grad_scale, td_abs, loss, dH, dhead,
+                       ws, q_out, zero, lo[2], isn, dt)
+
+    def _iqn_tail(self, T, th_t, pre, cf, tau0, h, Pon, act, isw, kappa, grad_scale, td_abs, loss, dH, dhead, ws, q_out,
+                  zero, dH_lo, isn, dt) -> None:
+        """What :meth:`iqn_head` and :meth:`miqn_head` share once the target samples ``T [B, N]`` stand: the
+        quantile Huber loss of theta(S_t)[a_b] (``th_t``, ``pre``, ``cf`` of :meth:`_iqn_theta` at the fractions
+        ``tau0`` of set 0) against them, the priority, and the backward to ``dhead`` / ``dH`` / ``ws`` (``h``: the
+        online S_t rows)."""
+        from ..learner.losses import quantile_huber_terms
+        B = act.shape[0]
+        A, HS = Pon["wa"].shape[0], Pon["wv"].shape[-1]
+        q_t = th_t.mean(-1)
+        th = th_t[torch.arange(B, device=h.device), act.long()]
+        rho, c = quantile_huber_terms(th, T, kappa, tau0)
+        w = isw.to(dt) if isw is not None else torch.ones(B, dtype=dt, device=h.device)
         td_abs.copy_((T.mean(-1) - th.mean(-1)).abs())
         loss.copy_(w * rho.sum(-1))
         g = -w[:, None] * grad_scale * c                           # d loss / d theta of (a_b, .)
@@ -589,14 +598,45 @@ class TorchBackend:
         dxa = torch.einsum("bak,ac->bkc", dadv, Pon["wa"].to(dt))
         dx = torch.cat([dxv, dxa], -1)
         phi = torch.relu(pre)
-        h = Hon[:B]
         dh = (phi * dx).sum(1) * (h > 0).to(dt)
-        split_into(dh, dH, lo[2])
+        split_into(dh, dH, dH_lo)
         ws["dpre"].copy_((pre > 0).to(dt) * dx * h[:, None, :])
         ws["cos"].copy_(cf)
         ws["xg"].copy_((g[:, :, None] * (h[:, None, :] * phi)).sum(1))
         ws["gsum"].copy_(g.sum(1))
         self._head_close(q_out, q_t, zero, isn, w.float())
+
+    def miqn_head(self, Hon, Htg, Pon: Dict[str, torch.Tensor], Ptg: Dict[str, torch.Tensor],
+                  Eon: Dict[str, torch.Tensor], Etg: Dict[str, torch.Tensor], act, rew, gam, isw, num_samples: int,
+                  kappa: float, alpha: float, tau: float, clip: float, grad_scale: float, seed_q: int, ctr, base,
+                  td_abs, loss, dH, dhead, ws, aux=None, q_out=None, tau_out=None,
+                  zero: Optional[torch.Tensor] = None, lo=None, isn=None, max_blocks=None, logits=None):
+        """:meth:`iqn_head` with the Munchausen target (M-IQN; learner/losses.py ``miqn_targets`` is the
+        definition, this the oracle of csrc/iqn_wide_head.hip ``miqn_wide_finish_kernel``).  Row plan of
+        :meth:`mdqn_head`: ``Hon`` [B] the online net at S_t (tau set 0), ``Htg`` [2B] the target net at S_t+n
+        (rows [0, B), set 2) and at S_t (rows [B, 2B), set 1); no online argmax.  ``aux`` [B, 2] receives (bonus,
+        vsoft); everything else as :meth:`iqn_head`."""
+        from ..learner.iqn import learner_taus
+        from ..learner.losses import miqn_targets
+        B, N = act.shape[0], int(num_samples)
+        assert Hon.shape[0] == B and Htg.shape[0] == 2 * B
+        dt = _head_dtype(Pon["wv"])
+        if not float(kappa) > 0.0:
+            raise ValueError(f"miqn_head: kappa must be > 0, got {kappa}")
+        lo = lo if lo is not None else (None, None, None)
+        Hon, Htg = join(Hon, lo[0], dt), join(Htg, lo[1], dt)
+        taus = learner_taus(int(seed_q), self._iqn_update_index(ctr, base), B, N).to(Hon.device)
+        if tau_out is not None:
+            tau_out.copy_(taus)
+        th_t, pre, cf = self._iqn_theta(Hon, Pon, Eon, taus[:, 0], dt)
+        th1 = self._iqn_theta(Htg[:B], Ptg, Etg, taus[:, 2], dt)[0]
+        th0 = self._iqn_theta(Htg[B:], Ptg, Etg, taus[:, 1], dt)[0]
+        T, bonus, vsoft = miqn_targets(th0, th1, act, rew.to(dt), gam.to(dt), alpha, tau, clip)
+        if aux is not None:
+            aux[:, 0] = bonus
+            aux[:, 1] = vsoft
+        self._iqn_tail(T, th_t, pre, cf, taus[:, 0], Hon, Pon, act, isw, kappa, grad_scale, td_abs, loss, dH, dhead,
+                       ws, q_out, zero, lo[2], isn, dt)
 
     def iqn_wgrad(self, act, ws, g: Dict[str, torch.Tensor], prio=None) -> None:
         """The head and embedding weight gradients from what :meth:`iqn_head` left (the oracle of
@@ -960,7 +1000,7 @@ class HipBackend(TorchBackend):
         self.lib = _lib.require_kernels()
         self.native_conv = native_conv and hasattr(self.lib, "apex_conv_fwd")
         self.kernels = ["replay", "head", "head_wgrad", "optimizer", "actor_head", "c51_head", "c51_actor_head", "qr_head",
-                        "qr_actor_head", "noisy_compose", "noisy_sigma_grad", "mdqn_head", "iqn_head", "iqn_wgrad",
+                        "qr_actor_head", "noisy_compose", "noisy_sigma_grad", "mdqn_head", "iqn_head", "miqn_head", "iqn_wgrad",
                         "iqn_actor_head", "augment_shift", "hlg_head", "reset_perturb"]
         if self.native_conv:
             self.kernels += ["conv_fwd", "conv_dgrad", "conv_wgrad", "fc_fwd", "fc_bwd", "fc_ln_fwd", "fc_ln_bwd"]
@@ -972,6 +1012,8 @@ class HipBackend(TorchBackend):
                 raise RuntimeError(f"libapex_kernels: sizeof({cls.__name__}) differs from its mirror")
         if self.lib.apex_iqn_wide_args_size() != ctypes.sizeof(_lib.IqnWideArgs):
             raise RuntimeError("libapex_kernels: sizeof(IqnWideArgs) differs from its mirror")
+        if self.lib.apex_miqn_wide_args_size() != ctypes.sizeof(_lib.MiqnWideArgs):
+            raise RuntimeError("libapex_kernels: sizeof(MiqnWideArgs) differs from its mirror")
         for k, cls in enumerate((_lib.C51WideArgs, _lib.HlgWideArgs, _lib.C51WideActorArgs)):
             if self.lib.apex_cat_wide_args_size(k) != ctypes.sizeof(cls):
                 raise RuntimeError(f"libapex_kernels: sizeof({cls.__name__}) differs from its mirror")
@@ -1403,10 +1445,23 @@ class HipBackend(TorchBackend):
         """csrc/iqn_head.hip ``iqn_head_kernel`` (reads h: the fc epilogue is not deferred).  ``max_blocks``
         caps the persistent grid (default: the CU count).  With ``wide`` (``Runtime.iqn_wide``) the three launches
         of csrc/iqn_wide_head.hip for any N in [2, 256]; ``logits``: as :meth:`qr_head`'s."""
-        assert getattr(self, "_fc_part", None) is None, "the distributional head reads h: fc epilogue deferred"
         N = int(num_samples)
         aw = _lib.IqnWideArgs() if wide else None
         a = aw.h if wide else _lib.IqnArgs()
+        B, A = act.shape[0], Pon["wa"].shape[0]
+        self._iqn_args(a, 2 * B, B, Hon, Htg, Pon, Ptg, Eon, Etg, act, rew, gam, isw, N, kappa, grad_scale, seed_q,
+                       ctr, base, td_abs, loss, dH, dhead, ws, q_out, tau_out, zero, lo, isn, max_blocks, rescale_eps)
+        if wide:
+            assert a.io.hidden == 512 and Hon.shape[1] == 1024 and Htg.shape[1] == 1024
+            aw.L = self._qr_wide_L(logits, 3 * B, A, N, Hon.device)
+            return _lib.check(self.lib.apex_iqn_wide_head(aw, _lib.stream_ptr()), "iqn_wide_head")
+        _lib.check(self.lib.apex_iqn_head(a, _lib.stream_ptr()), "iqn_head")
+
+    def _iqn_args(self, a, rows_on, rows_tg, Hon, Htg, Pon, Ptg, Eon, Etg, act, rew, gam, isw, N, kappa, grad_scale,
+                  seed_q, ctr, base, td_abs, loss, dH, dhead, ws, q_out, tau_out, zero, lo, isn, max_blocks,
+                  rescale_eps=None) -> None:
+        """Fill an ``IqnArgs`` block; ``rows_on`` / ``rows_tg``: the rows the row plan reads of ``Hon`` / ``Htg``."""
+        assert getattr(self, "_fc_part", None) is None, "the distributional head reads h: fc epilogue deferred"
         B, A, hidden = act.shape[0], Pon["wa"].shape[0], Pon["wv"].shape[-1]
         self._head_io(a.io, Hon, Htg, Pon, Ptg, act, rew, gam, isw, A, hidden, grad_scale, td_abs, loss, dH, dhead,
                       q_out, zero, lo, isn, rescale_eps)
@@ -1418,7 +1473,7 @@ class HipBackend(TorchBackend):
                                         ws["gsum"].data_ptr())
         a.max_blocks = 0 if max_blocks is None else int(max_blocks)
         assert Pon["wv"].numel() == hidden and Ptg["wv"].numel() == hidden and Eon["wtau"].shape[0] == 2 * hidden
-        assert Hon.shape[0] >= 2 * B and Htg.shape[0] >= B and Hon.is_contiguous() and Htg.is_contiguous()
+        assert Hon.shape[0] >= rows_on and Htg.shape[0] >= rows_tg and Hon.is_contiguous() and Htg.is_contiguous()
         assert dhead.shape == (B, (A + 1) * N) and dhead.is_contiguous() and dhead.dtype == torch.float32
         assert dH.shape == (B, 2 * hidden) and dH.is_contiguous()
         assert ws["dpre"].shape == (B, N, 2 * hidden) and ws["cos"].shape == (B, N, 64)
@@ -1427,11 +1482,23 @@ class HipBackend(TorchBackend):
         assert tau_out is None or (tau_out.shape == (B, 3, N) and tau_out.is_contiguous()
                                    and tau_out.dtype == torch.float32)
         assert q_out is None or (q_out.shape == (B, A) and q_out.is_contiguous())
-        if wide:
-            assert hidden == 512 and Hon.shape[1] == 1024 and Htg.shape[1] == 1024
-            aw.L = self._qr_wide_L(logits, 3 * B, A, N, Hon.device)
-            return _lib.check(self.lib.apex_iqn_wide_head(aw, _lib.stream_ptr()), "iqn_wide_head")
-        _lib.check(self.lib.apex_iqn_head(a, _lib.stream_ptr()), "iqn_head")
+
+    def miqn_head(self, Hon, Htg, Pon, Ptg, Eon, Etg, act, rew, gam, isw, num_samples, kappa, alpha, tau, clip,
+                  grad_scale, seed_q, ctr, base, td_abs, loss, dH, dhead, ws, aux=None, q_out=None, tau_out=None,
+                  zero=None, lo=None, isn=None, max_blocks=None, logits=None, rescale_eps=None):
+        """csrc/iqn_wide_head.hip ``apex_miqn_wide_head``: the logits kernel on the Munchausen row plan,
+        ``miqn_wide_finish_kernel`` and the implicit head's backward, for any N in [2, 256].  ``aux`` [B, 2] fp32
+        is required (the launcher refuses a null one, and a ``rescale_eps``: the target is not rescaled)."""
+        N = int(num_samples)
+        m = _lib.MiqnWideArgs()
+        B, A = act.shape[0], Pon["wa"].shape[0]
+        self._iqn_args(m.w.h, B, 2 * B, Hon, Htg, Pon, Ptg, Eon, Etg, act, rew, gam, isw, N, kappa, grad_scale, seed_q,
+                       ctr, base, td_abs, loss, dH, dhead, ws, q_out, tau_out, zero, lo, isn, max_blocks, rescale_eps)
+        assert m.w.h.io.hidden == 512 and Hon.shape[1] == 1024 and Htg.shape[1] == 1024
+        assert aux is None or (aux.shape == (B, 2) and aux.dtype == torch.float32 and aux.is_contiguous())
+        m.w.L = self._qr_wide_L(logits, 3 * B, A, N, Hon.device)
+        m.alpha, m.tau, m.clip, m.aux = float(alpha), float(tau), float(clip), _lib.ptr(aux)
+        _lib.check(self.lib.apex_miqn_wide_head(m, _lib.stream_ptr()), "miqn_wide_head")
 
     def iqn_wgrad(self, act, ws, g, prio=None) -> None:
         """csrc/sumtree.hip ``iqn_wgrad_prio_kernel`` + ``iqn_wgrad_reduce_kernel`` (csrc/iqn_wgrad.h): G[wv, bv, wa, ba, wtau, btau];

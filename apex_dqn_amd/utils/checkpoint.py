@@ -130,7 +130,8 @@ def check_dist_head(ck: Dict[str, Any], runtime_conf) -> None:
     if isinstance(qs, dict):
         # the implicit quantile head is told by its keys (a reference-format state included)
         has_tau = any(k.startswith("tau_embed.") for k in qs)
-        want = int(runtime_conf.num_atoms) >= 2 and str(runtime_conf.dist_head) == "implicit"
+        want = int(runtime_conf.num_atoms) >= 2 and str(runtime_conf.dist_head) in (
+            "implicit", "implicit_munchausen")      # (M-IQN: the same keys; the kinds are told apart by the config below)
         if has_tau != want:
             raise ValueError("the checkpoint's Q_state has " + ("an" if has_tau else "no") + " implicit quantile "
                              f"embedding (tau_embed.*), this learner runs Runtime.dist_head="
