@@ -58,6 +58,7 @@ from .nstep import make_nstep_builder
 
 class GpuActorGroup:
     noisy = False     # (the groups of learners without noisy layers never set it)
+    env_noise = False  # (nor this: Runtime.noisy_actor_noise = "per_env")
     implicit = False  # (nor the implicit quantile head's)
 
     def __init__(self, cfg, learner, replay, env, num_envs: int, global_offset: int = 0,
@@ -127,7 +128,21 @@ class GpuActorGroup:
             from ..learner.noisy import actor_stream
             self._iqn = (iqn_seed(cfg.Runtime.seed), actor_stream(group), int(cfg.Runtime.iqn_actor_samples))
         self.noisy = bool(getattr(learner, "noisy", False))
-        if self.noisy:
+        # Runtime.noisy_actor_noise = "per_env": env row e acts under its own draw (u, s, e) -- no composed weight
+        # set, the fc layer and the heads as two products on the slot's mu and sigma (csrc/noisy_actor.hip); the
+        # group owns the draws xi [E, K], the fc GEMM's partial planes and the logits workspace
+        self.env_noise = self.noisy and cfg.Runtime.noisy_actor_noise == "per_env"
+        if self.env_noise:
+            from ..learner.noisy import NoisyPlan, actor_stream, noise_seed
+            if getattr(learner, "layer_norm", False):
+                raise ValueError("Runtime.noisy_actor_noise='per_env' with Runtime.layer_norm is not built")
+            self.xi = torch.zeros(self.E, learner.xi.shape[1], dtype=torch.float32, device=d)
+            self._env_part = self.ops.noisy_env_fc_ws(self.E, d)
+            self._env_L = self.ops.noisy_env_logits_ws(self.E, self.A, n_q, d)
+            rt = cfg.Runtime
+            self._env_head = ("scalar",) if n_q < 2 else ("quantile", n_q) if cfg.quantile else \
+                ("categorical", n_q, rt.v_min, rt.v_max)
+        elif self.noisy:
             from ..learner.noisy import NoisyPlan, actor_stream, noise_seed
             nm = learner.mu_layout.numel
             self._e32 = torch.zeros(nm, dtype=torch.float32, device=d)
@@ -136,6 +151,7 @@ class GpuActorGroup:
             self.EP = learner.mu_layout.views(self._e32)
             self.EPb = learner.mu_layout.views(self._ebf[:nm])
             self.EPl = learner.mu_layout.views(self._ebf[nm:]) if self.split else None
+        if self.noisy:
             self._nz = NoisyPlan(A=self.A, N=int(learner.N), offsets=dict(learner.layout.offsets),
                                  seed=noise_seed(cfg.Runtime.seed), ctr=self.ctr, base=None,
                                  every=int(cfg.Runtime.noisy_actor_resample), stream0=actor_stream(group))
@@ -301,6 +317,8 @@ class GpuActorGroup:
         # beside the learner, where the chip-filling split's partial planes cost HBM traffic)
         ks = dict(ksplit=SW.actor_fc_ksplit) if SW.actor_fc_ksplit > 0 else {}
         F, Fb, Fl = P, Pb, Pl          # where the fc layer and the heads read their parameters
+        if self.env_noise:
+            return self._env_noise_kernels(c3)
         if self.noisy:
             nm = self._e32.numel()
             ops.noisy_compose(self._nz, [(self.p32, self._e32, self._ebf[:nm], self._ebf[nm:] if self.split else None)],
@@ -321,6 +339,24 @@ class GpuActorGroup:
             ops.fc_fwd(self.y3.reshape(E, 3136), Fb["wfc"], F["bfc"], self.h, **ks)
         heads = {k: F[k] for k in ("wv", "bv", "wa", "ba")}
         self._actor_head(self.h, heads, self.h_lo)
+        self.ctr += 1
+
+    def _env_noise_kernels(self, c3) -> None:
+        """conv3 (unless it rode in the fused launch), then the per-env noisy fc layer and heads: draw -> fc ->
+        logits -> finish, no compose launch (csrc/noisy_actor.hip)."""
+        ops, P, Pb, Pl, E, sp = self.ops, self.P, self.Pb, self.Pl, self.E, self.split
+        if c3 is None:
+            ops.conv_fwd(self.y2, Pb["w3"], P["b3"], 1, self.y3, x_lo=self.y2_lo if sp else None,
+                         w_lo=Pl["w3"] if sp else None, out_lo=self.y3_lo if sp else None)
+        ops.noisy_env_draw(self._nz, self.xi)
+        ops.noisy_env_fc(self.y3.reshape(E, 3136), Pb["wfc"], Pb["swfc"], P["bfc"], P["sbfc"], self.xi, self.h,
+                         x_lo=self.y3_lo.reshape(E, 3136) if sp else None, w_lo=Pl["wfc"] if sp else None,
+                         sw_lo=Pl["swfc"] if sp else None, out_lo=self.h_lo, ws=self._env_part)
+        n = int(getattr(self.learner, "N", 1))
+        ops.noisy_env_logits(self.h, {k: P[k] for k in ("wv", "bv", "wa", "ba")},
+                             {k: P["s" + k] for k in ("wv", "bv", "wa", "ba")}, self.xi, n, self._env_L, H_lo=self.h_lo)
+        ops.noisy_env_finish(self.h, self._env_L, {k: P[k] for k in ("wv", "bv", "wa", "ba")}, self.eps, self.ctr,
+                             self.seed, self._env_head, self.q, self.act)
         self.ctr += 1
 
     def _actor_head(self, h, heads, h_lo) -> None:

@@ -150,6 +150,11 @@ class RuntimeConf:
     noisy: bool = False
     noisy_sigma0: float = 0.5
     noisy_actor_resample: int = 1
+    # the GPU actor groups' noise: "shared" (one draw per batched inference call serves all its envs) | "per_env"
+    # (env row e acts under its own draw, as the reference-style per-actor noise: csrc/noisy_actor.hip, two products
+    # on the shared weights instead of one composed weight set).  Read only with noisy; GpuActorGroup on either
+    # backend; not the CPU actor groups, the inline loop or Runtime.layer_norm
+    noisy_actor_noise: str = "shared"
     # Munchausen-DQN target for the scalar head (Vieillard et al. 2020; learner/losses.py munchausen_loss,
     # csrc/mdqn_head.hip): T = R + alpha clamp(tau ln pi(a | Q_target(S_t)), clip, 0) + Gamma * the target net's
     # soft value at S_t+n, pi = softmax(Q_target / tau); no online argmax.  The forward runs the online net on
@@ -451,6 +456,11 @@ class ApexConfig:
         if isinstance(nr, bool) or not isinstance(nr, int) or nr < 1:
             raise ValueError(f"Runtime.noisy_actor_resample (Runtime.noisy's inference calls per actor draw) must "
                              f"be an integer >= 1, got {nr!r}")
+        if rt.noisy_actor_noise not in ("shared", "per_env"):
+            raise ValueError(f"Runtime.noisy_actor_noise must be 'shared' or 'per_env', got {rt.noisy_actor_noise!r}")
+        if rt.noisy and rt.noisy_actor_noise == "per_env" and rt.layer_norm:
+            raise ValueError("Runtime.noisy_actor_noise='per_env' with Runtime.layer_norm is not built: the LayerNorm "
+                             "epilogue consumes the plain fc GEMM's partial planes")
         if rt.noisy:
             if net not in ("nature64", "nature32", "mlp"):
                 raise ValueError(f"Runtime.noisy needs network nature64, nature32 or mlp, got {net!r}")

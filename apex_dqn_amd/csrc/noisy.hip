@@ -23,14 +23,10 @@
 // fp32: within half an ulp (plus fp64 rounding) of the exact value, whatever mu and the
 // noise term cancel to.  The hi / lo planes are the project's split of that fp32 value
 // (apex_common.h split_pk_bf16_h, the optimizer's and cast_bf16's).
-#include "apex_common.h"
+#include "noisy_common.h"
 
-#define NZ_FC_IN 3136
-#define NZ_FC_OUT 1024
-#define NZ_HID 512
 #define NZ_FC_RT 4   // fc rows per block: 256 blocks per net
 #define NZ_HD_RT 8   // head rows per block
-#define NZ_STREAMS 64
 
 struct NoisyNet {
   const float* p;   // flat parameters: mu and sigma segments
@@ -63,29 +59,7 @@ struct NoisyGradArgs {
 
 enum { NZ_WV = 0, NZ_BV, NZ_WA, NZ_BA, NZ_WFC, NZ_BFC };
 
-// offsets of the seven parts of the concatenated draw (learner/noisy.py xi_offsets)
-struct XiOff {
-  int fc_out, v_in, a_in, v_out, a_out, K;
-};
-__host__ __device__ inline XiOff xi_off(int A, int N) {
-  XiOff o;
-  o.fc_out = 2 * NZ_FC_IN;
-  o.v_in = o.fc_out + NZ_FC_OUT;
-  o.a_in = o.v_in + NZ_HID;
-  o.v_out = o.a_in + NZ_HID;
-  o.a_out = o.v_out + N;
-  o.K = o.a_out + A * N;
-  return o;
-}
-
-// xi = sign(g) sqrt(|g|), g = sqrt(-2 ln u1) cos(2 pi u2) from the counter RNG's uniforms.
-// Accurate logf / sqrtf / cospif (no fast-math variants): the mirror evaluates g in fp64.
-__device__ __forceinline__ float noisy_xi(uint64_t seed, uint64_t c, uint32_t k) {
-  const float u1 = 1.0f - apex_uniform(seed, c, 2ull * k);        // (0, 1], exact
-  const float u2 = apex_uniform(seed, c, 2ull * k + 1ull);
-  const float g = sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
-  return copysignf(sqrtf(fabsf(g)), g);
-}
+// (XiOff / xi_off, the index plan of the concatenated draw, and noisy_xi, the draw: noisy_common.h)
 
 __device__ __forceinline__ float noisy_eff(float mu, float sg, float xo, float xin) {
   return (float)((double)mu + (double)sg * ((double)xo * (double)xin));

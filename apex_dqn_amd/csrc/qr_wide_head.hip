@@ -204,17 +204,29 @@ APEX_EXPORT int apex_qr_wide_head(QRWideArgs a, hipStream_t st) {
   APEX_CHECK_LAUNCH();
 }
 
-APEX_EXPORT int apex_qr_wide_actor_head(QRWideActorArgs a, hipStream_t st) {
-  const ActorIO& io = a.io;
-  if (!qw_actor_ok(io, a.N, a.L)) return (int)hipErrorInvalidValue;
-  qw_launch_actor_logits(io, a.N, a.L, st);
-  const int grid = (io.E + 3) / 4;
+static inline void qw_actor_finish_launch(const QRWideActorArgs& a, hipStream_t st) {
+  const int grid = (a.io.E + 3) / 4;
   switch ((a.N + 63) / 64) {
     case 1: qr_wide_actor_finish_kernel<1><<<grid, QW_NT, 0, st>>>(a); break;
     case 2: qr_wide_actor_finish_kernel<2><<<grid, QW_NT, 0, st>>>(a); break;
     case 3: qr_wide_actor_finish_kernel<3><<<grid, QW_NT, 0, st>>>(a); break;
     default: qr_wide_actor_finish_kernel<4><<<grid, QW_NT, 0, st>>>(a); break;
   }
+}
+
+APEX_EXPORT int apex_qr_wide_actor_head(QRWideActorArgs a, hipStream_t st) {
+  const ActorIO& io = a.io;
+  if (!qw_actor_ok(io, a.N, a.L)) return (int)hipErrorInvalidValue;
+  qw_launch_actor_logits(io, a.N, a.L, st);
+  qw_actor_finish_launch(a, st);
+  APEX_CHECK_LAUNCH();
+}
+
+// The finish alone, on logits the caller has written into L (csrc/noisy_actor.hip noisy_env_logits_kernel: the
+// per-env noisy logits; io.P then carries the mu biases, io.H is not read)
+APEX_EXPORT int apex_qr_wide_actor_finish(QRWideActorArgs a, hipStream_t st) {
+  if (!qw_actor_ok(a.io, a.N, a.L)) return (int)hipErrorInvalidValue;
+  qw_actor_finish_launch(a, st);
   APEX_CHECK_LAUNCH();
 }
 

@@ -57,10 +57,11 @@ def xi_offsets(A: int, N: int, hidden: int = HEAD_IN, fc_in: int = FC_IN) -> Dic
     return off
 
 
-def gaussians(seed: int, u: int, s: int, K: int) -> np.ndarray:
-    """The K standard normal draws of (seed, u, s), fp64 (Box-Muller on the fp32 uniforms)."""
+def gaussians(seed: int, u: int, s: int, K: int, e: int = 0) -> np.ndarray:
+    """The K standard normal draws of (seed, u, s), fp64 (Box-Muller on the fp32 uniforms); ``e``: env row e of a
+    per-env actor draw, whose value k sits at index e K + k of the same counter word (row 0: the shared draw)."""
     c = STREAMS_PER_INDEX * int(u) + int(s)
-    k = np.arange(int(K), dtype=np.uint64)
+    k = np.arange(int(K), dtype=np.uint64) + np.uint64(int(e) * int(K))
     u1 = 1.0 - apex_uniform(seed, c, 2 * k).astype(np.float64)
     u2 = apex_uniform(seed, c, 2 * k + 1).astype(np.float64)
     return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
@@ -71,12 +72,18 @@ def xi_of(g: np.ndarray) -> np.ndarray:
 
 
 def noise_vectors(seed: int, u: int, s: int, A: int, N: int, hidden: int = HEAD_IN,
-                  fc_in: int = FC_IN) -> Dict[str, torch.Tensor]:
+                  fc_in: int = FC_IN, e: int = 0) -> Dict[str, torch.Tensor]:
     """The draw (seed, u, s) as named fp64 vectors (the keys of :func:`xi_offsets`) plus the
-    concatenation under ``"xi"``.  ``seed`` is seed_n (:func:`noise_seed`)."""
+    concatenation under ``"xi"``.  ``seed`` is seed_n (:func:`noise_seed`); ``e``: :func:`gaussians`'s."""
     off = xi_offsets(A, N, hidden, fc_in)
-    xi = torch.from_numpy(xi_of(gaussians(seed, u, s, off["K"])))
+    xi = torch.from_numpy(xi_of(gaussians(seed, u, s, off["K"], e)))
     return split_xi(xi, A, N, hidden, fc_in)
+
+
+def env_noise_vectors(seed: int, u: int, s: int, e: int, A: int, N: int) -> Dict[str, torch.Tensor]:
+    """The draw env row ``e`` of actor stream ``s`` acts under at index ``u`` with ``Runtime.noisy_actor_noise =
+    "per_env"`` (csrc/noisy_actor.hip ``noisy_env_draw_kernel``): :func:`noise_vectors` at the indices e K + k."""
+    return noise_vectors(seed, u, s, A, N, e=e)
 
 
 def split_xi(xi: torch.Tensor, A: int, N: int, hidden: int = HEAD_IN, fc_in: int = FC_IN) -> Dict[str, torch.Tensor]:
@@ -162,6 +169,9 @@ def actor_noise_hook(cfg, net, group: int):
     rt = cfg.Runtime
     if not rt.noisy:
         return None
+    if getattr(rt, "noisy_actor_noise", "shared") != "shared":
+        raise ValueError(f"Runtime.noisy_actor_noise={rt.noisy_actor_noise!r} is the GPU actor groups' (--mode gpu): the "
+                         "CPU actor groups and the inline loop set one draw per batched call")
     every, s, last = int(rt.noisy_actor_resample), actor_stream(group), [-1]
 
     def hook(t: int) -> None:

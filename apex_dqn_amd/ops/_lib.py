@@ -186,6 +186,25 @@ class NoisyGradArgs(ctypes.Structure):
                 ("n_g", c_i64)]
 
 
+class NoisyEnvDraw(ctypes.Structure):
+    """Arguments of ``noisy_env_draw_kernel`` (``NoisyEnvDraw``, csrc/noisy_actor.hip)."""
+    _fields_ = [("xi", c_p), ("ld", c_i64), ("E", c_i), ("A", c_i), ("N", c_i), ("stream", c_i), ("seed", c_u64),
+                ("ctr", c_p), ("every", c_i64)]
+
+
+class NoisyEnvFc(ctypes.Structure):
+    """Arguments of ``noisy_env_fc_kernel`` and its epilogue (``NoisyEnvFc``, csrc/noisy_actor.hip)."""
+    _fields_ = [("X", c_p), ("X_lo", c_p), ("W", c_p), ("W_lo", c_p), ("S", c_p), ("S_lo", c_p), ("bfc", c_p),
+                ("sbfc", c_p), ("xi", c_p), ("ld", c_i64), ("E", c_i), ("ksplit", c_i), ("part", c_p),
+                ("n_part", c_i64), ("h", c_p), ("h_lo", c_p)]
+
+
+class NoisyEnvLogits(ctypes.Structure):
+    """Arguments of ``noisy_env_logits_kernel`` (``NoisyEnvLogits``, csrc/noisy_actor.hip)."""
+    _fields_ = [("H", c_p), ("H_lo", c_p), ("mu", HeadParams), ("sg", HeadParams), ("xi", c_p), ("ld", c_i64),
+                ("E", c_i), ("A", c_i), ("N", c_i), ("L", c_p)]
+
+
 class AugArgs(ctypes.Structure):
     """Arguments of ``augment_shift_kernel`` (``AugArgs``, csrc/augment.hip)."""
     _fields_ = [("ring", c_p), ("F", c_i64), ("slots", c_p), ("rows", c_i), ("C", c_i), ("pad", c_i), ("seed", c_u64),
@@ -409,6 +428,14 @@ _SIGS = {
     "apex_noisy_xi_len": ([c_i, c_i], c_i),
     "apex_noisy_compose": ([NoisyArgs, c_p], c_i),
     "apex_noisy_sigma_grad": ([NoisyGradArgs, c_p], c_i),
+    "apex_noisy_env_ksplit": ([c_i], c_i),
+    "apex_noisy_env_draw": ([NoisyEnvDraw, c_p], c_i),
+    "apex_noisy_env_fc": ([NoisyEnvFc, c_p], c_i),
+    "apex_noisy_env_logits": ([NoisyEnvLogits, c_p], c_i),
+    "apex_noisy_env_scalar_finish": ([ActorIO, c_p, c_p], c_i),
+    "apex_noisy_env_args_size": ([c_i], c_i),
+    "apex_qr_wide_actor_finish": ([QRWideActorArgs, c_p], c_i),
+    "apex_c51_wide_actor_finish": ([C51WideActorArgs, c_p], c_i),
     "apex_augment_shift": ([AugArgs, c_p], c_i),
     "apex_augment_debug_errors": ([c_p, c_p, c_i], c_i),
     "apex_reset_perturb": ([ResetArgs, c_p], c_i),

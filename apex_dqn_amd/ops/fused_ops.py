@@ -918,6 +918,77 @@ class TorchBackend:
             gm = plan.seg(g32, name).double()
             plan.seg(g32, NZ.SIGMA[name]).copy_((gm * NZ.outer(v, name, gm.shape).to(gm.device)).float())
 
+    # ------------------------------------------- per-env actor noise (Runtime.noisy_actor_noise = "per_env")
+    # The oracles of csrc/noisy_actor.hip, dtype-generic: fp64 inputs give the reference, anything else the fp32 CPU
+    # path.  ``xi`` [E, >= K]: row e is env row e's concatenated draw (learner/noisy.py env_noise_vectors).
+    @staticmethod
+    def wide_jp(A: int, N: int) -> int:
+        """Floats per row of a wide head's logits workspace: [N padded to 4 | A N padded to 4] (csrc/wide_head.h)."""
+        return ((int(N) + 3) & ~3) + ((int(A) * int(N) + 3) & ~3)
+
+    def noisy_env_fc_ws(self, E: int, device):
+        """The fc GEMM's split-K partial planes (HIP backend; nothing here)."""
+        return None
+
+    def noisy_env_logits_ws(self, E: int, A: int, N: int, device, dtype=torch.float32) -> torch.Tensor:
+        """A new logits workspace ``[E, wide_jp(A, N)]``; every actor group owns one."""
+        return torch.zeros(int(E), self.wide_jp(A, N), dtype=dtype, device=device)
+
+    def noisy_env_draw(self, plan, xi) -> None:
+        """``xi[e, :K]`` = the draw (u = ``plan.index()``, s = ``plan.stream0``, e) for every row of ``xi``."""
+        from ..learner import noisy as NZ
+        K, u = plan.K, plan.index()
+        for e in range(xi.shape[0]):
+            xi[e, :K].copy_(NZ.env_noise_vectors(plan.seed, u, plan.stream0, e, plan.A, plan.N)["xi"])
+
+    def noisy_env_fc(self, x, w, sw, b, sb, xi, out, x_lo=None, w_lo=None, sw_lo=None, out_lo=None, ws=None) -> None:
+        """h[e, c] = ReLU(P + b[c] + xi_out[e, c] (S + sb[c])), P = X w^T, S = (X * xi_in^{stream(c)}[e]) sw^T: the
+        noisy fc layer of env row e under its own draw, on the shared mean ``w`` and noise scale ``sw`` (+ their lo
+        planes).  ``ws``: :meth:`noisy_env_fc_ws`."""
+        dt = torch.float64 if x.dtype == torch.float64 else torch.float32
+        E = x.shape[0]
+        X = join(x.reshape(E, -1), None if x_lo is None else x_lo.reshape(E, -1), dt)
+        W, S, n = join(w, w_lo, dt), join(sw, sw_lo, dt), xi.to(dt)
+        fi, half = X.shape[1], W.shape[0] // 2
+        sv = torch.cat([(X * n[:, :fi]) @ S[:half].t(), (X * n[:, fi:2 * fi]) @ S[half:].t()], 1)
+        xo = n[:, 2 * fi:2 * fi + 2 * half]
+        split_into(torch.relu(X @ W.t() + b.to(dt) + xo * (sv + sb.to(dt))), out, out_lo)
+
+    def noisy_env_logits(self, H, P, S, xi, num_atoms: int, L, H_lo=None) -> None:
+        """The (A + 1) N head logits of every env row under its own draw, without the mean biases (the finish adds
+        them, as the wide heads' do): L[e, j] = h . mu[j] + xi_hout[e, j] ((h * xi_hin^{in(j)}[e]) . sigma[j] +
+        sigma_b[j]), value rows at [0, N), advantage rows at [N padded to 4, ..).  ``P`` / ``S``: the mean and the
+        noise-scale head segments under the keys wv, bv, wa, ba."""
+        from ..learner import noisy as NZ
+        dt, N = _head_dtype(P["wv"]), int(num_atoms)
+        h = join(H, H_lo, dt)
+        HS, AN = P["wv"].shape[-1], P["wa"].shape[0]
+        assert HS == NZ.HEAD_IN and AN % N == 0
+        off, n = NZ.xi_offsets(AN // N, N), xi.to(dt)
+        for cols, c0, hh, wn, bn, kin, kout in ((N, 0, h[:, :HS], "wv", "bv", "v_in", "v_out"),
+                                               (AN, (N + 3) & ~3, h[:, HS:], "wa", "ba", "a_in", "a_out")):
+            g = hh * n[:, off[kin]:off[kin] + HS]
+            noise = g @ S[wn].to(dt).reshape(cols, HS).t() + S[bn].to(dt).reshape(cols)
+            L[:, c0:c0 + cols] = hh @ P[wn].to(dt).reshape(cols, HS).t() + n[:, off[kout]:off[kout] + cols] * noise
+
+    def noisy_env_finish(self, H, L, P, eps, ctr, seed, head, q_out, a_out) -> None:
+        """q and the epsilon-greedy action from the logits of :meth:`noisy_env_logits` plus the mean biases of ``P``.
+        ``head``: ("scalar",) | ("quantile", N) | ("categorical", N, v_min, v_max); ``H``: the activations the
+        logits came from (the HIP finish kernels' argument block names them)."""
+        dt = _head_dtype(P["wv"])
+        N = 1 if head[0] == "scalar" else int(head[1])
+        E, A = q_out.shape
+        c0 = (N + 3) & ~3
+        v = L[:, :N].to(dt) + P["bv"].to(dt).reshape(N)
+        a = (L[:, c0:c0 + A * N].to(dt) + P["ba"].to(dt).reshape(A * N)).reshape(E, A, N)
+        th = v[:, None, :] + a - a.mean(1, keepdim=True)
+        if head[0] == "categorical":
+            z = float(head[2]) + torch.arange(N, dtype=dt, device=th.device) * ((float(head[3]) - float(head[2])) / (N - 1))
+            q = (torch.log_softmax(th, dim=-1).exp() * z).sum(-1)
+        else:
+            q = th.mean(-1)
+        self._eps_greedy(q, eps, ctr, seed, q_out, a_out)
+
     # ------------------------------------------------- frame augmentation
     @staticmethod
     def _augment_check(ring, slots, pad, ctr, base, out, off_out):
@@ -1001,7 +1072,8 @@ class HipBackend(TorchBackend):
         self.native_conv = native_conv and hasattr(self.lib, "apex_conv_fwd")
         self.kernels = ["replay", "head", "head_wgrad", "optimizer", "actor_head", "c51_head", "c51_actor_head", "qr_head",
                         "qr_actor_head", "noisy_compose", "noisy_sigma_grad", "mdqn_head", "iqn_head", "miqn_head", "iqn_wgrad",
-                        "iqn_actor_head", "augment_shift", "hlg_head", "reset_perturb"]
+                        "iqn_actor_head", "augment_shift", "hlg_head", "reset_perturb", "noisy_env_draw", "noisy_env_fc",
+                        "noisy_env_logits"]
         if self.native_conv:
             self.kernels += ["conv_fwd", "conv_dgrad", "conv_wgrad", "fc_fwd", "fc_bwd", "fc_ln_fwd", "fc_ln_bwd"]
             for k, cls in enumerate((_lib.FcLnEpiArgs, _lib.FcLnBwdArgs)):
@@ -1731,6 +1803,90 @@ class HipBackend(TorchBackend):
         a.g, a.xi, a.A, a.N, a.n_g = g32.data_ptr(), xi.data_ptr(), int(plan.A), int(plan.N), int(g32.numel())
         self._noisy_offsets(plan, a.mu, a.sg)
         _lib.check(self.lib.apex_noisy_sigma_grad(a, _lib.stream_ptr()), "noisy_sigma_grad")
+
+    # ---- per-env actor noise: csrc/noisy_actor.hip
+    @staticmethod
+    def _env_xi(a, xi, E: int, K: int) -> None:
+        assert xi.dtype == torch.float32 and xi.dim() == 2 and xi.shape[0] >= E and xi.shape[1] >= K \
+            and xi.stride(1) == 1 and xi.stride(0) % 4 == 0
+        a.xi, a.ld, a.E = xi.data_ptr(), int(xi.stride(0)), int(E)
+
+    def noisy_env_fc_ws(self, E: int, device) -> torch.Tensor:
+        return torch.zeros(self.lib.apex_noisy_env_ksplit(int(E)) * 2 * int(E) * 1024, dtype=torch.float32,
+                           device=device)
+
+    def noisy_env_logits_ws(self, E: int, A: int, N: int, device, dtype=torch.float32) -> torch.Tensor:
+        assert dtype == torch.float32 and self.wide_jp(A, N) == self.lib.apex_qr_wide_jp(int(A), int(N))
+        return super().noisy_env_logits_ws(E, A, N, device)
+
+    def noisy_env_draw(self, plan, xi) -> None:
+        """``noisy_env_draw_kernel``: the draw index is read on the device."""
+        a = _lib.NoisyEnvDraw()
+        assert ctypes.sizeof(a) == self.lib.apex_noisy_env_args_size(0)
+        self._env_xi(a, xi, xi.shape[0], plan.K)
+        assert plan.ctr.dtype == torch.int64 and plan.base is None
+        a.A, a.N, a.stream, a.seed = int(plan.A), int(plan.N), int(plan.stream0), int(plan.seed)
+        a.ctr, a.every = plan.ctr.data_ptr(), int(plan.every)
+        _lib.check(self.lib.apex_noisy_env_draw(a, _lib.stream_ptr()), "noisy_env_draw")
+
+    def noisy_env_fc(self, x, w, sw, b, sb, xi, out, x_lo=None, w_lo=None, sw_lo=None, out_lo=None, ws=None) -> None:
+        """``noisy_env_fc_kernel`` + its epilogue; ``ws``: the caller's partial planes (:meth:`noisy_env_fc_ws`; None:
+        fresh ones for this call)."""
+        a = _lib.NoisyEnvFc()
+        assert ctypes.sizeof(a) == self.lib.apex_noisy_env_args_size(1)
+        E = int(x.shape[0])
+        self._env_xi(a, xi, E, 2 * 3136 + 1024)
+        planes = (x, x_lo, w, w_lo, sw, sw_lo, out, out_lo)
+        assert all(t is None or (t.dtype == torch.bfloat16 and t.is_contiguous()) for t in planes)
+        assert x[0].numel() == 3136 and tuple(w.shape) == (1024, 3136) == tuple(sw.shape) and out.shape == (E, 1024)
+        assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == 1024 for t in (b, sb))
+        if ws is None:
+            ws = self.noisy_env_fc_ws(E, x.device)
+        assert ws.dtype == torch.float32 and ws.is_contiguous()
+        a.X, a.X_lo, a.W, a.W_lo, a.S, a.S_lo, a.h, a.h_lo = (_lib.ptr(t) for t in planes)
+        a.bfc, a.sbfc, a.part, a.n_part = b.data_ptr(), sb.data_ptr(), ws.data_ptr(), int(ws.numel())
+        a.ksplit = self.lib.apex_noisy_env_ksplit(E)
+        _lib.check(self.lib.apex_noisy_env_fc(a, _lib.stream_ptr()), "noisy_env_fc")
+
+    def noisy_env_logits(self, H, P, S, xi, num_atoms, L, H_lo=None) -> None:
+        """``noisy_env_logits_kernel`` into ``L`` (:meth:`noisy_env_logits_ws`)."""
+        a = _lib.NoisyEnvLogits()
+        assert ctypes.sizeof(a) == self.lib.apex_noisy_env_args_size(2)
+        N, E = int(num_atoms), int(L.shape[0])
+        A = P["wa"].shape[0] // N
+        from ..learner.noisy import xi_offsets
+        self._env_xi(a, xi, E, xi_offsets(A, N)["K"])
+        assert H.dtype == torch.bfloat16 and H.is_contiguous() and H.shape[0] >= E and H.shape[1] == 1024
+        assert H_lo is None or (H_lo.dtype == torch.bfloat16 and H_lo.is_contiguous() and H_lo.shape == H.shape)
+        assert L.dtype == torch.float32 and L.is_contiguous() and L.shape[1] == self.wide_jp(A, N)
+        for hp, D in ((a.mu, P), (a.sg, S)):
+            assert all(D[k].dtype == torch.float32 and D[k].is_contiguous() for k in ("wv", "bv", "wa", "ba"))
+            assert D["wv"].numel() == N * 512 and D["bv"].numel() == N and D["wa"].numel() == A * N * 512 \
+                and D["ba"].numel() == A * N
+            hp.wv, hp.bv, hp.wa, hp.ba = (D[k].data_ptr() for k in ("wv", "bv", "wa", "ba"))
+        a.H, a.H_lo, a.A, a.N, a.L = H.data_ptr(), _lib.ptr(H_lo), A, N, L.data_ptr()
+        _lib.check(self.lib.apex_noisy_env_logits(a, _lib.stream_ptr()), "noisy_env_logits")
+
+    def noisy_env_finish(self, H, L, P, eps, ctr, seed, head, q_out, a_out) -> None:
+        """The scalar finish of csrc/noisy_actor.hip, or the wide actor finish kernels alone (csrc/qr_wide_head.hip,
+        csrc/cat_wide_head.hip) on the logits ``L``."""
+        kind = head[0]
+        E, A = q_out.shape
+        N = 1 if kind == "scalar" else int(head[1])
+        assert L.dtype == torch.float32 and L.is_contiguous() and L.shape == (E, self.wide_jp(A, N))
+        assert H.shape[0] >= E and H.shape[1] == 1024 and H.is_contiguous()
+        if kind == "scalar":
+            a = _lib.ActorIO()
+            self._actor_io(a, H, P, eps, ctr, seed, q_out, a_out, None)
+            return _lib.check(self.lib.apex_noisy_env_scalar_finish(a, L.data_ptr(), _lib.stream_ptr()),
+                              "noisy_env_scalar_finish")
+        a = _lib.QRWideActorArgs() if kind == "quantile" else _lib.C51WideActorArgs()
+        self._actor_io(a.io, H, P, eps, ctr, seed, q_out, a_out, None)
+        a.N, a.L = N, L.data_ptr()
+        if kind == "quantile":
+            return _lib.check(self.lib.apex_qr_wide_actor_finish(a, _lib.stream_ptr()), "qr_wide_actor_finish")
+        a.vmin, a.vmax = float(head[2]), float(head[3])
+        _lib.check(self.lib.apex_c51_wide_actor_finish(a, _lib.stream_ptr()), "c51_wide_actor_finish")
 
     def augment_args(self, ring, slots, pad, seed, ctr, base, out, off_out) -> "_lib.AugArgs":
         """The argument block of ``apex_augment_shift`` (tests pass altered copies to the launcher)."""
